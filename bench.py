@@ -2,6 +2,7 @@
 """Benchmark of the semi-Markov decode path on MI355X (contract: see the task statement / DESIGN.md §Measurement).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg5|cfg3c|cfg2|cfg1|cfg4] [--scaling weak|strong]
+                    [--dump-outputs DIR]
 
 One "step" = one decode pass (emission scorer + Viterbi DP + back-trace + label expansion + labels on the host: the
 DP kernel writes them into pinned host memory over PCIe while it decodes) over this rank's share of a synthetic corpus,
@@ -22,6 +23,11 @@ relays rank 0's line.  Either way the job fails (non-zero exit) unless the group
     (Datasplit.accuracy_corpus, src/data/corpus.py:405-604, summed as src/main.py:486-532 does) are all-reduced over
     RCCL before they are finalised: the statistics printed are those of the whole corpus and do not depend on N.
     ``--scaling strong`` makes this leg the headline instead -- again at every N, so a curve never mixes the two.
+
+``--dump-outputs DIR``: after the timed steps, rank 0 writes what the headline leg's last timed step returned to the caller
+(frame labels, best path score and segment count per video; videos ordered by task, then name) as DIR/<name>.npy in
+float32 / float64.  The inputs are a function of the arguments alone (seeded corpus, closed-form fit on the host), so two
+builds can be compared output for output.
 
 Rank 0 prints ONE JSON line.  ``roofline`` is for the dominant kernel (the DP kernel), timed live with HIP events
 on the stream it is launched on; ``cpu_baseline`` is the oracle's dense reference-path restatement on a bounded
@@ -73,6 +79,8 @@ def parse(argv=None):
                    help="collectives: 'nccl' = RCCL (required for a measurement); 'gloo' only for rehearsals")
     p.add_argument('--share-gpus', action='store_true',
                    help='rehearsal only: ranks may share a GPU (LOCAL_RANK %% device_count); needs --backend gloo')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help="write the headline leg's decode outputs of the last timed step to DIR/<name>.npy (rank 0)")
     p.add_argument('--dry-run', action='store_true',
                    help='host-only rehearsal of the N-rank path: rendezvous, shard the corpus structure, reduce the '
                         'frame counters; nothing is decoded and no GPU is touched (implies --backend gloo)')
@@ -83,6 +91,8 @@ def parse(argv=None):
         p.error('--share-gpus needs --backend gloo (RCCL refuses two ranks on one GPU)')
     if a.gpus < 1:
         p.error('--gpus must be >= 1')
+    if a.steps < 1:
+        p.error('--steps must be >= 1')
     if a.scaling is None:
         a.scaling = 'weak'                  # ONE headline leg for every N (a 1 -> 8 curve must not change workload)
     return a
@@ -271,10 +281,12 @@ def cpu_factored(pc, model, gpu_labels=None, budget_s=12.0):
 # ------------------------------------------------------------------------------------------------ legs
 def fit_model(a, cfg, data, dev, D, world):
     """Closed-form fit on a few videos per task (untimed), the decode model around it.  N > 1: rank 0's parameters are
-    broadcast, like every rank loading the same pickle."""
+    broadcast, like every rank loading the same pickle.  The fit runs on the host (the module's host statement): the
+    device statistics sum through fp64 atomics in no fixed order, and the decode's inputs must not change from run to run
+    (--dump-outputs compares builds output for output)."""
     from action_segmentation_amd import synth
     from action_segmentation_amd.semimarkov import SemiMarkovModel
-    fit_args = synth.make_args(cfg['max_k'], cuda=True, batch_size=cfg['batch_size'])
+    fit_args = synth.make_args(cfg['max_k'], cuda=False, batch_size=cfg['batch_size'])
     fitted = SemiMarkovModel.from_args(fit_args, data)
     fitted.fit(data.subset(a.fit_videos), use_labels=True)
     args = synth.make_args(cfg['max_k'], cuda=True, batch_size=cfg['batch_size'],
@@ -288,7 +300,8 @@ def fit_model(a, cfg, data, dev, D, world):
 
 def timed_decode(a, pc, world, want_events=True):
     """W warm-up + exactly K timed decode steps of this rank's packed corpus, bracketed by barrier + synchronize.
-    Returns (wall seconds of the K steps, DP kernel launch statistics of those steps or None, last labels (host int64))."""
+    Returns (wall seconds of the K steps, DP kernel launch statistics of those steps or None, last labels (host int64),
+    what the last timed step returned to the caller as host numpy arrays: labels, best, n_segs)."""
     from action_segmentation_amd import ops
     empty = pc is None or pc.n_videos == 0
     t = None if empty else pc.tables
@@ -337,6 +350,10 @@ def timed_decode(a, pc, world, want_events=True):
     sync()
     dt = time.perf_counter() - t0
     gc.enable()
+    outputs = None
+    if not empty:
+        out = last['out']
+        outputs = {'labels': labels.numpy().copy(), 'best': out['best'].cpu().numpy(), 'n_segs': out['n_segs'].cpu().numpy()}
     dp = None
     if timing:
         ops.dp_timing(False)
@@ -361,7 +378,41 @@ def timed_decode(a, pc, world, want_events=True):
             dp["time_split"] = {"videos_split": words[4], "of_those_decoded_again_in_one_piece": words[5], "one_class_run_ties_resolved": words[7],
                                 "why": [n for bit, n in ((1, "a cut did not certify"), (2, "closing step"), (4, "two states within the margin"),
                                                          (8, "two lengths within the margin"), (16, "NaN / too many segments")) if words[6] & bit]}
-    return dt, dp, labels
+    return dt, dp, labels, outputs
+
+
+def dump_outputs(dirname, pc, outputs, max_bytes=64 << 20):
+    """--dump-outputs: the decode's outputs (``timed_decode``) as DIR/<name>.npy, videos in (task, name) order, so that the
+    files do not depend on how the corpus was packed:
+      labels      float32 [frames]  frame labels of the videos one after the other (class ids: exact in float32)
+      best        float64 [videos]  Viterbi score of the best segmentation
+      n_segs      float32 [videos]  its number of segments
+      lengths     float32 [videos]  frames per video (to cut ``labels`` into videos)
+    More frames than fit into ``max_bytes``: ``labels`` holds a fixed, seeded sample of them and ``labels_frame_index``
+    (float64) their positions on the frame axis.  Returns {name: shape}."""
+    os.makedirs(dirname, exist_ok=True)
+    n = 0 if pc is None else pc.n_videos
+    order = sorted(range(n), key=lambda i: (pc.task_names[i], pc.video_names[i]))
+    if outputs is None:
+        outputs = {'labels': np.zeros(0, np.int64), 'best': np.zeros(0), 'n_segs': np.zeros(0, np.int32)}
+    lab = outputs['labels']
+    arrays = {
+        'labels': np.concatenate([lab[pc.frame_offset[i]:pc.frame_offset[i] + pc.lengths[i]] for i in order]
+                                 or [np.zeros(0, lab.dtype)]).astype(np.float32),
+        'best': outputs['best'][order].astype(np.float64),
+        'n_segs': outputs['n_segs'][order].astype(np.float32),
+        'lengths': np.asarray([pc.lengths[i] for i in order], dtype=np.float32),
+    }
+    room = max_bytes - sum(v.nbytes for k, v in arrays.items() if k != 'labels') - (1 << 20)
+    n_frames = arrays['labels'].shape[0]
+    if n_frames * 4 > room:
+        keep = room // (4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(n_frames, size=keep, replace=False))
+        arrays['labels'] = arrays['labels'][idx]
+        arrays['labels_frame_index'] = idx.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + '.npy'), v)
+    return {k: list(v.shape) for k, v in arrays.items()}
 
 
 def gt_on_device(pc, data, dev):
@@ -379,7 +430,8 @@ def video_keys(pc, data):
 
 
 def strong_leg(a, rank, world, dev, D):
-    """ONE corpus (seed --seed) sharded by video over the ranks; evaluation counters reduced over the backend."""
+    """ONE corpus (seed --seed) sharded by video over the ranks; evaluation counters reduced over the backend.
+    Returns (the leg's result, (this rank's packed shard, its decode outputs) for --dump-outputs)."""
     from action_segmentation_amd import evaluation, synth
     from action_segmentation_amd.batching import batch_cost
     cfg = synth.CONFIGS[a.strong_workload]
@@ -395,7 +447,7 @@ def strong_leg(a, rank, world, dev, D):
     D.broadcast_parameters(model.model, src=0)
     pc = model.prepare(data, shard=(rank, world))
     assert sorted(pc.video_names) == sorted(n for i in mine for (_, n) in batches[i])
-    dt, dp, labels = timed_decode(a, pc, world, want_events=True)
+    dt, dp, labels, outputs = timed_decode(a, pc, world, want_events=True)
     dp_ms = dp["per_step_sum_ms"] if dp else None                    # DP kernel time of a step, all its launches
     space = evaluation.LabelSpace.from_corpus(data.corpus, list(data._videos_by_task))
     if pc.n_videos:
@@ -421,14 +473,14 @@ def strong_leg(a, rank, world, dev, D):
                 "frac": dp_bytes / (dp_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": None, "kernel": "smm_viterbi_kernel",
                 "kernel_ms": dp["launch_ms"], "launches_per_step": nl, "algorithmic_bytes_per_launch": dp_bytes / nl,
                 "note": "rank 0's shard of the sharded corpus; the DP is latency-bound (one serial chain per video), not HBM-bound"}
-    return {"scaling": "strong", "roofline_rank0": roof, "workload": "%s seed %d: %d videos, %d frames, sharded by video (whole single-task "
+    return ({"scaling": "strong", "roofline_rank0": roof, "workload": "%s seed %d: %d videos, %d frames, sharded by video (whole single-task "
             "batches of %d, greedy LPT on the DP work)" % (a.strong_workload, a.seed, int(tot[1]), int(tot[0]), cfg['batch_size']),
             "value": float(tot[0]) * a.steps / dt_all, "unit": "frames/s", "n_gpus": world, "ms_per_step": dt_all / a.steps * 1e3,
             "frames": int(tot[0]), "videos": int(tot[1]), "max_frames_on_a_rank": int(tmax[1]),
             "dp_kernel_ms_max_over_ranks": float(tmax[2]),
             "stats_reduced_over": ("%s all-reduce%s" % ("RCCL" if torch.distributed.get_backend() == 'nccl' else "gloo",
                                                          " (one-rank group)" if world == 1 else "")) if D.active() else "1 rank",
-            "stats": {k: round(v, 9) for k, v in summary.items()}}
+            "stats": {k: round(v, 9) for k, v in summary.items()}}, (pc, outputs))
 
 
 def predict_end_to_end(model, data):
@@ -812,7 +864,7 @@ def main():
     pc = model.prepare(data)                                         # inputs resident in HBM from here on
     frames = pc.n_frames
     stream = torch.cuda.current_stream()
-    dt, dp, labels = timed_decode(a, pc, world)
+    dt, dp, labels, outputs = timed_decode(a, pc, world)
     dp_ms = dp["per_step_sum_ms"]                                    # DP kernel time of a step, all its launches
     labels_dev = labels.to(dev)      # the evaluation kernels below (outside the timed region) read device labels
 
@@ -850,9 +902,12 @@ def main():
     dt = float(tmax[0])
 
     strong = None
+    dump = (pc, outputs)
     if not a.no_strong_leg:
         del labels_dev, gt_dev
-        strong = strong_leg(a, rank, world, dev, D)
+        strong, strong_dump = strong_leg(a, rank, world, dev, D)
+        if a.scaling == 'strong':
+            dump = strong_dump
 
     if rank == 0:
         c_avg = float(np.mean([pc.n_states[g] for g in pc.group]))
@@ -870,6 +925,8 @@ def main():
         wl_text = weak_workload_text(a, cfg, [t for t, _ in in_order], [c for _, c in in_order])
         if head is not weak:
             wl_text = head["workload"]
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, *dump)
         res = {
             "metric": METRIC,
             "value": head["value"], "unit": "frames/s", "n_gpus": world, "steps": a.steps,
@@ -961,7 +1018,7 @@ def main():
             data2 = synth.SynthDatasplit(a.workload, seed=a.second_seed, device=dev)
             _, model2 = fit_model(a, cfg, data2, dev, D, world)
             pc2 = model2.prepare(data2)
-            dt2, dp2, _ = timed_decode(a, pc2, world)
+            dt2, dp2, _, _ = timed_decode(a, pc2, world)
             dp2 = dp2["per_step_sum_ms"] if dp2 else None
             res["other_draw"] = {"seed": a.second_seed, "value": pc2.n_frames * a.steps / dt2, "unit": "frames/s",
                                  "ms_per_step": dt2 / a.steps * 1e3, "dp_kernel_ms": dp2, "frames": pc2.n_frames,

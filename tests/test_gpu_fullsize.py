@@ -334,9 +334,6 @@ def test_logz_gradient_error_does_not_grow_with_the_lattice(t_len, k):
                              rate=(10, 50) if k <= 64 else (20, min(400, k // 2)), all_cyclic=True)
     errs = _logz_both(cp, measure=True)
     import json
-    import os
-    os.makedirs('gpurun_out', exist_ok=True)
-    with open(os.path.join('gpurun_out', 'logz_error_growth.jsonl'), 'a') as f:
-        f.write(json.dumps(dict(T=t_len, K=k, states=c, **errs)) + '\n')
+    print(json.dumps(dict(T=t_len, K=k, states=c, **errs)))       # (the measured figures: pytest -rP shows them)
     assert errs['logz'] <= 1e-6, errs
     assert max(errs[key] for key in ('elp', 'trans', 'init', 'len')) <= 5e-5, errs
