@@ -1404,6 +1404,34 @@ extern "C" int smm_logz_bwd_f64(const smm_shape *shape, const int64_t *lengths_h
     return SMM_OK;
 }
 
+extern "C" int smm_sample_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                              const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                              const double *elp, const double *trans, const double *init, const double *len_scores,
+                              const double *endpen, const int64_t *class_map, const double *logz, int32_t n_samples,
+                              uint64_t seed, int64_t *spans_out, int64_t *labels_out, double *logp_out, void *workspace,
+                              size_t workspace_bytes, void *stream)
+{
+    if (n_samples <= 0 || (!spans_out && !labels_out && !logp_out)) return SMM_ERR_ARG;
+    Staged st;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes,
+                   hs, &st);
+    if (rc != SMM_OK) return rc;
+    if (!elp || !trans || !init || !len_scores || !logz) return SMM_ERR_ARG;
+    const bool no_eos = (shape->flags & SMM_SHAPE_NO_EOS) != 0;
+    SmmSampleArgs a{};
+    a.videos = st.videos; a.n_states = st.n_states; a.hist = st.hist;
+    a.elp = elp; a.trans = trans; a.init = init; a.len = len_scores; a.endpen = no_eos ? nullptr : endpen;
+    a.class_map = class_map; a.logz = logz;
+    a.spans = spans_out; a.labels = labels_out; a.logp = logp_out; a.err = st.err;
+    a.total_frames = shape->total_frames; a.seed = seed;
+    a.c_max = shape->c_max; a.k_rows = shape->k_rows; a.t_max = shape->t_max; a.b = shape->b; a.n_samples = n_samples;
+    a.no_eos = no_eos ? 1 : 0;
+    smm_launch_sample(a, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ dense boundary
 static size_t dense_off(size_t &cur, size_t bytes)
 {

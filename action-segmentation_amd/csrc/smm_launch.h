@@ -99,3 +99,25 @@ struct SmmDenseArgs {
 void smm_launch_dense(const SmmDenseArgs &a, bool log_semiring, hipStream_t stream);
 // posterior edge marginals (x upstream gradient) from the beta a LogSemiring smm_launch_dense left in a.beta and a.v
 void smm_launch_dense_marginals(const SmmDenseArgs &a, double *rmsg, const double *grad_v, float *out, hipStream_t stream);
+
+// posterior sampling (smm_sample.hip): after smm_launch_logz on the same workspace (forward histories)
+struct SmmSampleArgs {
+    const SmmVideo *videos;
+    const int32_t *n_states;
+    const double *hist;        // per video: F_cum, F_h, F_g, ... each [T+1][c_max] (smm_logz_bwd.hip)
+    const double *elp;         // [total_frames][c_max]
+    const double *trans;       // [g][c_max][c_max]  [to][from]
+    const double *init;        // [g][c_max]
+    const double *len;         // [g][k_rows][c_max]
+    const double *endpen;      // [b][c_max] or null (EOS mode only)
+    const int64_t *class_map;  // [g][c_max+1] or null
+    const double *logz;        // [b]
+    int64_t *spans;            // [n_samples][b][t_max+1] or null
+    int64_t *labels;           // [n_samples][total_frames] or null
+    double *logp;              // [n_samples][b] or null
+    int32_t *err;              // sticky error word (a decision without a finite candidate)
+    int64_t total_frames;
+    uint64_t seed;
+    int32_t c_max, k_rows, t_max, b, n_samples, no_eos;
+};
+void smm_launch_sample(const SmmSampleArgs &a, hipStream_t stream);

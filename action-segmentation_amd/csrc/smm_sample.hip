@@ -1,0 +1,253 @@
+// smm_sample.hip -- segmentations drawn from the semi-Markov posterior p(y | x) (forward filtering, backward sampling).
+//
+// Inputs are the forward histories smm_logz_kernel leaves in the workspace (smm_logz_bwd.hip has the layout):
+//   F_cum[n][c] = cumE,   F_h[s][c] = start[s][c] - cumE[s][c]  (start: log-weight of "a span of c starts at s", init at 0),
+//   F_g[n][c]   = gamma   (log-weight of "a span of c ends at n").
+// One walk per (video, sample), from the end (oracle/smm_oracle.c: smm_oracle_logz has the plain statement of the weights):
+//   last label   EOS:    j ~ exp(gamma[T][j] + wend[j]),  wend[j] = LSE(endpen[j], LSE_to(trans[to][j]) - 1e9)
+//                no EOS: to ~ exp(LSE_c(gamma[T][c] + trans[to][c]) + elp[T][to]), then its predecessor as below
+//   span start   a span of j that ends at n starts at n - k,  k ~ exp(F_h[n-k][j] + len[k][j]),  k = 1 .. min(kp-1, n)
+//                (cumE[n][j] is the same for every k)
+//   predecessor  a span of j that starts at s > 0 follows a span of j',  j' ~ exp(gamma[s][j'] + trans[j][j'])
+// The distribution sampled is the one whose normaliser smm_logz_f64 returns.  The histories carry the log Z kernel's fp32-internal
+// rounding (~1e-6 relative): they decide the draws, never the log-probability, which is summed in fp64 from the tables and elp
+// (init, emissions of every span, len, trans, the closing term) minus log Z.
+//
+// Work split: one wave per (video, sample), grid-stride over the pairs.  A decision has at most 1023 candidates: lane l takes
+// candidates l, l + 64, ...  (<= 16 per lane), wave max, fp64 exp(w - max), a wave inclusive prefix sum (DPP within rows of 16,
+// row offsets by readlane), then the first candidate whose prefix exceeds u * total (inverse CDF).  Nothing goes through LDS.
+//
+// Random numbers: Philox4x32-10 keyed by the seed; counter = (decision number, sample, video, 0).  A sample's draws depend on
+// (seed, video, sample) only: not on the grid, on n_samples or on the order the waves run in.  u takes 53 random bits.
+#include "smm_device.h"
+#include "smm_launch.h"
+#include "../../include/smmdp.h"
+
+#define SMM_SAMPLE_NI 16           // candidates per lane: 16 x 64 >= SMM_MAX_K_ROWS - 1
+
+struct SmmPhilox { uint32_t v[4]; };
+
+__device__ __forceinline__ SmmPhilox smm_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1)
+{
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t lo0 = 0xD2511F53u * c0, hi0 = __umulhi(0xD2511F53u, c0);
+        const uint32_t lo1 = 0xCD9E8D57u * c2, hi1 = __umulhi(0xCD9E8D57u, c2);
+        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
+        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    SmmPhilox r;
+    r.v[0] = c0; r.v[1] = c1; r.v[2] = c2; r.v[3] = c3;
+    return r;
+}
+
+// uniform in [0, 1) with 53 random bits, for decision `dec` of the stream (seed, video, sample)
+__device__ __forceinline__ double smm_uniform53(uint64_t seed, int vid, int smp, uint32_t dec)
+{
+    const SmmPhilox r = smm_philox4x32_10(dec, (uint32_t)smp, (uint32_t)vid, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const uint64_t bits = ((uint64_t)(r.v[0] >> 5) << 26) | (uint64_t)(r.v[1] >> 6);
+    return (double)bits * 0x1.0p-53;
+}
+
+__device__ __forceinline__ double smm_lse2_exact(double a, double b)
+{
+    const double m = fmax(a, b);
+    if (m == SMM_NEG_INF) return m;
+    return m + log(exp(a - m) + exp(b - m));
+}
+
+__device__ __forceinline__ double smm_wave_max(double x)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) x = fmax(x, __shfl_xor(x, off));
+    return x;
+}
+
+__device__ __forceinline__ double smm_wave_sum(double x)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
+    return x;
+}
+
+// lane i <- lane i - n of its row of 16, 0 where that lies outside the row
+template <int N>
+__device__ __forceinline__ double smm_row_shr0(double x)
+{
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), SMM_DPP_ROW_SHR(N), 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), SMM_DPP_ROW_SHR(N), 0xf, 0xf, false);
+    return smm_pack(lo, hi);
+}
+
+// inclusive prefix sum over the wave: within each row of 16 by DPP shifts, then the totals of the rows in front by readlane
+__device__ __forceinline__ double smm_wave_incl_sum(double x, int lane)
+{
+    x += smm_row_shr0<1>(x);
+    x += smm_row_shr0<2>(x);
+    x += smm_row_shr0<4>(x);
+    x += smm_row_shr0<8>(x);
+    const double r0 = smm_readlane(x, 15), r1 = smm_readlane(x, 31), r2 = smm_readlane(x, 47);
+    const int row = lane >> 4;
+    const double r01 = r0 + r1;
+    const double off = (row == 0) ? 0.0 : (row == 1) ? r0 : (row == 2) ? r01 : r01 + r2;
+    return x + off;
+}
+
+// One draw among the candidates w[i] of every lane (candidate number i * 64 + lane; -inf = none), probability
+// proportional to exp(w).  Returns the candidate number, or -1 when no candidate has a finite weight (or a NaN got in).
+template <int NI>
+__device__ __forceinline__ int smm_draw(const double (&w)[NI], double u, int lane)
+{
+    double m = w[0];
+#pragma unroll
+    for (int i = 1; i < NI; ++i) m = fmax(m, w[i]);
+    m = smm_wave_max(m);
+    if (!(m > SMM_NEG_INF) || m == -SMM_NEG_INF) return -1;
+    double e[NI], ls = 0.0;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        e[i] = exp(w[i] - m);                  // (w = -inf: 0)
+        ls += e[i];
+    }
+    const double incl = smm_wave_incl_sum(ls, lane);
+    const double tot = smm_readlane(incl, 63);
+    if (!(tot >= 1.0) || !(tot < 1e300)) return -1;      // (the maximal candidate alone gives 1; NaN fails both)
+    const double tgt = u * tot;
+    uint64_t mask = __ballot(incl > tgt);
+    if (mask == 0) {                                     // (rounding: u * total came out as total -- the last lane with mass)
+        const uint64_t nz = __ballot(ls > 0.0);
+        mask = nz ? (1ull << (63 - __builtin_clzll(nz))) : 0ull;
+    }
+    if (mask == 0) return -1;
+    const int L = __builtin_ctzll(mask);
+    // in every lane: the first of its own candidates whose running prefix exceeds the target (the last with mass otherwise)
+    double run = incl - ls;
+    int pick = -1, lastnz = -1;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        run += e[i];
+        if (e[i] > 0.0) lastnz = i;
+        if (pick < 0 && e[i] > 0.0 && run > tgt) pick = i;
+    }
+    if (pick < 0) pick = lastnz;
+    const int pi = __builtin_amdgcn_readlane(pick, L);
+    return pi < 0 ? -1 : pi * 64 + L;
+}
+
+__device__ __forceinline__ int64_t smm_gid(const int64_t *cmap, int c) { return cmap ? cmap[c] : (int64_t)c; }
+
+__device__ void smm_sample_one(const SmmSampleArgs &a, int vid, int smp, int lane)
+{
+    const SmmVideo mv = a.videos[vid];
+    const int Tf = mv.T, T = mv.T - a.no_eos, g = mv.group, cm = a.c_max;
+    const int C = a.n_states[g];
+    const size_t blk = (size_t)cm * (T + 1);
+    const double *F_h = a.hist + mv.hist_off + blk, *F_g = F_h + blk;
+    const double *trans = a.trans + (size_t)g * cm * cm;
+    const double *len = a.len + (size_t)g * a.k_rows * cm;
+    const double *elp = a.elp + (size_t)mv.frame_off * cm;
+    const int64_t *cmap = a.class_map ? a.class_map + (size_t)g * (cm + 1) : nullptr;
+    int64_t *sp = a.spans ? a.spans + ((size_t)smp * a.b + vid) * (size_t)(a.t_max + 1) : nullptr;
+    int64_t *lab = a.labels ? a.labels + (size_t)smp * a.total_frames + mv.frame_off : nullptr;
+    // every span position is written by lane (position & 63): the -1 filler and the labels that follow are one thread's stores
+    if (sp)
+        for (int q = lane; q <= a.t_max; q += 64) sp[q] = -1;
+    if (T <= 0 || C <= 0) {
+        if (lane == 0) atomicExch(a.err, 1);
+        return;
+    }
+    uint32_t dec = 0;
+    double lp = 0.0;               // (wave-uniform)
+    bool ok = true;
+    int j, n = T;
+    if (!a.no_eos) {
+        double w[1] = {SMM_NEG_INF}, wend = SMM_NEG_INF;
+        if (lane < C) {
+            double alt = SMM_NEG_INF;
+            for (int to = 0; to < C; ++to) alt = smm_lse2_exact(alt, trans[(size_t)to * cm + lane]);
+            wend = smm_lse2_exact(a.endpen ? a.endpen[(size_t)vid * cm + lane] : 0.0, alt + SMM_BIG_NEG);
+            w[0] = F_g[(size_t)T * cm + lane] + wend;
+        }
+        j = smm_draw<1>(w, smm_uniform53(a.seed, vid, smp, dec++), lane);
+        if (j < 0) ok = false;
+        else {
+            lp += smm_readlane(wend, j);
+            if (sp && lane == (Tf & 63)) sp[Tf] = smm_gid(cmap, C);
+        }
+    } else {
+        // the closing label of frame T (it only emits), then the label of the span that ends at T
+        double w[1] = {SMM_NEG_INF};
+        if (lane < C) {
+            double f = SMM_NEG_INF;
+            for (int c = 0; c < C; ++c) f = smm_lse2_exact(f, F_g[(size_t)T * cm + c] + trans[(size_t)lane * cm + c]);
+            w[0] = f + elp[(size_t)T * cm + lane];
+        }
+        const int to = smm_draw<1>(w, smm_uniform53(a.seed, vid, smp, dec++), lane);
+        j = -1;
+        if (to < 0) ok = false;
+        else {
+            lp += elp[(size_t)T * cm + to];
+            const int64_t gid = smm_gid(cmap, to);
+            if (sp && lane == (T & 63)) sp[T] = gid;
+            if (lab && lane == 0) lab[T] = gid;
+            double w1[1] = {lane < C ? F_g[(size_t)T * cm + lane] + trans[(size_t)to * cm + lane] : SMM_NEG_INF};
+            j = smm_draw<1>(w1, smm_uniform53(a.seed, vid, smp, dec++), lane);
+            if (j < 0) ok = false;
+            else lp += trans[(size_t)to * cm + j];
+        }
+    }
+    while (ok && n > 0) {
+        // start of the span of j that ends at n
+        const int kmax = (mv.kp - 1 < n) ? mv.kp - 1 : n;
+        double w[SMM_SAMPLE_NI];
+#pragma unroll
+        for (int i = 0; i < SMM_SAMPLE_NI; ++i) {
+            const int k = 1 + i * 64 + lane;
+            w[i] = (k <= kmax) ? F_h[(size_t)(n - k) * cm + j] + len[(size_t)k * cm + j] : SMM_NEG_INF;
+        }
+        const int kc = smm_draw<SMM_SAMPLE_NI>(w, smm_uniform53(a.seed, vid, smp, dec++), lane);
+        if (kc < 0 || kc + 1 > kmax) { ok = false; break; }
+        const int k = kc + 1, s = n - k;
+        const int64_t gid = smm_gid(cmap, j);
+        double es = 0.0;
+        for (int f = s + lane; f < n; f += 64) {
+            es += elp[(size_t)f * cm + j];
+            if (lab) lab[f] = gid;
+        }
+        lp += len[(size_t)k * cm + j] + smm_wave_sum(es);
+        if (sp && lane == (s & 63)) sp[s] = gid;
+        if (s == 0) {
+            lp += a.init[(size_t)g * cm + j];
+            break;
+        }
+        // the span in front of it
+        double w1[1] = {lane < C ? F_g[(size_t)s * cm + lane] + trans[(size_t)j * cm + lane] : SMM_NEG_INF};
+        const int jp = smm_draw<1>(w1, smm_uniform53(a.seed, vid, smp, dec++), lane);
+        if (jp < 0 || jp >= C) { ok = false; break; }
+        lp += trans[(size_t)j * cm + jp];
+        j = jp;
+        n = s;
+    }
+    if (!ok && lane == 0) atomicExch(a.err, 1);
+    if (a.logp && lane == 0) a.logp[(size_t)smp * a.b + vid] = ok ? lp - a.logz[vid] : __builtin_nan("");
+}
+
+__global__ void __launch_bounds__(256) smm_sample_kernel(SmmSampleArgs a)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t n_pairs = (int64_t)a.b * a.n_samples;
+    const int64_t stride = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t p = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); p < n_pairs; p += stride) {
+        const int vid = __builtin_amdgcn_readfirstlane((int)(p / a.n_samples));
+        const int smp = __builtin_amdgcn_readfirstlane((int)(p % a.n_samples));
+        smm_sample_one(a, vid, smp, lane);
+    }
+}
+
+void smm_launch_sample(const SmmSampleArgs &a, hipStream_t stream)
+{
+    const int64_t waves = (int64_t)a.b * a.n_samples;
+    const int64_t blocks = (waves + 3) / 4;
+    hipLaunchKernelGGL(smm_sample_kernel, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, stream, a);
+}

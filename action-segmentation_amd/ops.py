@@ -450,6 +450,36 @@ def logz_bwd(batch, elp, trans, init, len_scores, logz_val, grad_logz=None, endp
     return g
 
 
+def sample(batch, elp, trans, init, len_scores, logz_val, n_samples, seed=0, endpen=None, class_map=None, ws=None,
+           want_spans=True, want_labels=False, with_backward=False):
+    """Segmentations drawn from the posterior p(y | x) (smm_sample_f64).  Must follow ``logz`` for the same batch and tables
+    with the same workspace (``with_backward``: as passed to ``logz``); ``logz_val`` = its output.  Returns dict(spans int64
+    [n_samples, b, t_max+1] (span encoding, class map applied) or None, labels int64 [n_samples, total_frames] (global ids, -1
+    on frames no video covers) or None, logp fp64 [n_samples, b]: exact log p(sample | x)).  Sample j depends on
+    (seed, video, j) only."""
+    lib = _lib.load()
+    n_samples = int(n_samples)
+    if n_samples <= 0:
+        raise ValueError("n_samples must be positive, got %d" % n_samples)
+    shape = _shape_with(batch, _lib.SHAPE_LOGZ_BOTH if with_backward else 0)
+    dev = elp.device
+    f64 = torch.float64
+    spans = torch.empty((n_samples, batch.b, batch.t_max + 1), dtype=torch.int64, device=dev) if want_spans else None
+    labels = torch.full((n_samples, batch.total_frames), -1, dtype=torch.int64, device=dev) if want_labels else None
+    logp = torch.empty((n_samples, batch.b), dtype=f64, device=dev)
+    if ws is None:
+        ws = workspace(batch.workspace_bytes(), dev)
+    ln, fo, gr, kp, ns = batch.host_ptrs()
+    _lib.check(lib.smm_sample_f64(
+        ctypes.byref(shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(kp),
+        ctypes.c_void_p(ns), _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'),
+        _dev(len_scores, f64, 'len_scores'), _dev(endpen, f64, 'endpen'), _dev(class_map, torch.int64, 'class_map'),
+        _dev(logz_val, f64, 'logz'), ctypes.c_int32(n_samples), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+        _dev(spans, torch.int64, 'spans'), _dev(labels, torch.int64, 'labels'), _dev(logp, f64, 'logp'),
+        ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream()))
+    return dict(spans=spans, labels=labels, logp=logp, _err=_err_copy(batch, ws))
+
+
 _pinned = {}
 
 

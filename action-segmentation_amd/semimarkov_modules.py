@@ -656,6 +656,97 @@ class SemiMarkovModule(nn.Module):
         out['_keep'] = (tab, g1, endpen, x, cons)
         return out
 
+    # ------------------------------------------------------------------ posterior samples and marginals (smm_sample_f64)
+    def _posterior_launch(self, features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
+                          constraints, what):
+        """emission + log Z of a zero-padded single-task batch on a private workspace, for the launches that read the forward
+        (and backward) histories afterwards.  -> dict(batch, elp, tables as one group, endpen, logz, ws)."""
+        self._require_device(features, what)
+        valid_classes = self._check_valid_classes(valid_classes_per_instance)
+        b, tmax, d = features.shape
+        dev = features.device
+        lengths_host = lengths.detach().cpu().numpy().astype(np.int64)
+        assert int(lengths_host.max()) == tmax, "one instance must span the padded length (padding_colate)"
+        no_eos = not add_eos
+        self._check_no_eos_lengths(lengths_host, no_eos)
+        tab = self._decode_tables(valid_classes, dev)
+        c = tab['init'].numel()
+        batch = ops.Batch(lengths_host, [c], tab['len'].size(0), c_max=c, t_max=tmax, total_frames=b * tmax, d=d,
+                          no_eos=no_eos, no_time_split=self._hard_masks())
+        x = features.detach().to(torch.float32).contiguous().view(b * tmax, d)
+        cons = None
+        if constraints is not None:
+            cons = constraints.detach().to(device=dev, dtype=torch.float32).contiguous().view(b * tmax, c)
+        endpen = None if no_eos else self._endpen(valid_classes, additional_allowed_ends_per_instance, b, c, dev)
+        g1 = tab.get('_one_group')
+        if g1 is None:
+            g1 = tab['_one_group'] = tuple(tab[k].unsqueeze(0).contiguous() for k in ('w', 'cst', 'trans', 'init', 'len')) \
+                + (tab['class_map'].view(1, -1),)
+        ws = torch.empty(batch.workspace_bytes(), dtype=torch.uint8, device=dev)
+        elp, _ = ops.emission(batch, x, g1[0], g1[1], tab['inv_var'], cons=cons)
+        z = ops.logz(batch, elp, g1[2], g1[3], g1[4], endpen=endpen, ws=ws)
+        return dict(batch=batch, elp=elp, trans=g1[2], init=g1[3], len=g1[4], class_map=g1[5], endpen=endpen, logz=z, ws=ws)
+
+    @torch.no_grad()
+    def sample(self, features, lengths, valid_classes_per_instance, n_samples=1, seed=0, add_eos=True,
+               additional_allowed_ends_per_instance=None, constraints=None):
+        """Segmentations drawn from the posterior p(y | x) of a zero-padded single-task batch (argument conventions of
+        ``viterbi``): one emission launch, one log Z launch, one sampling launch.  Sample j depends on (seed, video, j) only.
+
+        Returns (spans, log_prob): spans CPU int64 n_samples x b x (Tmax+1) in ``viterbi``'s pred_spans format (n_samples x b x
+        Tmax with add_eos=False, as ``viterbi`` then returns), log_prob fp64 n_samples x b on the device: the exact
+        log p(spans | x) of each sample.  No autograd."""
+        r = self._posterior_launch(features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
+                                   constraints, 'sample')
+        out = ops.sample(r['batch'], r['elp'], r['trans'], r['init'], r['len'], r['logz'], n_samples, seed, endpen=r['endpen'],
+                         class_map=r['class_map'], ws=r['ws'], want_spans=True, want_labels=False)
+        spans = out['spans'].cpu()
+        ops.check_decoded(r['batch'], out)
+        if not add_eos:
+            spans = spans[:, :, :features.size(1)].contiguous()
+        return spans, out['logp']
+
+    @torch.no_grad()
+    def frame_posteriors(self, features, lengths, valid_classes_per_instance, add_eos=True,
+                         additional_allowed_ends_per_instance=None, constraints=None):
+        """Posterior class occupancy of every frame, P(frame t has label c | x): fp64 b x Tmax x C on the device, columns in
+        the order of the batch's valid classes (0 on padded frames).  The d log Z / d elp of smm_logz_bwd_f64 -- what the
+        label frequencies of ``sample`` converge to."""
+        r = self._posterior_launch(features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
+                                   constraints, 'frame_posteriors')
+        g = ops.logz_bwd(r['batch'], r['elp'], r['trans'], r['init'], r['len'], r['logz'], endpen=r['endpen'], ws=r['ws'])
+        b, tmax = features.shape[:2]
+        return g['elp'].view(b, tmax, -1)
+
+    def _packed_posterior_launch(self, pc, what):
+        x = pc.x
+        self._require_device(x, what)
+        self.prepare_packed(pc)
+        t = pc.tables
+        ws = torch.empty(pc.batch.workspace_bytes(), dtype=torch.uint8, device=x.device)
+        elp, _ = ops.emission(pc.batch, x, t['w'], t['cst'], t['inv_var'], cons=pc.cons)
+        z = ops.logz(pc.batch, elp, t['trans'], t['init'], t['len'], endpen=pc.endpen, ws=ws)
+        return t, elp, z, ws
+
+    @torch.no_grad()
+    def sample_packed(self, pc, n_samples, seed=0):
+        """``sample`` for a whole PackedCorpus: one emission launch, one smm_logz_f64 and one sampling launch.
+        Returns (labels, log_prob): device int64 n_samples x total_frames (global class ids on the packed frame axis) and fp64
+        n_samples x n_videos in the order of ``pc.video_names``."""
+        t, elp, z, ws = self._packed_posterior_launch(pc, 'sample_packed')
+        out = ops.sample(pc.batch, elp, t['trans'], t['init'], t['len'], z, n_samples, seed, endpen=pc.endpen,
+                         class_map=t['class_map'], ws=ws, want_spans=False, want_labels=True)
+        ops.check_decoded(pc.batch, out)
+        return out['labels'], out['logp']
+
+    @torch.no_grad()
+    def frame_posteriors_packed(self, pc):
+        """``frame_posteriors`` for a whole PackedCorpus: fp64 total_frames x c_max on the device; column c of a frame is local
+        state c of its video's group (``pc.tables['class_map']`` maps it to a global id)."""
+        t, elp, z, ws = self._packed_posterior_launch(pc, 'frame_posteriors_packed')
+        g = ops.logz_bwd(pc.batch, elp, t['trans'], t['init'], t['len'], z, endpen=pc.endpen, ws=ws)
+        return g['elp']
+
     # ------------------------------------------------------------------ packed multi-task decode
     def stacked_tables(self, pc, differentiable=False):
         """fp64 factor tables of every group of a PackedCorpus stacked to [groups, ...] and zero-padded to c_max columns.

@@ -13,6 +13,7 @@
  *   smm_decode_f32          <- SemiMarkovModule.viterbi end to end (modules:660-696)
  *   smm_logz_f64 / _bwd     <- SemiMarkovCRF(...).partition (modules:657) and its autograd backward
  *                              (reference src/models/semimarkov/semimarkov.py:286)
+ *   smm_sample_f64          <- pytorch-struct's SemiMarkovCRF(...).sample (posterior samples; the reference never calls it)
  *
  * The reference has no FFI: its boundary is the Python call SemiMarkovCRF(scores, lengths) on a dense
  * b x N x K x C x C tensor.  These entry points take the FACTORS of that tensor instead,
@@ -101,7 +102,7 @@ int smm_device_count(void);
 
 /* Bytes of device workspace any entry point below needs for this shape (lengths: host array [b]).
  * Returns 0 on invalid arguments.  The workspace is scratch: its contents are undefined after a call,
- * except between smm_logz_f64 and smm_logz_bwd_f64. */
+ * except between smm_logz_f64 and smm_logz_bwd_f64 / smm_sample_f64. */
 size_t smm_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host);
 
 /* Byte offset, inside the workspace, of the int32 error word the kernels set.  1: a NaN / inf-inf reached the DP of
@@ -257,6 +258,26 @@ int smm_logz_bwd_f64(const smm_shape *shape, const int64_t *lengths_host, const 
                      const double *endpen, const double *logz, const double *grad_logz,
                      double *g_elp, double *g_trans, double *g_init, double *g_len,
                      void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Segmentations drawn from the posterior p(y | x) whose normaliser smm_logz_f64 returns (forward filtering, backward
+ * sampling on the forward histories; csrc/smm_sample.hip).  Must follow smm_logz_f64 on the same shape, tables and workspace
+ * (with or without SMM_SHAPE_LOGZ_BOTH); logz = that call's output.  One walk per (video, sample); the random numbers are
+ * Philox4x32-10 keyed by `seed`, one stream per (video, sample): sample j of a call does not depend on n_samples.
+ *   spans_out   dev int64 [n_samples][b][t_max + 1]  the Viterbi entry points' span encoding (class map applied)   (nullable)
+ *   labels_out  dev int64 [n_samples][total_frames]  per-frame global class ids; frames no video covers are not written
+ *                                                                                                                 (nullable)
+ *   logp_out    dev fp64 [n_samples][b]  exact log p(y | x) of each sample: its score summed in fp64 from the tables
+ *               and elp, minus logz                                                                               (nullable)
+ * SMM_ERR_ARG when n_samples <= 0 or every output is NULL.  The error word is set (and that sample's logp is NaN) when a
+ * decision has no candidate of finite weight (NaN inputs, or log Z = -inf).
+ */
+int smm_sample_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                   const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                   const double *elp, const double *trans, const double *init, const double *len_scores,
+                   const double *endpen, const int64_t *class_map, const double *logz, int32_t n_samples, uint64_t seed,
+                   int64_t *spans_out, int64_t *labels_out, double *logp_out,
+                   void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Factor tables of every parameter group from the model parameters (training steps), and their chain rule.
