@@ -11,7 +11,8 @@
 #define SMM_BAND_LO 16
 #define SMM_BAND_N 8          // delayed bands
 #define SMM_BAND_ROW 1026      // doubles per state of the shifted state-major length table (row[k + 1] = len[k], k <= 1024)
-#define SMM_L0_ROW 130         // doubles per state of band 0's length table in LDS (ring distances 0..128 + padding)
+#define SMM_L0_PAIRS 64        // band 0's length table in LDS: (len[kr], len[kr + 1]) pairs per state and parity of kr
+#define SMM_GH_STRIDE (SMM_MAX_STATES_DEV + 1)   // (gamma, h) pairs per position row of the Viterbi kernel's LDS staging rows
 #define SMM_BAND_TAB 80       // doubles per (group, state) in SmmDpArgs::band_tab: [0] min len over 33..174, [m] max len over band m,
                               // [16 + delta] min len over 16 delta + 1 .. 16 delta + 142 for delta = 2 .. SMM_BAND_WIT (the lengths that
                               // connect the sources of group g - delta with the targets the band-groups of group g reach)

@@ -193,7 +193,7 @@ __device__ __forceinline__ void smm_ring_block(double (&A)[R], double (&L)[R], d
     constexpr int RING = 64 * R;
     double hv[B];
 #pragma unroll
-    for (int i = 0; i < B; ++i) hv[i] = h_blk[i * 2 * SMM_MAX_STATES_DEV];      // (h_blk: the h half of sh_gh's (gamma, h) pairs)
+    for (int i = 0; i < B; ++i) hv[i] = h_blk[i * 2 * SMM_GH_STRIDE];           // (h_blk: the h half of sh_gh's (gamma, h) pairs)
     if constexpr (D == 1) {
         smm_push<R>(A, L, hd, (jj * B) % R);
 #pragma unroll
@@ -430,18 +430,24 @@ smm_viterbi_kernel(SmmDpArgs a)
     // positions are made of: round 4 measured ~40 cycles of the wave's time per ds_write_b64 on a CU whose other seven waves
     // use the LDS too); h -> pushers and HBM, gamma -> HBM.  cumE never goes through LDS: the mover wave adds up the elp
     // rows it staged itself -- the same additions in the same order, hence the same bits.
-    __shared__ __attribute__((aligned(16))) double sh_gh[2][B][SMM_MAX_STATES_DEV][2];
+    // Rows are SMM_GH_STRIDE = 33 pairs apart, not 32: a BAND pusher gathers one element per lane from 8 rows of a state
+    // (see NHR in the pusher waves), and rows 512 B apart all start in the same LDS bank (an 8-way conflict on every such
+    // read, right behind the barrier where the chain wave reads its own rows); 528 B apart they fall 4 banks apart.
+    __shared__ __attribute__((aligned(16))) double sh_gh[2][B][SMM_GH_STRIDE][2];
     __shared__ __attribute__((aligned(16))) double sh_e[2][B][SMM_MAX_STATES_DEV];       // elp[n-1][c] HBM -> chain
     __shared__ double sh_hm[BAND ? SN : 1][BAND ? 64 : 1];   // band mode: max h per group of 16 sources, ring of 64 groups
-    // band mode: band 0's length ring as a TABLE (see DOM in the pusher waves): sh_l0[c][kr] = len[kr][c] for the ring
-    // distances kr band 0 owns, -inf elsewhere (entry 128 = entry 0: the pair of a lane whose first slot is at distance 127),
-    // and per state how far h must RISE from one source to the next for the older one to be beaten at every target
-    __shared__ __attribute__((aligned(16))) double sh_l0[BAND ? SN : 1][BAND ? SMM_L0_ROW : 1];
+    // band mode: band 0's length ring as a TABLE (see DOM in the pusher waves) of the PAIRS a lane reads:
+    // sh_l0[c][kr & 1][kr >> 1] = (l[kr], l[kr + 1]) with l[kr] = len[kr][c] for the ring distances kr band 0 owns, -inf
+    // elsewhere (l[128] = l[0]: the pair of a lane whose first slot is at distance 127).  Two tables, even and odd kr, so that
+    // every pair is one aligned 16-byte read: a ds_read_b128 over 16 consecutive pairs is conflict-free, where the two
+    // 8-byte halves of a pair at odd kr (every block's last-source push) were two ds_read_b64 at a 16-byte stride, 2-way each.
+    // sh_xd: per state how far h must RISE from one source to the next for the older one to be beaten at every target
+    __shared__ double2 sh_l0[BAND ? SN : 1][BAND ? 2 : 1][BAND ? SMM_L0_PAIRS : 1];
     __shared__ double sh_xd[BAND ? SN : 1];
     __shared__ double sh_dlow[(BAND && SMM_ANCHOR) ? SN : 1][(BAND && SMM_ANCHOR) ? 64 : 1];   // ANCHOR (pusher waves): min of D_c over buckets of 16 distances
     __shared__ __attribute__((aligned(16))) double sh_gam[SMM_MAX_STATES_DEV];           // gamma[n][.] chain-private broadcast
     __shared__ double sh_gfin[SMM_MAX_STATES_DEV];                                        // gamma[T][.] for the closing step
-    __shared__ __attribute__((aligned(16))) double sh_junk[2][B][SMM_MAX_STATES_DEV][2]; // where the chain wave's other lane groups store
+    __shared__ __attribute__((aligned(16))) double sh_junk[2][B][SMM_GH_STRIDE][2];      // where the chain wave's other lane groups store
     // speculative transition (see SPEC in the chain wave): the video's transition table and, per (leader cs, source c),
     // how far gamma[c] must lie below gamma[cs] for source c to lose against cs at EVERY target
     // (as small as the kernel's class sets allow)
@@ -483,9 +489,11 @@ smm_viterbi_kernel(SmmDpArgs a)
     if constexpr (BAND) {
         constexpr int KMIN0 = TRI ? B + D + 1 : 2 * B + D;                 // band 0's shortest length (the chain wave owns the rest)
         const int khi = (kp - 1 < 127) ? kp - 1 : 127;
-        for (int e = threadIdx.x; e < SN * SMM_L0_ROW; e += blockDim.x) {
-            const int c = e / SMM_L0_ROW, kr = e % SMM_L0_ROW;
-            sh_l0[c][kr] = (c < C && kr >= KMIN0 && kr <= khi) ? len[(size_t)kr * cm + c] : SMM_NEG_INF;
+        for (int e = threadIdx.x; e < SN * 2 * SMM_L0_PAIRS; e += blockDim.x) {
+            const int c = e / (2 * SMM_L0_PAIRS), par = (e / SMM_L0_PAIRS) & 1, kr = 2 * (e % SMM_L0_PAIRS) + par;
+            const bool on0 = c < C && kr >= KMIN0 && kr <= khi, on1 = c < C && kr + 1 >= KMIN0 && kr + 1 <= khi;   // (kr + 1 = 128: -inf)
+            sh_l0[c][par][kr >> 1] = make_double2(on0 ? len[(size_t)kr * cm + c] : SMM_NEG_INF,
+                                                  on1 ? len[(size_t)(kr + 1) * cm + c] : SMM_NEG_INF);
         }
         if constexpr (SMM_ANCHOR != 0) {
             const double *dl = a.dmin_t + (size_t)g * cm * 64;           // (smm_band_tables_kernel fills it in -DSMM_ANCHOR=1 builds only)
@@ -782,7 +790,7 @@ smm_viterbi_kernel(SmmDpArgs a)
                                     if (k <= kmax) acc = smm_fmax(acc, hg[i - k] + lk[k]);
                                 const double gm = cumv[i] + acc;
                                 viol = smm_fmax(viol, gm - gsv[i]);
-                                *reinterpret_cast<double2 *>(st_gh + ((jj & 1) * B + i) * 2 * SMM_MAX_STATES_DEV) = make_double2(gm, hg[i]);
+                                *reinterpret_cast<double2 *>(st_gh + ((jj & 1) * B + i) * 2 * SMM_GH_STRIDE) = make_double2(gm, hg[i]);
                             }
                             if (__ballot(viol > dlt) == 0) {
     #pragma unroll
@@ -923,7 +931,7 @@ smm_viterbi_kernel(SmmDpArgs a)
                                     if (i == B - 1) gm_last = gm;
                                 }
                                 hq[(jj * B + 1 + i) % M] = hcur;
-                                *reinterpret_cast<double2 *>(st_gh + ((jj & 1) * B + i) * 2 * SMM_MAX_STATES_DEV) = make_double2(gm, hcur);
+                                *reinterpret_cast<double2 *>(st_gh + ((jj & 1) * B + i) * 2 * SMM_GH_STRIDE) = make_double2(gm, hcur);
                             }
                         }
                     };
@@ -1013,7 +1021,7 @@ smm_viterbi_kernel(SmmDpArgs a)
 #pragma unroll
         for (int r = 0; r < NHR; ++r) {
             const int e = 16 * r + (lane & 15), ejs = e / B, ec = ejs * NPS + rank;
-            hoff[r] = ((e % B) * SMM_MAX_STATES_DEV + ((ejs < SPS && ec < C) ? ec : 0)) * 2 + 1;   // (the h half of the (gamma, h) pairs)
+            hoff[r] = ((e % B) * SMM_GH_STRIDE + ((ejs < SPS && ec < C) ? ec : 0)) * 2 + 1;   // (the h half of the (gamma, h) pairs)
             xdom[r] = sh_xd[BAND ? ((ejs < SPS && ec < C) ? ec : 0) : 0];
         }
         // ANCHOR (round 5): dominance by an OLDER source.  DOM leaves a source out when its SUCCESSOR beats it at every target;
@@ -1145,12 +1153,12 @@ smm_viterbi_kernel(SmmDpArgs a)
                 }
                 // the ring distance of this lane's first slot at the push of the block's LAST source (i = B - 1); source i: + B - 1 - i
                 const int kr_last = (2 * lane + 1 + D - j * B) & 127;
+                static_assert(!BAND || (B % 2 == 0 && D == 0), "kr_last is odd: the pairs of the last sources come from sh_l0's odd table");
                 // ... and the ring pairs of those pushes -- every state pushes its last source --, read with the rows
                 double2 lpl[SPS];
 #pragma unroll
                 for (int js = 0; js < SPS; ++js) {
-                    const double *l0row = &sh_l0[BAND ? ((js < nvw) ? js * NPS + rank : 0) : 0][0];
-                    lpl[js] = make_double2(l0row[kr_last], l0row[kr_last + 1]);
+                    lpl[js] = sh_l0[BAND ? ((js < nvw) ? js * NPS + rank : 0) : 0][1][kr_last >> 1];   // (kr_last is odd)
                 }
                 // DOM: which sources have to be pushed -- bit e = 8 js + i of keep[e / 16]: source i of the wave's js-th state is
                 // not known to be beaten by its successor (lane e: h of the successor from the lane above, one compare)
@@ -1196,7 +1204,7 @@ smm_viterbi_kernel(SmmDpArgs a)
                                 anc_s[js] = (j - 1) * B + 1 + il;
                                 anc_h[js] = smm_readlane(hvl[(B * js) / 16], (B * js) % 16 + il);
                             }
-                            const double *l0row = &sh_l0[BAND ? js * NPS + rank : 0][0];
+                            const double2 (*l0row)[SMM_L0_PAIRS] = sh_l0[BAND ? js * NPS + rank : 0];
                             if (__builtin_popcount(k7) < SMM_DOM_SPARSE) {
                                 // a few: ring pair from the table at the push's phase
                                 uint32_t rest = k7;
@@ -1205,7 +1213,7 @@ smm_viterbi_kernel(SmmDpArgs a)
                                     const int i = __builtin_ctz(rest);
                                     rest &= rest - 1;
                                     const int kr = (kr_last + B - 1 - i) & 127;
-                                    const double2 lp = make_double2(l0row[kr], l0row[kr + 1]);
+                                    const double2 lp = l0row[kr & 1][kr >> 1];
                                     const double hs = smm_readlane(hvl[(B * js) / 16], (B * js) % 16 + i);
                                     As[js][0] = smm_fmax(As[js][0], hs + lp.x);
                                     As[js][1] = smm_fmax(As[js][1], hs + lp.y);
@@ -1216,8 +1224,9 @@ smm_viterbi_kernel(SmmDpArgs a)
                                 // the last one pushed -- one that is beaten is still a candidate like any other
                                 double Lr[RS];
                                 const int kr0 = (kr_last + B - 1) & 127;
-                                Lr[0] = l0row[kr0];
-                                Lr[1] = l0row[kr0 + 1];
+                                const double2 lp = l0row[0][kr0 >> 1];              // (kr0 is even)
+                                Lr[0] = lp.x;
+                                Lr[1] = lp.y;
                                 npush += B - 1;
 #pragma unroll
                                 for (int i = 0; i < B - 1; ++i)
