@@ -12,22 +12,27 @@
 //             "h[a_j][c] = 0 for every state, nothing older" and from the SERIAL cumE[a_j][.] (smm_cum_anchor_kernel: the
 //             unsplit decode's additions in the unsplit decode's order), so its cumE rows are the unsplit decode's bits.
 //   certify   (smm_chunk_stitch_kernel, per cut) over the kp positions in front of r_j -- every source a target of the
-//             unit's own part can reach -- the unit's h and the previous unit's h must differ by ONE constant (to 2^-32
-//             of their magnitude), state by state and position by position; the previous unit is certified itself (unit 0
-//             is exact), so by induction every value of the unit's own part is the unsplit value + a constant +- noise,
-//             the noise being the rounding of <= 4 additions per position on values of that magnitude.
+//             unit's own part can reach -- the unit's h and the previous unit's h must differ by ONE constant to within
+//             tol = 2^-32 of their magnitude, state by state and position by position.  The gate says the cut is sound; it
+//             does not bound what the cut lets through: the spread omega_j = max - min of h(unit j) - h(unit j-1) over the
+//             window may be up to 2 tol, and the spreads ADD UP over the cuts.  So omega_j is measured, and by induction
+//             (unit 0 is exact; max-plus steps keep a spread, never widen it) every value of unit j's own part is the
+//             unsplit value + a constant + e, osc(e) <= W_j + noise, W_j = omega_1 + ... + omega_j, the noise being the
+//             rounding of <= 4 additions per position on values of that magnitude.
 //   decide    the back-trace walks the units' histories from T down, re-evaluating the forward pass's expressions as
-//             the unsplit kernel does, and asks MORE of every decision: the winner (state, then length) must beat every
-//             other candidate by tau = 2^-30 of the magnitude in play -- 250 x the noise bound.  Then the unsplit
-//             decode, whose values differ from these by a constant and less than tau / 2, decides the same, tie order
-//             included (there is no tie).  The path is the unsplit decode's path.
+//             the unsplit kernel does, and asks MORE of every decision made in unit j (the closing step: the last unit):
+//             the winner (state, then length) must beat every other candidate by tau + W_j, tau = 2^-30 of the magnitude in
+//             play -- 250 x the noise bound.  Then the unsplit decode, whose values differ from these by a constant and
+//             less than tau / 2 + W_j, decides the same, tie order included (there is no tie).  The path is the unsplit
+//             decode's path.  On lattices that forget their start W is at rounding level; a decision clear of tau but not
+//             of tau + W is repaired (reason 32).
 //   score     the best score is re-evaluated along that path in the unsplit decode's association (cumE rows are its
 //             bits; h along the path is add, add, add, sub per segment): the unsplit decode's number.
-//   ties      two lengths within tau at the end of a run of ONE class that is decoded as two spans -- the (k2, k1) / (k1, k2)
+//   ties      two lengths within tau + W at the end of a run of ONE class that is decoded as two spans -- the (k2, k1) / (k1, k2)
 //             orders of the same run, equal up to rounding -- are resolved, not repaired: both orders are verified, and the
 //             score pass, which has the exact h in front of the run, evaluates both rounded candidates and takes the
 //             one-piece decode's choice.
-//   repair    a cut that does not certify, any other decision inside tau (an exact tie on an integer lattice, a boundary
+//   repair    a cut that does not certify, any other decision inside tau + W (an exact tie on an integer lattice, a boundary
 //             that rounding decides), a NaN: the video's word in `redo` is set and the launch that follows decodes it again
 //             in one piece with the ordinary kernel (one workgroup per split video, all but the flagged ones return at
 //             once).  Correctness never rests on the split; only the time does.
@@ -213,7 +218,9 @@ smm_chunk_stitch_kernel(SmmDpArgs a, const SmmChunkVideo *cvs, int32_t *redo)
 
     __shared__ int sh_bad;
     __shared__ double sh_dref[SMM_CHUNK_MAX_UNITS];
-    __shared__ unsigned sh_kmin[2], sh_near[2], sh_nlo[2], sh_nhi[2];   // (two sets, used in turn: see decide)
+    __shared__ unsigned long long sh_up[SMM_CHUNK_MAX_UNITS], sh_dn[SMM_CHUNK_MAX_UNITS];   // a cut's spread: max and -min of (x1 - x0) - dref, as bits
+    __shared__ double sh_w[SMM_CHUNK_MAX_UNITS];                        // W_j: the spreads of the cuts 1..j, summed
+    __shared__ unsigned sh_kmin[2], sh_near[2], sh_nlo[2], sh_nhi[2], sh_near0[2];   // (two sets, used in turn: see decide)
     __shared__ int sh_tie_s2[SMM_STITCH_MAXSEG];
     __shared__ double sh_tie_c2[SMM_STITCH_MAXSEG];
     __shared__ int sh_guess[SMM_MAX_STATES_DEV + 1];
@@ -225,9 +232,14 @@ smm_chunk_stitch_kernel(SmmDpArgs a, const SmmChunkVideo *cvs, int32_t *redo)
     __shared__ double sh_ln[SMM_STITCH_MAXSEG], sh_tr[SMM_STITCH_MAXSEG];   // ... their length scores and the transitions behind them
     __shared__ double sh_h0;
 
-    if (threadIdx.x == 0) { sh_bad = 0; sh_kmin[0] = sh_kmin[1] = 0xffffffffu; sh_near[0] = sh_near[1] = 0; sh_nlo[0] = sh_nlo[1] = 0xffffffffu; sh_nhi[0] = sh_nhi[1] = 0; }
+    if (threadIdx.x == 0) {
+        sh_bad = 0; sh_kmin[0] = sh_kmin[1] = 0xffffffffu; sh_near[0] = sh_near[1] = 0; sh_nlo[0] = sh_nlo[1] = 0xffffffffu; sh_nhi[0] = sh_nhi[1] = 0;
+        sh_near0[0] = sh_near0[1] = 0;
+    }
     // (sh_bad: WHY the video goes to the repair launch -- 1 a cut does not certify, 2 the closing step, 4 two states within tau,
-    // 8 two lengths within tau / none attains the maximum, 16 NaN or too many segments; OR-ed into error block word 6)
+    // 8 two lengths within tau / none attains the maximum, 16 NaN or too many segments, 32 a decision clear of tau but not of
+    // tau + W, the spread the cuts in front of it let through (a state, more than two lengths, or a second length outside tau);
+    // OR-ed into error block word 6)
     if (spans)
         for (int i = threadIdx.x; i <= a.t_max; i += blockDim.x) spans[i] = -1;
     __syncthreads();
@@ -238,6 +250,7 @@ smm_chunk_stitch_kernel(SmmDpArgs a, const SmmChunkVideo *cvs, int32_t *redo)
         sh_ua[j] = units[j].pad >> 2;
         sh_ut[j] = units[j].T;
         sh_uoff[j] = units[j].hist_off;
+        sh_up[j] = 0; sh_dn[j] = 0; sh_w[j] = 0.0;
     }
     __syncthreads();
     auto u_a = [&](int j) { return sh_ua[j]; };
@@ -284,6 +297,7 @@ smm_chunk_stitch_kernel(SmmDpArgs a, const SmmChunkVideo *cvs, int32_t *redo)
             const double dref = sh_dref[j];
             const double cscale = fabs(c1[(size_t)(r - a1) * C]);     // the magnitude of the prefix sums there
             const int s = r - (kp - 1) + (int)threadIdx.x;
+            double up = 0.0, dn = 0.0;                            // this position's spread around dref (dref is one of the values: >= 0)
             if ((int)threadIdx.x < kp) {
                 for (int cb = 0; cb < C; cb += 8) {
                     double x1[8], x0[8];
@@ -299,10 +313,19 @@ smm_chunk_stitch_kernel(SmmDpArgs a, const SmmChunkVideo *cvs, int32_t *redo)
                         if (f1 != f0) { bad = 1; continue; }              // -inf on one side only (or a NaN)
                         if (!f1) { if (smm_nan_bits(x1[q]) || smm_nan_bits(x0[q]) || x1[q] != x0[q]) bad = 1; continue; }
                         const double tol = 0x1p-32 * (fabs(x1[q]) + fabs(x0[q]) + cscale + 1.0);
-                        if (!(fabs((x1[q] - x0[q]) - dref) <= tol)) bad = 1;
+                        const double dv = (x1[q] - x0[q]) - dref;
+                        if (!(fabs(dv) <= tol)) bad = 1;
+                        up = fmax(up, dv);
+                        dn = fmax(dn, 0.0 - dv);                  // (0.0 - dv, not -dv: +0.0 for dv = +0.0, never -0.0)
                     }
                 }
             }
+            // the cut's spread omega_j = max - min of (x1 - x0) over the window: one LDS max per wave and side (positive doubles
+            // order as their bits; a side that is not > 0 -- a zero of either sign -- is left at the +0.0 it was cleared to)
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) { up = fmax(up, __shfl_xor(up, off)); dn = fmax(dn, __shfl_xor(dn, off)); }
+            if (lane == 0 && up > 0.0) atomicMax(&sh_up[j], (unsigned long long)__double_as_longlong(up));
+            if (lane == 0 && dn > 0.0) atomicMax(&sh_dn[j], (unsigned long long)__double_as_longlong(dn));
             // the prefix sums of the two units are the same additions: the same bits
             for (int e = threadIdx.x; e < C; e += blockDim.x)
                 if (__double_as_longlong(c1[(size_t)(r - a1) * C + e]) != __double_as_longlong(c0[(size_t)(r - a0) * C + e])) bad = 1;
@@ -316,6 +339,12 @@ smm_chunk_stitch_kernel(SmmDpArgs a, const SmmChunkVideo *cvs, int32_t *redo)
     int n = T, to = 0, nseg = 0;
     int ju = nu - 1;                                              // the unit whose own part holds n
     if (!sh_bad) {
+        // W_j = omega_1 + ... + omega_j: unit j's values are the one-piece values + a constant + e, osc(e) <= W_j + rounding
+        double wsum = 0.0;
+        for (int j = 1; j < nu; ++j) {
+            wsum += __longlong_as_double((long long)sh_up[j]) + __longlong_as_double((long long)sh_dn[j]);
+            if (threadIdx.x == 0) sh_w[j] = wsum;
+        }
         const double *gT = u_gam(ju) + (size_t)(T - u_a(ju)) * C;
         double f = SMM_NEG_INF;
         if (lane <= C) {
@@ -335,8 +364,11 @@ smm_chunk_stitch_kernel(SmmDpArgs a, const SmmChunkVideo *cvs, int32_t *redo)
         }
         const double tau = 0x1p-30 * (fabs(m) + 1.0);
         const bool near = lane <= C && lane != mc && !(f < m - tau);
+        const bool near_w = lane <= C && lane != mc && !(f < m - (tau + wsum));
         // (a winner other than EOS -- every end penalised -- goes to the repair launch as well: the score below assumes EOS)
-        if ((__ballot(near) != 0 || !smm_finite_bits(m) || mc != C) && threadIdx.x == 0) sh_bad = 2;
+        const bool any_near = __ballot(near) != 0, any_near_w = __ballot(near_w) != 0;
+        if (threadIdx.x == 0 && (any_near || !smm_finite_bits(m) || mc != C)) sh_bad = 2;
+        else if (threadIdx.x == 0 && any_near_w) sh_bad = 32;
         to = mc;
     }
     __syncthreads();
@@ -411,10 +443,12 @@ smm_chunk_stitch_kernel(SmmDpArgs a, const SmmChunkVideo *cvs, int32_t *redo)
         for (int off = 16; off >= 1; off >>= 1) cmag = fmax(cmag, __shfl_xor(cmag, off));
         cmag = fmax(smm_readlane(cmag, 0), smm_readlane(cmag, 16));
         const double tau = 0x1p-30 * (fabs(best) + cmag + 1.0);
-        // ONE state within tau of the maximum
-        const unsigned long long nearm = __ballot(lane < C && !(gmv < best - tau));
+        const double tw = tau + sh_w[ju];                         // ... and the spread the cuts in front of unit ju let through
+        // ONE state within tau + W of the maximum
+        const unsigned long long nearm = __ballot(lane < C && !(gmv < best - tw));
         if (nan_row || __builtin_popcountll(nearm) != 1 || !smm_finite_bits(best)) {
-            if (threadIdx.x == 0) sh_bad = (nan_row || !smm_finite_bits(best)) ? 16 : 4;
+            const unsigned long long nearm0 = __ballot(lane < C && !(gmv < best - tau));
+            if (threadIdx.x == 0) sh_bad = (nan_row || !smm_finite_bits(best)) ? 16 : __builtin_popcountll(nearm0) == 1 ? 32 : 4;
             __syncthreads();
             return 0;
         }
@@ -427,15 +461,21 @@ smm_chunk_stitch_kernel(SmmDpArgs a, const SmmChunkVideo *cvs, int32_t *redo)
             const double lv = (c == fg) ? sp_l : len_of(c, kk);
             const double cand = (cn + (hv + lv)) + wf;
             if (cand == best) atomicMin(&sh_kmin[par], (unsigned)kk);
-            if (!(cand < best - tau)) { atomicAdd(&sh_near[par], 1u); atomicMin(&sh_nlo[par], (unsigned)kk); atomicMax(&sh_nhi[par], (unsigned)kk); }
+            if (!(cand < best - tw)) {
+                atomicAdd(&sh_near[par], 1u); atomicMin(&sh_nlo[par], (unsigned)kk); atomicMax(&sh_nhi[par], (unsigned)kk);
+                if (!(cand < best - tau)) atomicAdd(&sh_near0[par], 1u);
+            }
         }
         __syncthreads();
-        const unsigned kf = sh_kmin[par], nn = sh_near[par], nlo = sh_nlo[par], nhi = sh_nhi[par];
+        const unsigned kf = sh_kmin[par], nn = sh_near[par], nlo = sh_nlo[par], nhi = sh_nhi[par], nn0 = sh_near0[par];
         // the OTHER set: read for the last time in front of the barrier above (by the previous decision), written next by the next
         // decision's atomics, which every thread issues behind the barrier of the walk's loop (or the tie's look-aside)
-        if (threadIdx.x == 0) { sh_kmin[par ^ 1] = 0xffffffffu; sh_near[par ^ 1] = 0; sh_nlo[par ^ 1] = 0xffffffffu; sh_nhi[par ^ 1] = 0; }
+        if (threadIdx.x == 0) { sh_kmin[par ^ 1] = 0xffffffffu; sh_near[par ^ 1] = 0; sh_nlo[par ^ 1] = 0xffffffffu; sh_nhi[par ^ 1] = 0; sh_near0[par ^ 1] = 0; }
         d_c = c; d_cn = cn;
-        if (kf == 0xffffffffu || nn < 1 || nn > 2) { if (threadIdx.x == 0) sh_bad = 8; __syncthreads(); return 0; }
+        if (kf == 0xffffffffu || nn < 1 || nn > 2) { if (threadIdx.x == 0) sh_bad = (kf != 0xffffffffu && nn > 2 && nn0 <= 2) ? 32 : 8; __syncthreads(); return 0; }
+        // a second length inside tau + W but not inside tau is no rounding tie (the two orders of a one-class run tie to within
+        // rounding: both inside tau): the decision fails only because of W
+        if (nn == 2 && nn0 == 1) { if (threadIdx.x == 0) sh_bad = 32; __syncthreads(); return 0; }
         d_k1 = (int)nlo; d_k2 = (int)nhi;
         return (int)nn;
     };

@@ -561,7 +561,9 @@ def error_flag(batch, out=None, ws=None):
 def error_words(batch, out=None, ws=None):
     """[error word, 0, sources pushed into band 0, delayed band-blocks evaluated (words 2 and 3: diagnostics of the Viterbi
     kernel's BAND mode, smm_viterbi.hip: DOM and the band skip test), videos decoded as several units along the time axis, of
-    those the ones that were decoded again in one piece, why (a bit mask), one-class-run ties the stitch resolved (words 4..7:
+    those the ones that were decoded again in one piece, why (a bit mask: 1 a cut did not certify, 2 the closing step, 4 two
+    states within the margin, 8 two lengths within the margin, 16 NaN or too many segments, 32 a decision clear of the rounding
+    margin but not of the spread the cuts in front of it let through), one-class-run ties the stitch resolved (words 4..7:
     csrc/smm_chunk.hip)] of a decode (synchronises).
     (Words 1 and 2 counted gang time-outs in rounds 1-3.)"""
     if out is not None and out.get('_err') is not None:

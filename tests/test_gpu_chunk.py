@@ -152,3 +152,55 @@ def test_cfg1_one_long_video_is_split_by_default(monkeypatch):
     check_equivalent(cp, *res)
     err = res[0]['_err'].cpu().numpy()
     assert err[4] == 1 and err[5] == 0, err
+
+
+@pytest.mark.parametrize('shape', [(14000, 5, 130, 0), (60000, 5, 1024, 0), (14000, 5, 130, 1)])
+def test_offsets_that_accumulate_across_cuts_are_repaired(shape, monkeypatch):
+    """The mirror lattice (tests/chunk_lattice.py, checked on the host by test_chunk_certificate_host.py): two groups of states
+    that differ only by a per-class constant in their length tables.  Every cut lets through a spread of half the certificate's
+    tolerance, and over ~50 cuts these add up: the last unit sees group A ahead by more than two of the stitch's margins while
+    the one-piece decode ends in group B.  The stitch must count what the cuts let through and send the video to the repair
+    launch (reason 32); the outputs are the one-piece decode's.  Ring kernels (K = 130) and BAND mode (K = 1024); group A or
+    group B drifting (the spreads lie above or below the cuts' reference state, a group-A state)."""
+    import chunk_lattice as L
+    t, c, k, drifting = shape
+    units = L.unit_layout([t], 2 * c, k)[0]
+    p = L.mirror_problem(5, t, c, k, units, drifting=drifting)
+    out = decode_split_and_whole(p, monkeypatch, unit=1)
+    assert out['_err'][4] == 1 and out['_err'][5] == 1, out['_err']
+    assert out['_err'][6] & 32, out['_err']
+    other = (1 - drifting) * c
+    assert ((out['labels'][:t] >= other) & (out['labels'][:t] < other + c)).all()   # the other group, as the one-piece decode
+
+
+@pytest.mark.parametrize('m', [0.5, 1, 2, 4, 16])
+def test_near_ties_straddling_a_cut(m, monkeypatch):
+    """A converged lattice with ONE decision whose one-piece margin is m x tau: the segment that crosses a cut, starting inside
+    the certified window in front of it, against the same segment one frame longer (tests/chunk_lattice.py: near_tie_problem).
+    The outputs are the one-piece decode's whatever m; from m = 4 on the stitch decides it itself (the margin it adds for the
+    cuts is at rounding level on such a lattice) and nothing is repaired."""
+    import chunk_lattice as L
+    t, c, k = 6000, 5, 130
+    units = L.unit_layout([t], c, k)[0]
+    p, s, n, got = L.near_tie_problem(3, t, c, k, units, m)
+    assert got == pytest.approx(m, rel=1e-3)
+    out = decode_split_and_whole(p, monkeypatch, unit=1)
+    assert out['_err'][4] == 1, out['_err']
+    assert out['spans'][0, s] >= 0 and out['spans'][0, s - 1] == -1
+    if m >= 4:
+        assert out['_err'][5] == 0, out['_err']
+
+
+def test_a_one_class_run_decoded_as_three_spans_across_a_cut_is_repaired(monkeypatch):
+    """A run of one class that the length table cuts into THREE spans (tests/chunk_lattice.py: three_span_problem, checked on the
+    host), starting inside the certified window in front of a cut and crossing it.  The three orders of its spans tie to within
+    rounding and the stitch resolves only ties of two: the video goes to the repair launch, and the outputs are the one-piece
+    decode's and the twin's, the three spans included."""
+    import chunk_lattice as L
+    t, c, k = 6000, 5, 130
+    units = L.unit_layout([t], c, k)[0]
+    p, s0, e0 = L.three_span_problem(3, t, c, k, units)
+    out = decode_split_and_whole(p, monkeypatch, unit=1)
+    assert out['_err'][4] >= 1 and out['_err'][5] == 1, out['_err']
+    inside = np.nonzero(out['spans'][0, s0:e0] >= 0)[0]
+    assert len(inside) == 3 and inside[0] == 0
