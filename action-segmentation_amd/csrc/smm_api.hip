@@ -1432,6 +1432,44 @@ extern "C" int smm_sample_f64(const smm_shape *shape, const int64_t *lengths_hos
     return SMM_OK;
 }
 
+extern "C" int smm_entropy_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                               const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                               const double *elp, const double *trans, const double *init, const double *len_scores,
+                               const double *endpen, const double *logz, double *entropy_out, void *workspace,
+                               size_t workspace_bytes, void *stream)
+{
+    if (!entropy_out || !elp || !trans || !init || !len_scores || !logz) return SMM_ERR_ARG;
+    Staged st;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes,
+                   hs, &st);
+    if (rc != SMM_OK) return rc;
+    const size_t g = shape->n_groups, cm = shape->c_max;
+    const bool no_eos = (shape->flags & SMM_SHAPE_NO_EOS) != 0;
+    if (!(shape->flags & SMM_SHAPE_LOGZ_BOTH)) {   // the backward histories, as smm_logz_bwd_f64 makes them
+        double *trans_t = st.tabs;
+        double *logz_b = trans_t + g * cm * cm;
+        smm_launch_transpose(trans, trans_t, (int)g, (int)cm, hs);
+        SmmDpArgs a{};
+        a.videos = st.videos; a.order = st.order; a.n_states = st.n_states;
+        a.elp = elp; a.trans = trans_t; a.init = init; a.len = len_scores; a.endpen = endpen;
+        a.hist = st.hist; a.err = st.err;
+        a.c_max = shape->c_max; a.k_rows = shape->k_rows; a.t_max = shape->t_max; a.b = shape->b;
+        a.flags = 2;
+        if (no_eos) { a.flags |= 8; a.endpen = nullptr; }
+        rc = smm_launch_logz(a, logz_b, ring_regs(st.kp_max), st.c_need, hs);
+        if (rc != SMM_OK) return rc;
+    }
+    SmmEntropyArgs e{};
+    e.videos = st.videos; e.n_states = st.n_states; e.hist = st.hist;
+    e.elp = elp; e.trans = trans; e.len = len_scores; e.endpen = no_eos ? nullptr : endpen; e.logz = logz;
+    e.entropy = entropy_out; e.err = st.err;
+    e.c_max = shape->c_max; e.k_rows = shape->k_rows; e.b = shape->b; e.no_eos = no_eos ? 1 : 0;
+    smm_launch_entropy(e, shape->t_max, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ k best
 // Behind the plan's workspace (its `total`): the length table state-major, the H lists of the last `ring` positions (and their
 // heads apart, class-major), the back-pointers of G and H at every position, the closing lists, the back-trace's scratch.

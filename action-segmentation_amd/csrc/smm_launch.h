@@ -148,3 +148,19 @@ struct SmmKbestArgs {
     int32_t c_max, k_rows, t_max, b, n_groups, k, ring, no_eos;
 };
 void smm_launch_kbest(const SmmKbestArgs &a, hipStream_t stream);
+
+// exact posterior entropy (smm_entropy.hip): after smm_launch_logz forward AND time-reversed on the same workspace
+struct SmmEntropyArgs {
+    const SmmVideo *videos;
+    const int32_t *n_states;
+    const double *hist;        // per video: F_cum, F_h, F_g, B_cum, B_h, B_g, (scratch) hT0, hT1; each [T+1][c_max]
+    const double *elp;         // [total_frames][c_max]   (no_eos only: the closing label's emission)
+    const double *trans;       // [g][c_max][c_max]  [to][from]
+    const double *len;         // [g][k_rows][c_max]
+    const double *endpen;      // [b][c_max] or null (EOS mode only)
+    const double *logz;        // [b]
+    double *entropy;           // [b] nats
+    int32_t *err;              // sticky error word
+    int32_t c_max, k_rows, b, no_eos;
+};
+void smm_launch_entropy(const SmmEntropyArgs &a, int t_max, hipStream_t stream);

@@ -480,6 +480,29 @@ def sample(batch, elp, trans, init, len_scores, logz_val, n_samples, seed=0, end
     return dict(spans=spans, labels=labels, logp=logp, _err=_err_copy(batch, ws))
 
 
+
+def entropy(batch, elp, trans, init, len_scores, logz_val, endpen=None, ws=None, with_backward=False):
+    """Exact entropy H(y | x) of each video's segmentation posterior in nats (smm_entropy_f64): fp64 [b].  Must follow
+    ``logz`` for the same batch and tables with the same workspace (``with_backward``: as passed to ``logz``; without it the
+    call runs the time-reversed recursion itself); ``logz_val`` = its output.  A video whose log Z is not finite, or whose
+    histories a NaN reached, gets NaN and sets the error word (``error_flag(batch, ws=ws)``).  Bit-identical run to run.
+    No gradient: d H / d theta needs the posterior covariance of the potentials, which no kernel computes."""
+    lib = _lib.load()
+    shape = _shape_with(batch, _lib.SHAPE_LOGZ_BOTH if with_backward else 0)
+    dev = elp.device
+    f64 = torch.float64
+    out = torch.empty(batch.b, dtype=f64, device=dev)
+    if ws is None:
+        ws = workspace(batch.workspace_bytes(), dev)
+    ln, fo, gr, kp, ns = batch.host_ptrs()
+    _lib.check(lib.smm_entropy_f64(
+        ctypes.byref(shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(kp),
+        ctypes.c_void_p(ns), _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'),
+        _dev(len_scores, f64, 'len_scores'), _dev(endpen, f64, 'endpen'), _dev(logz_val, f64, 'logz'),
+        _dev(out, f64, 'entropy'), ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream()))
+    return out
+
+
 MAX_KBEST = 16
 
 

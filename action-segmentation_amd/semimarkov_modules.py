@@ -658,9 +658,10 @@ class SemiMarkovModule(nn.Module):
 
     # ------------------------------------------------------------------ posterior samples and marginals (smm_sample_f64)
     def _posterior_launch(self, features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
-                          constraints, what):
+                          constraints, what, with_backward=False):
         """emission + log Z of a zero-padded single-task batch on a private workspace, for the launches that read the forward
-        (and backward) histories afterwards.  -> dict(batch, elp, tables as one group, endpen, logz, ws)."""
+        (and backward) histories afterwards.  -> dict(batch, elp, tables as one group, endpen, logz, ws).
+        ``with_backward``: the log Z launch also runs the time-reversed recursion (SMM_SHAPE_LOGZ_BOTH)."""
         self._require_device(features, what)
         valid_classes = self._check_valid_classes(valid_classes_per_instance)
         b, tmax, d = features.shape
@@ -684,7 +685,7 @@ class SemiMarkovModule(nn.Module):
                 + (tab['class_map'].view(1, -1),)
         ws = torch.empty(batch.workspace_bytes(), dtype=torch.uint8, device=dev)
         elp, _ = ops.emission(batch, x, g1[0], g1[1], tab['inv_var'], cons=cons)
-        z = ops.logz(batch, elp, g1[2], g1[3], g1[4], endpen=endpen, ws=ws)
+        z = ops.logz(batch, elp, g1[2], g1[3], g1[4], endpen=endpen, ws=ws, with_backward=with_backward)
         return dict(batch=batch, elp=elp, trans=g1[2], init=g1[3], len=g1[4], class_map=g1[5], endpen=endpen, logz=z, ws=ws)
 
     @torch.no_grad()
@@ -718,6 +719,20 @@ class SemiMarkovModule(nn.Module):
         b, tmax = features.shape[:2]
         return g['elp'].view(b, tmax, -1)
 
+    @torch.no_grad()
+    def entropy(self, features, lengths, valid_classes_per_instance, add_eos=True, additional_allowed_ends_per_instance=None,
+                constraints=None):
+        """Exact entropy H(y | x) = -sum_y p(y | x) log p(y | x) of each video's segmentation posterior, in nats: fp64 b on the
+        device (argument conventions of ``viterbi``).  One emission launch, one log Z launch (forward and time-reversed), one
+        entropy launch (smm_entropy_f64); the value keeps its relative accuracy on confident videos (H -> 0).  Raises
+        SmmError when a NaN reached the DP.  No autograd: the gradient of H needs second-order terms (a follow-up)."""
+        r = self._posterior_launch(features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
+                                   constraints, 'entropy', with_backward=True)
+        h = ops.entropy(r['batch'], r['elp'], r['trans'], r['init'], r['len'], r['logz'], endpen=r['endpen'], ws=r['ws'],
+                        with_backward=True)
+        ops.check_decoded(r['batch'], dict(_err=ops._err_copy(r['batch'], r['ws'])))
+        return h
+
     def _packed_posterior_launch(self, pc, what):
         x = pc.x
         self._require_device(x, what)
@@ -746,6 +761,14 @@ class SemiMarkovModule(nn.Module):
         t, elp, z, ws = self._packed_posterior_launch(pc, 'frame_posteriors_packed')
         g = ops.logz_bwd(pc.batch, elp, t['trans'], t['init'], t['len'], z, endpen=pc.endpen, ws=ws)
         return g['elp']
+
+    @torch.no_grad()
+    def entropy_packed(self, pc):
+        """``entropy`` for a whole PackedCorpus: fp64 n_videos on the device, in the order of ``pc.video_names``."""
+        t, elp, z, ws = self._packed_posterior_launch(pc, 'entropy_packed')
+        h = ops.entropy(pc.batch, elp, t['trans'], t['init'], t['len'], z, endpen=pc.endpen, ws=ws)
+        ops.check_decoded(pc.batch, dict(_err=ops._err_copy(pc.batch, ws)))
+        return h
 
     # ------------------------------------------------------------------ the k best segmentations (smm_kbest_f64)
     @torch.no_grad()

@@ -14,6 +14,8 @@
  *   smm_logz_f64 / _bwd     <- SemiMarkovCRF(...).partition (modules:657) and its autograd backward
  *                              (reference src/models/semimarkov/semimarkov.py:286)
  *   smm_sample_f64          <- pytorch-struct's SemiMarkovCRF(...).sample (posterior samples; the reference never calls it)
+ *   smm_entropy_f64         <- pytorch-struct's SemiMarkovCRF(...).entropy (exact H(y | x) per video; the reference never
+ *                              calls it)
  *   smm_kbest_f64           <- pytorch-struct's SemiMarkovCRF(...).kmax / topk (the k best segmentations; the reference never
  *                              calls it)
  *
@@ -104,7 +106,7 @@ int smm_device_count(void);
 
 /* Bytes of device workspace any entry point below needs for this shape (lengths: host array [b]).
  * Returns 0 on invalid arguments.  The workspace is scratch: its contents are undefined after a call,
- * except between smm_logz_f64 and smm_logz_bwd_f64 / smm_sample_f64. */
+ * except between smm_logz_f64 and smm_logz_bwd_f64 / smm_sample_f64 / smm_entropy_f64. */
 size_t smm_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host);
 
 /* Byte offset, inside the workspace, of the int32 error word the kernels set.  1: a NaN / inf-inf reached the DP of
@@ -280,6 +282,24 @@ int smm_sample_f64(const smm_shape *shape, const int64_t *lengths_host, const in
                    const double *endpen, const int64_t *class_map, const double *logz, int32_t n_samples, uint64_t seed,
                    int64_t *spans_out, int64_t *labels_out, double *logp_out,
                    void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Exact entropy H(y | x) = -sum_y p(y | x) log p(y | x) of each video's segmentation posterior, in nats (csrc/smm_entropy.hip:
+ * the chain rule over the decisions of smm_sample_f64's backward walk, every term >= 0, so the value keeps its relative
+ * accuracy as H -> 0).  Must follow smm_logz_f64 on the same shape, tables and workspace; logz = that call's output.  Without
+ * SMM_SHAPE_LOGZ_BOTH the call runs the time-reversed recursion itself (as smm_logz_bwd_f64 does); with it, smm_logz_f64 has.
+ * The forward and backward histories are left as they were (smm_sample_f64 / smm_logz_bwd_f64 may follow); the per-video
+ * partial sums are reduced in a fixed order, so the result is bit-identical run to run.  No gradient.
+ *   entropy_out  dev fp64 [b]
+ * SMM_ERR_ARG when entropy_out or a required input (elp, trans, init, len_scores, logz) is NULL, before anything is staged.
+ * The error word is set (and that video's value is NaN) when log Z is not finite, a NaN reached the histories, or a node of
+ * non-zero probability has no candidate of finite weight.
+ */
+int smm_entropy_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                    const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                    const double *elp, const double *trans, const double *init, const double *len_scores,
+                    const double *endpen, const double *logz, double *entropy_out,
+                    void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * The k highest-scoring segmentations (k-best Viterbi: the DP in the k-max semiring; csrc/smm_kbest.hip).  The candidate set
