@@ -2,7 +2,7 @@
 """Benchmark of the semi-Markov decode path on MI355X (contract: see the task statement / DESIGN.md §Measurement).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg5|cfg3c|cfg2|cfg1|cfg4] [--scaling weak|strong]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one decode pass (emission scorer + Viterbi DP + back-trace + label expansion + labels on the host: the
 DP kernel writes them into pinned host memory over PCIe while it decodes) over this rank's share of a synthetic corpus,
@@ -17,7 +17,7 @@ relays rank 0's line.  Either way the job fails (non-zero exit) unless the group
   * headline, at EVERY N (``scaling: weak``; the same ``config.workload`` string for N = 1, 2, 4, 8): every rank decodes
     its own cfg3-sized corpus (seed + rank); videos are independent, so there is no data-path collective; RCCL carries
     the MAX of the step time and the SUM of the frame counters;
-  * ``strong_scaling`` (second object in the same line, at every N including 1; --no-strong-leg skips it): ONE corpus
+  * ``strong_scaling`` (second object in the same line with --full, at every N including 1; --no-strong-leg skips it): ONE corpus
     (default cfg5 = the full CrossTask primary set, 2754 videos) sharded by video over the ranks
     (distributed.shard_batches), every rank decodes its share, and the reference's evaluation counters
     (Datasplit.accuracy_corpus, src/data/corpus.py:405-604, summed as src/main.py:486-532 does) are all-reduced over
@@ -29,9 +29,16 @@ relays rank 0's line.  Either way the job fails (non-zero exit) unless the group
 float32 / float64.  The inputs are a function of the arguments alone (seeded corpus, closed-form fit on the host), so two
 builds can be compared output for output.
 
-Rank 0 prints ONE JSON line.  ``roofline`` is for the dominant kernel (the DP kernel), timed live with HIP events
-on the stream it is launched on; ``cpu_baseline`` is the oracle's dense reference-path restatement on a bounded
-sample (N = 1 only).
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: it sets up the headline leg's corpus,
+warms up, times the K steps, writes --dump-outputs and prints the line.  ``roofline`` is for the dominant kernel (the DP
+kernel), timed live with HIP events on the stream it is launched on during those steps.
+
+``--full`` adds everything else the benchmark measures or checks, each outside the timed steps: the evaluation and
+fit statistics of the headline corpus (``mof``, ``evaluation``, ``fit_stats``), the strong-scaling leg when it is not
+the headline, and at N = 1 ``predict`` end to end, the host-features leg, the reference's default shapes, the cfg4
+training step, the second draw of cfg3 and the CPU baselines with their ``parity`` checks against the C twin
+(``cpu_baseline`` is the oracle's dense reference-path restatement on a bounded sample).  ``--no-strong-leg``,
+``--no-predict-e2e``, ``--no-cpu-baseline`` and ``--second-seed -1`` leave parts of it out.
 """
 import argparse
 import json
@@ -69,7 +76,8 @@ def parse(argv=None):
                         'BASELINE config 5, ONE corpus sharded by video over the ranks')
     p.add_argument('--strong-workload', default='cfg5', choices=['cfg3', 'cfg5', 'cfg4', 'tiny'],
                    help='corpus of the strong-scaling leg (one corpus, seed --seed, sharded by video over the ranks)')
-    p.add_argument('--strong-leg', action='store_true', help='(kept for old command lines: the strong-scaling leg runs at every N since round 5)')
+    p.add_argument('--strong-leg', action='store_true',
+                   help='(kept for old command lines: with --full the strong-scaling leg runs at every N since round 5)')
     p.add_argument('--no-strong-leg', action='store_true')
     p.add_argument('--no-predict-e2e', action='store_true', help='skip the SemiMarkovModel.predict wall-time figures')
     p.add_argument('--second-seed', type=int, default=1000,
@@ -81,6 +89,10 @@ def parse(argv=None):
                    help='rehearsal only: ranks may share a GPU (LOCAL_RANK %% device_count); needs --backend gloo')
     p.add_argument('--dump-outputs', metavar='DIR', default=None,
                    help="write the headline leg's decode outputs of the last timed step to DIR/<name>.npy (rank 0)")
+    p.add_argument('--full', action='store_true',
+                   help='also run every secondary leg (evaluation and fit statistics, the strong-scaling leg when it is '
+                        'not the headline, predict end to end, host features, reference default shapes, the cfg4 '
+                        'training step, the second draw, CPU baselines and parity); a plain run times the headline only')
     p.add_argument('--dry-run', action='store_true',
                    help='host-only rehearsal of the N-rank path: rendezvous, shard the corpus structure, reduce the '
                         'frame counters; nothing is decoded and no GPU is touched (implies --backend gloo)')
@@ -429,8 +441,52 @@ def video_keys(pc, data):
     return [pos[(t, n)] for t, n in zip(pc.task_names, pc.video_names)]
 
 
+def weak_quality(cfg, data, pc, labels, lab, dev):
+    """--full, outside the timed region: the evaluation of the timed decode's labels -- the reference's
+    per-task statistics from device counters of THIS rank's corpus (weak scaling: the corpora differ per rank; the strong
+    leg reduces one corpus's counters), its MoF checked against the host's count -- and the closed-form fit statistics
+     over the whole resident corpus: one HBM pass over the features."""
+    from action_segmentation_amd import evaluation, ops
+    stream = torch.cuda.current_stream()
+    frames = pc.n_frames
+    labels_dev = labels.to(dev)      # the evaluation kernels read device labels
+    space = evaluation.LabelSpace.from_corpus(data.corpus, list(data._videos_by_task))
+    gt_dev = gt_on_device(pc, data, dev)
+    eval_ms = []
+    for _ in range(3):
+        torch.cuda.synchronize()
+        e0 = time.perf_counter()
+        stats_by_task = evaluation.evaluate_labels(labels_dev, gt_dev, pc.lengths, pc.frame_offset, pc.task_names, space,
+                                                   optimal_assignment=False, seed=0, video_key=video_keys(pc, data))
+        eval_ms.append((time.perf_counter() - e0) * 1e3)
+    summary = evaluation.summarise(stats_by_task, evaluation.STAT_KEYS)
+    fit_ms = []
+    for _ in range(4):
+        f0, f1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        f0.record(stream)
+        ops.fit_stats(pc.x, gt_dev, pc.lengths, pc.frame_offset, data.corpus.n_classes, cfg['max_k'])
+        f1.record(stream)
+        torch.cuda.synchronize()
+        fit_ms.append(f0.elapsed_time(f1))
+    fit_bytes = frames * (4 * cfg['d'] + 16)
+    correct = sum(int((lab[o:o + n] == data._videos[(tk, nm)]['gt_single'].cpu().numpy()).sum())
+                  for nm, tk, o, n in zip(pc.video_names, pc.task_names, pc.frame_offset, pc.lengths))
+    assert abs(summary['mof'] - correct / frames) < 1e-12, "device MoF != host MoF"
+    return {"correct": correct,
+            "evaluation": {"ms": min(eval_ms), "frames_per_s": frames / (min(eval_ms) * 1e-3),
+                           "what": "accuracy_corpus statistics of rank 0's corpus (confusion + per-video counters on the "
+                                   "device, assignment and ratios on the host), all tasks, outside the timed decode",
+                           "stats": {k: round(v, 9) for k, v in summary.items()}},
+            "fit_stats": {"ms": min(fit_ms[1:]), "frames_per_s": frames / (min(fit_ms[1:]) * 1e-3),
+                          "roofline": {"bound": "hbm", "achieved": fit_bytes / (min(fit_ms[1:]) * 1e-3) / 1e9,
+                                       "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                       "frac": fit_bytes / (min(fit_ms[1:]) * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                       "algorithmic_bytes_per_launch": fit_bytes},
+                          "what": "smm_fit_stats_f64 (class sums + span statistics) over every frame of the workload"}}
+
+
 def strong_leg(a, rank, world, dev, D):
-    """ONE corpus (seed --seed) sharded by video over the ranks; evaluation counters reduced over the backend.
+    """ONE corpus (seed --seed) sharded by video over the ranks; with --full, evaluation counters reduced over the backend.
     Returns (the leg's result, (this rank's packed shard, its decode outputs) for --dump-outputs)."""
     from action_segmentation_amd import evaluation, synth
     from action_segmentation_amd.batching import batch_cost
@@ -449,16 +505,18 @@ def strong_leg(a, rank, world, dev, D):
     assert sorted(pc.video_names) == sorted(n for i in mine for (_, n) in batches[i])
     dt, dp, labels, outputs = timed_decode(a, pc, world, want_events=True)
     dp_ms = dp["per_step_sum_ms"] if dp else None                    # DP kernel time of a step, all its launches
-    space = evaluation.LabelSpace.from_corpus(data.corpus, list(data._videos_by_task))
-    if pc.n_videos:
-        stats_by_task = evaluation.evaluate_labels(labels.to(dev), gt_on_device(pc, data, dev), pc.lengths, pc.frame_offset,
-                                                   pc.task_names, space, optimal_assignment=False, seed=0,
-                                                   video_key=video_keys(pc, data), reduce=D.all_reduce_tensor)
-    else:
-        z = torch.zeros(1, dtype=torch.int64, device=dev)
-        stats_by_task = evaluation.evaluate_labels(z, z, [], [], [], space, optimal_assignment=False, seed=0,
-                                                   video_key=[], reduce=D.all_reduce_tensor)
-    summary = evaluation.summarise(stats_by_task, evaluation.STAT_KEYS)
+    summary = None
+    if a.full:
+        space = evaluation.LabelSpace.from_corpus(data.corpus, list(data._videos_by_task))
+        if pc.n_videos:
+            stats_by_task = evaluation.evaluate_labels(labels.to(dev), gt_on_device(pc, data, dev), pc.lengths, pc.frame_offset,
+                                                       pc.task_names, space, optimal_assignment=False, seed=0,
+                                                       video_key=video_keys(pc, data), reduce=D.all_reduce_tensor)
+        else:
+            z = torch.zeros(1, dtype=torch.int64, device=dev)
+            stats_by_task = evaluation.evaluate_labels(z, z, [], [], [], space, optimal_assignment=False, seed=0,
+                                                       video_key=[], reduce=D.all_reduce_tensor)
+        summary = evaluation.summarise(stats_by_task, evaluation.STAT_KEYS)
     rd = D.reduce_device()
     tot = D.all_reduce_tensor(torch.tensor([float(pc.n_frames), float(pc.n_videos), float(sum(costs[i] for i in mine))],
                                            dtype=torch.float64, device=rd))
@@ -473,14 +531,16 @@ def strong_leg(a, rank, world, dev, D):
                 "frac": dp_bytes / (dp_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": None, "kernel": "smm_viterbi_kernel",
                 "kernel_ms": dp["launch_ms"], "launches_per_step": nl, "algorithmic_bytes_per_launch": dp_bytes / nl,
                 "note": "rank 0's shard of the sharded corpus; the DP is latency-bound (one serial chain per video), not HBM-bound"}
-    return ({"scaling": "strong", "roofline_rank0": roof, "workload": "%s seed %d: %d videos, %d frames, sharded by video (whole single-task "
-            "batches of %d, greedy LPT on the DP work)" % (a.strong_workload, a.seed, int(tot[1]), int(tot[0]), cfg['batch_size']),
-            "value": float(tot[0]) * a.steps / dt_all, "unit": "frames/s", "n_gpus": world, "ms_per_step": dt_all / a.steps * 1e3,
-            "frames": int(tot[0]), "videos": int(tot[1]), "max_frames_on_a_rank": int(tmax[1]),
-            "dp_kernel_ms_max_over_ranks": float(tmax[2]),
-            "stats_reduced_over": ("%s all-reduce%s" % ("RCCL" if torch.distributed.get_backend() == 'nccl' else "gloo",
-                                                         " (one-rank group)" if world == 1 else "")) if D.active() else "1 rank",
-            "stats": {k: round(v, 9) for k, v in summary.items()}}, (pc, outputs))
+    res = {"scaling": "strong", "roofline_rank0": roof, "workload": "%s seed %d: %d videos, %d frames, sharded by video (whole single-task "
+           "batches of %d, greedy LPT on the DP work)" % (a.strong_workload, a.seed, int(tot[1]), int(tot[0]), cfg['batch_size']),
+           "value": float(tot[0]) * a.steps / dt_all, "unit": "frames/s", "n_gpus": world, "ms_per_step": dt_all / a.steps * 1e3,
+           "frames": int(tot[0]), "videos": int(tot[1]), "max_frames_on_a_rank": int(tmax[1]),
+           "dp_kernel_ms_max_over_ranks": float(tmax[2])}
+    if summary is not None:
+        res.update(stats_reduced_over=("%s all-reduce%s" % ("RCCL" if torch.distributed.get_backend() == 'nccl' else "gloo",
+                                                             " (one-rank group)" if world == 1 else "")) if D.active() else "1 rank",
+                   stats={k: round(v, 9) for k, v in summary.items()})
+    return res, (pc, outputs)
 
 
 def predict_end_to_end(model, data):
@@ -855,7 +915,7 @@ def main():
             torch.distributed.destroy_process_group()
         return
     dev = torch.device('cuda', torch.cuda.current_device())
-    from action_segmentation_amd import evaluation, ops, synth
+    from action_segmentation_amd import synth
 
     # ---------------------------------------------------------------- weak leg: every rank its own corpus
     cfg = synth.CONFIGS[a.workload]
@@ -863,39 +923,13 @@ def main():
     args, model = fit_model(a, cfg, data, dev, D, world)
     pc = model.prepare(data)                                         # inputs resident in HBM from here on
     frames = pc.n_frames
-    stream = torch.cuda.current_stream()
     dt, dp, labels, outputs = timed_decode(a, pc, world)
     dp_ms = dp["per_step_sum_ms"]                                    # DP kernel time of a step, all its launches
-    labels_dev = labels.to(dev)      # the evaluation kernels below (outside the timed region) read device labels
-
-    # evaluation, outside the timed region: the reference's per-task statistics from device counters
-    # of THIS rank's corpus (weak scaling: the corpora differ per rank; the strong leg reduces one corpus's counters)
-    space = evaluation.LabelSpace.from_corpus(data.corpus, list(data._videos_by_task))
-    gt_dev = gt_on_device(pc, data, dev)
-    eval_ms = []
-    for _ in range(3):
-        torch.cuda.synchronize()
-        e0 = time.perf_counter()
-        stats_by_task = evaluation.evaluate_labels(labels_dev, gt_dev, pc.lengths, pc.frame_offset, pc.task_names, space,
-                                                   optimal_assignment=False, seed=0, video_key=video_keys(pc, data))
-        eval_ms.append((time.perf_counter() - e0) * 1e3)
-    summary = evaluation.summarise(stats_by_task, evaluation.STAT_KEYS)
-    # closed-form fit statistics over the whole resident corpus: one HBM pass over the features
-    fit_ms = []
-    for _ in range(4):
-        f0, f1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        f0.record(stream)
-        ops.fit_stats(pc.x, gt_dev, pc.lengths, pc.frame_offset, data.corpus.n_classes, cfg['max_k'])
-        f1.record(stream)
-        torch.cuda.synchronize()
-        fit_ms.append(f0.elapsed_time(f1))
-    fit_bytes = frames * (4 * cfg['d'] + 16)
     lab = labels.numpy()
-    correct = sum(int((lab[o:o + n] == data._videos[(tk, nm)]['gt_single'].cpu().numpy()).sum())
-                  for nm, tk, o, n in zip(pc.video_names, pc.task_names, pc.frame_offset, pc.lengths))
-    assert abs(summary['mof'] - correct / frames) < 1e-12, "device MoF != host MoF"
+    quality = weak_quality(cfg, data, pc, labels, lab, dev) if a.full else None
     rd = D.reduce_device()
-    counters = D.all_reduce_tensor(torch.tensor([float(correct), float(frames), float(frames)], dtype=torch.float64, device=rd))
+    counters = D.all_reduce_tensor(torch.tensor([float(quality["correct"] if quality else 0), float(frames), float(frames)],
+                                                dtype=torch.float64, device=rd))
     tmax = D.all_reduce_tensor(torch.tensor([dt], dtype=torch.float64, device=rd),
                                op=torch.distributed.ReduceOp.MAX if D.active() else None)
     total_frames = float(counters[2])
@@ -903,8 +937,7 @@ def main():
 
     strong = None
     dump = (pc, outputs)
-    if not a.no_strong_leg:
-        del labels_dev, gt_dev
+    if not a.no_strong_leg and (a.full or a.scaling == 'strong'):
         strong, strong_dump = strong_leg(a, rank, world, dev, D)
         if a.scaling == 'strong':
             dump = strong_dump
@@ -932,7 +965,7 @@ def main():
             "value": head["value"], "unit": "frames/s", "n_gpus": world, "steps": a.steps,
             "warmup": a.warmup, "ms_per_step": head["ms_per_step"], "higher_is_better": True,
             "scaling": "weak" if head is weak else "strong",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic", "backend": backend,
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic", "backend": backend, "full": a.full,
             "config": {"workload": wl_text,
                        "parallelism": "videos sharded across %d GPU(s), no data-path collective; step time MAX and frame counters "
                                       "SUM all-reduced over: %s" % (world, par)},
@@ -957,20 +990,11 @@ def main():
                                  "position), and the launch lasts as long as its longest video; %.3g lattice cells per step, "
                                  "of which the BAND kernel evaluates the part its bound tests cannot exclude" % cells},
             "time_split": dp.get("time_split"),
-            "mof": float(counters[0] / counters[1]),
             "weak_scaling": dict(weak, scaling="weak", n_gpus=world,
                                  note="every rank decodes its own corpus of this size (seed + rank)"),
-            "evaluation": {"ms": min(eval_ms), "frames_per_s": frames / (min(eval_ms) * 1e-3),
-                           "what": "accuracy_corpus statistics of rank 0's corpus (confusion + per-video counters on the "
-                                   "device, assignment and ratios on the host), all tasks, outside the timed decode",
-                           "stats": {k: round(v, 9) for k, v in summary.items()}},
-            "fit_stats": {"ms": min(fit_ms[1:]), "frames_per_s": frames / (min(fit_ms[1:]) * 1e-3),
-                          "roofline": {"bound": "hbm", "achieved": fit_bytes / (min(fit_ms[1:]) * 1e-3) / 1e9,
-                                       "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                       "frac": fit_bytes / (min(fit_ms[1:]) * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                       "algorithmic_bytes_per_launch": fit_bytes},
-                          "what": "smm_fit_stats_f64 (class sums + span statistics) over every frame of the workload"},
         }
+        if quality is not None:
+            res.update(mof=float(counters[0] / counters[1]), evaluation=quality["evaluation"], fit_stats=quality["fit_stats"])
         # the launches of a split decode overlap: their sum may exceed the step, the critical one may not
         assert dp["critical_launch_ms"] is None or dp["critical_launch_ms"] <= weak["ms_per_step"] * 1.001, \
             (dp["critical_launch_ms"], weak["ms_per_step"])
@@ -979,50 +1003,51 @@ def main():
             if head is strong and strong.get("roofline_rank0"):
                 res["roofline_weak_leg"] = res["roofline"]
                 res["roofline"] = strong["roofline_rank0"]
-        # (before any CPU-baseline leg: the oracle's OpenMP pool -- one spinning thread per host core -- and torch's own
-        # intra-op pool would fight over the cores, and predict()'s host work would be timed under that contention:
-        # round 2 reported 4 s for a 25 ms call this way)
-        if world == 1 and not a.no_predict_e2e:
-            res["predict_end_to_end"] = predict_end_to_end(model, data)
-            try:
-                res["host_features"] = host_features_leg(a, cfg, model, data, lab, pc)
-            except Exception as e:
-                res["host_features"] = {"error": repr(e)}
-            if a.workload == 'cfg3':
+        if a.full:
+            # (before any CPU-baseline leg: the oracle's OpenMP pool -- one spinning thread per host core -- and torch's own
+            # intra-op pool would fight over the cores, and predict()'s host work would be timed under that contention:
+            # round 2 reported 4 s for a 25 ms call this way)
+            if world == 1 and not a.no_predict_e2e:
+                res["predict_end_to_end"] = predict_end_to_end(model, data)
                 try:
-                    res["reference_default"] = reference_default_leg(a, dev, D, not a.no_cpu_baseline)
+                    res["host_features"] = host_features_leg(a, cfg, model, data, lab, pc)
                 except Exception as e:
-                    res["reference_default"] = {"error": repr(e)}
-        parity = {"frames_checked": 0, "label_mismatches": None, "logz_max_rel": None, "grad_max_abs": None,
-                  "what": "the C twin (oracle/smm_oracle.c) against the GPU on this workload, checker side only: frame "
-                          "labels of the TIMED decode for every video the cpu_factored leg covered; cfg4: logZ and the "
-                          "four gradients of smm_logz_f64 / smm_logz_bwd_f64 for the videos of the logZ baseline"}
-        if a.workload == 'cfg4':
-            res["logz_fwd_bwd"] = train_step_rate(args, data, model)
-            if not a.no_cpu_baseline:
+                    res["host_features"] = {"error": repr(e)}
+                if a.workload == 'cfg3':
+                    try:
+                        res["reference_default"] = reference_default_leg(a, dev, D, not a.no_cpu_baseline)
+                    except Exception as e:
+                        res["reference_default"] = {"error": repr(e)}
+            parity = {"frames_checked": 0, "label_mismatches": None, "logz_max_rel": None, "grad_max_abs": None,
+                      "what": "the C twin (oracle/smm_oracle.c) against the GPU on this workload, checker side only: frame "
+                              "labels of the TIMED decode for every video the cpu_factored leg covered; cfg4: logZ and the "
+                              "four gradients of smm_logz_f64 / smm_logz_bwd_f64 for the videos of the logZ baseline"}
+            if a.workload == 'cfg4':
+                res["logz_fwd_bwd"] = train_step_rate(args, data, model)
+                if not a.no_cpu_baseline:
+                    try:
+                        res["logz_fwd_bwd"]["cpu_baseline"], zp = logz_cpu_baseline(pc)
+                        parity.update(zp)
+                    except Exception as e:
+                        res["logz_fwd_bwd"]["cpu_baseline"] = {"error": str(e)}
+            if world == 1 and not a.no_cpu_baseline:
+                res["cpu_baseline"] = cpu_baseline(data, model, pc)
                 try:
-                    res["logz_fwd_bwd"]["cpu_baseline"], zp = logz_cpu_baseline(pc)
-                    parity.update(zp)
-                except Exception as e:
-                    res["logz_fwd_bwd"]["cpu_baseline"] = {"error": str(e)}
-        if world == 1 and not a.no_cpu_baseline:
-            res["cpu_baseline"] = cpu_baseline(data, model, pc)
-            try:
-                res["cpu_factored"], lp = cpu_factored(pc, model, gpu_labels=lab)
-                parity.update(lp)
-            except Exception as e:                              # the C oracle needs gcc on the box; report, don't fail
-                res["cpu_factored"] = {"error": str(e)}
-        res["parity"] = parity
-        if world == 1 and a.workload == 'cfg3' and a.second_seed >= 0 and a.second_seed != a.seed and a.scale == 1.0:
-            # the other draw of states per task (not the headline: same shapes, friendlier state counts)
-            data2 = synth.SynthDatasplit(a.workload, seed=a.second_seed, device=dev)
-            _, model2 = fit_model(a, cfg, data2, dev, D, world)
-            pc2 = model2.prepare(data2)
-            dt2, dp2, _, _ = timed_decode(a, pc2, world)
-            dp2 = dp2["per_step_sum_ms"] if dp2 else None
-            res["other_draw"] = {"seed": a.second_seed, "value": pc2.n_frames * a.steps / dt2, "unit": "frames/s",
-                                 "ms_per_step": dt2 / a.steps * 1e3, "dp_kernel_ms": dp2, "frames": pc2.n_frames,
-                                 "states_per_task": ' '.join(str(c) for c in sorted(pc2.n_states))}
+                    res["cpu_factored"], lp = cpu_factored(pc, model, gpu_labels=lab)
+                    parity.update(lp)
+                except Exception as e:                              # the C oracle needs gcc on the box; report, don't fail
+                    res["cpu_factored"] = {"error": str(e)}
+            res["parity"] = parity
+            if world == 1 and a.workload == 'cfg3' and a.second_seed >= 0 and a.second_seed != a.seed and a.scale == 1.0:
+                # the other draw of states per task (not the headline: same shapes, friendlier state counts)
+                data2 = synth.SynthDatasplit(a.workload, seed=a.second_seed, device=dev)
+                _, model2 = fit_model(a, cfg, data2, dev, D, world)
+                pc2 = model2.prepare(data2)
+                dt2, dp2, _, _ = timed_decode(a, pc2, world)
+                dp2 = dp2["per_step_sum_ms"] if dp2 else None
+                res["other_draw"] = {"seed": a.second_seed, "value": pc2.n_frames * a.steps / dt2, "unit": "frames/s",
+                                     "ms_per_step": dt2 / a.steps * 1e3, "dp_kernel_ms": dp2, "frames": pc2.n_frames,
+                                     "states_per_task": ' '.join(str(c) for c in sorted(pc2.n_states))}
         print(json.dumps(res), flush=True)
     if torch.distributed.is_initialized():
         torch.distributed.barrier()

@@ -1,5 +1,6 @@
 """bench.py --dump-outputs: what the timed decode returned in its last step, written as .npy files that two builds can be
-compared on (inputs fixed by the arguments alone), and --steps as the number of timed steps."""
+compared on (inputs fixed by the arguments alone), --steps as the number of timed steps, and what a plain run leaves to
+--full."""
 import json
 import os
 import subprocess
@@ -87,3 +88,22 @@ def test_bench_dumps_the_same_outputs_on_every_run(tmp_path):
         np.testing.assert_array_equal(one[k], two[k], err_msg=k)
     assert one['labels'].shape[0] == one['lengths'].sum()
     assert np.all(np.isfinite(one['best'])) and np.all(one['n_segs'] >= 1) and np.all(one['labels'] >= 0)
+
+
+@pytest.mark.gpu
+def test_plain_run_leaves_the_secondary_legs_to_full():
+    """A plain run prints the headline and the figures of its own timed steps; --full adds every secondary leg."""
+    common = ['--gpus', '1', '--workload', 'tiny', '--strong-workload', 'tiny', '--steps', '2', '--warmup', '1']
+    plain = _bench(common)
+    full = _bench(common + ['--full'])
+    secondary = {'mof', 'evaluation', 'fit_stats', 'strong_scaling', 'predict_end_to_end', 'host_features', 'cpu_baseline',
+                 'cpu_factored', 'parity'}
+    assert plain['full'] is False and not secondary & set(plain)
+    assert full['full'] is True and secondary <= set(full)
+    for line in (plain, full):
+        assert line['unit'] == 'frames/s' and line['higher_is_better'] is True and line['dtype'] == 'f64'
+        assert line['steps'] == 2 and line['ms_per_step'] > 0 and line['value'] > 0
+        assert line['roofline']['launches_per_step'] > 0
+    assert plain['config'] == full['config']
+    assert full['parity']['label_mismatches'] == 0 and full['parity']['frames_checked'] > 0
+    assert 'stats' in full['strong_scaling'] and 0.0 < full['mof'] <= 1.0

@@ -31,7 +31,7 @@ def test_every_collective_runs_through_rccl_on_one_rank():
 
 def test_bench_strong_leg_reduces_over_rccl():
     common = ['--workload', 'tiny', '--strong-workload', 'tiny', '--steps', '2', '--warmup', '1', '--no-cpu-baseline',
-              '--no-predict-e2e', '--seed', '5', '--gpus', '1', '--strong-leg']
+              '--no-predict-e2e', '--seed', '5', '--gpus', '1', '--strong-leg', '--full']
     bench = os.path.join(ROOT, 'bench.py')
     r = subprocess.run([sys.executable, bench] + common, env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]

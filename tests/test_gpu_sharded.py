@@ -129,7 +129,7 @@ def test_bench_two_ranks_one_corpus_same_stats_as_one_rank():
     """`python bench.py --gpus 2` spawns two ranks (here both on the one GPU of the box, gloo for the reductions --
     RCCL refuses two ranks on one device) and the strong-scaling leg's reduced statistics equal the one-rank ones."""
     common = ['--workload', 'tiny', '--strong-workload', 'tiny', '--steps', '2', '--warmup', '1', '--no-cpu-baseline',
-              '--no-predict-e2e', '--seed', '5']
+              '--no-predict-e2e', '--seed', '5', '--full']
     one = _bench(['--gpus', '1', '--strong-leg'] + common)
     two = _bench(['--gpus', '2', '--backend', 'gloo', '--share-gpus'] + common)
     assert one['n_gpus'] == 1 and two['n_gpus'] == 2
@@ -151,7 +151,7 @@ def test_bench_two_ranks_one_corpus_same_stats_as_one_rank():
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs (RCCL refuses two ranks on one device)")
 def test_bench_two_ranks_rccl():
     common = ['--workload', 'tiny', '--strong-workload', 'tiny', '--steps', '2', '--warmup', '1', '--no-cpu-baseline',
-              '--no-predict-e2e', '--seed', '5']
+              '--no-predict-e2e', '--seed', '5', '--full']
     one = _bench(['--gpus', '1', '--strong-leg'] + common)
     two = _bench(['--gpus', '2'] + common)
     assert two['n_gpus'] == 2 and two['backend'] == 'nccl'
@@ -171,7 +171,7 @@ def test_bench_under_torchrun_launcher():
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--share-gpus',
            '--workload', 'tiny', '--strong-workload', 'tiny', '--steps', '2', '--warmup', '1', '--no-cpu-baseline',
-           '--no-predict-e2e', '--seed', '5']
+           '--no-predict-e2e', '--seed', '5', '--full']
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith('{')]
@@ -179,7 +179,7 @@ def test_bench_under_torchrun_launcher():
     line = json.loads(lines[0])
     assert line['n_gpus'] == 2 and line['strong_scaling']['n_gpus'] == 2 and line['scaling'] == 'weak'
     one = _bench(['--gpus', '1', '--strong-leg', '--workload', 'tiny', '--strong-workload', 'tiny', '--steps', '2', '--warmup', '1',
-                  '--no-cpu-baseline', '--no-predict-e2e', '--seed', '5'])
+                  '--no-cpu-baseline', '--no-predict-e2e', '--seed', '5', '--full'])
     assert one['strong_scaling']['stats'] == line['strong_scaling']['stats']
 
 
