@@ -99,7 +99,10 @@ def viterbi(elp, lengths, trans, init, len_scores, endpen=None, no_eos=False):
     return spans, v
 
 
-def logz(elp, lengths, trans, init, len_scores, endpen=None, grad=False, upstream=None):
+def logz(elp, lengths, trans, init, len_scores, endpen=None, grad=False, upstream=None, no_eos=False, starts=False):
+    """log Z per instance [, gradients of sum_i upstream_i * logZ_i w.r.t. elp (per instance) and the shared tables].
+    ``no_eos``: add_eos=False of the reference (as ``viterbi``; every length >= 2, end penalties unused).
+    ``starts`` (with grad): also g['start'] b x tmax x c, the posterior of a span of c starting at s (times upstream)."""
     elp = _f64(elp)
     b, tmax, c = elp.shape
     len_scores = _f64(len_scores)[:tmax]
@@ -108,11 +111,14 @@ def logz(elp, lengths, trans, init, len_scores, endpen=None, grad=False, upstrea
     trans, init, endpen, upstream = _f64(trans), _f64(init), _f64(endpen), _f64(upstream)
     z = np.empty(b, np.float64)
     g = dict(elp=np.empty((b, tmax, c)), trans=np.empty((c, c)), init=np.empty(c), len=np.empty((kp, c))) if grad else {}
-    rc = lib().smm_oracle_logz(_p(elp, ctypes.c_double), _p(lengths, ctypes.c_int64), _p(trans, ctypes.c_double),
-                               _p(init, ctypes.c_double), _p(len_scores, ctypes.c_double), _p(endpen, ctypes.c_double),
-                               _p(upstream, ctypes.c_double), b, tmax, c, kp, _p(z, ctypes.c_double),
-                               _p(g.get('elp'), ctypes.c_double), _p(g.get('trans'), ctypes.c_double),
-                               _p(g.get('init'), ctypes.c_double), _p(g.get('len'), ctypes.c_double))
+    if grad and starts:
+        g['start'] = np.empty((b, tmax, c))
+    rc = lib().smm_oracle_logz_ex(_p(elp, ctypes.c_double), _p(lengths, ctypes.c_int64), _p(trans, ctypes.c_double),
+                                  _p(init, ctypes.c_double), _p(len_scores, ctypes.c_double), _p(endpen, ctypes.c_double),
+                                  _p(upstream, ctypes.c_double), b, tmax, c, kp, int(bool(no_eos)), _p(z, ctypes.c_double),
+                                  _p(g.get('elp'), ctypes.c_double), _p(g.get('trans'), ctypes.c_double),
+                                  _p(g.get('init'), ctypes.c_double), _p(g.get('len'), ctypes.c_double),
+                                  _p(g.get('start'), ctypes.c_double))
     assert rc == 0, rc
     return (z, g) if grad else z
 

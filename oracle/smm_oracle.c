@@ -172,20 +172,26 @@ static inline double lse2(double a, double b)
  *   g_elp  b x tmax x c   d sum_i gl[i]*logZ_i / d elp      (posterior state occupancy of each frame)
  *   g_trans c x c, g_init c, g_len kp x c                    (summed over the batch)
  * gl (nullable) = upstream gradient per instance (default 1).
+ * no_eos != 0: add_eos=False of the reference (as smm_oracle_viterbi_ex): segments cover frames 0 .. T-2, the video
+ * closes with a transition into the label of frame T-1, which only emits; no EOS label, no end penalties (T >= 2).
  */
-int smm_oracle_logz(const double *elp, const int64_t *lengths, const double *trans, const double *init,
-                    const double *len, const double *endpen, const double *gl, int b, int tmax, int c, int kp,
-                    double *logz, double *g_elp, double *g_trans, double *g_init, double *g_len)
+/* g_start (nullable) b x tmax x c: P(a span of c starts at s), times the upstream gradient. */
+int smm_oracle_logz_ex(const double *elp, const int64_t *lengths, const double *trans, const double *init,
+                       const double *len, const double *endpen, const double *gl, int b, int tmax, int c, int kp,
+                       int no_eos, double *logz, double *g_elp, double *g_trans, double *g_init, double *g_len,
+                       double *g_start)
 {
-    const int want_grad = g_elp || g_trans || g_init || g_len;
+    const int want_grad = g_elp || g_trans || g_init || g_len || g_start;
+    if (g_start) memset(g_start, 0, sizeof(double) * (size_t)b * tmax * c);
     if (g_elp) memset(g_elp, 0, sizeof(double) * (size_t)b * tmax * c);
     if (g_trans) memset(g_trans, 0, sizeof(double) * (size_t)c * c);
     if (g_init) memset(g_init, 0, sizeof(double) * (size_t)c);
     if (g_len) memset(g_len, 0, sizeof(double) * (size_t)kp * c);
     for (int i = 0; i < b; ++i) {
-        const int t_i = (int)lengths[i];
+        if (no_eos && lengths[i] < 2) return -3;
+        const int t_i = (int)lengths[i] - (no_eos ? 1 : 0);
         const double *e = elp + (size_t)i * tmax * c;
-        const double *ep = endpen ? endpen + (size_t)i * c : NULL;
+        const double *ep = (endpen && !no_eos) ? endpen + (size_t)i * c : NULL;
         size_t sz = (size_t)(t_i + 1) * c;
         double *cum = (double *)calloc(sz, sizeof(double));
         double *start = (double *)calloc(sz, sizeof(double)); /* log-weight of "a span of c starts at s" (incl. init at 0) */
@@ -210,14 +216,16 @@ int smm_oracle_logz(const double *elp, const int64_t *lengths, const double *tra
                 }
         }
         /* v = logsumexp over ALL last-position labels (torch_struct sums beta[len-1] over C incl. EOS) */
+        /* (no EOS: over the labels of the last frame, fin[to] = lse_j(gam[T-1][j] + trans[to][j]) + elp[T-1][to]) */
+        const double *elast = e + (size_t)t_i * c;
         double z = -INFINITY;
-        for (int to = 0; to <= c; ++to) {
+        for (int to = 0; to <= c - (no_eos ? 1 : 0); ++to) {
             double f = -INFINITY;
             for (int j = 0; j < c; ++j) {
-                double w = (to == c) ? (ep ? ep[j] : 0.0) : trans[(size_t)to * c + j] + SMM_BIG_NEG;
+                double w = (to == c) ? (ep ? ep[j] : 0.0) : trans[(size_t)to * c + j] + (no_eos ? 0.0 : SMM_BIG_NEG);
                 f = lse2(f, gam[(size_t)t_i * c + j] + w);
             }
-            z = lse2(z, f);
+            z = lse2(z, no_eos ? f + elast[to] : f);
         }
         logz[i] = z;
         if (want_grad) {
@@ -227,9 +235,9 @@ int smm_oracle_logz(const double *elp, const int64_t *lengths, const double *tra
             double *occ = (double *)calloc((size_t)(t_i + 2) * c, sizeof(double)); /* difference array over frames */
             const double up = gl ? gl[i] : 1.0;
             for (int j = 0; j < c; ++j) {
-                double w = ep ? ep[j] : 0.0;
-                double f = w;
-                for (int to = 0; to < c; ++to) f = lse2(f, trans[(size_t)to * c + j] + SMM_BIG_NEG);
+                double f = no_eos ? -INFINITY : (ep ? ep[j] : 0.0);
+                for (int to = 0; to < c; ++to)
+                    f = lse2(f, trans[(size_t)to * c + j] + (no_eos ? elast[to] : SMM_BIG_NEG));
                 bend[(size_t)t_i * c + j] = f;
             }
             for (int s = t_i - 1; s >= 0; --s) {
@@ -250,6 +258,7 @@ int smm_oracle_logz(const double *elp, const int64_t *lengths, const double *tra
             for (int s = 0; s < t_i; ++s)
                 for (int j = 0; j < c; ++j) {
                     if (s == 0 && g_init) g_init[j] += up * exp(start[j] + bstart[j] - z);
+                    if (g_start) g_start[((size_t)i * tmax + s) * c + j] = up * exp(start[(size_t)s * c + j] + bstart[(size_t)s * c + j] - z);
                     for (int k = 1; k <= kp - 1 && s + k <= t_i; ++k) {
                         double p = up * exp(start[(size_t)s * c + j] + len[(size_t)k * c + j]
                                             + (cum[(size_t)(s + k) * c + j] - cum[(size_t)s * c + j])
@@ -259,6 +268,13 @@ int smm_oracle_logz(const double *elp, const int64_t *lengths, const double *tra
                         occ[(size_t)(s + k) * c + j] -= p;
                     }
                 }
+            if (no_eos)             /* the closing transition into the label of the last frame, and that frame's emission */
+                for (int to = 0; to < c; ++to)
+                    for (int j = 0; j < c; ++j) {
+                        double p = up * exp(gam[(size_t)t_i * c + j] + trans[(size_t)to * c + j] + elast[to] - z);
+                        if (g_trans) g_trans[(size_t)to * c + j] += p;
+                        if (g_elp) g_elp[((size_t)i * tmax + t_i) * c + to] += p;
+                    }
             if (g_trans)
                 for (int n = 1; n < t_i; ++n)
                     for (int to = 0; to < c; ++to)
@@ -278,4 +294,12 @@ int smm_oracle_logz(const double *elp, const int64_t *lengths, const double *tra
         free(cum); free(start); free(gam);
     }
     return 0;
+}
+
+int smm_oracle_logz(const double *elp, const int64_t *lengths, const double *trans, const double *init,
+                    const double *len, const double *endpen, const double *gl, int b, int tmax, int c, int kp,
+                    double *logz, double *g_elp, double *g_trans, double *g_init, double *g_len)
+{
+    return smm_oracle_logz_ex(elp, lengths, trans, init, len, endpen, gl, b, tmax, c, kp, 0, logz, g_elp, g_trans,
+                              g_init, g_len, NULL);
 }

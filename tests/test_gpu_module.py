@@ -1,4 +1,6 @@
 """GPU parity of the product SemiMarkovModule.viterbi (features -> spans) against the oracles."""
+import math
+
 import numpy as np
 import pytest
 import torch
@@ -8,6 +10,7 @@ from oracle import factored as F
 from golden_util import (CASES, case_inputs, assert_spans_equivalent, span_start_differences, crosstask_magnitude_case,
                          fp32_near_tie_certificate)
 from module_util import module_from_golden, make_args
+import train_ref as R
 
 pytestmark = pytest.mark.gpu
 EOS_CASES = [c for c in CASES if CASES[c].get('add_eos', True)]
@@ -167,10 +170,12 @@ def test_log_likelihood_matches_reference_path(golden, case):
     assert js.item() <= ll.item() + 1e-6
 
 
-@pytest.mark.parametrize('case', ['tiny', 'subset_merge', 'constrained'])
+@pytest.mark.parametrize('case', ['tiny', 'subset_merge', 'constrained', 'hmm_k1', 'k_gt_t'])
 def test_log_likelihood_gradients_match_dense_autograd(golden, case):
     """d mean(logZ) / d parameters through the HIP forward/backward kernels vs autograd through the dense reference
-    path (fp64 log_hsmm potentials + LogSemiring DP)."""
+    path (fp64 log_hsmm potentials + LogSemiring DP), every parameter row held to its own size at 2e-5 (the bar the
+    log Z backward kernels hold; tests/train_ref.py: assert_rows_close).  hmm_k1: max_k = 1 (the two-row HMM length
+    table, built outside the table kernel); k_gt_t: K > T (the length table cut to kp = T rows)."""
     dev = torch.device('cuda:0')
     m = module_from_golden(golden, case).to(dev)
     p, feats, lengths, valid, cons, cfg = case_inputs(golden, case, torch.float64)
@@ -191,10 +196,11 @@ def test_log_likelihood_gradients_match_dense_autograd(golden, case):
     z, _ = O.semimarkov_dp(scores, lengths + 1, O.LogSemiring)
     z.mean().backward()
     assert abs(ll.item() - z.mean().item()) <= 1e-6 * abs(z.mean().item()) + 1e-4
+    got_all = R.module_grads(m)                      # (hmm_k1: the constant length table gives the rates no gradient)
     for n in names:
-        got = getattr(m, n).grad.detach().cpu().double().numpy()
-        ref = leaves[n].grad.numpy()
-        np.testing.assert_allclose(got, ref, rtol=5e-4, atol=5e-4 * max(1.0, np.abs(ref).max()), err_msg=n)
+        got = got_all[n]
+        ref = np.zeros(tuple(leaves[n].shape)) if leaves[n].grad is None else leaves[n].grad.numpy()
+        R.assert_rows_close(got, ref, 2e-5, '%s %s' % (case, n))
 
 
 def test_no_eos_viterbi_and_log_likelihood_match_reference_path(golden):
@@ -228,7 +234,7 @@ def test_no_eos_viterbi_and_log_likelihood_match_reference_path(golden):
     for n in names:
         got = getattr(m, n).grad.detach().cpu().double().numpy()
         refg = leaves[n].grad.numpy()
-        np.testing.assert_allclose(got, refg, rtol=5e-4, atol=5e-4 * max(1.0, np.abs(refg).max()), err_msg=n)
+        R.assert_rows_close(got, refg, 2e-5, 'no_eos %s' % n)
     # gold-span score of the Viterbi path (to_parts has no edge for the last span: reference :641-655)
     js, _ = m.log_likelihood(feats.float().to(dev), lengths.to(dev), vc, spans=r['spans'][:, :tmax].to(dev), add_eos=False)
     parts = O.to_parts(r['spans'][:, :tmax], scores.shape[-1], scores.shape[2], lengths)
@@ -291,7 +297,8 @@ def test_factor_tables_kernel_matches_torch_tables(variant):
         st, n_states, cm, k_rows = m._stacked_tables_batched(pc, dev, use_hip=use_hip)
         assert (cm, k_rows, n_states) == ((14, k, [12, 3, 5, 14]) if variant != 'big' else (32, k, [32, 3, 23]))
         g = torch.Generator(device='cpu').manual_seed(3)
-        loss = sum((st[n] * torch.randn(st[n].shape, generator=g, dtype=torch.float64).to(dev)).sum() for n in names)
+        wts = {n: torch.randn(st[n].shape, generator=g, dtype=torch.float64) for n in names}
+        loss = sum((st[n] * wts[n].to(dev)).sum() for n in names)
         loss.backward()
         tabs[use_hip] = {n: st[n].detach().cpu().numpy() for n in names}
         grads[use_hip] = {n: p.grad.detach().cpu().numpy().copy() for n, p in m.named_parameters() if p.grad is not None}
@@ -301,3 +308,185 @@ def test_factor_tables_kernel_matches_torch_tables(variant):
     for n in grads[False]:
         np.testing.assert_allclose(grads[True][n], grads[False][n], rtol=2e-5, atol=1e-5 * np.abs(grads[False][n]).max(),
                                    err_msg=n)
+    # ... and both against the independent reference (dense_ref's tables by fp64 autograd)
+    _check_tables_against_reference(m, kw, sets, tabs[True], grads[True], wts, variant)
+
+
+def _reference_tables(m, structure, sets, wts):
+    """The tables of every group by oracle/dense_ref.py (factor_tables; the emission factors are the expanded form of
+    dense_ref.emission_log_probs, w = mu / var, cst = -0.5 sum mu^2 / var - 0.5 sum log var - D/2 log 2 pi) on the
+    module's fp32 parameter values in fp64, and the gradient of sum(table * wts) (wts: the kernel test's weights,
+    [groups, ...] padded to c_max) w.r.t. the four trained parameters.  ``structure``: the sets the module was
+    constructed with (the reference builds its own masks from them).  -> (tables per group, gradients)."""
+    p, leaves = R.params_from_module(m, **structure)
+    var = p.gaussian_cov_diag
+    d = var.numel()
+    out, loss = [], 0.0
+    for gi, vc in enumerate(sets):
+        trans, init, lens, merged = O.factor_tables(p, None if vc is None else torch.tensor(vc))
+        mu = p.gaussian_means[merged]
+        t = dict(trans=trans, init=init, len=lens, w=(mu / var).t(),
+                 cst=-0.5 * (mu * mu / var).sum(1) - 0.5 * var.log().sum() - 0.5 * d * math.log(2 * math.pi),
+                 inv_var=1.0 / var)
+        c = init.numel()
+        loss = loss + ((t['trans'] * wts['trans'][gi, :c, :c]).sum() + (t['init'] * wts['init'][gi, :c]).sum()
+                       + (t['len'] * wts['len'][gi, :, :c]).sum() + (t['w'] * wts['w'][gi, :, :c]).sum()
+                       + (t['cst'] * wts['cst'][gi, :c]).sum())
+        out.append({n: v.detach().numpy() for n, v in t.items()})
+    return out, R.grads(leaves, loss)
+
+
+def _check_tables_against_reference(m, structure, sets, hip_tabs, hip_grads, wts, label):
+    """HIP tables (stacked, padded to c_max) equal dense_ref's to 1e-13 relative (padding exactly 0); the parameter
+    gradients equal the reference's at fp32 rounding of the fp64 result (assert_rows_close at 1e-6)."""
+    ref_tabs, ref_grads = _reference_tables(m, structure, sets, wts)
+    for gi, rt in enumerate(ref_tabs):
+        c = rt['init'].shape[0]
+        for n in ('trans', 'init', 'len', 'w', 'cst'):
+            got = hip_tabs[n][gi]
+            sl = {'trans': np.s_[:c, :c], 'init': np.s_[:c], 'len': np.s_[:, :c], 'w': np.s_[:, :c], 'cst': np.s_[:c]}[n]
+            ref = rt[n]
+            scale = max(1.0, float(np.abs(ref[np.abs(ref) < 1e8]).max(initial=0.0)))     # (-1e9 masks aside)
+            np.testing.assert_allclose(got[sl], ref, rtol=1e-13, atol=1e-13 * scale, err_msg='%s group %d %s' % (label, gi, n))
+            pad = np.ones(got.shape, bool)
+            pad[sl] = False
+            assert not got[pad].any(), (label, gi, n)
+        np.testing.assert_allclose(hip_tabs['inv_var'], rt['inv_var'], rtol=1e-15)
+    for n in R.PARAMS:
+        R.assert_rows_close(hip_grads[n], ref_grads[n], 1e-6, 'tables %s %s' % (label, n))
+
+
+def _table_module(n_classes, d, k, seed, **kw):
+    from action_segmentation_amd.semimarkov_modules import SemiMarkovModule
+    torch.manual_seed(seed)
+    self_tr = kw.pop('allow_self_transitions', True)
+    m = SemiMarkovModule(make_args(k), n_classes, d, allow_self_transitions=self_tr, **kw).cuda()
+    with torch.no_grad():
+        m.init_logits.normal_(); m.transition_logits.normal_(); m.poisson_log_rates.uniform_(0.5, 4.5)
+        m.gaussian_means.normal_()
+        m.gaussian_cov.copy_(torch.diag(0.5 + torch.rand(d)))
+    return m, kw
+
+
+def _tables_hip(m, sets, seed=3):
+    """smm_factor_tables_f64 forward and backward (one launch each) for the class sets -> (tables, grads, weights)."""
+    import types
+    dev = torch.device('cuda:0')
+    pc = types.SimpleNamespace(groups=[dict(valid_classes=None if v is None else torch.tensor(v)) for v in sets])
+    m.zero_grad()
+    st, n_states, cm, k_rows = m._stacked_tables_batched(pc, dev, use_hip=True)
+    assert n_states == [m.n_classes if v is None else len(v) for v in sets] and k_rows == m.max_k
+    g = torch.Generator(device='cpu').manual_seed(seed)
+    names = ('trans', 'init', 'len', 'w', 'cst')
+    wts = {n: torch.randn(st[n].shape, generator=g, dtype=torch.float64) for n in names}
+    sum((st[n] * wts[n].to(dev)).sum() for n in names).backward()
+    torch.cuda.synchronize()
+    tabs = {n: st[n].detach().cpu().numpy() for n in names + ('inv_var',)}
+    return tabs, R.module_grads(m), wts
+
+
+def _edge_case(name):
+    """-> ((module, its structure sets), class sets) of one edge of the table kernels."""
+    if name.startswith('k_rows'):
+        # length-table slabs of SMM_TAB_LEN_ROWS = 64 rows per workgroup: one row short of, at, one past a boundary
+        k = int(name.split('=')[1])
+        return _table_module(9, 6, k, k), [[0, 3, 5, 8], [1, 2, 3], None]
+    if name == 'one_state':
+        # a one-state group: init is log_softmax of one logit (0), the column its own (self) transition
+        return _table_module(7, 5, 12, 1), [[4], [4, 1, 6], [2]]
+    if name == 'no_self_one_state':
+        # allow_self_transitions=False and one state: its only target is masked, the column is log_softmax over -1e9
+        return _table_module(7, 5, 12, 2, allow_self_transitions=False), [[3], [0, 3, 5]]
+    if name == 'masked_column':
+        # transition constraints that forbid every `to` of class 2 (and class 5 only leads outside most sets)
+        allowed = {i: {j for j in range(10) if (i + j) % 3 != 0} for i in range(10) if i != 2}
+        allowed[5] = {9}
+        return (_table_module(10, 4, 20, 3, allowed_starts={0, 2, 5, 7}, allowed_transitions=allowed, allowed_ends={1, 2}),
+                [[2, 5, 7, 0], [5, 2], None, [9, 5, 2]])
+    if name.startswith('d='):
+        d = int(name.split('=')[1])
+        return _table_module(11, d, 30, d), [[0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10], [10, 4, 7], [6]]
+    if name == 'shared_groups':
+        # ~300 classes in 18 groups of up to 32 states that share classes: the backward's atomic scatter into shared rows
+        g = np.random.default_rng(18)
+        sets = [sorted(g.choice(300, size=int(g.integers(2, 33)), replace=False).tolist()) for _ in range(18)]
+        sets[0] = list(range(0, 32)); sets[1] = list(range(16, 48)); sets[2] = [0, 1, 2]
+        return _table_module(300, 20, 70, 4), sets
+    if name == 'merge3':
+        # merge_classes maps three states of one group onto one parameter row (lengths and means share it)
+        merge = {i: (1 if i in (1, 4, 6) else i) for i in range(9)}
+        return _table_module(9, 7, 40, 5, merge_classes=merge), [[1, 4, 6, 0], [6, 2, 4], [0, 8]]
+    raise KeyError(name)
+
+
+TABLE_EDGES = ['k_rows=63', 'k_rows=64', 'k_rows=65', 'k_rows=129', 'k_rows=1024', 'one_state', 'no_self_one_state',
+               'masked_column', 'd=1', 'd=37', 'd=300', 'shared_groups', 'merge3']
+
+
+@pytest.mark.parametrize('edge', TABLE_EDGES)
+def test_factor_tables_kernel_edges_against_reference(edge):
+    """smm_factor_tables_f64 / _bwd_f64 at the edges of their layout against the independent dense_ref tables: slab
+    boundaries of the length rows, one-state groups, fully masked transition columns, feature widths 1 / not a multiple
+    of 4 / > 256, many groups sharing classes, three states on one merged row."""
+    (m, structure), sets = _edge_case(edge)
+    tabs, grads, wts = _tables_hip(m, sets)
+    _check_tables_against_reference(m, structure, sets, tabs, grads, wts, edge)
+    if edge in ('no_self_one_state', 'masked_column'):
+        # the fully masked column: torch's log_softmax over all -1e9 (uniform over the group's states)
+        c = len(sets[0])                    # (group 0, local state 0: class 3 without its self transition / class 2)
+        expect = torch.log_softmax(torch.full((c,), -1e9, dtype=torch.float64), 0).numpy()
+        np.testing.assert_allclose(tabs['trans'][0][:c, 0], expect, rtol=1e-15, atol=0)
+    if edge == 'shared_groups':
+        unused = sorted(set(range(m.n_classes)) - set(v for s in sets for v in s))
+        assert unused and not grads['gaussian_means'][unused].any() and not grads['poisson_log_rates'][unused].any()
+
+
+@pytest.mark.parametrize('case', list(CASES))
+def test_factor_tables_kernel_against_golden_tables(golden, case):
+    """The table kernel's trans / init / len against the reference module's own fp64 tables in the fixture
+    (tests/golden/make_golden.py: one class set per case, before EOS is added) -- the first C states of the padded
+    group -- and the emission kernel fed the kernel's w / cst / inv_var against the fixture's fp64 elp.  hmm_k1
+    (max_k = 1) takes factor_tables, the path log_partition takes there (the kernel needs two length rows).
+    The fixture's fp64 length tables carry one piece of fp32: the reference evaluates Poisson.log_prob at
+    ``time_steps.float()`` (its semimarkov_modules.py:387-388), so lgamma(k + 1) is taken in fp32 even in its fp64 run
+    (up to 4e-7 off at k = 7).  The comparison puts exactly that rounding back -- lgamma64(k + 1) - lgamma32(k + 1) --
+    and then holds 1e-13."""
+    import types
+    from action_segmentation_amd import ops
+    dev = torch.device('cuda:0')
+    m = module_from_golden(golden, case).to(dev)
+    p, feats, lengths, valid, cons, cfg = case_inputs(golden, case, torch.float64)
+    with torch.no_grad():
+        if m.max_k > 1:
+            pc = types.SimpleNamespace(groups=[dict(valid_classes=valid)])
+            st, n_states, c, k_rows = m._stacked_tables_batched(pc, dev, use_hip=True)
+            t = {n: st[n][0] for n in ('trans', 'init', 'len', 'w', 'cst')}
+            t['inv_var'] = st['inv_var']
+        else:
+            t = m.factor_tables(valid, dev)
+            c = t['init'].numel()
+    t = {n: v.cpu().numpy() for n, v in t.items() if n != 'class_map'}
+    n_ref = golden[case + '/f64/init'].shape[0]
+    assert c == n_ref
+    rel = lambda got, ref, what: np.testing.assert_allclose(got, ref, rtol=1e-13, atol=1e-13 * np.abs(ref[np.abs(ref) < 1e8]).max(),
+                                                             err_msg='%s %s' % (case, what))
+    rel(t['trans'][:c, :c], golden[case + '/f64/trans'], 'trans')
+    rel(t['init'][:c], golden[case + '/f64/init'], 'init')
+    k_rows = t['len'].shape[0]
+    lg32 = np.zeros((k_rows, 1))
+    if m.max_k > 1:
+        ks = torch.arange(k_rows, dtype=torch.float64) + 1
+        lg32 = (torch.lgamma(ks) - torch.lgamma(ks.float()).double()).numpy()[:, None]
+    rel(t['len'][:, :c] + lg32, golden[case + '/f64/len'].astype(np.float64), 'len')
+    # emission: the kernel's own factors through smm_emission_f64 against the reference module's elp (constraints added)
+    b, tmax, d = feats.shape
+    batch = ops.Batch(lengths.numpy(), [c], max(m.max_k, 2), c_max=c, t_max=tmax, total_frames=b * tmax, d=d)
+    tt = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    x = feats.float().reshape(b * tmax, d).contiguous().to(dev)
+    cn = None if cons is None else cons.float().reshape(b * tmax, c).contiguous().to(dev)
+    elp, _ = ops.emission(batch, x, tt(t['w'][None, :, :c]), tt(t['cst'][None, :c]), tt(t['inv_var']), cons=cn)
+    elp = elp.cpu().numpy().reshape(b, tmax, c)
+    ref = golden[case + '/f64/elp']
+    for i, ti in enumerate(lengths.tolist()):
+        np.testing.assert_allclose(elp[i, :ti], ref[i, :ti], rtol=1e-12, atol=1e-11 * np.abs(ref[i, :ti]).max(),
+                                   err_msg='%s elp video %d' % (case, i))
