@@ -1470,6 +1470,55 @@ extern "C" int smm_entropy_f64(const smm_shape *shape, const int64_t *lengths_ho
     return SMM_OK;
 }
 
+extern "C" int smm_kl_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                          const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                          const double *elp_p, const double *trans_p, const double *init_p, const double *len_p,
+                          const double *endpen_p, const double *logz_p, void *ws_p, size_t ws_p_bytes,
+                          const double *elp_q, const double *trans_q, const double *init_q, const double *len_q,
+                          const double *endpen_q, const double *logz_q, void *ws_q, size_t ws_q_bytes,
+                          double *kl_out, double *xent_out, void *stream)
+{
+    if (!kl_out || !elp_p || !trans_p || !init_p || !len_p || !logz_p || !elp_q || !trans_q || !init_q || !len_q || !logz_q ||
+        !ws_q)
+        return SMM_ERR_ARG;
+    // q's workspace is only read (its forward histories): checked against the plan before p's is staged
+    const size_t need = smm_workspace_bytes(shape, lengths_host);
+    if (need == 0) return SMM_ERR_ARG;
+    if (ws_q_bytes < need) return SMM_ERR_WORKSPACE;
+    Staged st;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, ws_p, ws_p_bytes, hs, &st);
+    if (rc != SMM_OK) return rc;
+    Staged sq;
+    plan_point(make_plan(shape, lengths_host), ws_q, &sq);
+    const size_t g = shape->n_groups, cm = shape->c_max;
+    const bool no_eos = (shape->flags & SMM_SHAPE_NO_EOS) != 0;
+    if (!(shape->flags & SMM_SHAPE_LOGZ_BOTH)) {   // p's backward histories, as smm_logz_bwd_f64 makes them
+        double *trans_t = st.tabs;
+        double *logz_b = trans_t + g * cm * cm;
+        smm_launch_transpose(trans_p, trans_t, (int)g, (int)cm, hs);
+        SmmDpArgs a{};
+        a.videos = st.videos; a.order = st.order; a.n_states = st.n_states;
+        a.elp = elp_p; a.trans = trans_t; a.init = init_p; a.len = len_p; a.endpen = endpen_p;
+        a.hist = st.hist; a.err = st.err;
+        a.c_max = shape->c_max; a.k_rows = shape->k_rows; a.t_max = shape->t_max; a.b = shape->b;
+        a.flags = 2;
+        if (no_eos) { a.flags |= 8; a.endpen = nullptr; }
+        rc = smm_launch_logz(a, logz_b, ring_regs(st.kp_max), st.c_need, hs);
+        if (rc != SMM_OK) return rc;
+    }
+    SmmKlArgs k{};
+    k.videos = st.videos; k.n_states = st.n_states; k.hist_p = st.hist; k.hist_q = sq.hist;
+    k.elp_p = elp_p; k.elp_q = elp_q; k.trans_p = trans_p; k.trans_q = trans_q; k.len_p = len_p; k.len_q = len_q;
+    k.endpen_p = no_eos ? nullptr : endpen_p; k.endpen_q = no_eos ? nullptr : endpen_q;
+    k.logz_p = logz_p; k.logz_q = logz_q;
+    k.kl = kl_out; k.xent = xent_out; k.err = st.err;
+    k.c_max = shape->c_max; k.k_rows = shape->k_rows; k.b = shape->b; k.no_eos = no_eos ? 1 : 0;
+    smm_launch_kl(k, shape->t_max, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ k best
 // Behind the plan's workspace (its `total`): the length table state-major, the H lists of the last `ring` positions (and their
 // heads apart, class-major), the back-pointers of G and H at every position, the closing lists, the back-trace's scratch.

@@ -164,3 +164,22 @@ struct SmmEntropyArgs {
     int32_t c_max, k_rows, b, no_eos;
 };
 void smm_launch_entropy(const SmmEntropyArgs &a, int t_max, hipStream_t stream);
+
+// KL divergence and cross-entropy between two posteriors of one lattice (smm_kl.hip): after smm_launch_logz forward AND
+// time-reversed on p's workspace and forward on q's (the same shape and metadata, so the same history offsets)
+struct SmmKlArgs {
+    const SmmVideo *videos;
+    const int32_t *n_states;
+    const double *hist_p;      // p's per video: F_cum, F_h, F_g, B_cum, B_h, B_g, (scratch) hT0, hT1; each [T+1][c_max]
+    const double *hist_q;      // q's: F_cum, F_h, F_g (forward only)
+    const double *elp_p, *elp_q;          // [total_frames][c_max]   (no_eos only: the closing label's emission)
+    const double *trans_p, *trans_q;      // [g][c_max][c_max]  [to][from]
+    const double *len_p, *len_q;          // [g][k_rows][c_max]
+    const double *endpen_p, *endpen_q;    // [b][c_max] or null (EOS mode only)
+    const double *logz_p, *logz_q;        // [b]
+    double *kl;                // [b] nats
+    double *xent;              // [b] nats, or null
+    int32_t *err;              // sticky error word (p's workspace)
+    int32_t c_max, k_rows, b, no_eos;
+};
+void smm_launch_kl(const SmmKlArgs &a, int t_max, hipStream_t stream);

@@ -503,6 +503,35 @@ def entropy(batch, elp, trans, init, len_scores, logz_val, endpen=None, ws=None,
     return out
 
 
+def kl(batch, p, q, with_backward=False, want_cross_entropy=False):
+    """Exact KL divergence KL(p || q) = sum_y p(y | x) log(p(y | x) / q(y | x)) between two segmentation posteriors of the same
+    lattice, in nats (smm_kl_f64): fp64 [b]; with ``want_cross_entropy`` the pair (KL, H(p, q) = H(p) + KL).  ``p`` and ``q``
+    are each ``(elp, trans, init, len_scores, endpen, logz_val, ws)``: the tables of that side, and the workspace and output of
+    its own ``logz`` on ``batch`` (``with_backward``: as passed to p's ``logz``; without it the call runs p's time-reversed
+    recursion itself; q needs only its forward histories and its workspace is only read).  +inf, without an error, where q gives
+    probability 0 to what p does not.  A video whose log Z_p is not finite, or whose histories a NaN reached on either side,
+    gets NaN and sets the error word of p's workspace (``error_flag(batch, ws=p[6])``).  Exactly 0 for bit-identical sides;
+    bit-identical run to run.  No gradient."""
+    lib = _lib.load()
+    shape = _shape_with(batch, _lib.SHAPE_LOGZ_BOTH if with_backward else 0)
+    f64 = torch.float64
+    dev = p[0].device
+    out = torch.empty(batch.b, dtype=f64, device=dev)
+    xent = torch.empty(batch.b, dtype=f64, device=dev) if want_cross_entropy else None
+
+    def side(t, tag):
+        elp, trans, init, len_scores, endpen, logz_val, ws = t
+        return [_dev(elp, f64, 'elp_' + tag), _dev(trans, f64, 'trans_' + tag), _dev(init, f64, 'init_' + tag),
+                _dev(len_scores, f64, 'len_scores_' + tag), _dev(endpen, f64, 'endpen_' + tag), _dev(logz_val, f64, 'logz_' + tag),
+                ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel())]
+
+    ln, fo, gr, kp, ns = batch.host_ptrs()
+    _lib.check(lib.smm_kl_f64(
+        ctypes.byref(shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(kp),
+        ctypes.c_void_p(ns), *side(p, 'p'), *side(q, 'q'), _dev(out, f64, 'kl'), _dev(xent, f64, 'cross_entropy'), _stream()))
+    return (out, xent) if want_cross_entropy else out
+
+
 MAX_KBEST = 16
 
 

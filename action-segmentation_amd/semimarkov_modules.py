@@ -770,6 +770,90 @@ class SemiMarkovModule(nn.Module):
         ops.check_decoded(pc.batch, dict(_err=ops._err_copy(pc.batch, ws)))
         return h
 
+    # ------------------------------------------------------------------ KL divergence and cross-entropy (smm_kl_f64)
+    def _check_same_lattice(self, other, what):
+        if not isinstance(other, SemiMarkovModule):
+            raise TypeError("%s: other must be a SemiMarkovModule" % what)
+        mine = (self.n_classes, self.input_feature_dim, self.max_k)
+        theirs = (other.n_classes, other.input_feature_dim, other.max_k)
+        if mine != theirs:
+            raise ValueError("%s: the two posteriors must share the lattice: (n_classes, n_dims, max_k) %s against %s"
+                             % (what, mine, theirs))
+
+    @staticmethod
+    def _check_same_batch(bp, bq, what):
+        same = (bp.c_max == bq.c_max and bp.k_rows == bq.k_rows and bp.no_eos == bq.no_eos
+                and np.array_equal(bp.lengths, bq.lengths) and np.array_equal(bp.n_states, bq.n_states)
+                and np.array_equal(bp.frame_offset, bq.frame_offset)
+                and (bp.kp is None) == (bq.kp is None) and (bp.kp is None or np.array_equal(bp.kp, bq.kp))
+                and (bp.group is None) == (bq.group is None) and (bp.group is None or np.array_equal(bp.group, bq.group)))
+        if not same:
+            raise ValueError("%s: the two posteriors' batches differ (states, span limit or lengths)" % what)
+
+    def _kl(self, other, features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
+            constraints, other_constraints, what, want_cross_entropy):
+        self._check_same_lattice(other, what)
+        q = other._posterior_launch(features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
+                                    other_constraints, what)
+        r = self._posterior_launch(features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
+                                   constraints, what, with_backward=True)
+        self._check_same_batch(r['batch'], q['batch'], what)
+        side = lambda t: (t['elp'], t['trans'], t['init'], t['len'], t['endpen'], t['logz'], t['ws'])
+        out = ops.kl(r['batch'], side(r), side(q), with_backward=True, want_cross_entropy=want_cross_entropy)
+        ops.check_decoded(r['batch'], dict(_err=ops._err_copy(r['batch'], r['ws'])))
+        return out[1] if want_cross_entropy else out
+
+    @torch.no_grad()
+    def kl_divergence(self, other, features, lengths, valid_classes_per_instance, add_eos=True,
+                      additional_allowed_ends_per_instance=None, constraints=None, other_constraints=None):
+        """Exact KL(p || q) = sum_y p(y | x) log(p(y | x) / q(y | x)) per video, in nats: fp64 b on the device (argument
+        conventions of ``viterbi``).  p is this module's posterior under ``constraints``, q is ``other``'s under
+        ``other_constraints`` (``other`` may be ``self``); each side builds its tables, emissions and end penalties from its own
+        parameters and allowed ends.  Two emission launches, two log Z launches (p's forward and time-reversed), one KL launch
+        (smm_kl_f64); the value keeps its relative accuracy as q -> p and is exactly 0 for the same inputs.  +inf where q gives
+        probability 0 to a segmentation p does not.  Raises ValueError when the two modules' lattices differ (n_classes,
+        n_dims, max_k), SmmError when a NaN reached the DP.  No autograd."""
+        return self._kl(other, features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
+                        constraints, other_constraints, 'kl_divergence', False)
+
+    @torch.no_grad()
+    def cross_entropy(self, other, features, lengths, valid_classes_per_instance, add_eos=True,
+                      additional_allowed_ends_per_instance=None, constraints=None, other_constraints=None):
+        """Exact cross-entropy H(p, q) = -sum_y p(y | x) log q(y | x) = H(p) + KL(p || q) per video, in nats: fp64 b on the
+        device.  Arguments and launches as ``kl_divergence``; with ``other`` = ``self`` and the same constraints it is
+        ``entropy``'s value."""
+        return self._kl(other, features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
+                        constraints, other_constraints, 'cross_entropy', True)
+
+    def _kl_packed(self, other, pc, what, want_cross_entropy):
+        self._check_same_lattice(other, what)
+        # q first, on a copy of the corpus' cached state that is put back afterwards: prepare_packed keeps one module's
+        # tables, end penalties and launch metadata on the corpus, and `pc` is left prepared for `self`
+        saved = dict(pc.__dict__)
+        try:
+            tq, elp_q, z_q, ws_q = other._packed_posterior_launch(pc, what)
+            ep_q, batch_q = pc.endpen, pc.batch
+        finally:
+            pc.__dict__.clear()
+            pc.__dict__.update(saved)
+        t, elp, z, ws = self._packed_posterior_launch(pc, what)
+        self._check_same_batch(pc.batch, batch_q, what)
+        out = ops.kl(pc.batch, (elp, t['trans'], t['init'], t['len'], pc.endpen, z, ws),
+                     (elp_q, tq['trans'], tq['init'], tq['len'], ep_q, z_q, ws_q), want_cross_entropy=want_cross_entropy)
+        ops.check_decoded(pc.batch, dict(_err=ops._err_copy(pc.batch, ws)))
+        return out[1] if want_cross_entropy else out
+
+    @torch.no_grad()
+    def kl_packed(self, other, pc):
+        """``kl_divergence`` for a whole PackedCorpus: fp64 n_videos on the device, in the order of ``pc.video_names``.  q's
+        stacked tables and end penalties are built on ``pc``'s layout; ``pc`` is left prepared for ``self``."""
+        return self._kl_packed(other, pc, 'kl_packed', False)
+
+    @torch.no_grad()
+    def cross_entropy_packed(self, other, pc):
+        """``cross_entropy`` for a whole PackedCorpus: fp64 n_videos on the device, in the order of ``pc.video_names``."""
+        return self._kl_packed(other, pc, 'cross_entropy_packed', True)
+
     # ------------------------------------------------------------------ the k best segmentations (smm_kbest_f64)
     @torch.no_grad()
     def viterbi_kbest(self, features, lengths, valid_classes_per_instance, k, add_eos=True,

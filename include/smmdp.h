@@ -16,6 +16,8 @@
  *   smm_sample_f64          <- pytorch-struct's SemiMarkovCRF(...).sample (posterior samples; the reference never calls it)
  *   smm_entropy_f64         <- pytorch-struct's SemiMarkovCRF(...).entropy (exact H(y | x) per video; the reference never
  *                              calls it)
+ *   smm_kl_f64              <- pytorch-struct's SemiMarkovCRF(...).kl / cross_entropy (exact KL(p || q) and H(p, q) per
+ *                              video between two posteriors of one lattice; the reference never calls them)
  *   smm_kbest_f64           <- pytorch-struct's SemiMarkovCRF(...).kmax / topk (the k best segmentations; the reference never
  *                              calls it)
  *
@@ -106,7 +108,7 @@ int smm_device_count(void);
 
 /* Bytes of device workspace any entry point below needs for this shape (lengths: host array [b]).
  * Returns 0 on invalid arguments.  The workspace is scratch: its contents are undefined after a call,
- * except between smm_logz_f64 and smm_logz_bwd_f64 / smm_sample_f64 / smm_entropy_f64. */
+ * except between smm_logz_f64 and smm_logz_bwd_f64 / smm_sample_f64 / smm_entropy_f64 / smm_kl_f64. */
 size_t smm_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host);
 
 /* Byte offset, inside the workspace, of the int32 error word the kernels set.  1: a NaN / inf-inf reached the DP of
@@ -300,6 +302,31 @@ int smm_entropy_f64(const smm_shape *shape, const int64_t *lengths_host, const i
                     const double *elp, const double *trans, const double *init, const double *len_scores,
                     const double *endpen, const double *logz, double *entropy_out,
                     void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Exact KL divergence KL(p || q) = sum_y p(y | x) log(p(y | x) / q(y | x)) and cross-entropy H(p, q) = H(p) + KL(p || q) between
+ * two segmentation posteriors of the same lattice (same shape, lengths, frame offsets, groups, kp, state counts; other tables),
+ * in nats (csrc/smm_kl.hip: the chain rule of relative entropy over the decisions of smm_sample_f64's backward walk, every term
+ * >= 0).  ws_p must follow smm_logz_f64 on this shape with p's tables, ws_q smm_logz_f64 on this shape with q's; logz_p / logz_q
+ * are their outputs.  Without SMM_SHAPE_LOGZ_BOTH the call runs p's time-reversed recursion itself (as smm_entropy_f64 does);
+ * with it, p's smm_logz_f64 has.  q needs only its forward histories, and ws_q is not written.  The value is exactly 0.0 when
+ * p's and q's inputs are bit-identical; the per-video partial sums are reduced in a fixed order (bit-identical run to run).
+ * xent_out of p with itself is smm_entropy_f64's value.  No gradient.
+ *   kl_out    dev fp64 [b]
+ *   xent_out  dev fp64 [b] or NULL
+ * +inf (no error) when q gives probability 0 to a segmentation p does not (a true -inf on q's side only, or log Z_q = -inf).
+ * SMM_ERR_ARG when kl_out, a required input (elp, trans, init, len_scores, logz of either side) or ws_q is NULL, before
+ * anything is staged; SMM_ERR_WORKSPACE when either workspace is shorter than smm_workspace_bytes.  The error word (in ws_p) is
+ * set, and that video's values are NaN, when log Z_p is not finite, a NaN reached either side's histories or tables, or a node
+ * of non-zero p-probability has no candidate of finite p-weight.
+ */
+int smm_kl_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+               const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+               const double *elp_p, const double *trans_p, const double *init_p, const double *len_p,
+               const double *endpen_p, const double *logz_p, void *ws_p, size_t ws_p_bytes,
+               const double *elp_q, const double *trans_q, const double *init_q, const double *len_q,
+               const double *endpen_q, const double *logz_q, void *ws_q, size_t ws_q_bytes,
+               double *kl_out, double *xent_out, void *stream);
 
 /*
  * The k highest-scoring segmentations (k-best Viterbi: the DP in the k-max semiring; csrc/smm_kbest.hip).  The candidate set
