@@ -11,6 +11,7 @@ SYMBOLS = [
     "smm_env_reload", "smm_release_cached_plans", "smm_cached_plan_bytes",
     "smm_emission_f64", "smm_emission_bwd_f64", "smm_viterbi_f64", "smm_viterbi_f32", "smm_decode_f32", "smm_logz_f64", "smm_logz_bwd_f64",
     "smm_sample_f64", "smm_entropy_f64", "smm_kl_f64", "smm_kbest_workspace_bytes", "smm_kbest_f64",
+    "smm_entropy_bwd_scratch_bytes", "smm_entropy_bwd_f64", "smm_kl_bwd_f64",
     "smm_factor_tables_f64", "smm_factor_tables_bwd_f64",
     "smm_dense_workspace_bytes", "smm_dense_dp_f32", "smm_dense_marginals_f32",
     "smm_eval_workspace_bytes", "smm_eval_confusion_i64", "smm_eval_videos_i64",
@@ -32,6 +33,8 @@ class SmmTablesShape(ctypes.Structure):
 SHAPE_NO_EOS = 1
 SHAPE_LOGZ_BOTH = 2
 SHAPE_NO_TIME_SPLIT = 4
+KL_BWD_CROSS_ENTROPY = 0
+KL_BWD_KL = 1
 
 
 class SmmEvalShape(ctypes.Structure):
@@ -89,6 +92,15 @@ def load():
     lib.smm_kl_f64.restype = ctypes.c_int
     lib.smm_kl_f64.argtypes = [ctypes.POINTER(SmmShape)] + [ctypes.c_void_p] * 11 + [ctypes.c_void_p, ctypes.c_size_t] \
         + [ctypes.c_void_p] * 6 + [ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 3
+    lib.smm_entropy_bwd_scratch_bytes.restype = ctypes.c_size_t
+    lib.smm_entropy_bwd_scratch_bytes.argtypes = [ctypes.POINTER(SmmShape), ctypes.c_void_p]
+    lib.smm_entropy_bwd_f64.restype = ctypes.c_int
+    lib.smm_entropy_bwd_f64.argtypes = [ctypes.POINTER(SmmShape)] + [ctypes.c_void_p] * 17 + [ctypes.c_void_p, ctypes.c_size_t] \
+        + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.smm_kl_bwd_f64.restype = ctypes.c_int
+    lib.smm_kl_bwd_f64.argtypes = [ctypes.POINTER(SmmShape)] + [ctypes.c_void_p] * 11 + [ctypes.c_void_p, ctypes.c_size_t] \
+        + [ctypes.c_void_p] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32] + [ctypes.c_void_p] * 6 \
+        + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     lib.smm_dp_timing_enable.restype = None
     lib.smm_dp_timing_enable.argtypes = [ctypes.c_int]
     lib.smm_dp_timing_read.restype = ctypes.c_int

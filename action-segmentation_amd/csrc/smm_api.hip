@@ -1519,6 +1519,141 @@ extern "C" int smm_kl_f64(const smm_shape *shape, const int64_t *lengths_host, c
     return SMM_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ entropy / KL gradients
+// The caller's scratch of smm_entropy_bwd_f64 / smm_kl_bwd_f64: per video six [T+1][c_max] blocks (the etas of both directions
+// and the occupancy differences), then one fixed part per video (its tables and values)
+static bool ebwd_layout(const smm_shape *s, const int64_t *lengths, size_t *pv_base, size_t *total_doubles)
+{
+    if (!shape_ok(s) || !lengths) return false;
+    if (s->c_max > SMM_MAX_STATES || s->k_rows > SMM_MAX_K_ROWS) return false;
+    size_t h = 0;
+    for (int i = 0; i < s->b; ++i) {
+        if (lengths[i] < 1 || lengths[i] > s->t_max) return false;
+        h += 6 * (size_t)s->c_max * (size_t)(lengths[i] + 1);
+    }
+    *pv_base = h;
+    *total_doubles = h + (size_t)s->b * smm_entropy_bwd_fixed_doubles(s->c_max, s->k_rows);
+    return true;
+}
+
+extern "C" size_t smm_entropy_bwd_scratch_bytes(const smm_shape *shape, const int64_t *lengths_host)
+{
+    size_t pv = 0, tot = 0;
+    if (!ebwd_layout(shape, lengths_host, &pv, &tot)) return 0;
+    return sizeof(double) * tot;
+}
+
+// the time-reversed recursion of one side into `hist` (smm_logz_bwd_f64's): transposed transitions and closing values in `tabs`
+static int ebwd_reversed(const smm_shape *shape, const Staged &st, double *hist, double *tabs, const double *elp,
+                         const double *trans, const double *init, const double *len, const double *endpen, hipStream_t hs)
+{
+    const size_t g = shape->n_groups, cm = shape->c_max;
+    double *trans_t = tabs, *logz_b = tabs + g * cm * cm;
+    smm_launch_transpose(trans, trans_t, (int)g, (int)cm, hs);
+    SmmDpArgs a{};
+    a.videos = st.videos; a.order = st.order; a.n_states = st.n_states;
+    a.elp = elp; a.trans = trans_t; a.init = init; a.len = len; a.endpen = endpen;
+    a.hist = hist; a.err = st.err;
+    a.c_max = shape->c_max; a.k_rows = shape->k_rows; a.t_max = shape->t_max; a.b = shape->b;
+    a.flags = 2;
+    if (shape->flags & SMM_SHAPE_NO_EOS) { a.flags |= 8; a.endpen = nullptr; }
+    return smm_launch_logz(a, logz_b, ring_regs(st.kp_max), st.c_need, hs);
+}
+
+// both entry points: p's histories in st, r's in hist_r (r = p for the entropy)
+static int ebwd_run(const smm_shape *shape, const int64_t *lengths_host, const Staged &st, const double *hist_r,
+                    const double *elp_p, const double *trans_p, const double *init_p, const double *len_p,
+                    const double *endpen_p, const double *logz_p, const double *elp_r, const double *trans_r,
+                    const double *init_r, const double *len_r, const double *endpen_r, const double *logz_r, int kl,
+                    const double *grad_out, double *g_elp, double *g_trans, double *g_init, double *g_len, double *value_out,
+                    void *scratch, hipStream_t hs)
+{
+    size_t pv_base = 0, tot = 0;
+    ebwd_layout(shape, lengths_host, &pv_base, &tot);
+    const size_t g = shape->n_groups, cm = shape->c_max;
+    const bool no_eos = (shape->flags & SMM_SHAPE_NO_EOS) != 0;
+    double *sc = static_cast<double *>(scratch);
+    {
+        void *const zp[2] = {g_elp, sc + pv_base};
+        const size_t zb[2] = {sizeof(double) * (size_t)shape->total_frames * cm, sizeof(double) * (tot - pv_base)};
+        SMM_HIP((hipError_t)smm_zero_multi_async(zp, zb, 2, hs));
+    }
+    SmmEntBwdArgs e{};
+    e.videos = st.videos; e.n_states = st.n_states; e.hist_p = st.hist; e.hist_r = hist_r;
+    e.elp_p = elp_p; e.elp_r = elp_r; e.trans_p = trans_p; e.trans_r = trans_r; e.init_p = init_p; e.init_r = init_r;
+    e.len_p = len_p; e.len_r = len_r;
+    e.endpen_p = no_eos ? nullptr : endpen_p; e.endpen_r = no_eos ? nullptr : endpen_r;
+    e.logz_p = logz_p; e.logz_r = logz_r; e.grad_out = grad_out;
+    e.g_elp = g_elp; e.g_trans = g_trans; e.g_init = g_init; e.g_len = g_len; e.value = value_out;
+    e.scratch = sc; e.pv_base = (int64_t)pv_base; e.err = st.err;
+    e.c_max = shape->c_max; e.k_rows = shape->k_rows; e.b = shape->b; e.n_groups = (int32_t)g; e.no_eos = no_eos ? 1 : 0;
+    e.kl = kl;
+    smm_launch_entropy_bwd(e, shape->t_max, st.kp_max, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
+extern "C" int smm_entropy_bwd_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                   const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                   const double *elp, const double *trans, const double *init, const double *len_scores,
+                                   const double *endpen, const double *logz, const double *grad_out, double *g_elp,
+                                   double *g_trans, double *g_init, double *g_len, double *value_out, void *scratch,
+                                   size_t scratch_bytes, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!elp || !trans || !init || !len_scores || !logz || !g_elp || !g_trans || !g_init || !g_len || !scratch)
+        return SMM_ERR_ARG;
+    const size_t need = smm_entropy_bwd_scratch_bytes(shape, lengths_host);
+    if (need == 0) return SMM_ERR_ARG;
+    if (scratch_bytes < need) return SMM_ERR_WORKSPACE;
+    Staged st;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes,
+                   hs, &st);
+    if (rc != SMM_OK) return rc;
+    if (!(shape->flags & SMM_SHAPE_LOGZ_BOTH)) {   // the backward histories, as smm_logz_bwd_f64 makes them
+        rc = ebwd_reversed(shape, st, st.hist, st.tabs, elp, trans, init, len_scores, endpen, hs);
+        if (rc != SMM_OK) return rc;
+    }
+    return ebwd_run(shape, lengths_host, st, st.hist, elp, trans, init, len_scores, endpen, logz, elp, trans, init, len_scores,
+                    endpen, logz, 0, grad_out, g_elp, g_trans, g_init, g_len, value_out, scratch, hs);
+}
+
+extern "C" int smm_kl_bwd_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                              const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                              const double *elp_p, const double *trans_p, const double *init_p, const double *len_p,
+                              const double *endpen_p, const double *logz_p, void *ws_p, size_t ws_p_bytes,
+                              const double *elp_q, const double *trans_q, const double *init_q, const double *len_q,
+                              const double *endpen_q, const double *logz_q, void *ws_q, size_t ws_q_bytes, int32_t mode,
+                              const double *grad_out, double *g_elp, double *g_trans, double *g_init, double *g_len,
+                              double *value_out, void *scratch, size_t scratch_bytes, void *stream)
+{
+    if (mode != SMM_KL_BWD_CROSS_ENTROPY && mode != SMM_KL_BWD_KL) return SMM_ERR_ARG;
+    if (!elp_p || !trans_p || !init_p || !len_p || !logz_p || !elp_q || !trans_q || !init_q || !len_q || !logz_q || !ws_q ||
+        !g_elp || !g_trans || !g_init || !g_len || !scratch)
+        return SMM_ERR_ARG;
+    const size_t need = smm_workspace_bytes(shape, lengths_host);
+    if (need == 0) return SMM_ERR_ARG;
+    if (ws_q_bytes < need) return SMM_ERR_WORKSPACE;
+    const size_t sneed = smm_entropy_bwd_scratch_bytes(shape, lengths_host);
+    if (sneed == 0) return SMM_ERR_ARG;
+    if (scratch_bytes < sneed) return SMM_ERR_WORKSPACE;
+    Staged st;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, ws_p, ws_p_bytes, hs, &st);
+    if (rc != SMM_OK) return rc;
+    Staged sq;
+    plan_point(make_plan(shape, lengths_host), ws_q, &sq);
+    if (!(shape->flags & SMM_SHAPE_LOGZ_BOTH)) {   // both sides' backward histories
+        rc = ebwd_reversed(shape, st, st.hist, st.tabs, elp_p, trans_p, init_p, len_p, endpen_p, hs);
+        if (rc == SMM_OK && sq.hist != st.hist)
+            rc = ebwd_reversed(shape, st, sq.hist, sq.tabs, elp_q, trans_q, init_q, len_q, endpen_q, hs);
+        if (rc != SMM_OK) return rc;
+    }
+    return ebwd_run(shape, lengths_host, st, sq.hist, elp_p, trans_p, init_p, len_p, endpen_p, logz_p, elp_q, trans_q, init_q,
+                    len_q, endpen_q, logz_q, mode == SMM_KL_BWD_KL ? 1 : 0, grad_out, g_elp, g_trans, g_init, g_len, value_out,
+                    scratch, hs);
+}
+
 // ------------------------------------------------------------------------------------------------ k best
 // Behind the plan's workspace (its `total`): the length table state-major, the H lists of the last `ring` positions (and their
 // heads apart, class-major), the back-pointers of G and H at every position, the closing lists, the back-trace's scratch.

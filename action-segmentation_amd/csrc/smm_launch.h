@@ -183,3 +183,26 @@ struct SmmKlArgs {
     int32_t c_max, k_rows, b, no_eos;
 };
 void smm_launch_kl(const SmmKlArgs &a, int t_max, hipStream_t stream);
+
+// gradients of the entropy, cross-entropy and KL with respect to p's tables (smm_entropy_bwd.hip): after smm_launch_logz forward
+// AND time-reversed on p's workspace and on r's (r = q; for the entropy r = p, the same pointers)
+struct SmmEntBwdArgs {
+    const SmmVideo *videos;
+    const int32_t *n_states;
+    const double *hist_p, *hist_r;        // per video: F_cum, F_h, F_g, B_cum, B_h, B_g, ...; each [T+1][c_max]
+    const double *elp_p, *elp_r;          // [total_frames][c_max]   (no_eos only: the closing label's emission)
+    const double *trans_p, *trans_r;      // [g][c_max][c_max]  [to][from]
+    const double *init_p, *init_r;        // [g][c_max]
+    const double *len_p, *len_r;          // [g][k_rows][c_max]
+    const double *endpen_p, *endpen_r;    // [b][c_max] or null (EOS mode only)
+    const double *logz_p, *logz_r;        // [b]
+    const double *grad_out;               // [b] or null (= 1)
+    double *g_elp, *g_trans, *g_init, *g_len;   // smm_logz_bwd_f64's layouts; g_elp zero at launch
+    double *value;                        // [b][2] or null: the value by the two decompositions
+    double *scratch;                      // caller's: per video 6 [T+1][c_max] blocks at 6/8 of hist_off, then the fixed parts
+    int64_t pv_base;                      // doubles in front of the fixed parts (zero at launch)
+    int32_t *err;                         // sticky error word (p's workspace)
+    int32_t c_max, k_rows, b, n_groups, no_eos, kl;
+};
+size_t smm_entropy_bwd_fixed_doubles(int c_max, int k_rows);   // the fixed part of one video
+void smm_launch_entropy_bwd(const SmmEntBwdArgs &a, int t_max, int kp_max, hipStream_t stream);

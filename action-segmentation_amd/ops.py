@@ -486,7 +486,7 @@ def entropy(batch, elp, trans, init, len_scores, logz_val, endpen=None, ws=None,
     ``logz`` for the same batch and tables with the same workspace (``with_backward``: as passed to ``logz``; without it the
     call runs the time-reversed recursion itself); ``logz_val`` = its output.  A video whose log Z is not finite, or whose
     histories a NaN reached, gets NaN and sets the error word (``error_flag(batch, ws=ws)``).  Bit-identical run to run.
-    No gradient: d H / d theta needs the posterior covariance of the potentials, which no kernel computes."""
+    Its gradient: ``entropy_bwd``."""
     lib = _lib.load()
     shape = _shape_with(batch, _lib.SHAPE_LOGZ_BOTH if with_backward else 0)
     dev = elp.device
@@ -511,7 +511,7 @@ def kl(batch, p, q, with_backward=False, want_cross_entropy=False):
     recursion itself; q needs only its forward histories and its workspace is only read).  +inf, without an error, where q gives
     probability 0 to what p does not.  A video whose log Z_p is not finite, or whose histories a NaN reached on either side,
     gets NaN and sets the error word of p's workspace (``error_flag(batch, ws=p[6])``).  Exactly 0 for bit-identical sides;
-    bit-identical run to run.  No gradient."""
+    bit-identical run to run.  Its gradient: ``kl_bwd``."""
     lib = _lib.load()
     shape = _shape_with(batch, _lib.SHAPE_LOGZ_BOTH if with_backward else 0)
     f64 = torch.float64
@@ -530,6 +530,76 @@ def kl(batch, p, q, with_backward=False, want_cross_entropy=False):
         ctypes.byref(shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(kp),
         ctypes.c_void_p(ns), *side(p, 'p'), *side(q, 'q'), _dev(out, f64, 'kl'), _dev(xent, f64, 'cross_entropy'), _stream()))
     return (out, xent) if want_cross_entropy else out
+
+
+def entropy_bwd_scratch_bytes(batch):
+    """Bytes of the caller's scratch ``entropy_bwd`` / ``kl_bwd`` need (smm_entropy_bwd_scratch_bytes; host only)."""
+    n = _lib.load().smm_entropy_bwd_scratch_bytes(ctypes.byref(batch.shape), batch.lengths.ctypes.data)
+    if n == 0:
+        raise _lib.SmmError("libsmmdp: invalid batch shape for the entropy gradient")
+    return n
+
+
+def _ebwd_outputs(batch, elp, trans, init, len_scores, want_value):
+    f64 = torch.float64
+    dev = elp.device
+    g = dict(elp=torch.empty_like(elp), trans=torch.empty_like(trans), init=torch.empty_like(init),
+             len=torch.empty_like(len_scores))
+    g['value'] = torch.empty((batch.b, 2), dtype=f64, device=dev) if want_value else None
+    scratch = torch.empty(entropy_bwd_scratch_bytes(batch), dtype=torch.uint8, device=dev)
+    return g, scratch
+
+
+def entropy_bwd(batch, elp, trans, init, len_scores, logz_val, grad_out=None, endpen=None, ws=None, with_backward=False,
+                want_value=False):
+    """Gradient of sum_i grad_out[i] * H_i, H = ``entropy``, with respect to the tables (smm_entropy_bwd_f64).  Must follow
+    ``logz`` for the same batch and tables with the same workspace (``with_backward``: its time-reversed recursion already ran,
+    in ``logz`` or in ``entropy``).  -> dict(elp [total_frames, c_max], trans, init, len) fp64 in ``logz_bwd``'s layouts, and
+    ``value`` fp64 [b, 2] (H by the two decompositions) with ``want_value``.  A video whose H is not finite gets NaN rows.
+    Bit-identical run to run."""
+    lib = _lib.load()
+    shape = _shape_with(batch, _lib.SHAPE_LOGZ_BOTH if with_backward else 0)
+    f64 = torch.float64
+    g, scratch = _ebwd_outputs(batch, elp, trans, init, len_scores, want_value)
+    if ws is None:
+        ws = workspace(batch.workspace_bytes(), elp.device)
+    ln, fo, gr, kp, ns = batch.host_ptrs()
+    _lib.check(lib.smm_entropy_bwd_f64(
+        ctypes.byref(shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(kp),
+        ctypes.c_void_p(ns), _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'),
+        _dev(len_scores, f64, 'len_scores'), _dev(endpen, f64, 'endpen'), _dev(logz_val, f64, 'logz'),
+        _dev(grad_out, f64, 'grad_out'), _dev(g['elp'], f64, 'g_elp'), _dev(g['trans'], f64, 'g_trans'),
+        _dev(g['init'], f64, 'g_init'), _dev(g['len'], f64, 'g_len'), _dev(g['value'], f64, 'value'),
+        ctypes.c_void_p(scratch.data_ptr()), ctypes.c_size_t(scratch.numel()),
+        ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream()))
+    return g
+
+
+def kl_bwd(batch, p, q, grad_out=None, with_backward=False, cross_entropy=False, want_value=False):
+    """Gradient of sum_i grad_out[i] * V_i with respect to p's tables (smm_kl_bwd_f64): V = KL(p || q), or H(p, q) with
+    ``cross_entropy``.  ``p`` and ``q`` as for ``kl``; ``with_backward``: both sides' time-reversed recursions already ran
+    (else the call runs both, and q's workspace is written).  -> dict as ``entropy_bwd``.  q's gradient is mu_q - mu_p: two
+    ``logz_bwd`` calls.  Exactly 0 for bit-identical sides (KL); bit-identical run to run."""
+    lib = _lib.load()
+    shape = _shape_with(batch, _lib.SHAPE_LOGZ_BOTH if with_backward else 0)
+    f64 = torch.float64
+    g, scratch = _ebwd_outputs(batch, p[0], p[1], p[2], p[3], want_value)
+
+    def side(t, tag):
+        elp, trans, init, len_scores, endpen, logz_val, ws = t
+        return [_dev(elp, f64, 'elp_' + tag), _dev(trans, f64, 'trans_' + tag), _dev(init, f64, 'init_' + tag),
+                _dev(len_scores, f64, 'len_scores_' + tag), _dev(endpen, f64, 'endpen_' + tag), _dev(logz_val, f64, 'logz_' + tag),
+                ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel())]
+
+    ln, fo, gr, kp, ns = batch.host_ptrs()
+    mode = _lib.KL_BWD_CROSS_ENTROPY if cross_entropy else _lib.KL_BWD_KL
+    _lib.check(lib.smm_kl_bwd_f64(
+        ctypes.byref(shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(kp),
+        ctypes.c_void_p(ns), *side(p, 'p'), *side(q, 'q'), ctypes.c_int32(mode), _dev(grad_out, f64, 'grad_out'),
+        _dev(g['elp'], f64, 'g_elp'), _dev(g['trans'], f64, 'g_trans'), _dev(g['init'], f64, 'g_init'),
+        _dev(g['len'], f64, 'g_len'), _dev(g['value'], f64, 'value'),
+        ctypes.c_void_p(scratch.data_ptr()), ctypes.c_size_t(scratch.numel()), _stream()))
+    return g
 
 
 MAX_KBEST = 16

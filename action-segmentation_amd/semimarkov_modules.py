@@ -74,6 +74,45 @@ class _LogPartition(torch.autograd.Function):
         return None, None, None, None, None, g_w, g_cst, g_iv, g['trans'], g['init'], g['len']
 
 
+def _table_grads(batch, x, g, ws):
+    """(g_w, g_cst, g_trans, g_init, g_len) from the gradients of the tables and elp: the emission chain rule, one pass over x."""
+    g_w, g_cst, _ = ops.emission_bwd(batch, x, g['elp'], ws=ws)
+    return g_w, g_cst, g['trans'], g['init'], g['len']
+
+
+class _PosteriorValue(torch.autograd.Function):
+    """The entropy H(p), cross-entropy H(p, q) or KL(p || q) of every video as a differentiable function of the fp64 factor
+    tables (w, cst, trans, init, len) of p, and of q for the two-sided values.  ``launch()`` computes the value exactly as the
+    non-differentiable method does and returns (value, p's launch, q's launch or None); each launch keeps its private workspace
+    (forward and time-reversed histories) until the backward runs.  Backward: smm_entropy_bwd_f64 / smm_kl_bwd_f64 for p's
+    tables, mu_q - mu_p (two smm_logz_bwd_f64) for q's, then the emission chain rule of each side."""
+
+    @staticmethod
+    def forward(ctx, kind, launch, *tables):
+        value, r, q = launch()
+        ctx.kind, ctx.r, ctx.q = kind, r, q
+        return value
+
+    @staticmethod
+    def backward(ctx, gv):
+        up = gv.to(torch.float64).contiguous()
+        r, q = ctx.r, ctx.q
+        b = r['batch']
+        side = lambda t: (t['elp'], t['trans'], t['init'], t['len'], t['endpen'], t['logz'], t['ws'])
+        if ctx.kind == 'entropy':
+            g = ops.entropy_bwd(b, r['elp'], r['trans'], r['init'], r['len'], r['logz'], grad_out=up, endpen=r['endpen'],
+                                ws=r['ws'], with_backward=True)
+            return (None, None) + _table_grads(b, r['x'], g, r['ws'])
+        # (kl_bwd runs both sides' time-reversed recursions: q's launch ran only the forward one)
+        g = ops.kl_bwd(b, side(r), side(q), grad_out=up, cross_entropy=ctx.kind == 'cross_entropy')
+        mq = ops.logz_bwd(b, q['elp'], q['trans'], q['init'], q['len'], q['logz'], grad_logz=up, endpen=q['endpen'],
+                          ws=q['ws'], with_backward=True)
+        mp = ops.logz_bwd(b, r['elp'], r['trans'], r['init'], r['len'], r['logz'], grad_logz=up, endpen=r['endpen'],
+                          ws=r['ws'], with_backward=True)
+        gq = {k: mq[k] - mp[k] for k in ('elp', 'trans', 'init', 'len')}
+        return (None, None) + _table_grads(b, r['x'], g, r['ws']) + _table_grads(b, q['x'], gq, q['ws'])
+
+
 class _FactorTables(torch.autograd.Function):
     """The fp64 factor tables of every parameter group of a launch as ONE differentiable node: smm_factor_tables_f64
     forward, smm_factor_tables_bwd_f64 backward (csrc/smm_tables.hip), instead of ~45 small torch ops each way.
@@ -686,7 +725,8 @@ class SemiMarkovModule(nn.Module):
         ws = torch.empty(batch.workspace_bytes(), dtype=torch.uint8, device=dev)
         elp, _ = ops.emission(batch, x, g1[0], g1[1], tab['inv_var'], cons=cons)
         z = ops.logz(batch, elp, g1[2], g1[3], g1[4], endpen=endpen, ws=ws, with_backward=with_backward)
-        return dict(batch=batch, elp=elp, trans=g1[2], init=g1[3], len=g1[4], class_map=g1[5], endpen=endpen, logz=z, ws=ws)
+        return dict(batch=batch, elp=elp, trans=g1[2], init=g1[3], len=g1[4], class_map=g1[5], endpen=endpen, logz=z, ws=ws,
+                    x=x, valid_classes=valid_classes)
 
     @torch.no_grad()
     def sample(self, features, lengths, valid_classes_per_instance, n_samples=1, seed=0, add_eos=True,
@@ -719,19 +759,30 @@ class SemiMarkovModule(nn.Module):
         b, tmax = features.shape[:2]
         return g['elp'].view(b, tmax, -1)
 
-    @torch.no_grad()
-    def entropy(self, features, lengths, valid_classes_per_instance, add_eos=True, additional_allowed_ends_per_instance=None,
-                constraints=None):
-        """Exact entropy H(y | x) = -sum_y p(y | x) log p(y | x) of each video's segmentation posterior, in nats: fp64 b on the
-        device (argument conventions of ``viterbi``).  One emission launch, one log Z launch (forward and time-reversed), one
-        entropy launch (smm_entropy_f64); the value keeps its relative accuracy on confident videos (H -> 0).  Raises
-        SmmError when a NaN reached the DP.  No autograd: the gradient of H needs second-order terms (a follow-up)."""
+    def _entropy(self, features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
+                 constraints):
         r = self._posterior_launch(features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
                                    constraints, 'entropy', with_backward=True)
         h = ops.entropy(r['batch'], r['elp'], r['trans'], r['init'], r['len'], r['logz'], endpen=r['endpen'], ws=r['ws'],
                         with_backward=True)
         ops.check_decoded(r['batch'], dict(_err=ops._err_copy(r['batch'], r['ws'])))
-        return h
+        return h, r, None
+
+    def entropy(self, features, lengths, valid_classes_per_instance, add_eos=True, additional_allowed_ends_per_instance=None,
+                constraints=None, *, differentiable=False):
+        """Exact entropy H(y | x) = -sum_y p(y | x) log p(y | x) of each video's segmentation posterior, in nats: fp64 b on the
+        device (argument conventions of ``viterbi``).  One emission launch, one log Z launch (forward and time-reversed), one
+        entropy launch (smm_entropy_f64); the value keeps its relative accuracy on confident videos (H -> 0).  Raises
+        SmmError when a NaN reached the DP.
+        ``differentiable``: the same value (bit for bit), differentiable with respect to the module's parameters: the backward
+        runs smm_entropy_bwd_f64 and the chain rule through the emission scorer and the factor tables (``log_partition``'s)."""
+        args = (features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance, constraints)
+        if not differentiable:
+            with torch.no_grad():
+                return self._entropy(*args)[0]
+        self._require_device(features, 'entropy')
+        tabs = self._differentiable_tables(self._check_valid_classes(valid_classes_per_instance), features.device)
+        return _PosteriorValue.apply('entropy', lambda: self._entropy(*args), *tabs)
 
     def _packed_posterior_launch(self, pc, what):
         x = pc.x
@@ -762,13 +813,24 @@ class SemiMarkovModule(nn.Module):
         g = ops.logz_bwd(pc.batch, elp, t['trans'], t['init'], t['len'], z, endpen=pc.endpen, ws=ws)
         return g['elp']
 
-    @torch.no_grad()
-    def entropy_packed(self, pc):
-        """``entropy`` for a whole PackedCorpus: fp64 n_videos on the device, in the order of ``pc.video_names``."""
+    def _entropy_packed(self, pc):
         t, elp, z, ws = self._packed_posterior_launch(pc, 'entropy_packed')
         h = ops.entropy(pc.batch, elp, t['trans'], t['init'], t['len'], z, endpen=pc.endpen, ws=ws)
         ops.check_decoded(pc.batch, dict(_err=ops._err_copy(pc.batch, ws)))
-        return h
+        # (the entropy launch ran the time-reversed recursion into ws: the backward finds both directions there)
+        r = dict(batch=pc.batch, elp=elp, trans=t['trans'], init=t['init'], len=t['len'], endpen=pc.endpen, logz=z, ws=ws, x=pc.x)
+        return h, r, None
+
+    def entropy_packed(self, pc, *, differentiable=False):
+        """``entropy`` for a whole PackedCorpus: fp64 n_videos on the device, in the order of ``pc.video_names``.
+        ``differentiable``: as ``entropy``'s; the tables are ``stacked_tables(pc, differentiable=True)``."""
+        if not differentiable:
+            with torch.no_grad():
+                return self._entropy_packed(pc)[0]
+        self._require_device(pc.x, 'entropy_packed')
+        st = self.stacked_tables(pc, differentiable=True)[0]
+        return _PosteriorValue.apply('entropy', lambda: self._entropy_packed(pc),
+                                     *(st[k] for k in ('w', 'cst', 'trans', 'init', 'len')))
 
     # ------------------------------------------------------------------ KL divergence and cross-entropy (smm_kl_f64)
     def _check_same_lattice(self, other, what):
@@ -801,29 +863,44 @@ class SemiMarkovModule(nn.Module):
         side = lambda t: (t['elp'], t['trans'], t['init'], t['len'], t['endpen'], t['logz'], t['ws'])
         out = ops.kl(r['batch'], side(r), side(q), with_backward=True, want_cross_entropy=want_cross_entropy)
         ops.check_decoded(r['batch'], dict(_err=ops._err_copy(r['batch'], r['ws'])))
-        return out[1] if want_cross_entropy else out
+        return (out[1] if want_cross_entropy else out), r, q
 
-    @torch.no_grad()
+    def _kl_value(self, other, args, what, want_cross_entropy, differentiable):
+        if not differentiable:
+            with torch.no_grad():
+                return self._kl(other, *args, what, want_cross_entropy)[0]
+        self._check_same_lattice(other, what)
+        features = args[0]
+        self._require_device(features, what)
+        valid = self._check_valid_classes(args[2])
+        tabs = self._differentiable_tables(valid, features.device) + other._differentiable_tables(valid, features.device)
+        return _PosteriorValue.apply(what, lambda: self._kl(other, *args, what, want_cross_entropy), *tabs)
+
     def kl_divergence(self, other, features, lengths, valid_classes_per_instance, add_eos=True,
-                      additional_allowed_ends_per_instance=None, constraints=None, other_constraints=None):
+                      additional_allowed_ends_per_instance=None, constraints=None, other_constraints=None, *,
+                      differentiable=False):
         """Exact KL(p || q) = sum_y p(y | x) log(p(y | x) / q(y | x)) per video, in nats: fp64 b on the device (argument
         conventions of ``viterbi``).  p is this module's posterior under ``constraints``, q is ``other``'s under
         ``other_constraints`` (``other`` may be ``self``); each side builds its tables, emissions and end penalties from its own
         parameters and allowed ends.  Two emission launches, two log Z launches (p's forward and time-reversed), one KL launch
         (smm_kl_f64); the value keeps its relative accuracy as q -> p and is exactly 0 for the same inputs.  +inf where q gives
         probability 0 to a segmentation p does not.  Raises ValueError when the two modules' lattices differ (n_classes,
-        n_dims, max_k), SmmError when a NaN reached the DP.  No autograd."""
-        return self._kl(other, features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
-                        constraints, other_constraints, 'kl_divergence', False)
+        n_dims, max_k), SmmError when a NaN reached the DP.
+        ``differentiable``: the same value (bit for bit), differentiable with respect to both modules' parameters: p's side by
+        smm_kl_bwd_f64, q's as mu_q - mu_p (two smm_logz_bwd_f64); a video whose KL is +inf gets NaN gradients."""
+        args = (features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance, constraints,
+                other_constraints)
+        return self._kl_value(other, args, 'kl_divergence', False, differentiable)
 
-    @torch.no_grad()
     def cross_entropy(self, other, features, lengths, valid_classes_per_instance, add_eos=True,
-                      additional_allowed_ends_per_instance=None, constraints=None, other_constraints=None):
+                      additional_allowed_ends_per_instance=None, constraints=None, other_constraints=None, *,
+                      differentiable=False):
         """Exact cross-entropy H(p, q) = -sum_y p(y | x) log q(y | x) = H(p) + KL(p || q) per video, in nats: fp64 b on the
         device.  Arguments and launches as ``kl_divergence``; with ``other`` = ``self`` and the same constraints it is
-        ``entropy``'s value."""
-        return self._kl(other, features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
-                        constraints, other_constraints, 'cross_entropy', True)
+        ``entropy``'s value.  ``differentiable``: as ``kl_divergence``'s."""
+        args = (features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance, constraints,
+                other_constraints)
+        return self._kl_value(other, args, 'cross_entropy', True, differentiable)
 
     def _kl_packed(self, other, pc, what, want_cross_entropy):
         self._check_same_lattice(other, what)
@@ -1144,16 +1221,8 @@ class SemiMarkovModule(nn.Module):
             total = total.index_add(0, li(pen_i), torch.full((len(pen_i),), BIG_NEG, dtype=f64, device=dev))
         return total
 
-    def log_partition(self, features, lengths, valid_classes, additional_allowed_ends_per_instance=None,
-                      constraints=None, no_eos=False):
-        """log Z per instance on the device, differentiable w.r.t. the module's parameters
-        (smm_emission_f64 + smm_logz_f64 forward, smm_logz_bwd_f64 backward)."""
-        self._require_device(features, 'log_partition')
-        b, tmax, d = features.shape
-        dev = features.device
-        lengths_host = lengths.detach().cpu().numpy().astype(np.int64)
-        assert int(lengths_host.max()) == tmax
-        self._check_no_eos_lengths(lengths_host, no_eos)
+    def _one_group_tables(self, valid_classes, dev):
+        """The fp64 tables of one class set as a stack of one group, with autograd history -> (tables, c, k_rows)."""
         if self.max_k > 1:
             # one-group stack (HIP table kernels for fp32 parameters on the GPU); the index tensors are kept per class set
             cache = self.__dict__.setdefault('_single_group', {})
@@ -1168,6 +1237,24 @@ class SemiMarkovModule(nn.Module):
             c, k_rows = tab['init'].numel(), tab['len'].size(0)
             st = {n: tab[n].unsqueeze(0).contiguous() for n in ('w', 'cst', 'trans', 'init', 'len')}
             st['inv_var'] = tab['inv_var'].contiguous()
+        return st, c, k_rows
+
+    def _differentiable_tables(self, valid_classes, dev):
+        """(w, cst, trans, init, len) of one class set with autograd history: the inputs of _PosteriorValue."""
+        st = self._one_group_tables(valid_classes, dev)[0]
+        return tuple(st[k] for k in ('w', 'cst', 'trans', 'init', 'len'))
+
+    def log_partition(self, features, lengths, valid_classes, additional_allowed_ends_per_instance=None,
+                      constraints=None, no_eos=False):
+        """log Z per instance on the device, differentiable w.r.t. the module's parameters
+        (smm_emission_f64 + smm_logz_f64 forward, smm_logz_bwd_f64 backward)."""
+        self._require_device(features, 'log_partition')
+        b, tmax, d = features.shape
+        dev = features.device
+        lengths_host = lengths.detach().cpu().numpy().astype(np.int64)
+        assert int(lengths_host.max()) == tmax
+        self._check_no_eos_lengths(lengths_host, no_eos)
+        st, c, k_rows = self._one_group_tables(valid_classes, dev)
         batch = ops.Batch(lengths_host, [c], k_rows, c_max=c, t_max=tmax, total_frames=b * tmax, d=d, no_eos=no_eos,
                           no_time_split=self._hard_masks())
         x = features.detach().to(torch.float32).contiguous().view(b * tmax, d)

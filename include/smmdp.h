@@ -18,6 +18,8 @@
  *                              calls it)
  *   smm_kl_f64              <- pytorch-struct's SemiMarkovCRF(...).kl / cross_entropy (exact KL(p || q) and H(p, q) per
  *                              video between two posteriors of one lattice; the reference never calls them)
+ *   smm_entropy_bwd_f64 /   <- autograd through pytorch-struct's entropy / kl / cross_entropy (the gradients of the three
+ *   smm_kl_bwd_f64             values with respect to p's tables)
  *   smm_kbest_f64           <- pytorch-struct's SemiMarkovCRF(...).kmax / topk (the k best segmentations; the reference never
  *                              calls it)
  *
@@ -291,7 +293,7 @@ int smm_sample_f64(const smm_shape *shape, const int64_t *lengths_host, const in
  * accuracy as H -> 0).  Must follow smm_logz_f64 on the same shape, tables and workspace; logz = that call's output.  Without
  * SMM_SHAPE_LOGZ_BOTH the call runs the time-reversed recursion itself (as smm_logz_bwd_f64 does); with it, smm_logz_f64 has.
  * The forward and backward histories are left as they were (smm_sample_f64 / smm_logz_bwd_f64 may follow); the per-video
- * partial sums are reduced in a fixed order, so the result is bit-identical run to run.  No gradient.
+ * partial sums are reduced in a fixed order, so the result is bit-identical run to run.  Gradient: smm_entropy_bwd_f64.
  *   entropy_out  dev fp64 [b]
  * SMM_ERR_ARG when entropy_out or a required input (elp, trans, init, len_scores, logz) is NULL, before anything is staged.
  * The error word is set (and that video's value is NaN) when log Z is not finite, a NaN reached the histories, or a node of
@@ -311,7 +313,7 @@ int smm_entropy_f64(const smm_shape *shape, const int64_t *lengths_host, const i
  * are their outputs.  Without SMM_SHAPE_LOGZ_BOTH the call runs p's time-reversed recursion itself (as smm_entropy_f64 does);
  * with it, p's smm_logz_f64 has.  q needs only its forward histories, and ws_q is not written.  The value is exactly 0.0 when
  * p's and q's inputs are bit-identical; the per-video partial sums are reduced in a fixed order (bit-identical run to run).
- * xent_out of p with itself is smm_entropy_f64's value.  No gradient.
+ * xent_out of p with itself is smm_entropy_f64's value.  Gradient: smm_kl_bwd_f64.
  *   kl_out    dev fp64 [b]
  *   xent_out  dev fp64 [b] or NULL
  * +inf (no error) when q gives probability 0 to a segmentation p does not (a true -inf on q's side only, or log Z_q = -inf).
@@ -327,6 +329,45 @@ int smm_kl_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_
                const double *elp_q, const double *trans_q, const double *init_q, const double *len_q,
                const double *endpen_q, const double *logz_q, void *ws_q, size_t ws_q_bytes,
                double *kl_out, double *xent_out, void *stream);
+
+/*
+ * Gradients of the entropy, the cross-entropy and the KL divergence (csrc/smm_entropy_bwd.hip): d sum_i grad_out[i] V_i with
+ * respect to p's tables, V = H(p) (smm_entropy_bwd_f64) or H(p, q) / KL(p || q) (smm_kl_bwd_f64, `mode`).  The covariance
+ * -Cov_p(s_q, phi) (KL: Cov_p(s_p - s_q, phi)) of each occurrence is p(o) times its deviation, assembled from the prefix and
+ * suffix values eta- and eta+ of the chain rule over the sampler's decisions (two serial passes per video, one per direction),
+ * so every local term is >= 0 and nothing of the size of the scores cancels.  q's tables get no gradient here: it is
+ * mu_q - mu_p, two smm_logz_bwd_f64 calls.  Sums run in a fixed order: bit-identical run to run.  KL of bit-identical sides:
+ * exactly 0.0.
+ *   grad_out   dev fp64 [b] upstream gradient (NULL = ones)
+ *   g_elp, g_trans, g_init, g_len   smm_logz_bwd_f64's outputs and layouts (overwritten; padded rows and columns 0)
+ *   value_out  dev fp64 [b][2] or NULL: V by the two decompositions (eta- at the sampler's final decision, eta+ at the initial
+ *              class); both are the value smm_entropy_f64 / smm_kl_f64 returns, up to rounding
+ *   scratch    dev, smm_entropy_bwd_scratch_bytes: the etas (4 c_max (T+1) doubles per video) and the per-video sums; its contents
+ *              are undefined after the call.  smm_workspace_bytes does not change.
+ * Inputs as smm_entropy_f64 / smm_kl_f64 (ws_p after smm_logz_f64 with p's tables, ws_q with q's).  Without SMM_SHAPE_LOGZ_BOTH
+ * the call runs the time-reversed recursions itself (smm_kl_bwd_f64: of both sides; ws_q is written); with it, both sides'
+ * smm_logz_f64 have.  A video whose value is +inf or NaN gets NaN rows in g_elp, and its group's tables are NaN; a NaN value also
+ * sets the error word (in p's workspace).  SMM_ERR_ARG for a NULL output, table, logz or scratch, or a mode other than the two
+ * below, before anything is staged; SMM_ERR_WORKSPACE for a short scratch or q workspace.
+ */
+#define SMM_KL_BWD_CROSS_ENTROPY 0
+#define SMM_KL_BWD_KL 1
+/* host only; 0 on invalid arguments (those of smm_workspace_bytes, c_max or k_rows too large) */
+size_t smm_entropy_bwd_scratch_bytes(const smm_shape *shape, const int64_t *lengths_host);
+int smm_entropy_bwd_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                        const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                        const double *elp, const double *trans, const double *init, const double *len_scores,
+                        const double *endpen, const double *logz, const double *grad_out,
+                        double *g_elp, double *g_trans, double *g_init, double *g_len, double *value_out,
+                        void *scratch, size_t scratch_bytes, void *workspace, size_t workspace_bytes, void *stream);
+int smm_kl_bwd_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                   const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                   const double *elp_p, const double *trans_p, const double *init_p, const double *len_p,
+                   const double *endpen_p, const double *logz_p, void *ws_p, size_t ws_p_bytes,
+                   const double *elp_q, const double *trans_q, const double *init_q, const double *len_q,
+                   const double *endpen_q, const double *logz_q, void *ws_q, size_t ws_q_bytes, int32_t mode,
+                   const double *grad_out, double *g_elp, double *g_trans, double *g_init, double *g_len, double *value_out,
+                   void *scratch, size_t scratch_bytes, void *stream);
 
 /*
  * The k highest-scoring segmentations (k-best Viterbi: the DP in the k-max semiring; csrc/smm_kbest.hip).  The candidate set
