@@ -1738,6 +1738,52 @@ extern "C" int smm_kbest_f64(const smm_shape *shape, const int64_t *lengths_host
     return SMM_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ MBR decode
+// The history area of the plan (8 c_max (T + 1) doubles per video) holds what the MBR kernel keeps per video: cum, h, bt and the
+// suffix maxima of h, then the frame labels.  Nothing behind the plan's `total`.
+static bool mbr_shape_ok(const smm_shape *s, const int64_t *lengths)
+{
+    if (!shape_ok(s) || !lengths || s->c_max > SMM_MAX_STATES || s->k_rows > SMM_MAX_K_ROWS) return false;
+    for (int i = 0; i < s->b; ++i)
+        if (lengths[i] < 1 || lengths[i] > s->t_max) return false;
+    return true;
+}
+
+extern "C" size_t smm_mbr_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host)
+{
+    return mbr_shape_ok(shape, lengths_host) ? make_plan(shape, lengths_host).total : 0;
+}
+
+extern "C" int smm_mbr_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                           const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                           const double *gain, const double *trans, const double *init, const double *endpen,
+                           const int64_t *class_map, int64_t *spans, int64_t *labels, double *best, double *gain_sum,
+                           int32_t *n_segs, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!shape_ok(shape) || !lengths_host || !frame_offset_host || !n_states_host) return SMM_ERR_ARG;
+    if (shape->c_max > SMM_MAX_STATES || shape->k_rows > SMM_MAX_K_ROWS) return SMM_ERR_UNSUPPORTED;
+    if (!gain || !trans || !init || !workspace) return SMM_ERR_ARG;
+    if (!spans && !labels && !best && !gain_sum && !n_segs) return SMM_ERR_ARG;
+    const size_t need = smm_mbr_workspace_bytes(shape, lengths_host);
+    if (need == 0) return SMM_ERR_ARG;
+    if (workspace_bytes < need) return SMM_ERR_WORKSPACE;
+    Staged st;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    const int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes,
+                         hs, &st);
+    if (rc != SMM_OK) return rc;
+    const bool no_eos = (shape->flags & SMM_SHAPE_NO_EOS) != 0;
+    SmmMbrArgs a{};
+    a.videos = st.videos; a.order = st.order; a.n_states = st.n_states;
+    a.gain = gain; a.trans = trans; a.init = init; a.endpen = no_eos ? nullptr : endpen; a.class_map = class_map;
+    a.hist = st.hist;
+    a.spans = spans; a.labels = labels; a.best = best; a.gain_sum = gain_sum; a.n_segs = n_segs; a.err = st.err;
+    a.c_max = shape->c_max; a.t_max = shape->t_max; a.b = shape->b; a.no_eos = no_eos ? 1 : 0;
+    smm_launch_mbr(a, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ dense boundary
 static size_t dense_off(size_t &cur, size_t bytes)
 {

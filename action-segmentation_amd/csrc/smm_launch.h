@@ -206,3 +206,26 @@ struct SmmEntBwdArgs {
 };
 size_t smm_entropy_bwd_fixed_doubles(int c_max, int k_rows);   // the fixed part of one video
 void smm_launch_entropy_bwd(const SmmEntBwdArgs &a, int t_max, int kp_max, hipStream_t stream);
+
+// minimum-Bayes-risk decode under frame loss (smm_mbr.hip): the Viterbi DP on the substituted inputs of smmdp.h (smm_mbr_f64);
+// per video, behind hist_off: cum, h, bt (the transition max before - cum), the suffix maxima of h, each [T+1][c_max], then
+// the frame labels (int32 [T+1])
+struct SmmMbrArgs {
+    const SmmVideo *videos;
+    const int32_t *order;      // [b] wave -> video (most work first)
+    const int32_t *n_states;
+    const double *gain;        // [total_frames][c_max]
+    const double *trans;       // [g][c_max][c_max]  [to][from] (made binary on load)
+    const double *init;        // [g][c_max]
+    const double *endpen;      // [b][c_max] or null (EOS mode only)
+    const int64_t *class_map;  // [g][c_max+1] or null
+    double *hist;              // the workspace's history area
+    int64_t *spans;            // [b][t_max+1] or null
+    int64_t *labels;           // [total_frames] or null
+    double *best;              // [b] or null
+    double *gain_sum;          // [b] or null
+    int32_t *n_segs;           // [b] or null
+    int32_t *err;              // sticky error word
+    int32_t c_max, t_max, b, no_eos;
+};
+void smm_launch_mbr(const SmmMbrArgs &a, hipStream_t stream);

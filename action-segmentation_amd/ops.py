@@ -641,6 +641,43 @@ def kbest(batch, elp, trans, init, len_scores, k, endpen=None, class_map=None, w
     return dict(spans=spans, labels=labels, score=score, n_segs=n_segs, _err=_err_copy(batch, ws))
 
 
+def mbr_workspace_bytes(batch):
+    """Bytes of workspace smm_mbr_f64 needs for this batch (host only)."""
+    n = _lib.load().smm_mbr_workspace_bytes(ctypes.byref(batch.shape), batch.lengths.ctypes.data)
+    if n == 0:
+        raise _lib.SmmError("libsmmdp: invalid batch shape for the MBR decode")
+    return n
+
+
+def mbr(batch, gain, trans, init, endpen=None, class_map=None, ws=None, want_spans=True, want_labels=True):
+    """Minimum-Bayes-risk decode under frame loss (smm_mbr_f64): per video the feasible segmentation that maximises
+    sum_t gain[t][y_t] -- with gain = the frame posteriors (``logz_bwd``'s ``elp``), the expected number of correct frames.  It is
+    ``viterbi`` on the substituted inputs elp = gain, zero length scores, and trans / init / endpen made binary (-1e9 where the
+    table is <= -5e8, else 0).  gain fp64 [total_frames, c_max].  Returns dict(spans int64 [b, t_max+1] (span encoding, class
+    map applied) or None, labels int64 [total_frames] (global ids, -1 on frames no video covers) or None, best fp64 [b] (the DP
+    value), gain_sum fp64 [b] (sum_t gain[t][y_t], in frame order), n_segs int32 [b]).  ``ws``: a uint8 workspace of at least
+    ``mbr_workspace_bytes(batch)`` (default: a private one for this call)."""
+    lib = _lib.load()
+    dev = gain.device
+    f64 = torch.float64
+    spans = torch.empty((batch.b, batch.t_max + 1), dtype=torch.int64, device=dev) if want_spans else None
+    labels = torch.full((batch.total_frames,), -1, dtype=torch.int64, device=dev) if want_labels else None
+    best = torch.empty(batch.b, dtype=f64, device=dev)
+    gain_sum = torch.empty(batch.b, dtype=f64, device=dev)
+    n_segs = torch.empty(batch.b, dtype=torch.int32, device=dev)
+    need = mbr_workspace_bytes(batch)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ln, fo, gr, kp, ns = batch.host_ptrs()
+    _lib.check(lib.smm_mbr_f64(
+        ctypes.byref(batch.shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(kp),
+        ctypes.c_void_p(ns), _dev(gain, f64, 'gain'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'),
+        _dev(endpen, f64, 'endpen'), _dev(class_map, torch.int64, 'class_map'), _dev(spans, torch.int64, 'spans'),
+        _dev(labels, torch.int64, 'labels'), _dev(best, f64, 'best'), _dev(gain_sum, f64, 'gain_sum'),
+        _dev(n_segs, torch.int32, 'n_segs'), ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream()))
+    return dict(spans=spans, labels=labels, best=best, gain_sum=gain_sum, n_segs=n_segs, _err=_err_copy(batch, ws))
+
+
 _pinned = {}
 
 

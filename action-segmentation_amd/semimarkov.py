@@ -23,9 +23,14 @@ class SemiMarkovModel(object):
                                # done with a batch (0.17 us per frame) before the host has launched the next (0.25 ms), and
                                # a second stream would only add its hand-over (refdef, T <= 600: 4.4 -> 5.1 ms for 18 batches)
 
+    DECODERS = ('viterbi', 'mbr')
+
     @classmethod
     def add_args(cls, parser):
         SemiMarkovModule.add_args(parser)
+        # which segmentation predict() returns: the most probable one, or the one with the most expected correct frames
+        # (minimum-Bayes-risk decode under frame loss, the metric evaluation reports)
+        parser.add_argument('--sm_decoder', choices=list(cls.DECODERS), default='viterbi')
         parser.add_argument('--sm_component_model', action='store_true')
         parser.add_argument('--sm_constrain_transitions', action='store_true')
         parser.add_argument('--sm_constrain_with_narration', choices=['train', 'test'], nargs='*', default=[])
@@ -335,6 +340,36 @@ class SemiMarkovModel(object):
         state.pop('_step_columns', None)
         return state
 
+    def _predict_mbr(self, test_data, fused, shard):
+        """``predict(decoder='mbr')``: the minimum-Bayes-risk segmentation under frame loss of every video."""
+        if fused:
+            pc = self.prepare(test_data, shard=shard)
+            if pc.n_videos == 0:
+                return {}                                   # this rank's shard is empty
+            self.last_predict_path = 'fused MBR: posteriors + smm_mbr_f64 on the packed corpus'
+            labels, _ = self.model.mbr_decode_packed(pc)
+            lab = labels.cpu().numpy()
+            assert lab.size == 0 or int(lab.max()) < self.model.n_classes, "predictions should not contain EOS"
+            return {name: lab[off:off + t] for name, off, t in zip(pc.video_names, pc.frame_offset, pc.lengths)}
+        self.last_predict_path = 'per batch, padded: mbr_decode() spans'
+        cons_fn = self._test_constraints(test_data)
+        loader = make_data_loader(self.args, test_data, shuffle=False, batch_by_task=True, batch_size=self.args.batch_size,
+                                  shard=shard)
+        predictions = {}
+        for batch in loader:
+            tasks = batch['task_name']
+            assert len(set(tasks)) == 1
+            features, lengths = batch['features'].to(self.device), batch['lengths']
+            cons = cons_fn(batch) if cons_fn else None
+            addl = self.make_additional_allowed_ends(tasks, lengths)
+            spans, _ = self.model.mbr_decode(features, lengths, batch['task_indices'], add_eos=True,
+                                             additional_allowed_ends_per_instance=addl, constraints=cons)
+            pred_labels = semimarkov_utils.spans_to_labels(spans)
+            for video, seq in zip(batch['video_name'], self.model.trim(pred_labels, batch['lengths'], check_eos=True)):
+                predictions[video] = seq.numpy()
+                assert self.model.n_classes not in predictions[video], "predictions should not contain EOS"
+        return predictions
+
     def predict_packed(self, pc):
         import torch
         from . import ops
@@ -469,15 +504,24 @@ class SemiMarkovModel(object):
             off += pc.x.size(0)
         return out
 
-    def predict(self, test_data, fused=True, shard=None):
+    def predict(self, test_data, fused=True, shard=None, decoder=None):
         """``{video: int64[T]}``.  ``shard=(rank, world)`` (default: the torch.distributed group when one is up) limits the
-        result to this rank's videos; reduce the evaluation counters with ``evaluation.accuracy_corpus(reduce=...)``."""
+        result to this rank's videos; reduce the evaluation counters with ``evaluation.accuracy_corpus(reduce=...)``.
+        ``decoder``: 'viterbi' (the most probable segmentation) or 'mbr' (the segmentation with the most expected correct
+        frames: ``SemiMarkovModule.mbr_decode_packed``; with ``fused=False`` one ``mbr_decode`` per single-task batch); default
+        ``--sm_decoder``."""
+        if decoder is None:
+            decoder = getattr(self.args, 'sm_decoder', None) or 'viterbi'
+        if decoder not in self.DECODERS:
+            raise ValueError("decoder must be one of %s, got %r" % (self.DECODERS, decoder))
         self.model.eval()
         if shard is None:
             from . import distributed
             if distributed.active():
                 import torch.distributed as dist
                 shard = (dist.get_rank(), dist.get_world_size())
+        if decoder == 'mbr':
+            return self._predict_mbr(test_data, fused, shard)
         if fused:
             return self.predict_packed(self.prepare(test_data, shard=shard))
         predictions = {}

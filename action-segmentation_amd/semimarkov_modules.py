@@ -784,14 +784,14 @@ class SemiMarkovModule(nn.Module):
         tabs = self._differentiable_tables(self._check_valid_classes(valid_classes_per_instance), features.device)
         return _PosteriorValue.apply('entropy', lambda: self._entropy(*args), *tabs)
 
-    def _packed_posterior_launch(self, pc, what):
+    def _packed_posterior_launch(self, pc, what, with_backward=False):
         x = pc.x
         self._require_device(x, what)
         self.prepare_packed(pc)
         t = pc.tables
         ws = torch.empty(pc.batch.workspace_bytes(), dtype=torch.uint8, device=x.device)
         elp, _ = ops.emission(pc.batch, x, t['w'], t['cst'], t['inv_var'], cons=pc.cons)
-        z = ops.logz(pc.batch, elp, t['trans'], t['init'], t['len'], endpen=pc.endpen, ws=ws)
+        z = ops.logz(pc.batch, elp, t['trans'], t['init'], t['len'], endpen=pc.endpen, ws=ws, with_backward=with_backward)
         return t, elp, z, ws
 
     @torch.no_grad()
@@ -986,6 +986,43 @@ class SemiMarkovModule(nn.Module):
                         want_spans=False, want_labels=True)
         ops.check_decoded(pc.batch, out)
         return out['labels'], out['score']
+
+    # ------------------------------------------------------------------ minimum-Bayes-risk decode (smm_mbr_f64)
+    @torch.no_grad()
+    def mbr_decode(self, features, lengths, valid_classes_per_instance, add_eos=True, additional_allowed_ends_per_instance=None,
+                   constraints=None):
+        """The segmentation with the most expected correct frames (minimum-Bayes-risk decode under frame loss) of a zero-padded
+        single-task batch (argument conventions of ``viterbi``): among the segmentations the posterior gives non-zero mass, the
+        one that maximises sum_t P(y_t = label_t | x).  Unlike the per-frame argmax of ``frame_posteriors`` it obeys the span
+        limit, the transition, start and end constraints and the narration masks.  One emission launch, one log Z launch
+        (forward and time-reversed), one marginals launch (smm_logz_bwd_f64), one MBR launch (smm_mbr_f64).
+
+        Returns (pred_spans, expected_correct): pred_spans CPU int64 b x (Tmax+1) in ``viterbi``'s format (b x Tmax with
+        add_eos=False), expected_correct fp64 b on the device: sum_t P(y_t = label_t | x) along the result.  Raises SmmError
+        when a NaN reached the DP.  No autograd."""
+        r = self._posterior_launch(features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
+                                   constraints, 'mbr_decode', with_backward=True)
+        g = ops.logz_bwd(r['batch'], r['elp'], r['trans'], r['init'], r['len'], r['logz'], endpen=r['endpen'], ws=r['ws'],
+                         with_backward=True)
+        out = ops.mbr(r['batch'], g['elp'], r['trans'], r['init'], endpen=r['endpen'], class_map=r['class_map'], ws=r['ws'],
+                      want_spans=True, want_labels=False)
+        spans = out['spans'].cpu()
+        ops.check_decoded(r['batch'], out)
+        if not add_eos:
+            spans = spans[:, :features.size(1)].contiguous()
+        return spans, out['gain_sum']
+
+    @torch.no_grad()
+    def mbr_decode_packed(self, pc):
+        """``mbr_decode`` for a whole PackedCorpus: one emission, one log Z (both directions), one marginals and one MBR launch.
+        Returns (labels, expected_correct): device int64 total_frames (global class ids on the packed frame axis, -1 on frames
+        no video covers) and fp64 n_videos in the order of ``pc.video_names``."""
+        t, elp, z, ws = self._packed_posterior_launch(pc, 'mbr_decode_packed', with_backward=True)
+        g = ops.logz_bwd(pc.batch, elp, t['trans'], t['init'], t['len'], z, endpen=pc.endpen, ws=ws, with_backward=True)
+        out = ops.mbr(pc.batch, g['elp'], t['trans'], t['init'], endpen=pc.endpen, class_map=t['class_map'], ws=ws,
+                      want_spans=False, want_labels=True)
+        ops.check_decoded(pc.batch, out)
+        return out['labels'], out['gain_sum']
 
     # ------------------------------------------------------------------ packed multi-task decode
     def stacked_tables(self, pc, differentiable=False):

@@ -22,6 +22,8 @@
  *   smm_kl_bwd_f64             values with respect to p's tables)
  *   smm_kbest_f64           <- pytorch-struct's SemiMarkovCRF(...).kmax / topk (the k best segmentations; the reference never
  *                              calls it)
+ *   smm_mbr_f64             <- minimum-Bayes-risk decode under frame loss: the feasible segmentation with the most expected
+ *                              correct frames (the reference has none)
  *
  * The reference has no FFI: its boundary is the Python call SemiMarkovCRF(scores, lengths) on a dense
  * b x N x K x C x C tensor.  These entry points take the FACTORS of that tensor instead,
@@ -395,6 +397,36 @@ int smm_kbest_f64(const smm_shape *shape, const int64_t *lengths_host, const int
                   const double *endpen, const int64_t *class_map, int32_t k,
                   int64_t *spans_out, int64_t *labels_out, double *score_out, int32_t *n_segs_out,
                   void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Minimum-Bayes-risk (maximum expected accuracy) decode under frame (Hamming) loss (csrc/smm_mbr.hip): per video, the feasible
+ * segmentation that maximises sum_t gain[t][y_t] -- with gain = the frame posteriors P(y_t = c | x) (the g_elp of
+ * smm_logz_bwd_f64), the expected number of correct frames.  Exact definition: the result is what smm_viterbi_f64 returns on the
+ * substituted inputs
+ *   elp' = gain;   len'[k][c] = 0 for every usable row (the span limit k_rows / kp still applies);
+ *   trans' = M(trans), init' = M(init), endpen' = M(endpen),   M(x) = SMM_BIG_NEG if x <= SMM_BIG_NEG / 2 (-inf included), else 0;
+ * everything else unchanged: class map, groups, kp, SMM_SHAPE_NO_EOS, and the EOS closing step (a real class closes at
+ * + SMM_BIG_NEG).  A term is forbidden exactly when the posterior gives it zero mass; the gains sum to at most T << 1e9, so the
+ * result uses the fewest forbidden terms and, among those paths, has the most expected correct frames.  Ties: the C twin's rule
+ * (oracle/smm_oracle.c: in the back-trace the shortest segment first, then the smallest source state; each value
+ * re-evaluated as (cum + h) + w); spans, labels, n_segs and best are bit-identical to the twin and to smm_viterbi_f64 on the
+ * substituted inputs.  A video is never split along the time axis (SMM_SHAPE_NO_TIME_SPLIT is accepted and ignored).
+ *   gain        dev fp64 [total_frames][c_max]
+ *   trans, init, endpen, class_map: as smm_viterbi_f64 reads them (made binary on load; endpen nullable); there is no length table
+ *   spans, labels, best, n_segs: smm_viterbi_f64's outputs and layouts (best = the DP value)                           (nullable)
+ *   gain_sum    dev fp64 [b]: sum_t gain[t][y_t] along the result, summed serially in frame order in fp64              (nullable)
+ * Enqueued on `stream` only; never synchronises.  The workspace is smm_mbr_workspace_bytes; the error word sits at
+ * smm_error_word_offset.  A NaN in a video's gain sets it (that video's best and gain_sum are NaN, its n_segs 0).
+ * SMM_ERR_ARG for a NULL gain / trans / init / workspace, every output NULL or invalid metadata; SMM_ERR_UNSUPPORTED for c_max
+ * or k_rows beyond the compiled kernels; SMM_ERR_WORKSPACE below smm_mbr_workspace_bytes -- all before anything is staged.
+ */
+/* host only; 0 on invalid arguments (those of smm_workspace_bytes, c_max or k_rows too large) */
+size_t smm_mbr_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host);
+int smm_mbr_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                const double *gain, const double *trans, const double *init, const double *endpen,
+                const int64_t *class_map, int64_t *spans, int64_t *labels, double *best, double *gain_sum, int32_t *n_segs,
+                void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Factor tables of every parameter group from the model parameters (training steps), and their chain rule.
