@@ -1784,6 +1784,100 @@ extern "C" int smm_mbr_f64(const smm_shape *shape, const int64_t *lengths_host, 
     return SMM_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ forced alignment
+// Behind the plan's workspace: the transcript offsets, the offsets of the videos' h columns and the launch order (uploaded
+// per call: they are no part of a resident plan), then the h columns, M (T + 1) doubles per video.  cum uses the history area.
+struct AlignLayout {
+    size_t o_toff, o_hoff, o_order, meta_end, o_hcols, total;
+};
+
+// SMM_OK, or the refusal; everything here is host arithmetic on the caller's arrays
+static int align_layout(const smm_shape *s, const int64_t *lengths, const int64_t *toff, AlignLayout *lo)
+{
+    if (!shape_ok(s) || !lengths || !toff) return SMM_ERR_ARG;
+    if ((s->flags & SMM_SHAPE_NO_EOS) || s->c_max > SMM_MAX_STATES || s->k_rows > SMM_MAX_K_ROWS) return SMM_ERR_UNSUPPORTED;
+    if (toff[0] < 0) return SMM_ERR_ARG;
+    size_t cells = 0;
+    bool too_long = false;
+    for (int i = 0; i < s->b; ++i) {
+        if (lengths[i] < 1 || lengths[i] > s->t_max) return SMM_ERR_ARG;
+        const int64_t m = toff[i + 1] - toff[i];
+        if (m < 1) return SMM_ERR_ARG;                      // non-monotone offsets, or an empty transcript
+        too_long |= m > SMM_MAX_TRANSCRIPT;
+        cells += (size_t)m * (size_t)(lengths[i] + 1);
+    }
+    if (too_long) return SMM_ERR_UNSUPPORTED;
+    const size_t b = (size_t)s->b;
+    lo->o_toff = align_up(make_plan(s, lengths).total, 256);
+    lo->o_hoff = lo->o_toff + sizeof(int64_t) * (b + 1);
+    lo->o_order = lo->o_hoff + sizeof(int64_t) * b;
+    lo->meta_end = lo->o_order + sizeof(int32_t) * b;
+    lo->o_hcols = align_up(lo->meta_end, 256);
+    lo->total = lo->o_hcols + sizeof(double) * cells;
+    return SMM_OK;
+}
+
+extern "C" size_t smm_align_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host,
+                                            const int64_t *transcript_offset_host)
+{
+    AlignLayout lo;
+    return align_layout(shape, lengths_host, transcript_offset_host, &lo) == SMM_OK ? lo.total : 0;
+}
+
+extern "C" int smm_align_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                             const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                             const double *elp, const double *trans, const double *init, const double *len_scores,
+                             const double *endpen, const int64_t *class_map, const int32_t *transcript,
+                             const int64_t *transcript_offset_host, int64_t *spans, int64_t *labels, double *best,
+                             int32_t *n_segs, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!shape_ok(shape) || !lengths_host || !frame_offset_host || !n_states_host || !transcript_offset_host) return SMM_ERR_ARG;
+    if (!elp || !trans || !init || !len_scores || !transcript || !workspace) return SMM_ERR_ARG;
+    if (!spans && !labels && !best && !n_segs) return SMM_ERR_ARG;
+    AlignLayout lo;
+    int rc = align_layout(shape, lengths_host, transcript_offset_host, &lo);
+    if (rc != SMM_OK) return rc;
+    if (workspace_bytes < lo.total) return SMM_ERR_WORKSPACE;
+    Staged st;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes, hs, &st);
+    if (rc != SMM_OK) return rc;
+    // this call's own metadata: offsets, and the launch order -- most lattice cells (T x M x span limit) first
+    const int b = shape->b;
+    std::vector<char> host(lo.meta_end - lo.o_toff, 0);
+    int64_t *h_toff = reinterpret_cast<int64_t *>(host.data());
+    int64_t *h_hoff = reinterpret_cast<int64_t *>(host.data() + (lo.o_hoff - lo.o_toff));
+    int32_t *h_order = reinterpret_cast<int32_t *>(host.data() + (lo.o_order - lo.o_toff));
+    std::vector<double> work(b);
+    int64_t cells = 0;
+    for (int i = 0; i < b; ++i) {
+        const int64_t m = transcript_offset_host[i + 1] - transcript_offset_host[i];
+        const int k = kp_host ? kp_host[i] : std::min<int>(shape->k_rows, shape->t_max);
+        h_toff[i] = transcript_offset_host[i];
+        h_hoff[i] = cells;
+        cells += m * (lengths_host[i] + 1);
+        work[i] = (double)m * (double)lengths_host[i] * (double)std::min<int64_t>(k, lengths_host[i]);
+    }
+    h_toff[b] = transcript_offset_host[b];
+    std::iota(h_order, h_order + b, 0);
+    std::stable_sort(h_order, h_order + b, [&](int x, int y) { return work[x] > work[y]; });
+    char *base = static_cast<char *>(workspace);
+    SMM_HIP((hipError_t)smm_upload_meta(base + lo.o_toff, host.data(), host.size(), hs));
+    SmmAlignArgs a{};
+    a.videos = st.videos; a.n_states = st.n_states;
+    a.order = reinterpret_cast<const int32_t *>(base + lo.o_order);
+    a.toff = reinterpret_cast<const int64_t *>(base + lo.o_toff);
+    a.hoff = reinterpret_cast<const int64_t *>(base + lo.o_hoff);
+    a.elp = elp; a.trans = trans; a.init = init; a.len = len_scores; a.endpen = endpen; a.class_map = class_map;
+    a.transcript = transcript;
+    a.hist = st.hist; a.hcols = reinterpret_cast<double *>(base + lo.o_hcols);
+    a.spans = spans; a.labels = labels; a.best = best; a.n_segs = n_segs; a.err = st.err;
+    a.c_max = shape->c_max; a.k_rows = shape->k_rows; a.t_max = shape->t_max; a.b = b;
+    smm_launch_align(a, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ dense boundary
 static size_t dense_off(size_t &cur, size_t bytes)
 {

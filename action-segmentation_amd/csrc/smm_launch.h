@@ -229,3 +229,29 @@ struct SmmMbrArgs {
     int32_t c_max, t_max, b, no_eos;
 };
 void smm_launch_mbr(const SmmMbrArgs &a, hipStream_t stream);
+
+// forced alignment to a given transcript (smm_align.hip).  cum sits class-major [C][T+1] at the video's hist_off; the h columns
+// [M][T+1] of video i at hcols + hoff[i]
+struct SmmAlignArgs {
+    const SmmVideo *videos;
+    const int32_t *order;      // [b] workgroup -> video (most lattice cells first)
+    const int32_t *n_states;
+    const double *elp;         // [total_frames][c_max]
+    const double *trans;       // [g][c_max][c_max]  [to][from]
+    const double *init;        // [g][c_max]
+    const double *len;         // [g][k_rows][c_max]
+    const double *endpen;      // [b][c_max] or null
+    const int64_t *class_map;  // [g][c_max+1] or null
+    const int32_t *transcript; // [toff[b]] local state ids (caller's; checked against n_states on load)
+    const int64_t *toff;       // [b + 1]
+    const int64_t *hoff;       // [b] doubles
+    double *hist;              // the workspace's history area
+    double *hcols;             // behind the plan's workspace
+    int64_t *spans;            // [b][t_max+1] or null
+    int64_t *labels;           // [total_frames] or null
+    double *best;              // [b] or null
+    int32_t *n_segs;           // [b] or null
+    int32_t *err;              // sticky error word
+    int32_t c_max, k_rows, t_max, b;
+};
+void smm_launch_align(const SmmAlignArgs &a, hipStream_t stream);

@@ -678,6 +678,70 @@ def mbr(batch, gain, trans, init, endpen=None, class_map=None, ws=None, want_spa
     return dict(spans=spans, labels=labels, best=best, gain_sum=gain_sum, n_segs=n_segs, _err=_err_copy(batch, ws))
 
 
+MAX_TRANSCRIPT = _lib.MAX_TRANSCRIPT
+
+
+def _transcript_arrays(batch, transcripts):
+    """Per-video sequences of local state ids -> (ids int32 [sum M], offsets int64 [b + 1]) on the host."""
+    if len(transcripts) != batch.b:
+        raise ValueError("align: %d transcripts for %d videos" % (len(transcripts), batch.b))
+    seqs = [np.asarray(t.detach().cpu() if torch.is_tensor(t) else t, dtype=np.int64).reshape(-1) for t in transcripts]
+    for i, q in enumerate(seqs):
+        if q.size == 0:
+            raise ValueError("align: the transcript of video %d is empty" % i)
+        if q.size > MAX_TRANSCRIPT:
+            raise ValueError("align: the transcript of video %d has %d entries (at most %d)" % (i, q.size, MAX_TRANSCRIPT))
+    off = np.zeros(batch.b + 1, np.int64)
+    np.cumsum([q.size for q in seqs], out=off[1:])
+    return np.ascontiguousarray(np.concatenate(seqs).astype(np.int32)), off
+
+
+def align_workspace_bytes(batch, transcript_offset):
+    """Bytes of workspace smm_align_f64 needs for this batch and these transcript offsets (int64 [b + 1]; host only)."""
+    off = np.ascontiguousarray(np.asarray(transcript_offset, dtype=np.int64).reshape(-1))
+    if off.shape[0] != batch.b + 1:
+        raise ValueError("align_workspace_bytes: b + 1 transcript offsets expected")
+    n = _lib.load().smm_align_workspace_bytes(ctypes.byref(batch.shape), ctypes.c_void_p(batch.lengths.ctypes.data),
+                                              ctypes.c_void_p(off.ctypes.data))
+    if n == 0:
+        raise _lib.SmmError("libsmmdp: invalid batch shape or transcript offsets for the alignment (add_eos=True only, "
+                            "1..%d entries per video)" % MAX_TRANSCRIPT)
+    return n
+
+
+def align(batch, elp, trans, init, len_scores, transcripts, endpen=None, class_map=None, ws=None, want_spans=True,
+          want_labels=True):
+    """Forced alignment (smm_align_f64): per video the best segmentation whose class sequence is its transcript -- a sequence
+    of LOCAL state ids, one per segment, consecutive repeats allowed -- so only the boundaries are free.  Bit for bit
+    ``viterbi`` on the lattice whose states are the transcript positions; with the transcript of the Viterbi path, the Viterbi
+    decode.  Returns dict(spans int64 [b, t_max+1] (span encoding, class map applied) or None, labels int64 [total_frames]
+    (global ids, -1 on frames no video covers) or None, best fp64 [b], n_segs int32 [b] (the transcript's length)).  A video
+    whose transcript cannot be laid over its frames (more entries than frames, too few for the span limit, an id that is no
+    state of the video) gets best -inf, n_segs 0, spans and labels -1.  ``ws``: a uint8 workspace of at least
+    ``align_workspace_bytes`` (default: a private one for this call)."""
+    lib = _lib.load()
+    dev = elp.device
+    f64 = torch.float64
+    ids, off = _transcript_arrays(batch, transcripts)
+    need = align_workspace_bytes(batch, off)
+    spans = torch.empty((batch.b, batch.t_max + 1), dtype=torch.int64, device=dev) if want_spans else None
+    labels = torch.full((batch.total_frames,), -1, dtype=torch.int64, device=dev) if want_labels else None
+    best = torch.empty(batch.b, dtype=f64, device=dev)
+    n_segs = torch.empty(batch.b, dtype=torch.int32, device=dev)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ids_dev = torch.from_numpy(ids).to(dev)
+    ln, fo, gr, kp, ns = batch.host_ptrs()
+    _lib.check(lib.smm_align_f64(
+        ctypes.byref(batch.shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(kp),
+        ctypes.c_void_p(ns), _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'),
+        _dev(len_scores, f64, 'len_scores'), _dev(endpen, f64, 'endpen'), _dev(class_map, torch.int64, 'class_map'),
+        _dev(ids_dev, torch.int32, 'transcript'), ctypes.c_void_p(off.ctypes.data), _dev(spans, torch.int64, 'spans'),
+        _dev(labels, torch.int64, 'labels'), _dev(best, f64, 'best'), _dev(n_segs, torch.int32, 'n_segs'),
+        ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream()))
+    return dict(spans=spans, labels=labels, best=best, n_segs=n_segs, _err=_err_copy(batch, ws), _keep=(ids_dev, ws))
+
+
 _pinned = {}
 
 

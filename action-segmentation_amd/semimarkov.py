@@ -370,6 +370,23 @@ class SemiMarkovModel(object):
                 assert self.model.n_classes not in predictions[video], "predictions should not contain EOS"
         return predictions
 
+    def align(self, data, transcripts_by_video, shard=None):
+        """Forced alignment of every video of ``data`` to its transcript: ``transcripts_by_video[name]`` is the video's class
+        sequence in global class ids, one entry per segment.  Returns what ``predict`` returns, ``{video: int64[T]}``: the frame
+        labels of the best segmentation with that class sequence (-1 on a video whose transcript cannot be laid over its
+        frames).  One emission launch and one alignment launch on the packed corpus (``SemiMarkovModule.align_packed``)."""
+        self.model.eval()
+        pc = self.prepare(data, shard=shard)
+        if pc.n_videos == 0:
+            return {}
+        missing = [name for name in pc.video_names if name not in transcripts_by_video]
+        if missing:
+            raise ValueError("align: no transcript for video %r" % (missing[0],))
+        labels, _ = self.model.align_packed(pc, [transcripts_by_video[name] for name in pc.video_names])
+        lab = labels.cpu().numpy()
+        assert lab.size == 0 or int(lab.max()) < self.model.n_classes, "alignments should not contain EOS"
+        return {name: lab[off:off + t] for name, off, t in zip(pc.video_names, pc.frame_offset, pc.lengths)}
+
     def predict_packed(self, pc):
         import torch
         from . import ops

@@ -1024,6 +1024,84 @@ class SemiMarkovModule(nn.Module):
         ops.check_decoded(pc.batch, out)
         return out['labels'], out['gain_sum']
 
+    # ------------------------------------------------------------------ forced alignment (smm_align_f64)
+    @staticmethod
+    def _local_transcripts(transcripts, class_map_host, n_states, group):
+        """Transcripts in GLOBAL class ids -> local state ids: the position of each id among its video's valid classes."""
+        if len(transcripts) != len(group):
+            raise ValueError("align: %d transcripts for %d videos" % (len(transcripts), len(group)))
+        lookup = [{int(c): j for j, c in reversed(list(enumerate(class_map_host[g, :n_states[g]])))} for g in range(len(n_states))]
+        out = []
+        for i, t in enumerate(transcripts):
+            ids = np.asarray(t.detach().cpu() if torch.is_tensor(t) else t, dtype=np.int64).reshape(-1)
+            if ids.size == 0:
+                raise ValueError("align: the transcript of video %d is empty" % i)
+            lk = lookup[int(group[i])]
+            bad = [int(c) for c in ids if int(c) not in lk]
+            if bad:
+                raise ValueError("align: class %d in the transcript of video %d is not a valid class of that video" % (bad[0], i))
+            out.append(np.array([lk[int(c)] for c in ids], np.int64))
+        return out
+
+    @torch.no_grad()
+    def align(self, features, lengths, valid_classes_per_instance, transcripts, add_eos=True,
+              additional_allowed_ends_per_instance=None, constraints=None):
+        """Forced alignment of a zero-padded single-task batch (argument conventions of ``viterbi``): ``transcripts[i]`` is the
+        class sequence of video i in GLOBAL class ids, one entry per segment (consecutive repeats are two segments); the result
+        is the best segmentation with exactly that sequence.  One emission launch, one alignment launch (smm_align_f64).
+
+        Returns (pred_spans, scores): pred_spans CPU int64 b x (Tmax+1) in ``viterbi``'s format, scores fp64 b on the device.
+        A transcript that cannot be laid over its video (more entries than frames, or too few for the span limit) gives a row
+        of -1 and score -inf.  ValueError for an id that is not valid for the video, an empty transcript or add_eos=False.
+        Raises SmmError when a NaN reached the DP.  No autograd."""
+        if not add_eos:
+            raise ValueError("align: add_eos=False is not supported")
+        self._require_device(features, 'align')
+        valid_classes = self._check_valid_classes(valid_classes_per_instance)
+        b, tmax, d = features.shape
+        dev = features.device
+        lengths_host = lengths.detach().cpu().numpy().astype(np.int64)
+        assert int(lengths_host.max()) == tmax, "one instance must span the padded length (padding_colate)"
+        tab = self._decode_tables(valid_classes, dev)
+        c = tab['init'].numel()
+        local = self._local_transcripts(transcripts, tab['class_map'].view(1, -1).cpu().numpy(), [c], np.zeros(b, np.int64))
+        batch = ops.Batch(lengths_host, [c], tab['len'].size(0), c_max=c, t_max=tmax, total_frames=b * tmax, d=d)
+        x = features.detach().to(torch.float32).contiguous().view(b * tmax, d)
+        cons = None
+        if constraints is not None:
+            cons = constraints.detach().to(device=dev, dtype=torch.float32).contiguous().view(b * tmax, c)
+        endpen = self._endpen(valid_classes, additional_allowed_ends_per_instance, b, c, dev)
+        g1 = tab.get('_one_group')
+        if g1 is None:
+            g1 = tab['_one_group'] = tuple(tab[n].unsqueeze(0).contiguous() for n in ('w', 'cst', 'trans', 'init', 'len')) \
+                + (tab['class_map'].view(1, -1),)
+        elp, _ = ops.emission(batch, x, g1[0], g1[1], tab['inv_var'], cons=cons)
+        out = ops.align(batch, elp, g1[2], g1[3], g1[4], local, endpen=endpen, class_map=g1[5], want_spans=True,
+                        want_labels=False)
+        spans = out['spans'].cpu()
+        ops.check_decoded(batch, out)
+        return spans, out['best']
+
+    @torch.no_grad()
+    def align_packed(self, pc, transcripts):
+        """``align`` for a whole PackedCorpus: one emission launch and one alignment launch.  ``transcripts``: one sequence of
+        GLOBAL class ids per video, in the order of ``pc.video_names``.  Returns (labels, scores): device int64 total_frames
+        (global class ids on the packed frame axis, -1 on frames no video covers and on videos without an alignment) and fp64
+        n_videos."""
+        x = pc.x
+        self._require_device(x, 'align_packed')
+        if pc.batch.no_eos:
+            raise ValueError("align_packed: add_eos=False is not supported")
+        self.prepare_packed(pc)
+        t = pc.tables
+        group = pc.batch.group if pc.batch.group is not None else np.zeros(pc.batch.b, np.int64)
+        local = self._local_transcripts(transcripts, t['class_map'].cpu().numpy(), pc.batch.n_states, group)
+        elp, _ = ops.emission(pc.batch, x, t['w'], t['cst'], t['inv_var'], cons=pc.cons)
+        out = ops.align(pc.batch, elp, t['trans'], t['init'], t['len'], local, endpen=pc.endpen, class_map=t['class_map'],
+                        want_spans=False, want_labels=True)
+        ops.check_decoded(pc.batch, out)
+        return out['labels'], out['best']
+
     # ------------------------------------------------------------------ packed multi-task decode
     def stacked_tables(self, pc, differentiable=False):
         """fp64 factor tables of every group of a PackedCorpus stacked to [groups, ...] and zero-padded to c_max columns.

@@ -79,6 +79,18 @@ def rle_spans(spans, lengths):
     return res
 
 
+def spans_to_transcripts(spans, lengths):
+    """The class sequence of every instance of a span encoding: the class at every span start within the first
+    ``lengths[i]`` positions, in order (consecutive equal classes stay two entries).  The EOS entry at position lengths[i]
+    of ``viterbi``'s format lies outside that range and is dropped.  -> list of int64 arrays."""
+    sp = spans.detach().cpu().numpy() if torch.is_tensor(spans) else np.asarray(spans)
+    out = []
+    for i in range(sp.shape[0]):
+        row = sp[i, :int(lengths[i])]
+        out.append(row[row != -1].astype(np.int64))
+    return out
+
+
 def semimarkov_sufficient_stats(feature_list, label_list, covariance_type, n_classes, max_k=None):
     """Closed-form statistics of reference utils.py:74-126 without the sklearn dependency.
 

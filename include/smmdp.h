@@ -24,6 +24,8 @@
  *                              calls it)
  *   smm_mbr_f64             <- minimum-Bayes-risk decode under frame loss: the feasible segmentation with the most expected
  *                              correct frames (the reference has none)
+ *   smm_align_f64           <- forced alignment: the best segmentation whose class sequence is a given transcript (the
+ *                              reference has none)
  *
  * The reference has no FFI: its boundary is the Python call SemiMarkovCRF(scores, lengths) on a dense
  * b x N x K x C x C tensor.  These entry points take the FACTORS of that tensor instead,
@@ -427,6 +429,48 @@ int smm_mbr_f64(const smm_shape *shape, const int64_t *lengths_host, const int64
                 const double *gain, const double *trans, const double *init, const double *endpen,
                 const int64_t *class_map, int64_t *spans, int64_t *labels, double *best, double *gain_sum, int32_t *n_segs,
                 void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Forced alignment (csrc/smm_align.hip): per video, the best segmentation whose class sequence is the given transcript
+ * a[0..M-1] (local state ids, 1 <= M <= SMM_MAX_TRANSCRIPT; consecutive equal ids are two segments); only the boundaries are
+ * free.  EOS mode only.  With kp the video's span limit (kp_host, NULL: min(k_rows, t_max)), every + one IEEE fp64 add in
+ * this association:
+ *   cum[0][c] = 0;  cum[n][c] = cum[n-1][c] + elp[n-1][c]                                    (serial prefix sums)
+ *   h[0][0] = init[a_0];  h[0][m>0] = -inf
+ *   gam[n][m] = cum[n][a_m] + max_{k=1..min(kp-1,n)} ( h[n-k][m] + len[k][a_m] )              n = 1..T
+ *   h[n][m]   = ( gam[n][m-1] + trans[a_m][a_{m-1}] ) - cum[n][a_m]                          0 < n < T, m >= 1; h[n>0][0] = -inf
+ *   best      = gam[T][M-1] + (endpen ? endpen[i][a_{M-1}] : 0.0)
+ * Back-trace from (n, m, w) = (T, M-1, the closing term): the smallest k whose (cum[n][a_m] + (h[n-k][m] + len[k][a_m])) + w
+ * equals the maximum of that expression over k; segment m starts at n - k; on to (n - k, m - 1, trans[a_m][a_{m-1}]).
+ * This is, bit for bit, what smm_viterbi_f64 and the C twin (oracle/smm_oracle.c: smm_oracle_viterbi_ex) return on the
+ * expanded lattice -- states = transcript positions, elp'[t][m] = elp[t][a_m], len'[k][m] = len[k][a_m],
+ * trans'[m][m-1] = trans[a_m][a_{m-1}], init'[0] = init[a_0], endpen'[M-1] = the closing term, every other entry -1e9 -- as
+ * long as a path exists and its score stays far from -1e9; with the transcript of the Viterbi path it is the Viterbi decode.
+ * Model-forbidden transitions (-1e9 in trans) are ordinary finite scores here.
+ *   transcript              dev int32 [transcript_offset_host[b]]: video i's ids at [offset[i], offset[i+1])
+ *   transcript_offset_host  host int64 [b + 1], non-decreasing; every video has at least one id
+ *   elp, trans, init, len_scores, endpen, class_map: as smm_viterbi_f64 reads them (endpen, class_map nullable)
+ *   spans, labels, best, n_segs: smm_viterbi_f64's outputs and layouts; n_segs = M                              (nullable)
+ * A video without a path by counting (M > T or M (kp - 1) < T), or with an id outside [0, n_states), gets best = -inf,
+ * n_segs = 0, spans and labels -1; the error word stays clear and no table is read with such an id.  The error word is set
+ * (best NaN, n_segs 0, spans and labels -1) when the prefix sum cum[T][c] of ANY state c < n_states of the video is not finite
+ * -- a NaN, +inf or -inf anywhere in the video's elp, also in a class the transcript never names: h = gam - cum has no value
+ * then, as in the twin -- or when a table entry the transcript reads (init[a_0], trans[a_m][a_{m-1}], len[k][a_m] for
+ * k < kp, endpen[a_{M-1}]) is a NaN or +inf; -inf in such a table entry is an ordinary "impossible".  Enqueued on `stream` only; never synchronises; a video is never split along the time axis.  The workspace is
+ * smm_align_workspace_bytes; the error word sits at smm_error_word_offset.
+ * SMM_ERR_ARG for a NULL required pointer, every output NULL, non-monotone offsets or an empty transcript;
+ * SMM_ERR_UNSUPPORTED for SMM_SHAPE_NO_EOS, a transcript longer than SMM_MAX_TRANSCRIPT, c_max or k_rows beyond the compiled
+ * kernels; SMM_ERR_WORKSPACE below smm_align_workspace_bytes -- all before anything is staged.
+ */
+#define SMM_MAX_TRANSCRIPT 256
+/* host only; 0 on invalid arguments (whatever smm_align_f64 refuses for the shape, the lengths or the offsets) */
+size_t smm_align_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host, const int64_t *transcript_offset_host);
+int smm_align_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                  const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                  const double *elp, const double *trans, const double *init, const double *len_scores,
+                  const double *endpen, const int64_t *class_map, const int32_t *transcript,
+                  const int64_t *transcript_offset_host, int64_t *spans, int64_t *labels, double *best, int32_t *n_segs,
+                  void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Factor tables of every parameter group from the model parameters (training steps), and their chain rule.
