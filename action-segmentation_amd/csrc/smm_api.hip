@@ -263,15 +263,40 @@ static bool shape_ok(const smm_shape *s)
     return s && s->b > 0 && s->n_groups > 0 && s->c_max > 0 && s->k_rows >= 2 && s->t_max > 0 && s->total_frames > 0;
 }
 
+// (of a shape that is shape_ok) within what the kernels are compiled for / every video has 1..t_max frames
+static bool limits_ok(const smm_shape *s) { return s->c_max <= SMM_MAX_STATES && s->k_rows <= SMM_MAX_K_ROWS; }
+static bool lengths_ok(const smm_shape *s, const int64_t *lengths)
+{
+    for (int i = 0; i < s->b; ++i)
+        if (lengths[i] < 1 || lengths[i] > s->t_max) return false;
+    return true;
+}
+
+// Regions of a workspace, one behind the other: take() rounds the next region's start up to 256 bytes, packed() does not
+// (regions that go up in one upload)
+struct Carver {
+    size_t cur;
+    size_t packed(size_t bytes) { const size_t o = cur; cur += bytes; return o; }
+    size_t take(size_t bytes) { const size_t o = packed(bytes); cur = align_up(cur, 256); return o; }
+};
+
+// the metadata in front of a plan (what smm_error_word_offset tells python, too)
+static void plan_meta(const smm_shape *s, SmmPlan *p)
+{
+    Carver c{0};
+    c.take(sizeof(SmmVideo) * s->b);
+    p->o_order = c.take(sizeof(int32_t) * s->b);
+    p->o_nstates = c.take(sizeof(int32_t) * s->n_groups);
+    p->o_emcum = c.take(sizeof(int32_t) * ((size_t)s->b + 1));
+    p->o_err = c.cur;
+    p->meta_bytes = p->o_err + 512;   // error word + diagnostic counters
+}
+
 static SmmPlan make_plan(const smm_shape *s, const int64_t *lengths)
 {
     SmmPlan p{};
     p.b = (size_t)s->b;
-    p.o_order = align_up(sizeof(SmmVideo) * s->b, 256);
-    p.o_nstates = p.o_order + align_up(sizeof(int32_t) * s->b, 256);
-    p.o_emcum = p.o_nstates + align_up(sizeof(int32_t) * s->n_groups, 256);
-    p.o_err = p.o_emcum + align_up(sizeof(int32_t) * ((size_t)s->b + 1), 256);
-    p.meta_bytes = p.o_err + 512;   // error word + diagnostic counters
+    plan_meta(s, &p);
     size_t h = 0;
     for (int i = 0; i < s->b; ++i) h += 8 * (size_t)s->c_max * (size_t)(lengths[i] + 1);
     p.hist_doubles = h;
@@ -290,17 +315,16 @@ static SmmPlan make_plan(const smm_shape *s, const int64_t *lengths)
 
 extern "C" size_t smm_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host)
 {
-    if (!shape_ok(shape) || !lengths_host) return 0;
-    for (int i = 0; i < shape->b; ++i)
-        if (lengths_host[i] < 1 || lengths_host[i] > shape->t_max) return 0;
+    if (!shape_ok(shape) || !lengths_host || !lengths_ok(shape, lengths_host)) return 0;
     return make_plan(shape, lengths_host).total;
 }
 
 extern "C" size_t smm_error_word_offset(const smm_shape *shape)
 {
     if (!shape_ok(shape)) return 0;
-    return align_up(sizeof(SmmVideo) * shape->b, 256) + align_up(sizeof(int32_t) * shape->b, 256) +
-           align_up(sizeof(int32_t) * shape->n_groups, 256) + align_up(sizeof(int32_t) * ((size_t)shape->b + 1), 256);
+    SmmPlan p{};
+    plan_meta(shape, &p);
+    return p.o_err;
 }
 
 struct Staged {
@@ -729,7 +753,7 @@ static int stage_uncached(const smm_shape *s, const int64_t *lengths, const int6
                           SmmPlan *plan_out)
 {
     if (!shape_ok(s) || !lengths || !frame_off || !n_states || !ws) return SMM_ERR_ARG;
-    if (s->c_max > SMM_MAX_STATES || s->k_rows > SMM_MAX_K_ROWS) return SMM_ERR_UNSUPPORTED;
+    if (!limits_ok(s)) return SMM_ERR_UNSUPPORTED;
     int c_need = 0;
     for (int g = 0; g < s->n_groups; ++g) {
         if (n_states[g] < 1 || n_states[g] > s->c_max) return SMM_ERR_ARG;
@@ -943,6 +967,47 @@ static int ring_regs(int kp_max)
 }
 
 // ------------------------------------------------------------------------------------------------ pieces
+// One side's tables as an entry point was given them (host only: the kernels' argument structs are in smm_launch.h)
+struct Tables {
+    const double *elp, *trans, *init, *len, *endpen, *logz;
+};
+
+// what every DP launch is told: the staged videos, the tables, history and error words, the sizes, and add_eos=False
+static SmmDpArgs dp_args(const smm_shape *s, const Staged &st, const Tables &t)
+{
+    SmmDpArgs a{};
+    a.videos = st.videos; a.order = st.order; a.n_states = st.n_states;
+    a.elp = t.elp; a.trans = t.trans; a.init = t.init; a.len = t.len; a.endpen = t.endpen;
+    a.hist = st.hist; a.err = st.err;
+    a.c_max = s->c_max; a.k_rows = s->k_rows; a.t_max = s->t_max; a.b = s->b;
+    if (s->flags & SMM_SHAPE_NO_EOS) { a.flags |= 8; a.endpen = nullptr; }
+    return a;
+}
+
+// The `tabs` area of a plan as the time-reversed recursion uses it
+struct ReversedTabs {
+    double *trans_t;       // [g][cm][cm] transposed
+    double *logz_b;        // [b] log Z as closed by the backward recursion (consistency value)
+};
+static ReversedTabs reversed_tabs(const smm_shape *s, double *tabs)
+{
+    return {tabs, tabs + (size_t)s->n_groups * s->c_max * s->c_max};
+}
+
+// The time-reversed recursion of one side into `hist` (backward messages in the second history half): transposed transitions
+// and closing values in `tabs`.  With SMM_SHAPE_LOGZ_BOTH smm_logz_f64 already ran it, in the forward run's launch.
+static int run_reversed(const smm_shape *shape, const Staged &st, double *hist, double *tabs, const Tables &t, hipStream_t hs)
+{
+    if (shape->flags & SMM_SHAPE_LOGZ_BOTH) return SMM_OK;
+    const ReversedTabs rt = reversed_tabs(shape, tabs);
+    smm_launch_transpose(t.trans, rt.trans_t, shape->n_groups, shape->c_max, hs);
+    SmmDpArgs a = dp_args(shape, st, t);
+    a.trans = rt.trans_t;
+    a.hist = hist;
+    a.flags |= 2;                                  // time-reversed run
+    return smm_launch_logz(a, rt.logz_b, ring_regs(st.kp_max), st.c_need, hs);
+}
+
 static int run_emission(const smm_shape *s, const Staged &st, const float *x, const double *w, const double *cst,
                         const double *inv_var, const float *cons, double *elp64, float *elp32, hipStream_t stream,
                         int first = 0, int count = -1)
@@ -1032,12 +1097,9 @@ static int run_viterbi(const smm_shape *s, const Staged &st, const double *elp, 
                        bool prep = true, bool launch = true, int timing_tag = 0)
 {
     if (!elp || !trans || !init || !len_scores) return SMM_ERR_ARG;
-    SmmDpArgs a{};
-    a.videos = st.videos; a.order = st.order; a.n_states = st.n_states;
-    const bool no_eos = (s->flags & SMM_SHAPE_NO_EOS) != 0;
-    a.elp = elp; a.trans = trans; a.init = init; a.len = len_scores; a.endpen = no_eos ? nullptr : endpen; a.class_map = class_map;
-    a.hist = st.hist; a.spans = spans; a.labels = labels; a.best = best; a.n_segs = n_segs; a.err = st.err;
-    a.c_max = s->c_max; a.k_rows = s->k_rows; a.t_max = s->t_max; a.b = s->b;
+    SmmDpArgs a = dp_args(s, st, Tables{elp, trans, init, len_scores, endpen, nullptr});
+    a.class_map = class_map;
+    a.spans = spans; a.labels = labels; a.best = best; a.n_segs = n_segs;
     if (count >= 0) { a.order = st.order + first; a.b = count; }
     // time-split videos (smm_chunk.hip): the launch runs over UNITS -- [the split videos' units | the unsplit videos]; a stream
     // split's first part is exactly the units
@@ -1050,11 +1112,9 @@ static int run_viterbi(const smm_shape *s, const Staged &st, const double *elp, 
         else if (first == 0) { a.order = st.uorder; a.b = st.u_part1; }
         else { a.order = st.uorder + st.u_part1; a.b = st.n_units - st.u_part1; }
     }
-    a.flags = 0;
 #ifdef SMM_DEV
-    a.flags = env().debug_flags;                              // (SmmDpArgs::flags bit 0: profiling, outputs undefined)
+    a.flags |= env().debug_flags;                             // (SmmDpArgs::flags bit 0: profiling, outputs undefined)
 #endif
-    if (no_eos) a.flags |= 8;
     if (!env().spec) a.flags |= 256;                          // A/B aid: no speculative transition
     if (st.band_mode) {
         double *len_t = st.band, *band_tab = st.band + (size_t)s->n_groups * s->c_max * SMM_BAND_ROW;
@@ -1340,20 +1400,14 @@ extern "C" int smm_logz_f64(const smm_shape *shape, const int64_t *lengths_host,
                    hs, &st);
     if (rc != SMM_OK) return rc;
     if (!elp || !trans || !init || !len_scores || !logz) return SMM_ERR_ARG;
-    SmmDpArgs a{};
-    a.videos = st.videos; a.order = st.order; a.n_states = st.n_states;
-    a.elp = elp; a.trans = trans; a.init = init; a.len = len_scores; a.endpen = endpen;
-    a.hist = st.hist; a.err = st.err;
-    a.c_max = shape->c_max; a.k_rows = shape->k_rows; a.t_max = shape->t_max; a.b = shape->b;
-    if (shape->flags & SMM_SHAPE_NO_EOS) { a.flags |= 8; a.endpen = nullptr; }
+    SmmDpArgs a = dp_args(shape, st, Tables{elp, trans, init, len_scores, endpen, nullptr});
     if (shape->flags & SMM_SHAPE_LOGZ_BOTH) {
         // forward and time-reversed recursion in one launch: the transposed tables and the reversed runs' closing values
-        // live where smm_logz_bwd_f64 keeps them
-        const size_t g = shape->n_groups, cm = shape->c_max;
-        double *trans_t = st.tabs;
-        smm_launch_transpose(trans, trans_t, (int)g, (int)cm, hs);
-        a.trans_t = trans_t;
-        a.logz_b = trans_t + g * cm * cm;
+        // live where run_reversed keeps them
+        const ReversedTabs rt = reversed_tabs(shape, st.tabs);
+        smm_launch_transpose(trans, rt.trans_t, shape->n_groups, shape->c_max, hs);
+        a.trans_t = rt.trans_t;
+        a.logz_b = rt.logz_b;
         a.flags |= 64;
     }
     rc = smm_launch_logz(a, logz, ring_regs(st.kp_max), st.c_need, hs);
@@ -1376,21 +1430,9 @@ extern "C" int smm_logz_bwd_f64(const smm_shape *shape, const int64_t *lengths_h
     if (rc != SMM_OK) return rc;
     if (!elp || !trans || !init || !len_scores || !logz || !g_elp || !g_trans || !g_init || !g_len) return SMM_ERR_ARG;
     const size_t g = shape->n_groups, cm = shape->c_max;
-    double *trans_t = st.tabs;                 // [g][cm][cm] transposed
-    double *logz_b = trans_t + g * cm * cm;    // [b] log Z as closed by the backward recursion (consistency value)
     const bool no_eos = (shape->flags & SMM_SHAPE_NO_EOS) != 0;
-    if (!(shape->flags & SMM_SHAPE_LOGZ_BOTH)) {   // (else: smm_logz_f64 already ran the reversed recursion)
-        smm_launch_transpose(trans, trans_t, (int)g, (int)cm, hs);
-        SmmDpArgs a{};
-        a.videos = st.videos; a.order = st.order; a.n_states = st.n_states;
-        a.elp = elp; a.trans = trans_t; a.init = init; a.len = len_scores; a.endpen = endpen;
-        a.hist = st.hist; a.err = st.err;
-        a.c_max = shape->c_max; a.k_rows = shape->k_rows; a.t_max = shape->t_max; a.b = shape->b;
-        a.flags = 2;                               // time-reversed run -> backward messages in the second history half
-        if (no_eos) { a.flags |= 8; a.endpen = nullptr; }
-        rc = smm_launch_logz(a, logz_b, ring_regs(st.kp_max), st.c_need, hs);
-        if (rc != SMM_OK) return rc;
-    }
+    rc = run_reversed(shape, st, st.hist, st.tabs, Tables{elp, trans, init, len_scores, endpen, logz}, hs);
+    if (rc != SMM_OK) return rc;
     {
         void *const zp[4] = {g_trans, g_init, g_len, g_elp};
         const size_t zb[4] = {sizeof(double) * g * cm * cm, sizeof(double) * g * cm, sizeof(double) * g * shape->k_rows * cm,
@@ -1444,22 +1486,9 @@ extern "C" int smm_entropy_f64(const smm_shape *shape, const int64_t *lengths_ho
     int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes,
                    hs, &st);
     if (rc != SMM_OK) return rc;
-    const size_t g = shape->n_groups, cm = shape->c_max;
     const bool no_eos = (shape->flags & SMM_SHAPE_NO_EOS) != 0;
-    if (!(shape->flags & SMM_SHAPE_LOGZ_BOTH)) {   // the backward histories, as smm_logz_bwd_f64 makes them
-        double *trans_t = st.tabs;
-        double *logz_b = trans_t + g * cm * cm;
-        smm_launch_transpose(trans, trans_t, (int)g, (int)cm, hs);
-        SmmDpArgs a{};
-        a.videos = st.videos; a.order = st.order; a.n_states = st.n_states;
-        a.elp = elp; a.trans = trans_t; a.init = init; a.len = len_scores; a.endpen = endpen;
-        a.hist = st.hist; a.err = st.err;
-        a.c_max = shape->c_max; a.k_rows = shape->k_rows; a.t_max = shape->t_max; a.b = shape->b;
-        a.flags = 2;
-        if (no_eos) { a.flags |= 8; a.endpen = nullptr; }
-        rc = smm_launch_logz(a, logz_b, ring_regs(st.kp_max), st.c_need, hs);
-        if (rc != SMM_OK) return rc;
-    }
+    rc = run_reversed(shape, st, st.hist, st.tabs, Tables{elp, trans, init, len_scores, endpen, logz}, hs);
+    if (rc != SMM_OK) return rc;
     SmmEntropyArgs e{};
     e.videos = st.videos; e.n_states = st.n_states; e.hist = st.hist;
     e.elp = elp; e.trans = trans; e.len = len_scores; e.endpen = no_eos ? nullptr : endpen; e.logz = logz;
@@ -1467,6 +1496,17 @@ extern "C" int smm_entropy_f64(const smm_shape *shape, const int64_t *lengths_ho
     e.c_max = shape->c_max; e.k_rows = shape->k_rows; e.b = shape->b; e.no_eos = no_eos ? 1 : 0;
     smm_launch_entropy(e, shape->t_max, hs);
     SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
+// The second workspace of the KL calls (q's forward histories) is only read: checked against the plan, before p's is staged,
+// and pointed into
+static int point_q(const smm_shape *shape, const int64_t *lengths_host, void *ws_q, size_t ws_q_bytes, Staged *sq)
+{
+    const size_t need = smm_workspace_bytes(shape, lengths_host);
+    if (need == 0) return SMM_ERR_ARG;
+    if (ws_q_bytes < need) return SMM_ERR_WORKSPACE;
+    plan_point(make_plan(shape, lengths_host), ws_q, sq);
     return SMM_OK;
 }
 
@@ -1481,32 +1521,16 @@ extern "C" int smm_kl_f64(const smm_shape *shape, const int64_t *lengths_host, c
     if (!kl_out || !elp_p || !trans_p || !init_p || !len_p || !logz_p || !elp_q || !trans_q || !init_q || !len_q || !logz_q ||
         !ws_q)
         return SMM_ERR_ARG;
-    // q's workspace is only read (its forward histories): checked against the plan before p's is staged
-    const size_t need = smm_workspace_bytes(shape, lengths_host);
-    if (need == 0) return SMM_ERR_ARG;
-    if (ws_q_bytes < need) return SMM_ERR_WORKSPACE;
+    Staged sq;
+    const int rq = point_q(shape, lengths_host, ws_q, ws_q_bytes, &sq);
+    if (rq != SMM_OK) return rq;
     Staged st;
     hipStream_t hs = static_cast<hipStream_t>(stream);
     int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, ws_p, ws_p_bytes, hs, &st);
     if (rc != SMM_OK) return rc;
-    Staged sq;
-    plan_point(make_plan(shape, lengths_host), ws_q, &sq);
-    const size_t g = shape->n_groups, cm = shape->c_max;
     const bool no_eos = (shape->flags & SMM_SHAPE_NO_EOS) != 0;
-    if (!(shape->flags & SMM_SHAPE_LOGZ_BOTH)) {   // p's backward histories, as smm_logz_bwd_f64 makes them
-        double *trans_t = st.tabs;
-        double *logz_b = trans_t + g * cm * cm;
-        smm_launch_transpose(trans_p, trans_t, (int)g, (int)cm, hs);
-        SmmDpArgs a{};
-        a.videos = st.videos; a.order = st.order; a.n_states = st.n_states;
-        a.elp = elp_p; a.trans = trans_t; a.init = init_p; a.len = len_p; a.endpen = endpen_p;
-        a.hist = st.hist; a.err = st.err;
-        a.c_max = shape->c_max; a.k_rows = shape->k_rows; a.t_max = shape->t_max; a.b = shape->b;
-        a.flags = 2;
-        if (no_eos) { a.flags |= 8; a.endpen = nullptr; }
-        rc = smm_launch_logz(a, logz_b, ring_regs(st.kp_max), st.c_need, hs);
-        if (rc != SMM_OK) return rc;
-    }
+    rc = run_reversed(shape, st, st.hist, st.tabs, Tables{elp_p, trans_p, init_p, len_p, endpen_p, logz_p}, hs);   // (p's side only)
+    if (rc != SMM_OK) return rc;
     SmmKlArgs k{};
     k.videos = st.videos; k.n_states = st.n_states; k.hist_p = st.hist; k.hist_q = sq.hist;
     k.elp_p = elp_p; k.elp_q = elp_q; k.trans_p = trans_p; k.trans_q = trans_q; k.len_p = len_p; k.len_q = len_q;
@@ -1524,13 +1548,9 @@ extern "C" int smm_kl_f64(const smm_shape *shape, const int64_t *lengths_host, c
 // and the occupancy differences), then one fixed part per video (its tables and values)
 static bool ebwd_layout(const smm_shape *s, const int64_t *lengths, size_t *pv_base, size_t *total_doubles)
 {
-    if (!shape_ok(s) || !lengths) return false;
-    if (s->c_max > SMM_MAX_STATES || s->k_rows > SMM_MAX_K_ROWS) return false;
+    if (!shape_ok(s) || !lengths || !limits_ok(s) || !lengths_ok(s, lengths)) return false;
     size_t h = 0;
-    for (int i = 0; i < s->b; ++i) {
-        if (lengths[i] < 1 || lengths[i] > s->t_max) return false;
-        h += 6 * (size_t)s->c_max * (size_t)(lengths[i] + 1);
-    }
+    for (int i = 0; i < s->b; ++i) h += 6 * (size_t)s->c_max * (size_t)(lengths[i] + 1);
     *pv_base = h;
     *total_doubles = h + (size_t)s->b * smm_entropy_bwd_fixed_doubles(s->c_max, s->k_rows);
     return true;
@@ -1543,30 +1563,10 @@ extern "C" size_t smm_entropy_bwd_scratch_bytes(const smm_shape *shape, const in
     return sizeof(double) * tot;
 }
 
-// the time-reversed recursion of one side into `hist` (smm_logz_bwd_f64's): transposed transitions and closing values in `tabs`
-static int ebwd_reversed(const smm_shape *shape, const Staged &st, double *hist, double *tabs, const double *elp,
-                         const double *trans, const double *init, const double *len, const double *endpen, hipStream_t hs)
-{
-    const size_t g = shape->n_groups, cm = shape->c_max;
-    double *trans_t = tabs, *logz_b = tabs + g * cm * cm;
-    smm_launch_transpose(trans, trans_t, (int)g, (int)cm, hs);
-    SmmDpArgs a{};
-    a.videos = st.videos; a.order = st.order; a.n_states = st.n_states;
-    a.elp = elp; a.trans = trans_t; a.init = init; a.len = len; a.endpen = endpen;
-    a.hist = hist; a.err = st.err;
-    a.c_max = shape->c_max; a.k_rows = shape->k_rows; a.t_max = shape->t_max; a.b = shape->b;
-    a.flags = 2;
-    if (shape->flags & SMM_SHAPE_NO_EOS) { a.flags |= 8; a.endpen = nullptr; }
-    return smm_launch_logz(a, logz_b, ring_regs(st.kp_max), st.c_need, hs);
-}
-
 // both entry points: p's histories in st, r's in hist_r (r = p for the entropy)
 static int ebwd_run(const smm_shape *shape, const int64_t *lengths_host, const Staged &st, const double *hist_r,
-                    const double *elp_p, const double *trans_p, const double *init_p, const double *len_p,
-                    const double *endpen_p, const double *logz_p, const double *elp_r, const double *trans_r,
-                    const double *init_r, const double *len_r, const double *endpen_r, const double *logz_r, int kl,
-                    const double *grad_out, double *g_elp, double *g_trans, double *g_init, double *g_len, double *value_out,
-                    void *scratch, hipStream_t hs)
+                    const Tables &p, const Tables &r, int kl, const double *grad_out, double *g_elp, double *g_trans,
+                    double *g_init, double *g_len, double *value_out, void *scratch, hipStream_t hs)
 {
     size_t pv_base = 0, tot = 0;
     ebwd_layout(shape, lengths_host, &pv_base, &tot);
@@ -1580,10 +1580,10 @@ static int ebwd_run(const smm_shape *shape, const int64_t *lengths_host, const S
     }
     SmmEntBwdArgs e{};
     e.videos = st.videos; e.n_states = st.n_states; e.hist_p = st.hist; e.hist_r = hist_r;
-    e.elp_p = elp_p; e.elp_r = elp_r; e.trans_p = trans_p; e.trans_r = trans_r; e.init_p = init_p; e.init_r = init_r;
-    e.len_p = len_p; e.len_r = len_r;
-    e.endpen_p = no_eos ? nullptr : endpen_p; e.endpen_r = no_eos ? nullptr : endpen_r;
-    e.logz_p = logz_p; e.logz_r = logz_r; e.grad_out = grad_out;
+    e.elp_p = p.elp; e.elp_r = r.elp; e.trans_p = p.trans; e.trans_r = r.trans; e.init_p = p.init; e.init_r = r.init;
+    e.len_p = p.len; e.len_r = r.len;
+    e.endpen_p = no_eos ? nullptr : p.endpen; e.endpen_r = no_eos ? nullptr : r.endpen;
+    e.logz_p = p.logz; e.logz_r = r.logz; e.grad_out = grad_out;
     e.g_elp = g_elp; e.g_trans = g_trans; e.g_init = g_init; e.g_len = g_len; e.value = value_out;
     e.scratch = sc; e.pv_base = (int64_t)pv_base; e.err = st.err;
     e.c_max = shape->c_max; e.k_rows = shape->k_rows; e.b = shape->b; e.n_groups = (int32_t)g; e.no_eos = no_eos ? 1 : 0;
@@ -1610,12 +1610,10 @@ extern "C" int smm_entropy_bwd_f64(const smm_shape *shape, const int64_t *length
     int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes,
                    hs, &st);
     if (rc != SMM_OK) return rc;
-    if (!(shape->flags & SMM_SHAPE_LOGZ_BOTH)) {   // the backward histories, as smm_logz_bwd_f64 makes them
-        rc = ebwd_reversed(shape, st, st.hist, st.tabs, elp, trans, init, len_scores, endpen, hs);
-        if (rc != SMM_OK) return rc;
-    }
-    return ebwd_run(shape, lengths_host, st, st.hist, elp, trans, init, len_scores, endpen, logz, elp, trans, init, len_scores,
-                    endpen, logz, 0, grad_out, g_elp, g_trans, g_init, g_len, value_out, scratch, hs);
+    const Tables p{elp, trans, init, len_scores, endpen, logz};
+    rc = run_reversed(shape, st, st.hist, st.tabs, p, hs);
+    if (rc != SMM_OK) return rc;
+    return ebwd_run(shape, lengths_host, st, st.hist, p, p, 0, grad_out, g_elp, g_trans, g_init, g_len, value_out, scratch, hs);
 }
 
 extern "C" int smm_kl_bwd_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
@@ -1631,9 +1629,9 @@ extern "C" int smm_kl_bwd_f64(const smm_shape *shape, const int64_t *lengths_hos
     if (!elp_p || !trans_p || !init_p || !len_p || !logz_p || !elp_q || !trans_q || !init_q || !len_q || !logz_q || !ws_q ||
         !g_elp || !g_trans || !g_init || !g_len || !scratch)
         return SMM_ERR_ARG;
-    const size_t need = smm_workspace_bytes(shape, lengths_host);
-    if (need == 0) return SMM_ERR_ARG;
-    if (ws_q_bytes < need) return SMM_ERR_WORKSPACE;
+    Staged sq;
+    const int rq = point_q(shape, lengths_host, ws_q, ws_q_bytes, &sq);
+    if (rq != SMM_OK) return rq;
     const size_t sneed = smm_entropy_bwd_scratch_bytes(shape, lengths_host);
     if (sneed == 0) return SMM_ERR_ARG;
     if (scratch_bytes < sneed) return SMM_ERR_WORKSPACE;
@@ -1641,17 +1639,12 @@ extern "C" int smm_kl_bwd_f64(const smm_shape *shape, const int64_t *lengths_hos
     hipStream_t hs = static_cast<hipStream_t>(stream);
     int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, ws_p, ws_p_bytes, hs, &st);
     if (rc != SMM_OK) return rc;
-    Staged sq;
-    plan_point(make_plan(shape, lengths_host), ws_q, &sq);
-    if (!(shape->flags & SMM_SHAPE_LOGZ_BOTH)) {   // both sides' backward histories
-        rc = ebwd_reversed(shape, st, st.hist, st.tabs, elp_p, trans_p, init_p, len_p, endpen_p, hs);
-        if (rc == SMM_OK && sq.hist != st.hist)
-            rc = ebwd_reversed(shape, st, sq.hist, sq.tabs, elp_q, trans_q, init_q, len_q, endpen_q, hs);
-        if (rc != SMM_OK) return rc;
-    }
-    return ebwd_run(shape, lengths_host, st, sq.hist, elp_p, trans_p, init_p, len_p, endpen_p, logz_p, elp_q, trans_q, init_q,
-                    len_q, endpen_q, logz_q, mode == SMM_KL_BWD_KL ? 1 : 0, grad_out, g_elp, g_trans, g_init, g_len, value_out,
-                    scratch, hs);
+    const Tables p{elp_p, trans_p, init_p, len_p, endpen_p, logz_p}, q{elp_q, trans_q, init_q, len_q, endpen_q, logz_q};
+    rc = run_reversed(shape, st, st.hist, st.tabs, p, hs);          // both sides' backward histories
+    if (rc == SMM_OK && sq.hist != st.hist) rc = run_reversed(shape, st, sq.hist, sq.tabs, q, hs);
+    if (rc != SMM_OK) return rc;
+    return ebwd_run(shape, lengths_host, st, sq.hist, p, q, mode == SMM_KL_BWD_KL ? 1 : 0, grad_out, g_elp, g_trans, g_init,
+                    g_len, value_out, scratch, hs);
 }
 
 // ------------------------------------------------------------------------------------------------ k best
@@ -1665,27 +1658,22 @@ struct KbestLayout {
 
 static bool kbest_layout(const smm_shape *s, const int64_t *lengths, int32_t k, KbestLayout *lo)
 {
-    if (k < 1 || k > SMM_MAX_KBEST || !shape_ok(s) || !lengths) return false;
-    if (s->c_max > SMM_MAX_STATES || s->k_rows > SMM_MAX_K_ROWS) return false;
+    if (k < 1 || k > SMM_MAX_KBEST || !shape_ok(s) || !lengths || !limits_ok(s) || !lengths_ok(s, lengths)) return false;
     int64_t n_pos = 0;
-    for (int i = 0; i < s->b; ++i) {
-        if (lengths[i] < 1 || lengths[i] > s->t_max) return false;
-        n_pos += lengths[i] + 1;
-    }
+    for (int i = 0; i < s->b; ++i) n_pos += lengths[i] + 1;
     const size_t cm = (size_t)s->c_max, kk = (size_t)k, b = (size_t)s->b;
     lo->n_pos = n_pos;
     lo->ring = std::min<int>(s->k_rows, s->t_max + 1);
-    size_t cur = align_up(make_plan(s, lengths).total, 256);
-    auto take = [&](size_t bytes) { const size_t o = cur; cur = align_up(cur + bytes, 256); return o; };
-    lo->o_lent = take(sizeof(double) * s->n_groups * cm * s->k_rows);
-    lo->o_hh = take(sizeof(double) * b * cm * lo->ring);
-    lo->o_h = take(sizeof(double) * b * lo->ring * cm * kk);
-    lo->o_gbp = take(sizeof(uint16_t) * (size_t)n_pos * cm * kk);
-    lo->o_hbp = take(sizeof(uint16_t) * (size_t)n_pos * cm * kk);
-    lo->o_fv = take(sizeof(double) * b * kk);
-    lo->o_fk = take(sizeof(int32_t) * b * kk);
-    lo->o_segs = take(sizeof(int32_t) * kk * (size_t)n_pos);
-    lo->total = cur;
+    Carver c{align_up(make_plan(s, lengths).total, 256)};
+    lo->o_lent = c.take(sizeof(double) * s->n_groups * cm * s->k_rows);
+    lo->o_hh = c.take(sizeof(double) * b * cm * lo->ring);
+    lo->o_h = c.take(sizeof(double) * b * lo->ring * cm * kk);
+    lo->o_gbp = c.take(sizeof(uint16_t) * (size_t)n_pos * cm * kk);
+    lo->o_hbp = c.take(sizeof(uint16_t) * (size_t)n_pos * cm * kk);
+    lo->o_fv = c.take(sizeof(double) * b * kk);
+    lo->o_fk = c.take(sizeof(int32_t) * b * kk);
+    lo->o_segs = c.take(sizeof(int32_t) * kk * (size_t)n_pos);
+    lo->total = c.cur;
     return true;
 }
 
@@ -1704,7 +1692,7 @@ extern "C" int smm_kbest_f64(const smm_shape *shape, const int64_t *lengths_host
 {
     if (k < 1 || k > SMM_MAX_KBEST || (!spans_out && !labels_out && !score_out && !n_segs_out)) return SMM_ERR_ARG;
     if (!shape_ok(shape) || !lengths_host) return SMM_ERR_ARG;
-    if (shape->c_max > SMM_MAX_STATES || shape->k_rows > SMM_MAX_K_ROWS) return SMM_ERR_UNSUPPORTED;
+    if (!limits_ok(shape)) return SMM_ERR_UNSUPPORTED;
     KbestLayout lo;
     if (!kbest_layout(shape, lengths_host, k, &lo)) return SMM_ERR_ARG;
     if (!workspace) return SMM_ERR_ARG;
@@ -1743,10 +1731,7 @@ extern "C" int smm_kbest_f64(const smm_shape *shape, const int64_t *lengths_host
 // suffix maxima of h, then the frame labels.  Nothing behind the plan's `total`.
 static bool mbr_shape_ok(const smm_shape *s, const int64_t *lengths)
 {
-    if (!shape_ok(s) || !lengths || s->c_max > SMM_MAX_STATES || s->k_rows > SMM_MAX_K_ROWS) return false;
-    for (int i = 0; i < s->b; ++i)
-        if (lengths[i] < 1 || lengths[i] > s->t_max) return false;
-    return true;
+    return shape_ok(s) && lengths && limits_ok(s) && lengths_ok(s, lengths);
 }
 
 extern "C" size_t smm_mbr_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host)
@@ -1761,7 +1746,7 @@ extern "C" int smm_mbr_f64(const smm_shape *shape, const int64_t *lengths_host, 
                            int32_t *n_segs, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!shape_ok(shape) || !lengths_host || !frame_offset_host || !n_states_host) return SMM_ERR_ARG;
-    if (shape->c_max > SMM_MAX_STATES || shape->k_rows > SMM_MAX_K_ROWS) return SMM_ERR_UNSUPPORTED;
+    if (!limits_ok(shape)) return SMM_ERR_UNSUPPORTED;
     if (!gain || !trans || !init || !workspace) return SMM_ERR_ARG;
     if (!spans && !labels && !best && !gain_sum && !n_segs) return SMM_ERR_ARG;
     const size_t need = smm_mbr_workspace_bytes(shape, lengths_host);
@@ -1795,12 +1780,11 @@ struct AlignLayout {
 static int align_layout(const smm_shape *s, const int64_t *lengths, const int64_t *toff, AlignLayout *lo)
 {
     if (!shape_ok(s) || !lengths || !toff) return SMM_ERR_ARG;
-    if ((s->flags & SMM_SHAPE_NO_EOS) || s->c_max > SMM_MAX_STATES || s->k_rows > SMM_MAX_K_ROWS) return SMM_ERR_UNSUPPORTED;
-    if (toff[0] < 0) return SMM_ERR_ARG;
+    if ((s->flags & SMM_SHAPE_NO_EOS) || !limits_ok(s)) return SMM_ERR_UNSUPPORTED;
+    if (toff[0] < 0 || !lengths_ok(s, lengths)) return SMM_ERR_ARG;
     size_t cells = 0;
     bool too_long = false;
     for (int i = 0; i < s->b; ++i) {
-        if (lengths[i] < 1 || lengths[i] > s->t_max) return SMM_ERR_ARG;
         const int64_t m = toff[i + 1] - toff[i];
         if (m < 1) return SMM_ERR_ARG;                      // non-monotone offsets, or an empty transcript
         too_long |= m > SMM_MAX_TRANSCRIPT;
@@ -1808,12 +1792,13 @@ static int align_layout(const smm_shape *s, const int64_t *lengths, const int64_
     }
     if (too_long) return SMM_ERR_UNSUPPORTED;
     const size_t b = (size_t)s->b;
-    lo->o_toff = align_up(make_plan(s, lengths).total, 256);
-    lo->o_hoff = lo->o_toff + sizeof(int64_t) * (b + 1);
-    lo->o_order = lo->o_hoff + sizeof(int64_t) * b;
+    Carver c{align_up(make_plan(s, lengths).total, 256)};
+    lo->o_toff = c.packed(sizeof(int64_t) * (b + 1));      // (the three arrays go up in one upload)
+    lo->o_hoff = c.packed(sizeof(int64_t) * b);
+    lo->o_order = c.take(sizeof(int32_t) * b);
     lo->meta_end = lo->o_order + sizeof(int32_t) * b;
-    lo->o_hcols = align_up(lo->meta_end, 256);
-    lo->total = lo->o_hcols + sizeof(double) * cells;
+    lo->o_hcols = c.packed(sizeof(double) * cells);
+    lo->total = c.cur;
     return SMM_OK;
 }
 
@@ -1879,47 +1864,63 @@ extern "C" int smm_align_f64(const smm_shape *shape, const int64_t *lengths_host
 }
 
 // ------------------------------------------------------------------------------------------------ dense boundary
-static size_t dense_off(size_t &cur, size_t bytes)
+struct DenseLayout {
+    size_t o_len, o_alpha, o_beta, o_bp_from, o_bp_k, o_rmsg, total;
+};
+
+static DenseLayout dense_layout(int32_t b, int32_t n1, int32_t k, int32_t c)
 {
-    const size_t o = cur;
-    cur += align_up(bytes, 256);
-    return o;
+    DenseLayout lo;
+    Carver cv{0};
+    lo.o_len = cv.take(sizeof(int64_t) * b);
+    lo.o_alpha = cv.take(sizeof(double) * (size_t)b * k * k * c);
+    lo.o_beta = cv.take(sizeof(double) * (size_t)b * (n1 + 1) * c);
+    lo.o_bp_from = cv.take((size_t)b * n1 * k * c);
+    lo.o_bp_k = cv.take(sizeof(uint16_t) * (size_t)b * (n1 + 1) * c);
+    lo.o_rmsg = cv.take(sizeof(double) * (size_t)b * (n1 + 1) * c);       // backward messages (smm_dense_marginals_f32)
+    lo.total = cv.cur;
+    return lo;
 }
 
 extern "C" size_t smm_dense_workspace_bytes(int32_t b, int32_t n1, int32_t k, int32_t c)
 {
     if (b < 1 || n1 < 1 || k < 1 || c < 1) return 0;
-    size_t cur = 0;
-    dense_off(cur, sizeof(int64_t) * b);
-    dense_off(cur, sizeof(double) * (size_t)b * k * k * c);
-    dense_off(cur, sizeof(double) * (size_t)b * (n1 + 1) * c);
-    dense_off(cur, (size_t)b * n1 * k * c);
-    dense_off(cur, sizeof(uint16_t) * (size_t)b * (n1 + 1) * c);
-    dense_off(cur, sizeof(double) * (size_t)b * (n1 + 1) * c);      // backward messages (smm_dense_marginals_f32)
-    return cur;
+    return dense_layout(b, n1, k, c).total;
+}
+
+// both entry points: the refusals (ptrs_ok: no required pointer is null), then what every launch is told
+static int dense_args(bool ptrs_ok, const float *scores, const int64_t *lengths_host, int32_t b, int32_t n1, int32_t k, int32_t c,
+                      void *workspace, size_t workspace_bytes, DenseLayout *lo, SmmDenseArgs *a)
+{
+    if (!ptrs_ok || !scores || !lengths_host || !workspace || b < 1 || n1 < 1 || k < 1 || c < 1) return SMM_ERR_ARG;
+    if (c > 255 || k > 65535) return SMM_ERR_UNSUPPORTED;
+    *lo = dense_layout(b, n1, k, c);
+    if (workspace_bytes < lo->total) return SMM_ERR_WORKSPACE;
+    for (int i = 0; i < b; ++i)
+        if (lengths_host[i] < 1 || lengths_host[i] > n1 + 1) return SMM_ERR_ARG;
+    char *base = static_cast<char *>(workspace);
+    a->edge = scores;
+    a->lengths = reinterpret_cast<int64_t *>(base + lo->o_len);
+    a->alpha = reinterpret_cast<double *>(base + lo->o_alpha);
+    a->beta = reinterpret_cast<double *>(base + lo->o_beta);
+    a->b = b; a->n1 = n1; a->k = k; a->c = c;
+    return SMM_OK;
 }
 
 extern "C" int smm_dense_dp_f32(const float *scores, const int64_t *lengths_host, int32_t b, int32_t n1, int32_t k,
                                 int32_t c, int32_t semiring, double *v, int64_t *spans, void *workspace,
                                 size_t workspace_bytes, void *stream)
 {
-    if (!scores || !lengths_host || !v || !workspace || b < 1 || n1 < 1 || k < 1 || c < 1) return SMM_ERR_ARG;
-    if (c > 255 || k > 65535) return SMM_ERR_UNSUPPORTED;
-    if (workspace_bytes < smm_dense_workspace_bytes(b, n1, k, c)) return SMM_ERR_WORKSPACE;
-    for (int i = 0; i < b; ++i)
-        if (lengths_host[i] < 1 || lengths_host[i] > n1 + 1) return SMM_ERR_ARG;
+    DenseLayout lo;
+    SmmDenseArgs a{};
+    const int rc = dense_args(v != nullptr, scores, lengths_host, b, n1, k, c, workspace, workspace_bytes, &lo, &a);
+    if (rc != SMM_OK) return rc;
     hipStream_t hs = static_cast<hipStream_t>(stream);
     char *base = static_cast<char *>(workspace);
-    size_t cur = 0;
-    SmmDenseArgs a{};
-    int64_t *dlen = reinterpret_cast<int64_t *>(base + dense_off(cur, sizeof(int64_t) * b));
-    a.alpha = reinterpret_cast<double *>(base + dense_off(cur, sizeof(double) * (size_t)b * k * k * c));
-    a.beta = reinterpret_cast<double *>(base + dense_off(cur, sizeof(double) * (size_t)b * (n1 + 1) * c));
-    a.bp_from = reinterpret_cast<uint8_t *>(base + dense_off(cur, (size_t)b * n1 * k * c));
-    a.bp_k = reinterpret_cast<uint16_t *>(base + dense_off(cur, sizeof(uint16_t) * (size_t)b * (n1 + 1) * c));
-    SMM_HIP((hipError_t)smm_upload_meta(dlen, lengths_host, sizeof(int64_t) * b, hs));
-    a.edge = scores; a.lengths = dlen; a.v = v; a.spans = spans;
-    a.b = b; a.n1 = n1; a.k = k; a.c = c;
+    a.bp_from = reinterpret_cast<uint8_t *>(base + lo.o_bp_from);
+    a.bp_k = reinterpret_cast<uint16_t *>(base + lo.o_bp_k);
+    SMM_HIP((hipError_t)smm_upload_meta(base + lo.o_len, lengths_host, sizeof(int64_t) * b, hs));
+    a.v = v; a.spans = spans;
     smm_launch_dense(a, semiring != 0, hs);
     SMM_HIP(hipGetLastError());
     return SMM_OK;
@@ -1929,24 +1930,14 @@ extern "C" int smm_dense_marginals_f32(const float *scores, const int64_t *lengt
                                        int32_t c, const double *v, const double *grad_v, float *marginals, void *workspace,
                                        size_t workspace_bytes, void *stream)
 {
-    if (!scores || !lengths_host || !v || !marginals || !workspace || b < 1 || n1 < 1 || k < 1 || c < 1) return SMM_ERR_ARG;
-    if (c > 255 || k > 65535) return SMM_ERR_UNSUPPORTED;
-    if (workspace_bytes < smm_dense_workspace_bytes(b, n1, k, c)) return SMM_ERR_WORKSPACE;
-    for (int i = 0; i < b; ++i)
-        if (lengths_host[i] < 1 || lengths_host[i] > n1 + 1) return SMM_ERR_ARG;
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    char *base = static_cast<char *>(workspace);
-    size_t cur = 0;
+    DenseLayout lo;
     SmmDenseArgs a{};
-    int64_t *dlen = reinterpret_cast<int64_t *>(base + dense_off(cur, sizeof(int64_t) * b));
-    a.alpha = reinterpret_cast<double *>(base + dense_off(cur, sizeof(double) * (size_t)b * k * k * c));
-    a.beta = reinterpret_cast<double *>(base + dense_off(cur, sizeof(double) * (size_t)b * (n1 + 1) * c));
-    dense_off(cur, (size_t)b * n1 * k * c);
-    dense_off(cur, sizeof(uint16_t) * (size_t)b * (n1 + 1) * c);
-    double *rmsg = reinterpret_cast<double *>(base + dense_off(cur, sizeof(double) * (size_t)b * (n1 + 1) * c));
-    a.edge = scores; a.lengths = dlen; a.v = const_cast<double *>(v);
-    a.b = b; a.n1 = n1; a.k = k; a.c = c;
-    smm_launch_dense_marginals(a, rmsg, grad_v, marginals, hs);     // (dlen, beta: left by smm_dense_dp_f32, semiring 1)
+    const int rc = dense_args(v && marginals, scores, lengths_host, b, n1, k, c, workspace, workspace_bytes, &lo, &a);
+    if (rc != SMM_OK) return rc;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    double *rmsg = reinterpret_cast<double *>(static_cast<char *>(workspace) + lo.o_rmsg);
+    a.v = const_cast<double *>(v);
+    smm_launch_dense_marginals(a, rmsg, grad_v, marginals, hs);     // (lengths, beta: left by smm_dense_dp_f32, semiring 1)
     SMM_HIP(hipGetLastError());
     return SMM_OK;
 }

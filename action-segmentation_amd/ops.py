@@ -59,6 +59,16 @@ class Batch:
                 None if self.group is None else self.group.ctypes.data,
                 None if self.kp is None else self.kp.ctypes.data, self.n_states.ctypes.data)
 
+    def head(self, extra_flags=0, with_kp=True):
+        """The leading arguments of an entry point as ctypes values: the smm_shape -- with extra SMM_SHAPE_* bits for this one
+        call -- and the host arrays (lengths, frame_offset, group, kp, n_states; the emission pair takes no kp)."""
+        s = self.shape
+        if extra_flags:
+            s = SmmShape(s.b, s.d, s.n_groups, s.c_max, s.k_rows, s.t_max, s.flags | extra_flags, s.total_frames)
+        ln, fo, gr, kp, ns = self.host_ptrs()
+        p = ctypes.c_void_p
+        return (ctypes.byref(s), p(ln), p(fo), p(gr)) + ((p(kp),) if with_kp else ()) + (p(ns),)
+
 
 def _dev(t, dtype, name):
     if t is None:
@@ -70,6 +80,11 @@ def _dev(t, dtype, name):
     if not t.is_contiguous():
         raise ValueError("%s must be contiguous" % name)
     return ctypes.c_void_p(t.data_ptr())
+
+
+def _ws_args(ws):
+    """A workspace (or scratch) tensor as the C ABI takes it: pointer, bytes."""
+    return ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel())
 
 
 def _raw_stream():
@@ -197,6 +212,28 @@ def _outputs(batch, device, want_spans, want_labels, labels_on_host=False, label
     return spans, labels, best, n_segs
 
 
+def _device_outputs(batch, device, want_spans, want_labels, lead=()):
+    """spans / labels (-1 on frames no video covers) / an fp64 and an int32 value per video, all on the device, of ``sample``,
+    ``kbest``, ``mbr`` and ``align``; ``lead``: the leading [n_samples] / [k] dimension."""
+    spans = torch.empty(lead + (batch.b, batch.t_max + 1), dtype=torch.int64, device=device) if want_spans else None
+    labels = torch.full(lead + (batch.total_frames,), -1, dtype=torch.int64, device=device) if want_labels else None
+    best = torch.empty(lead + (batch.b,), dtype=torch.float64, device=device)
+    n_segs = torch.empty(lead + (batch.b,), dtype=torch.int32, device=device)
+    return spans, labels, best, n_segs
+
+
+def _grad_outputs(elp, trans, init, len_scores):
+    return dict(elp=torch.empty_like(elp), trans=torch.empty_like(trans), init=torch.empty_like(init),
+                len=torch.empty_like(len_scores))
+
+
+def _own_workspace(ws, need, device):
+    """``ws`` if the caller gave one that is large enough, else a private one of ``need`` bytes for this call."""
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
+    return ws
+
+
 def emission(batch, x, w, cst, inv_var, cons=None, want64=True, want32=False, out64=None):
     """x fp32 [total_frames, d] -> elp fp64 and/or fp32 [total_frames, c_max].  (smm_emission_f64)
     ``out64``: write into this [total_frames, c_max] tensor (sub-batches of one packed frame axis share it)."""
@@ -206,13 +243,10 @@ def emission(batch, x, w, cst, inv_var, cons=None, want64=True, want32=False, ou
         torch.empty((batch.total_frames, batch.c_max), dtype=torch.float64, device=dev) if want64 else None)
     elp32 = torch.zeros((batch.total_frames, batch.c_max), dtype=torch.float32, device=dev) if want32 else None
     ws = workspace(batch.workspace_bytes(), dev)
-    ln, fo, gr, _, ns = batch.host_ptrs()
     _lib.check(lib.smm_emission_f64(
-        ctypes.byref(batch.shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(ns),
-        _dev(x, torch.float32, 'x'), _dev(w, torch.float64, 'w'), _dev(cst, torch.float64, 'cst'),
+        *batch.head(with_kp=False), _dev(x, torch.float32, 'x'), _dev(w, torch.float64, 'w'), _dev(cst, torch.float64, 'cst'),
         _dev(inv_var, torch.float64, 'inv_var'), _dev(cons, torch.float32, 'cons'),
-        _dev(elp64, torch.float64, 'elp64'), _dev(elp32, torch.float32, 'elp32'),
-        ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream()))
+        _dev(elp64, torch.float64, 'elp64'), _dev(elp32, torch.float32, 'elp32'), *_ws_args(ws), _stream()))
     return elp64, elp32
 
 
@@ -231,11 +265,9 @@ def emission_bwd(batch, x, g_elp, ws=None):
     g_iv = torch.empty(d, dtype=f64, device=dev)
     if ws is None:
         ws = workspace(batch.workspace_bytes(), dev)
-    ln, fo, gr, _, ns = batch.host_ptrs()
     _lib.check(lib.smm_emission_bwd_f64(
-        ctypes.byref(batch.shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(ns),
-        _dev(x, torch.float32, 'x'), _dev(g_elp, f64, 'g_elp'), _dev(g_w, f64, 'g_w'), _dev(g_cst, f64, 'g_cst'),
-        _dev(g_iv, f64, 'g_inv_var'), ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream()))
+        *batch.head(with_kp=False), _dev(x, torch.float32, 'x'), _dev(g_elp, f64, 'g_elp'), _dev(g_w, f64, 'g_w'),
+        _dev(g_cst, f64, 'g_cst'), _dev(g_iv, f64, 'g_inv_var'), *_ws_args(ws), _stream()))
     return g_w.transpose(1, 2), g_cst, g_iv
 
 
@@ -315,13 +347,11 @@ def viterbi(batch, elp, trans, init, len_scores, endpen=None, class_map=None, wa
     fn = lib.smm_viterbi_f64 if dt == torch.float64 else lib.smm_viterbi_f32
     spans, labels, best, n_segs = _outputs(batch, dev, want_spans, want_labels, labels_on_host, labels_out)
     ws = workspace(batch.workspace_bytes(), dev)
-    ln, fo, gr, kp, ns = batch.host_ptrs()
     _lib.check(fn(
-        ctypes.byref(batch.shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(kp),
-        ctypes.c_void_p(ns), _dev(elp, dt, 'elp'), _dev(trans, dt, 'trans'), _dev(init, dt, 'init'),
+        *batch.head(), _dev(elp, dt, 'elp'), _dev(trans, dt, 'trans'), _dev(init, dt, 'init'),
         _dev(len_scores, dt, 'len_scores'), _dev(endpen, dt, 'endpen'), _dev(class_map, torch.int64, 'class_map'),
         _dev(spans, torch.int64, 'spans'), _dev(labels, torch.int64, 'labels'), _dev(best, torch.float64, 'best'),
-        _dev(n_segs, torch.int32, 'n_segs'), ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream()))
+        _dev(n_segs, torch.int32, 'n_segs'), *_ws_args(ws), _stream()))
     return dict(spans=spans, labels=labels, best=best, n_segs=n_segs, _err=_err_copy(batch, ws))
 
 
@@ -339,16 +369,14 @@ def decode(batch, x, w, cst, inv_var, trans, init, len_scores, cons=None, endpen
                                            host_slot)
     elp32 = torch.zeros((batch.total_frames, batch.c_max), dtype=torch.float32, device=dev) if want_elp else None
     ws = workspace(batch.workspace_bytes(), dev)
-    ln, fo, gr, kp, ns = batch.host_ptrs()
     f64 = torch.float64
     _lib.check(lib.smm_decode_f32(
-        ctypes.byref(batch.shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(kp),
-        ctypes.c_void_p(ns), _dev(x, torch.float32, 'x'), _dev(w, f64, 'w'), _dev(cst, f64, 'cst'),
+        *batch.head(), _dev(x, torch.float32, 'x'), _dev(w, f64, 'w'), _dev(cst, f64, 'cst'),
         _dev(inv_var, f64, 'inv_var'), _dev(cons, torch.float32, 'cons'), _dev(trans, f64, 'trans'),
         _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'), _dev(endpen, f64, 'endpen'),
         _dev(class_map, torch.int64, 'class_map'), _dev(spans, torch.int64, 'spans'),
         _dev(labels, torch.int64, 'labels'), _dev(best, f64, 'best'), _dev(n_segs, torch.int32, 'n_segs'),
-        _dev(elp32, torch.float32, 'elp32'), ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream()))
+        _dev(elp32, torch.float32, 'elp32'), *_ws_args(ws), _stream()))
     if spans_on_host:
         err = _pinned_small(('err', host_slot), dev, 8, torch.int32)
         err.copy_(_err_view(batch, ws), non_blocking=True)
@@ -374,9 +402,7 @@ class ResidentDecode:
         self.key = tuple(None if t is None else (t.data_ptr(), t._version) for t in self.keep)
         self.best = torch.empty(batch.b, dtype=f64, device=dev)
         self.n_segs = torch.empty(batch.b, dtype=torch.int32, device=dev)
-        ln, fo, gr, kp, ns = batch.host_ptrs()
-        self.head = (ctypes.byref(batch.shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(kp),
-                     ctypes.c_void_p(ns), _dev(x, torch.float32, 'x'), _dev(w, f64, 'w'), _dev(cst, f64, 'cst'),
+        self.head = (*batch.head(), _dev(x, torch.float32, 'x'), _dev(w, f64, 'w'), _dev(cst, f64, 'cst'),
                      _dev(inv_var, f64, 'inv_var'), _dev(cons, torch.float32, 'cons'), _dev(trans, f64, 'trans'),
                      _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'), _dev(endpen, f64, 'endpen'),
                      _dev(class_map, torch.int64, 'class_map'), None)
@@ -393,17 +419,8 @@ class ResidentDecode:
         else:
             labels = torch.full((batch.total_frames,), -1, dtype=torch.int64, device=self.dev)
         ws = workspace(self.ws_bytes, self.dev)
-        _lib.check(self.lib.smm_decode_f32(*self.head, _dev(labels, torch.int64, 'labels'), *self.tail,
-                                           ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream()))
+        _lib.check(self.lib.smm_decode_f32(*self.head, _dev(labels, torch.int64, 'labels'), *self.tail, *_ws_args(ws), _stream()))
         return dict(spans=None, labels=labels, best=self.best, n_segs=self.n_segs, elp=None, _err=_err_copy(batch, ws))
-
-
-def _shape_with(batch, extra_flags):
-    """The batch's smm_shape with extra SMM_SHAPE_* bits for one call."""
-    if not extra_flags:
-        return batch.shape
-    s = batch.shape
-    return SmmShape(s.b, s.d, s.n_groups, s.c_max, s.k_rows, s.t_max, s.flags | extra_flags, s.total_frames)
 
 
 def logz(batch, elp, trans, init, len_scores, endpen=None, ws=None, with_backward=False):
@@ -412,18 +429,15 @@ def logz(batch, elp, trans, init, len_scores, endpen=None, ws=None, with_backwar
     ``with_backward``: run the time-reversed recursion in the same launch (SMM_SHAPE_LOGZ_BOTH); pass the same to
     ``logz_bwd``."""
     lib = _lib.load()
-    shape = _shape_with(batch, _lib.SHAPE_LOGZ_BOTH if with_backward else 0)
+    head = batch.head(_lib.SHAPE_LOGZ_BOTH if with_backward else 0)
     dev = elp.device
     f64 = torch.float64
     out = torch.empty(batch.b, dtype=f64, device=dev)
     if ws is None:
         ws = workspace(batch.workspace_bytes(), dev)
-    ln, fo, gr, kp, ns = batch.host_ptrs()
     _lib.check(lib.smm_logz_f64(
-        ctypes.byref(shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(kp),
-        ctypes.c_void_p(ns), _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'),
-        _dev(len_scores, f64, 'len_scores'), _dev(endpen, f64, 'endpen'), _dev(out, f64, 'logz'),
-        ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream()))
+        *head, _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
+        _dev(endpen, f64, 'endpen'), _dev(out, f64, 'logz'), *_ws_args(ws), _stream()))
     return out
 
 
@@ -432,21 +446,16 @@ def logz_bwd(batch, elp, trans, init, len_scores, logz_val, grad_logz=None, endp
     same workspace (same device + stream).  -> dict(elp [total_frames, c_max], trans, init, len) fp64.
     ``with_backward``: ``logz`` was called with it (the backward messages are already in the workspace)."""
     lib = _lib.load()
-    shape = _shape_with(batch, _lib.SHAPE_LOGZ_BOTH if with_backward else 0)
+    head = batch.head(_lib.SHAPE_LOGZ_BOTH if with_backward else 0)
     dev = elp.device
     f64 = torch.float64
-    g = dict(elp=torch.empty_like(elp), trans=torch.empty_like(trans), init=torch.empty_like(init),
-             len=torch.empty_like(len_scores))
+    g = _grad_outputs(elp, trans, init, len_scores)
     if ws is None:
         ws = workspace(batch.workspace_bytes(), dev)
-    ln, fo, gr, kp, ns = batch.host_ptrs()
     _lib.check(lib.smm_logz_bwd_f64(
-        ctypes.byref(shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(kp),
-        ctypes.c_void_p(ns), _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'),
-        _dev(len_scores, f64, 'len_scores'), _dev(endpen, f64, 'endpen'), _dev(logz_val, f64, 'logz'),
-        _dev(grad_logz, f64, 'grad_logz'), _dev(g['elp'], f64, 'g_elp'), _dev(g['trans'], f64, 'g_trans'),
-        _dev(g['init'], f64, 'g_init'), _dev(g['len'], f64, 'g_len'),
-        ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream()))
+        *head, _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
+        _dev(endpen, f64, 'endpen'), _dev(logz_val, f64, 'logz'), _dev(grad_logz, f64, 'grad_logz'), _dev(g['elp'], f64, 'g_elp'),
+        _dev(g['trans'], f64, 'g_trans'), _dev(g['init'], f64, 'g_init'), _dev(g['len'], f64, 'g_len'), *_ws_args(ws), _stream()))
     return g
 
 
@@ -461,22 +470,17 @@ def sample(batch, elp, trans, init, len_scores, logz_val, n_samples, seed=0, end
     n_samples = int(n_samples)
     if n_samples <= 0:
         raise ValueError("n_samples must be positive, got %d" % n_samples)
-    shape = _shape_with(batch, _lib.SHAPE_LOGZ_BOTH if with_backward else 0)
+    head = batch.head(_lib.SHAPE_LOGZ_BOTH if with_backward else 0)
     dev = elp.device
     f64 = torch.float64
-    spans = torch.empty((n_samples, batch.b, batch.t_max + 1), dtype=torch.int64, device=dev) if want_spans else None
-    labels = torch.full((n_samples, batch.total_frames), -1, dtype=torch.int64, device=dev) if want_labels else None
-    logp = torch.empty((n_samples, batch.b), dtype=f64, device=dev)
+    spans, labels, logp, _ = _device_outputs(batch, dev, want_spans, want_labels, (n_samples,))
     if ws is None:
         ws = workspace(batch.workspace_bytes(), dev)
-    ln, fo, gr, kp, ns = batch.host_ptrs()
     _lib.check(lib.smm_sample_f64(
-        ctypes.byref(shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(kp),
-        ctypes.c_void_p(ns), _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'),
-        _dev(len_scores, f64, 'len_scores'), _dev(endpen, f64, 'endpen'), _dev(class_map, torch.int64, 'class_map'),
-        _dev(logz_val, f64, 'logz'), ctypes.c_int32(n_samples), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-        _dev(spans, torch.int64, 'spans'), _dev(labels, torch.int64, 'labels'), _dev(logp, f64, 'logp'),
-        ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream()))
+        *head, _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
+        _dev(endpen, f64, 'endpen'), _dev(class_map, torch.int64, 'class_map'), _dev(logz_val, f64, 'logz'),
+        ctypes.c_int32(n_samples), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _dev(spans, torch.int64, 'spans'),
+        _dev(labels, torch.int64, 'labels'), _dev(logp, f64, 'logp'), *_ws_args(ws), _stream()))
     return dict(spans=spans, labels=labels, logp=logp, _err=_err_copy(batch, ws))
 
 
@@ -488,19 +492,25 @@ def entropy(batch, elp, trans, init, len_scores, logz_val, endpen=None, ws=None,
     histories a NaN reached, gets NaN and sets the error word (``error_flag(batch, ws=ws)``).  Bit-identical run to run.
     Its gradient: ``entropy_bwd``."""
     lib = _lib.load()
-    shape = _shape_with(batch, _lib.SHAPE_LOGZ_BOTH if with_backward else 0)
+    head = batch.head(_lib.SHAPE_LOGZ_BOTH if with_backward else 0)
     dev = elp.device
     f64 = torch.float64
     out = torch.empty(batch.b, dtype=f64, device=dev)
     if ws is None:
         ws = workspace(batch.workspace_bytes(), dev)
-    ln, fo, gr, kp, ns = batch.host_ptrs()
     _lib.check(lib.smm_entropy_f64(
-        ctypes.byref(shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(kp),
-        ctypes.c_void_p(ns), _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'),
-        _dev(len_scores, f64, 'len_scores'), _dev(endpen, f64, 'endpen'), _dev(logz_val, f64, 'logz'),
-        _dev(out, f64, 'entropy'), ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream()))
+        *head, _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
+        _dev(endpen, f64, 'endpen'), _dev(logz_val, f64, 'logz'), _dev(out, f64, 'entropy'), *_ws_args(ws), _stream()))
     return out
+
+
+def _kl_side(t, tag):
+    """One side of ``kl`` / ``kl_bwd`` -- (elp, trans, init, len_scores, endpen, logz_val, ws) -- as the C ABI takes it."""
+    f64 = torch.float64
+    elp, trans, init, len_scores, endpen, logz_val, ws = t
+    return [_dev(elp, f64, 'elp_' + tag), _dev(trans, f64, 'trans_' + tag), _dev(init, f64, 'init_' + tag),
+            _dev(len_scores, f64, 'len_scores_' + tag), _dev(endpen, f64, 'endpen_' + tag), _dev(logz_val, f64, 'logz_' + tag),
+            *_ws_args(ws)]
 
 
 def kl(batch, p, q, with_backward=False, want_cross_entropy=False):
@@ -513,22 +523,13 @@ def kl(batch, p, q, with_backward=False, want_cross_entropy=False):
     gets NaN and sets the error word of p's workspace (``error_flag(batch, ws=p[6])``).  Exactly 0 for bit-identical sides;
     bit-identical run to run.  Its gradient: ``kl_bwd``."""
     lib = _lib.load()
-    shape = _shape_with(batch, _lib.SHAPE_LOGZ_BOTH if with_backward else 0)
+    head = batch.head(_lib.SHAPE_LOGZ_BOTH if with_backward else 0)
     f64 = torch.float64
     dev = p[0].device
     out = torch.empty(batch.b, dtype=f64, device=dev)
     xent = torch.empty(batch.b, dtype=f64, device=dev) if want_cross_entropy else None
-
-    def side(t, tag):
-        elp, trans, init, len_scores, endpen, logz_val, ws = t
-        return [_dev(elp, f64, 'elp_' + tag), _dev(trans, f64, 'trans_' + tag), _dev(init, f64, 'init_' + tag),
-                _dev(len_scores, f64, 'len_scores_' + tag), _dev(endpen, f64, 'endpen_' + tag), _dev(logz_val, f64, 'logz_' + tag),
-                ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel())]
-
-    ln, fo, gr, kp, ns = batch.host_ptrs()
-    _lib.check(lib.smm_kl_f64(
-        ctypes.byref(shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(kp),
-        ctypes.c_void_p(ns), *side(p, 'p'), *side(q, 'q'), _dev(out, f64, 'kl'), _dev(xent, f64, 'cross_entropy'), _stream()))
+    _lib.check(lib.smm_kl_f64(*head, *_kl_side(p, 'p'), *_kl_side(q, 'q'), _dev(out, f64, 'kl'), _dev(xent, f64, 'cross_entropy'),
+                              _stream()))
     return (out, xent) if want_cross_entropy else out
 
 
@@ -543,8 +544,7 @@ def entropy_bwd_scratch_bytes(batch):
 def _ebwd_outputs(batch, elp, trans, init, len_scores, want_value):
     f64 = torch.float64
     dev = elp.device
-    g = dict(elp=torch.empty_like(elp), trans=torch.empty_like(trans), init=torch.empty_like(init),
-             len=torch.empty_like(len_scores))
+    g = _grad_outputs(elp, trans, init, len_scores)
     g['value'] = torch.empty((batch.b, 2), dtype=f64, device=dev) if want_value else None
     scratch = torch.empty(entropy_bwd_scratch_bytes(batch), dtype=torch.uint8, device=dev)
     return g, scratch
@@ -558,20 +558,16 @@ def entropy_bwd(batch, elp, trans, init, len_scores, logz_val, grad_out=None, en
     ``value`` fp64 [b, 2] (H by the two decompositions) with ``want_value``.  A video whose H is not finite gets NaN rows.
     Bit-identical run to run."""
     lib = _lib.load()
-    shape = _shape_with(batch, _lib.SHAPE_LOGZ_BOTH if with_backward else 0)
+    head = batch.head(_lib.SHAPE_LOGZ_BOTH if with_backward else 0)
     f64 = torch.float64
     g, scratch = _ebwd_outputs(batch, elp, trans, init, len_scores, want_value)
     if ws is None:
         ws = workspace(batch.workspace_bytes(), elp.device)
-    ln, fo, gr, kp, ns = batch.host_ptrs()
     _lib.check(lib.smm_entropy_bwd_f64(
-        ctypes.byref(shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(kp),
-        ctypes.c_void_p(ns), _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'),
-        _dev(len_scores, f64, 'len_scores'), _dev(endpen, f64, 'endpen'), _dev(logz_val, f64, 'logz'),
-        _dev(grad_out, f64, 'grad_out'), _dev(g['elp'], f64, 'g_elp'), _dev(g['trans'], f64, 'g_trans'),
-        _dev(g['init'], f64, 'g_init'), _dev(g['len'], f64, 'g_len'), _dev(g['value'], f64, 'value'),
-        ctypes.c_void_p(scratch.data_ptr()), ctypes.c_size_t(scratch.numel()),
-        ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream()))
+        *head, _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
+        _dev(endpen, f64, 'endpen'), _dev(logz_val, f64, 'logz'), _dev(grad_out, f64, 'grad_out'), _dev(g['elp'], f64, 'g_elp'),
+        _dev(g['trans'], f64, 'g_trans'), _dev(g['init'], f64, 'g_init'), _dev(g['len'], f64, 'g_len'),
+        _dev(g['value'], f64, 'value'), *_ws_args(scratch), *_ws_args(ws), _stream()))
     return g
 
 
@@ -581,24 +577,14 @@ def kl_bwd(batch, p, q, grad_out=None, with_backward=False, cross_entropy=False,
     (else the call runs both, and q's workspace is written).  -> dict as ``entropy_bwd``.  q's gradient is mu_q - mu_p: two
     ``logz_bwd`` calls.  Exactly 0 for bit-identical sides (KL); bit-identical run to run."""
     lib = _lib.load()
-    shape = _shape_with(batch, _lib.SHAPE_LOGZ_BOTH if with_backward else 0)
+    head = batch.head(_lib.SHAPE_LOGZ_BOTH if with_backward else 0)
     f64 = torch.float64
     g, scratch = _ebwd_outputs(batch, p[0], p[1], p[2], p[3], want_value)
-
-    def side(t, tag):
-        elp, trans, init, len_scores, endpen, logz_val, ws = t
-        return [_dev(elp, f64, 'elp_' + tag), _dev(trans, f64, 'trans_' + tag), _dev(init, f64, 'init_' + tag),
-                _dev(len_scores, f64, 'len_scores_' + tag), _dev(endpen, f64, 'endpen_' + tag), _dev(logz_val, f64, 'logz_' + tag),
-                ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel())]
-
-    ln, fo, gr, kp, ns = batch.host_ptrs()
     mode = _lib.KL_BWD_CROSS_ENTROPY if cross_entropy else _lib.KL_BWD_KL
     _lib.check(lib.smm_kl_bwd_f64(
-        ctypes.byref(shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(kp),
-        ctypes.c_void_p(ns), *side(p, 'p'), *side(q, 'q'), ctypes.c_int32(mode), _dev(grad_out, f64, 'grad_out'),
+        *head, *_kl_side(p, 'p'), *_kl_side(q, 'q'), ctypes.c_int32(mode), _dev(grad_out, f64, 'grad_out'),
         _dev(g['elp'], f64, 'g_elp'), _dev(g['trans'], f64, 'g_trans'), _dev(g['init'], f64, 'g_init'),
-        _dev(g['len'], f64, 'g_len'), _dev(g['value'], f64, 'value'),
-        ctypes.c_void_p(scratch.data_ptr()), ctypes.c_size_t(scratch.numel()), _stream()))
+        _dev(g['len'], f64, 'g_len'), _dev(g['value'], f64, 'value'), *_ws_args(scratch), _stream()))
     return g
 
 
@@ -625,19 +611,14 @@ def kbest(batch, elp, trans, init, len_scores, k, endpen=None, class_map=None, w
         raise ValueError("k must be in 1..%d, got %d" % (MAX_KBEST, k))
     dev = elp.device
     f64 = torch.float64
-    spans = torch.empty((k, batch.b, batch.t_max + 1), dtype=torch.int64, device=dev) if want_spans else None
-    labels = torch.full((k, batch.total_frames), -1, dtype=torch.int64, device=dev) if want_labels else None
-    score = torch.empty((k, batch.b), dtype=f64, device=dev)
-    n_segs = torch.empty((k, batch.b), dtype=torch.int32, device=dev)
+    spans, labels, score, n_segs = _device_outputs(batch, dev, want_spans, want_labels, (k,))
     if ws is None:
         ws = torch.empty(kbest_workspace_bytes(batch, k), dtype=torch.uint8, device=dev)
-    ln, fo, gr, kp, ns = batch.host_ptrs()
     _lib.check(lib.smm_kbest_f64(
-        ctypes.byref(batch.shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(kp),
-        ctypes.c_void_p(ns), _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'),
+        *batch.head(), _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'),
         _dev(len_scores, f64, 'len_scores'), _dev(endpen, f64, 'endpen'), _dev(class_map, torch.int64, 'class_map'),
         ctypes.c_int32(k), _dev(spans, torch.int64, 'spans'), _dev(labels, torch.int64, 'labels'), _dev(score, f64, 'score'),
-        _dev(n_segs, torch.int32, 'n_segs'), ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream()))
+        _dev(n_segs, torch.int32, 'n_segs'), *_ws_args(ws), _stream()))
     return dict(spans=spans, labels=labels, score=score, n_segs=n_segs, _err=_err_copy(batch, ws))
 
 
@@ -660,21 +641,14 @@ def mbr(batch, gain, trans, init, endpen=None, class_map=None, ws=None, want_spa
     lib = _lib.load()
     dev = gain.device
     f64 = torch.float64
-    spans = torch.empty((batch.b, batch.t_max + 1), dtype=torch.int64, device=dev) if want_spans else None
-    labels = torch.full((batch.total_frames,), -1, dtype=torch.int64, device=dev) if want_labels else None
-    best = torch.empty(batch.b, dtype=f64, device=dev)
+    spans, labels, best, n_segs = _device_outputs(batch, dev, want_spans, want_labels)
     gain_sum = torch.empty(batch.b, dtype=f64, device=dev)
-    n_segs = torch.empty(batch.b, dtype=torch.int32, device=dev)
-    need = mbr_workspace_bytes(batch)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    ln, fo, gr, kp, ns = batch.host_ptrs()
+    ws = _own_workspace(ws, mbr_workspace_bytes(batch), dev)
     _lib.check(lib.smm_mbr_f64(
-        ctypes.byref(batch.shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(kp),
-        ctypes.c_void_p(ns), _dev(gain, f64, 'gain'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'),
+        *batch.head(), _dev(gain, f64, 'gain'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'),
         _dev(endpen, f64, 'endpen'), _dev(class_map, torch.int64, 'class_map'), _dev(spans, torch.int64, 'spans'),
         _dev(labels, torch.int64, 'labels'), _dev(best, f64, 'best'), _dev(gain_sum, f64, 'gain_sum'),
-        _dev(n_segs, torch.int32, 'n_segs'), ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream()))
+        _dev(n_segs, torch.int32, 'n_segs'), *_ws_args(ws), _stream()))
     return dict(spans=spans, labels=labels, best=best, gain_sum=gain_sum, n_segs=n_segs, _err=_err_copy(batch, ws))
 
 
@@ -724,21 +698,15 @@ def align(batch, elp, trans, init, len_scores, transcripts, endpen=None, class_m
     f64 = torch.float64
     ids, off = _transcript_arrays(batch, transcripts)
     need = align_workspace_bytes(batch, off)
-    spans = torch.empty((batch.b, batch.t_max + 1), dtype=torch.int64, device=dev) if want_spans else None
-    labels = torch.full((batch.total_frames,), -1, dtype=torch.int64, device=dev) if want_labels else None
-    best = torch.empty(batch.b, dtype=f64, device=dev)
-    n_segs = torch.empty(batch.b, dtype=torch.int32, device=dev)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    spans, labels, best, n_segs = _device_outputs(batch, dev, want_spans, want_labels)
+    ws = _own_workspace(ws, need, dev)
     ids_dev = torch.from_numpy(ids).to(dev)
-    ln, fo, gr, kp, ns = batch.host_ptrs()
     _lib.check(lib.smm_align_f64(
-        ctypes.byref(batch.shape), ctypes.c_void_p(ln), ctypes.c_void_p(fo), ctypes.c_void_p(gr), ctypes.c_void_p(kp),
-        ctypes.c_void_p(ns), _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'),
+        *batch.head(), _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'),
         _dev(len_scores, f64, 'len_scores'), _dev(endpen, f64, 'endpen'), _dev(class_map, torch.int64, 'class_map'),
         _dev(ids_dev, torch.int32, 'transcript'), ctypes.c_void_p(off.ctypes.data), _dev(spans, torch.int64, 'spans'),
         _dev(labels, torch.int64, 'labels'), _dev(best, f64, 'best'), _dev(n_segs, torch.int32, 'n_segs'),
-        ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream()))
+        *_ws_args(ws), _stream()))
     return dict(spans=spans, labels=labels, best=best, n_segs=n_segs, _err=_err_copy(batch, ws), _keep=(ids_dev, ws))
 
 
@@ -847,7 +815,7 @@ def eval_confusion(eb, pred, gt, local_of):
         ctypes.byref(eb.shape), ctypes.c_void_p(eb.lengths.ctypes.data), ctypes.c_void_p(eb.frame_offset.ctypes.data),
         ctypes.c_void_p(eb.group.ctypes.data), _dev(pred, torch.int64, 'pred'), _dev(gt, torch.int64, 'gt'),
         _dev(local_of, torch.int32, 'local_of'), _dev(conf, torch.int64, 'confusion'),
-        ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream()))
+        *_ws_args(ws), _stream()))
     return conf
 
 
@@ -865,7 +833,7 @@ def eval_videos(eb, pred, gt, local_of, cluster_of, gt_is_bg, pred_is_bg, seed=0
         _dev(pred, torch.int64, 'pred'), _dev(gt, torch.int64, 'gt'), _dev(local_of, torch.int32, 'local_of'),
         _dev(cluster_of, torch.int32, 'cluster_of'), _dev(gt_is_bg, torch.uint8, 'gt_is_bg'),
         _dev(pred_is_bg, torch.uint8, 'pred_is_bg'), ctypes.c_uint32(int(seed) & 0xFFFFFFFF),
-        _dev(out, torch.int64, 'counters'), ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream()))
+        _dev(out, torch.int64, 'counters'), *_ws_args(ws), _stream()))
     return out
 
 
@@ -898,7 +866,7 @@ def fit_stats(x, labels, lengths, frame_offset, n_classes, max_k):
         _dev(out['span_counts'], torch.int64, 'span_counts'),
         _dev(out['span_start_counts'], torch.int64, 'span_start_counts'),
         _dev(out['span_transition_counts'], torch.int64, 'span_transition_counts'),
-        ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream()))
+        *_ws_args(ws), _stream()))
     off = lib.smm_fit_error_word_offset(b)
     out['_err'] = ws[off:off + 4].view(torch.int32).clone()     # (a copy, stream-ordered behind the kernels: the shared
     return out                                                   #  workspace may be reused by the next call)
