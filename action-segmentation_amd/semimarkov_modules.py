@@ -13,6 +13,8 @@ There is no CPU path: ``viterbi`` / ``log_likelihood`` need CUDA(HIP) tensors an
 small-shape inspection; nothing in this package's decode path calls them.
 """
 import math
+import pickle
+import types
 from typing import Dict, Set
 
 import contextlib
@@ -45,33 +47,129 @@ def sliding_sum(inputs, k):
 BATCH_MEAN_DENSE_MAX = 1 << 22     # log_likelihood_packed: entries of the [batches, videos] mean matrix; beyond that, sums by index
 
 
+TABLE_NAMES = ('w', 'cst', 'trans', 'init', 'len')
+
+
+def _one_group(tab):
+    """The cached tables of one class set as a stack of ONE group -> (w, cst, trans, init, len, class_map), built on first use
+    (ten views less per call)."""
+    g1 = tab.get('_one_group')
+    if g1 is None:
+        g1 = tab['_one_group'] = tuple(tab[k].unsqueeze(0).contiguous() for k in TABLE_NAMES) + (tab['class_map'].view(1, -1),)
+    return g1
+
+
+def _emit(batch, x, cons, endpen, g, inv_var):
+    """The emission launch of a staged batch, padded or packed; ``g``: (w, cst, trans, init, len, class_map) stacked per group.
+    -> the record every operation below reads: dict(batch, elp, trans, init, len, class_map, endpen, x)."""
+    elp, _ = ops.emission(batch, x, g[0], g[1], inv_var, cons=cons)
+    return dict(batch=batch, elp=elp, trans=g[2], init=g[3], len=g[4], class_map=g[5], endpen=endpen, x=x)
+
+
+def _emit_logz(batch, x, cons, endpen, g, inv_var, with_backward):
+    """``_emit`` + log Z on a private workspace, for the launches that read the forward (and backward) histories afterwards:
+    the record gains ``ws`` and ``logz``.  ``with_backward``: the log Z launch also runs the time-reversed recursion
+    (SMM_SHAPE_LOGZ_BOTH), one more workgroup per video."""
+    r = _emit(batch, x, cons, endpen, g, inv_var)
+    r['ws'] = torch.empty(batch.workspace_bytes(), dtype=torch.uint8, device=x.device)
+    r['logz'] = ops.logz(batch, r['elp'], r['trans'], r['init'], r['len'], endpen=endpen, ws=r['ws'], with_backward=with_backward)
+    return r
+
+
+def _side(r):
+    """A launched posterior as one side of ops.kl / ops.kl_bwd."""
+    return r['elp'], r['trans'], r['init'], r['len'], r['endpen'], r['logz'], r['ws']
+
+
+def _after_logz(r):
+    """The same seven as the keyword arguments of the launchers that follow a log Z launch on its workspace."""
+    return dict(elp=r['elp'], trans=r['trans'], init=r['init'], len_scores=r['len'], logz_val=r['logz'], endpen=r['endpen'],
+                ws=r['ws'])
+
+
+def _paths(batch, out, want_spans):
+    """A path launch's result as its entry point hands it out: spans on the CPU for a padded batch (without the EOS column for
+    add_eos=False, as ``viterbi`` returns them), frame labels on the device for a packed one.  Raises SmmError when a NaN
+    reached the DP."""
+    paths = out['spans'].cpu() if want_spans else out['labels']
+    ops.check_decoded(batch, out)
+    if want_spans and batch.no_eos:
+        paths = paths[..., :batch.t_max].contiguous()
+    return paths
+
+
+def _check_workspace(r):
+    ops.check_decoded(r['batch'], dict(_err=ops._err_copy(r['batch'], r['ws'])))
+
+
+def _sample(r, n_samples, seed, want_spans):
+    out = ops.sample(r['batch'], n_samples=n_samples, seed=seed, class_map=r['class_map'], want_spans=want_spans,
+                     want_labels=not want_spans, **_after_logz(r))
+    return _paths(r['batch'], out, want_spans), out['logp']
+
+
+def _marginals(r, with_backward=False):
+    """Posterior class occupancy of every frame: the d log Z / d elp of smm_logz_bwd_f64, fp64 [total_frames, c_max]."""
+    return ops.logz_bwd(r['batch'], with_backward=with_backward, **_after_logz(r))['elp']
+
+
+def _mbr(r, want_spans):
+    out = ops.mbr(r['batch'], _marginals(r, with_backward=True), r['trans'], r['init'], endpen=r['endpen'],
+                  class_map=r['class_map'], ws=r['ws'], want_spans=want_spans, want_labels=not want_spans)
+    return _paths(r['batch'], out, want_spans), out['gain_sum']
+
+
+def _entropy(r, with_backward):
+    """-> (H, p's launch, None): what _PosteriorValue's ``launch`` returns.  ``with_backward``: as given to the log Z launch;
+    without it the entropy launch runs the time-reversed recursion itself, into ``ws``, where the backward finds both."""
+    h = ops.entropy(r['batch'], with_backward=with_backward, **_after_logz(r))
+    _check_workspace(r)
+    return h, r, None
+
+
+def _kl(r, q, what, with_backward, want_cross_entropy):
+    """-> (KL(p || q) or H(p, q), p's launch, q's launch).  ``with_backward``: as given to p's log Z launch."""
+    SemiMarkovModule._check_same_batch(r['batch'], q['batch'], what)
+    out = ops.kl(r['batch'], _side(r), _side(q), with_backward=with_backward, want_cross_entropy=want_cross_entropy)
+    _check_workspace(r)
+    return (out[1] if want_cross_entropy else out), r, q
+
+
+def _kbest(r, k, want_spans):
+    out = ops.kbest(r['batch'], r['elp'], r['trans'], r['init'], r['len'], k, endpen=r['endpen'], class_map=r['class_map'],
+                    want_spans=want_spans, want_labels=not want_spans)
+    return _paths(r['batch'], out, want_spans), out['score']
+
+
+def _align(r, local, want_spans):
+    out = ops.align(r['batch'], r['elp'], r['trans'], r['init'], r['len'], local, endpen=r['endpen'], class_map=r['class_map'],
+                    want_spans=want_spans, want_labels=not want_spans)
+    return _paths(r['batch'], out, want_spans), out['best']
+
+
 class _LogPartition(torch.autograd.Function):
     """log Z of every video of one launch as a differentiable function of the fp64 factor tables (emission factors w,
     cst; transition, initial and length tables; stacked per parameter group).  Forward: smm_emission_f64 +
     smm_logz_f64; backward: smm_logz_bwd_f64 (posterior marginals) + smm_emission_bwd_f64 (the chain rule through
-    elp = cst + x.w - 0.5 x^2.inv_var, one pass over the features).
-    ``runs``: unused (kept for callers of the round-1 signature)."""
+    elp = cst + x.w - 0.5 x^2.inv_var, one pass over the features)."""
 
     @staticmethod
-    def forward(ctx, batch, runs, x, cons, endpen, w, cst, inv_var, trans, init, len_scores):
-        ws = torch.empty(batch.workspace_bytes(), dtype=torch.uint8, device=x.device)   # private: survives until backward
-        elp64, _ = ops.emission(batch, x, w, cst, inv_var, cons=cons)
+    def forward(ctx, batch, x, cons, endpen, w, cst, inv_var, trans, init, len_scores):
         # a gradient will be asked for: the time-reversed recursion (independent of the forward one) rides in the same
-        # launch, one more workgroup per video
+        # launch; the private workspace survives until backward
         both = any(ctx.needs_input_grad)
-        z = ops.logz(batch, elp64, trans, init, len_scores, endpen=endpen, ws=ws, with_backward=both)
-        ctx.batch, ctx.endpen, ctx.ws, ctx.runs, ctx.both = batch, endpen, ws, runs, both
-        ctx.save_for_backward(x, elp64, trans, init, len_scores, z)
-        return z
+        r = _emit_logz(batch, x, cons, endpen, (w, cst, trans, init, len_scores, None), inv_var, with_backward=both)
+        ctx.batch, ctx.endpen, ctx.ws, ctx.both = batch, endpen, r['ws'], both
+        ctx.save_for_backward(x, r['elp'], trans, init, len_scores, r['logz'])
+        return r['logz']
 
     @staticmethod
     def backward(ctx, gz):
-        x, elp64, trans, init, len_scores, z = ctx.saved_tensors
-        g = ops.logz_bwd(ctx.batch, elp64, trans, init, len_scores, z, grad_logz=gz.to(torch.float64).contiguous(),
-                         endpen=ctx.endpen, ws=ctx.ws, with_backward=ctx.both)
+        r = dict(zip(('x', 'elp', 'trans', 'init', 'len', 'logz'), ctx.saved_tensors), endpen=ctx.endpen, ws=ctx.ws)
+        g = ops.logz_bwd(ctx.batch, grad_logz=gz.to(torch.float64).contiguous(), with_backward=ctx.both, **_after_logz(r))
         # chain rule through elp = cst + x.w - 0.5 x^2.inv_var: one pass over x (smm_emission_bwd_f64)
-        g_w, g_cst, g_iv = ops.emission_bwd(ctx.batch, x, g['elp'], ws=ctx.ws)
-        return None, None, None, None, None, g_w, g_cst, g_iv, g['trans'], g['init'], g['len']
+        g_w, g_cst, g_iv = ops.emission_bwd(ctx.batch, r['x'], g['elp'], ws=ctx.ws)
+        return None, None, None, None, g_w, g_cst, g_iv, g['trans'], g['init'], g['len']
 
 
 def _table_grads(batch, x, g, ws):
@@ -98,17 +196,13 @@ class _PosteriorValue(torch.autograd.Function):
         up = gv.to(torch.float64).contiguous()
         r, q = ctx.r, ctx.q
         b = r['batch']
-        side = lambda t: (t['elp'], t['trans'], t['init'], t['len'], t['endpen'], t['logz'], t['ws'])
         if ctx.kind == 'entropy':
-            g = ops.entropy_bwd(b, r['elp'], r['trans'], r['init'], r['len'], r['logz'], grad_out=up, endpen=r['endpen'],
-                                ws=r['ws'], with_backward=True)
+            g = ops.entropy_bwd(b, grad_out=up, with_backward=True, **_after_logz(r))
             return (None, None) + _table_grads(b, r['x'], g, r['ws'])
         # (kl_bwd runs both sides' time-reversed recursions: q's launch ran only the forward one)
-        g = ops.kl_bwd(b, side(r), side(q), grad_out=up, cross_entropy=ctx.kind == 'cross_entropy')
-        mq = ops.logz_bwd(b, q['elp'], q['trans'], q['init'], q['len'], q['logz'], grad_logz=up, endpen=q['endpen'],
-                          ws=q['ws'], with_backward=True)
-        mp = ops.logz_bwd(b, r['elp'], r['trans'], r['init'], r['len'], r['logz'], grad_logz=up, endpen=r['endpen'],
-                          ws=r['ws'], with_backward=True)
+        g = ops.kl_bwd(b, _side(r), _side(q), grad_out=up, cross_entropy=ctx.kind == 'cross_entropy')
+        mq = ops.logz_bwd(b, grad_logz=up, with_backward=True, **_after_logz(q))
+        mp = ops.logz_bwd(b, grad_logz=up, with_backward=True, **_after_logz(r))
         gq = {k: mq[k] - mp[k] for k in ('elp', 'trans', 'init', 'len')}
         return (None, None) + _table_grads(b, r['x'], g, r['ws']) + _table_grads(b, q['x'], gq, q['ws'])
 
@@ -172,7 +266,6 @@ class SemiMarkovModule(nn.Module):
         else:
             self.remove_transition_constraints()
         if getattr(args, 'sm_init_non_projection_parameters_from', None) is not None:
-            import pickle
             with open(args.sm_init_non_projection_parameters_from, 'rb') as f:
                 self.init_nonproject_parameters(pickle.load(f).model)
         if getattr(args, 'sm_feature_projection', False):
@@ -440,7 +533,6 @@ class SemiMarkovModule(nn.Module):
         if not all(vc is first for vc in valid_classes_per_instance):
             # ... then element-wise (one torch.equal per instance: the loader hands over equal COPIES of the task's indices),
             # and only then as sets, like the reference
-            import torch
             if not all(vc.shape == first.shape and torch.equal(vc, first) for vc in valid_classes_per_instance):
                 assert all_equal(set(int(v) for v in vc) for vc in valid_classes_per_instance), \
                     "must have same valid_classes for all instances in the batch"
@@ -637,10 +729,7 @@ class SemiMarkovModule(nn.Module):
                               frame_offset=off, kp=[min(tab['len'].size(0), tmax)] * b, no_time_split=self._hard_masks())
             x = torch.cat([f.detach().to(torch.float32) for f in feature_list]) if b > 1 else x0.detach().to(torch.float32).contiguous()
             endpen = self._endpen(valid_classes, additional_allowed_ends_per_instance, b, c, dev)
-            g1 = tab.get('_one_group')
-            if g1 is None:
-                g1 = tab['_one_group'] = tuple(tab[k].unsqueeze(0).contiguous() for k in ('w', 'cst', 'trans', 'init', 'len')) \
-                    + (tab['class_map'].view(1, -1),)
+            g1 = _one_group(tab)
             labels = ops.pinned_labels(('ragged', slot), dev, total)
             out = ops.decode(batch, x, g1[0], g1[1], tab['inv_var'], g1[2], g1[3], g1[4], endpen=endpen, class_map=g1[5],
                              want_spans=False, want_labels=True, labels_out=labels, spans_on_host=True, host_slot=('ragged', slot))
@@ -664,27 +753,39 @@ class SemiMarkovModule(nn.Module):
             raise ValueError("add_eos=False needs at least two frames per video (a one-frame video has no edge at all "
                              "in the reference's lattice)")
 
-    def _decode(self, features, lengths, valid_classes, additional_allowed_ends_per_instance, constraints,
-                want_elp=False, want_labels=True, want_spans=True, no_eos=False, spans_on_host=False, host_slot=0):
+    def _stage_padded(self, features, lengths, valid_classes, additional_allowed_ends_per_instance, constraints, no_eos=False,
+                      no_time_split=False, check_no_eos=True, tables=None):
+        """A zero-padded single-task batch as the launchers take it -> (batch, x, cons, endpen, tab, g1): the ``ops.Batch``, the
+        features fp32 [b * Tmax, D], the constraints fp32 [b * Tmax, C] or None, the end penalties (None with ``no_eos``), the
+        factor tables and their stack of one group.
+        ``no_time_split``: ``self._hard_masks()`` from the callers that ask the library to decode long videos in one piece.
+        ``check_no_eos``: False from ``align``, which refuses add_eos=False itself and stages with ``no_eos`` off.
+        ``tables``: the stacked differentiable tables of ``log_partition`` instead of the decode cache's (``g1`` is None then)."""
         b, tmax, d = features.shape
         dev = features.device
         lengths_host = lengths.detach().cpu().numpy().astype(np.int64)
-        assert int(lengths_host.max()) == tmax, "one instance must span the padded length (padding_colate)"
-        self._check_no_eos_lengths(lengths_host, no_eos)
-        tab = self._decode_tables(valid_classes, dev)
+        spans_tmax = int(lengths_host.max()) == tmax
+        if tables is None:
+            assert spans_tmax, "one instance must span the padded length (padding_colate)"
+        assert spans_tmax                               # (log_partition: without a message)
+        if check_no_eos:
+            self._check_no_eos_lengths(lengths_host, no_eos)
+        tab = self._decode_tables(valid_classes, dev) if tables is None else tables
         c = tab['init'].numel()
-        k_rows = tab['len'].size(0)
-        batch = ops.Batch(lengths_host, [c], k_rows, c_max=c, t_max=tmax, total_frames=b * tmax, d=d, no_eos=no_eos,
-                          no_time_split=self._hard_masks())
+        batch = ops.Batch(lengths_host, [c], tab['len'].size(-2), c_max=c, t_max=tmax, total_frames=b * tmax, d=d, no_eos=no_eos,
+                          no_time_split=no_time_split)
         x = features.detach().to(torch.float32).contiguous().view(b * tmax, d)
         cons = None
         if constraints is not None:
             cons = constraints.detach().to(device=dev, dtype=torch.float32).contiguous().view(b * tmax, c)
         endpen = None if no_eos else self._endpen(valid_classes, additional_allowed_ends_per_instance, b, c, dev)
-        g1 = tab.get('_one_group')            # the cached tables as a stack of ONE group (ten views less per call)
-        if g1 is None:
-            g1 = tab['_one_group'] = tuple(tab[k].unsqueeze(0).contiguous() for k in ('w', 'cst', 'trans', 'init', 'len')) \
-                + (tab['class_map'].view(1, -1),)
+        return batch, x, cons, endpen, tab, _one_group(tab) if tables is None else None
+
+    def _decode(self, features, lengths, valid_classes, additional_allowed_ends_per_instance, constraints,
+                want_elp=False, want_labels=True, want_spans=True, no_eos=False, spans_on_host=False, host_slot=0):
+        batch, x, cons, endpen, tab, g1 = self._stage_padded(features, lengths, valid_classes,
+                                                             additional_allowed_ends_per_instance, constraints, no_eos=no_eos,
+                                                             no_time_split=self._hard_masks())
         out = ops.decode(batch, x, g1[0], g1[1], tab['inv_var'], g1[2], g1[3], g1[4], cons=cons, endpen=endpen,
                          class_map=g1[5], want_spans=want_spans, want_labels=want_labels,
                          want_elp=want_elp, spans_on_host=spans_on_host, host_slot=host_slot)
@@ -698,35 +799,13 @@ class SemiMarkovModule(nn.Module):
     # ------------------------------------------------------------------ posterior samples and marginals (smm_sample_f64)
     def _posterior_launch(self, features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
                           constraints, what, with_backward=False):
-        """emission + log Z of a zero-padded single-task batch on a private workspace, for the launches that read the forward
-        (and backward) histories afterwards.  -> dict(batch, elp, tables as one group, endpen, logz, ws).
-        ``with_backward``: the log Z launch also runs the time-reversed recursion (SMM_SHAPE_LOGZ_BOTH)."""
+        """emission + log Z of a zero-padded single-task batch on a private workspace -> the record of ``_emit_logz``:
+        dict(batch, elp, tables as one group, class_map, endpen, logz, ws, x)."""
         self._require_device(features, what)
-        valid_classes = self._check_valid_classes(valid_classes_per_instance)
-        b, tmax, d = features.shape
-        dev = features.device
-        lengths_host = lengths.detach().cpu().numpy().astype(np.int64)
-        assert int(lengths_host.max()) == tmax, "one instance must span the padded length (padding_colate)"
-        no_eos = not add_eos
-        self._check_no_eos_lengths(lengths_host, no_eos)
-        tab = self._decode_tables(valid_classes, dev)
-        c = tab['init'].numel()
-        batch = ops.Batch(lengths_host, [c], tab['len'].size(0), c_max=c, t_max=tmax, total_frames=b * tmax, d=d,
-                          no_eos=no_eos, no_time_split=self._hard_masks())
-        x = features.detach().to(torch.float32).contiguous().view(b * tmax, d)
-        cons = None
-        if constraints is not None:
-            cons = constraints.detach().to(device=dev, dtype=torch.float32).contiguous().view(b * tmax, c)
-        endpen = None if no_eos else self._endpen(valid_classes, additional_allowed_ends_per_instance, b, c, dev)
-        g1 = tab.get('_one_group')
-        if g1 is None:
-            g1 = tab['_one_group'] = tuple(tab[k].unsqueeze(0).contiguous() for k in ('w', 'cst', 'trans', 'init', 'len')) \
-                + (tab['class_map'].view(1, -1),)
-        ws = torch.empty(batch.workspace_bytes(), dtype=torch.uint8, device=dev)
-        elp, _ = ops.emission(batch, x, g1[0], g1[1], tab['inv_var'], cons=cons)
-        z = ops.logz(batch, elp, g1[2], g1[3], g1[4], endpen=endpen, ws=ws, with_backward=with_backward)
-        return dict(batch=batch, elp=elp, trans=g1[2], init=g1[3], len=g1[4], class_map=g1[5], endpen=endpen, logz=z, ws=ws,
-                    x=x, valid_classes=valid_classes)
+        batch, x, cons, endpen, tab, g1 = self._stage_padded(
+            features, lengths, self._check_valid_classes(valid_classes_per_instance), additional_allowed_ends_per_instance,
+            constraints, no_eos=not add_eos, no_time_split=self._hard_masks())
+        return _emit_logz(batch, x, cons, endpen, g1, tab['inv_var'], with_backward)
 
     @torch.no_grad()
     def sample(self, features, lengths, valid_classes_per_instance, n_samples=1, seed=0, add_eos=True,
@@ -739,13 +818,7 @@ class SemiMarkovModule(nn.Module):
         log p(spans | x) of each sample.  No autograd."""
         r = self._posterior_launch(features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
                                    constraints, 'sample')
-        out = ops.sample(r['batch'], r['elp'], r['trans'], r['init'], r['len'], r['logz'], n_samples, seed, endpen=r['endpen'],
-                         class_map=r['class_map'], ws=r['ws'], want_spans=True, want_labels=False)
-        spans = out['spans'].cpu()
-        ops.check_decoded(r['batch'], out)
-        if not add_eos:
-            spans = spans[:, :, :features.size(1)].contiguous()
-        return spans, out['logp']
+        return _sample(r, n_samples, seed, want_spans=True)
 
     @torch.no_grad()
     def frame_posteriors(self, features, lengths, valid_classes_per_instance, add_eos=True,
@@ -755,18 +828,8 @@ class SemiMarkovModule(nn.Module):
         label frequencies of ``sample`` converge to."""
         r = self._posterior_launch(features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
                                    constraints, 'frame_posteriors')
-        g = ops.logz_bwd(r['batch'], r['elp'], r['trans'], r['init'], r['len'], r['logz'], endpen=r['endpen'], ws=r['ws'])
         b, tmax = features.shape[:2]
-        return g['elp'].view(b, tmax, -1)
-
-    def _entropy(self, features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
-                 constraints):
-        r = self._posterior_launch(features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
-                                   constraints, 'entropy', with_backward=True)
-        h = ops.entropy(r['batch'], r['elp'], r['trans'], r['init'], r['len'], r['logz'], endpen=r['endpen'], ws=r['ws'],
-                        with_backward=True)
-        ops.check_decoded(r['batch'], dict(_err=ops._err_copy(r['batch'], r['ws'])))
-        return h, r, None
+        return _marginals(r).view(b, tmax, -1)
 
     def entropy(self, features, lengths, valid_classes_per_instance, add_eos=True, additional_allowed_ends_per_instance=None,
                 constraints=None, *, differentiable=False):
@@ -776,61 +839,50 @@ class SemiMarkovModule(nn.Module):
         SmmError when a NaN reached the DP.
         ``differentiable``: the same value (bit for bit), differentiable with respect to the module's parameters: the backward
         runs smm_entropy_bwd_f64 and the chain rule through the emission scorer and the factor tables (``log_partition``'s)."""
-        args = (features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance, constraints)
+        launch = lambda: _entropy(self._posterior_launch(
+            features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance, constraints, 'entropy',
+            with_backward=True), with_backward=True)
         if not differentiable:
             with torch.no_grad():
-                return self._entropy(*args)[0]
+                return launch()[0]
         self._require_device(features, 'entropy')
         tabs = self._differentiable_tables(self._check_valid_classes(valid_classes_per_instance), features.device)
-        return _PosteriorValue.apply('entropy', lambda: self._entropy(*args), *tabs)
+        return _PosteriorValue.apply('entropy', launch, *tabs)
 
-    def _packed_posterior_launch(self, pc, what, with_backward=False):
-        x = pc.x
-        self._require_device(x, what)
+    def _packed_stage(self, pc, what):
+        """``_stage_padded`` for a PackedCorpus, prepared for this module here: (batch, x, cons, endpen, tables stacked per
+        group, inv_var) -- the arguments of ``_emit`` / ``_emit_logz``."""
+        self._require_device(pc.x, what)
         self.prepare_packed(pc)
         t = pc.tables
-        ws = torch.empty(pc.batch.workspace_bytes(), dtype=torch.uint8, device=x.device)
-        elp, _ = ops.emission(pc.batch, x, t['w'], t['cst'], t['inv_var'], cons=pc.cons)
-        z = ops.logz(pc.batch, elp, t['trans'], t['init'], t['len'], endpen=pc.endpen, ws=ws, with_backward=with_backward)
-        return t, elp, z, ws
+        return pc.batch, pc.x, pc.cons, pc.endpen, tuple(t[k] for k in TABLE_NAMES) + (t['class_map'],), t['inv_var']
+
+    def _packed_posterior_launch(self, pc, what, with_backward=False):
+        return _emit_logz(*self._packed_stage(pc, what), with_backward)
 
     @torch.no_grad()
     def sample_packed(self, pc, n_samples, seed=0):
         """``sample`` for a whole PackedCorpus: one emission launch, one smm_logz_f64 and one sampling launch.
         Returns (labels, log_prob): device int64 n_samples x total_frames (global class ids on the packed frame axis) and fp64
         n_samples x n_videos in the order of ``pc.video_names``."""
-        t, elp, z, ws = self._packed_posterior_launch(pc, 'sample_packed')
-        out = ops.sample(pc.batch, elp, t['trans'], t['init'], t['len'], z, n_samples, seed, endpen=pc.endpen,
-                         class_map=t['class_map'], ws=ws, want_spans=False, want_labels=True)
-        ops.check_decoded(pc.batch, out)
-        return out['labels'], out['logp']
+        return _sample(self._packed_posterior_launch(pc, 'sample_packed'), n_samples, seed, want_spans=False)
 
     @torch.no_grad()
     def frame_posteriors_packed(self, pc):
         """``frame_posteriors`` for a whole PackedCorpus: fp64 total_frames x c_max on the device; column c of a frame is local
         state c of its video's group (``pc.tables['class_map']`` maps it to a global id)."""
-        t, elp, z, ws = self._packed_posterior_launch(pc, 'frame_posteriors_packed')
-        g = ops.logz_bwd(pc.batch, elp, t['trans'], t['init'], t['len'], z, endpen=pc.endpen, ws=ws)
-        return g['elp']
-
-    def _entropy_packed(self, pc):
-        t, elp, z, ws = self._packed_posterior_launch(pc, 'entropy_packed')
-        h = ops.entropy(pc.batch, elp, t['trans'], t['init'], t['len'], z, endpen=pc.endpen, ws=ws)
-        ops.check_decoded(pc.batch, dict(_err=ops._err_copy(pc.batch, ws)))
-        # (the entropy launch ran the time-reversed recursion into ws: the backward finds both directions there)
-        r = dict(batch=pc.batch, elp=elp, trans=t['trans'], init=t['init'], len=t['len'], endpen=pc.endpen, logz=z, ws=ws, x=pc.x)
-        return h, r, None
+        return _marginals(self._packed_posterior_launch(pc, 'frame_posteriors_packed'))
 
     def entropy_packed(self, pc, *, differentiable=False):
         """``entropy`` for a whole PackedCorpus: fp64 n_videos on the device, in the order of ``pc.video_names``.
         ``differentiable``: as ``entropy``'s; the tables are ``stacked_tables(pc, differentiable=True)``."""
+        launch = lambda: _entropy(self._packed_posterior_launch(pc, 'entropy_packed'), with_backward=False)
         if not differentiable:
             with torch.no_grad():
-                return self._entropy_packed(pc)[0]
+                return launch()[0]
         self._require_device(pc.x, 'entropy_packed')
         st = self.stacked_tables(pc, differentiable=True)[0]
-        return _PosteriorValue.apply('entropy', lambda: self._entropy_packed(pc),
-                                     *(st[k] for k in ('w', 'cst', 'trans', 'init', 'len')))
+        return _PosteriorValue.apply('entropy', launch, *(st[k] for k in TABLE_NAMES))
 
     # ------------------------------------------------------------------ KL divergence and cross-entropy (smm_kl_f64)
     def _check_same_lattice(self, other, what):
@@ -859,11 +911,7 @@ class SemiMarkovModule(nn.Module):
                                     other_constraints, what)
         r = self._posterior_launch(features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
                                    constraints, what, with_backward=True)
-        self._check_same_batch(r['batch'], q['batch'], what)
-        side = lambda t: (t['elp'], t['trans'], t['init'], t['len'], t['endpen'], t['logz'], t['ws'])
-        out = ops.kl(r['batch'], side(r), side(q), with_backward=True, want_cross_entropy=want_cross_entropy)
-        ops.check_decoded(r['batch'], dict(_err=ops._err_copy(r['batch'], r['ws'])))
-        return (out[1] if want_cross_entropy else out), r, q
+        return _kl(r, q, what, True, want_cross_entropy)
 
     def _kl_value(self, other, args, what, want_cross_entropy, differentiable):
         if not differentiable:
@@ -908,17 +956,11 @@ class SemiMarkovModule(nn.Module):
         # tables, end penalties and launch metadata on the corpus, and `pc` is left prepared for `self`
         saved = dict(pc.__dict__)
         try:
-            tq, elp_q, z_q, ws_q = other._packed_posterior_launch(pc, what)
-            ep_q, batch_q = pc.endpen, pc.batch
+            q = other._packed_posterior_launch(pc, what)
         finally:
             pc.__dict__.clear()
             pc.__dict__.update(saved)
-        t, elp, z, ws = self._packed_posterior_launch(pc, what)
-        self._check_same_batch(pc.batch, batch_q, what)
-        out = ops.kl(pc.batch, (elp, t['trans'], t['init'], t['len'], pc.endpen, z, ws),
-                     (elp_q, tq['trans'], tq['init'], tq['len'], ep_q, z_q, ws_q), want_cross_entropy=want_cross_entropy)
-        ops.check_decoded(pc.batch, dict(_err=ops._err_copy(pc.batch, ws)))
-        return out[1] if want_cross_entropy else out
+        return _kl(self._packed_posterior_launch(pc, what), q, what, False, want_cross_entropy)[0]
 
     @torch.no_grad()
     def kl_packed(self, other, pc):
@@ -943,49 +985,18 @@ class SemiMarkovModule(nn.Module):
         other may come in either order).  A video with fewer than k segmentations gets score -inf and a row of -1 on the ranks
         past its last.  No autograd."""
         self._require_device(features, 'viterbi_kbest')
-        valid_classes = self._check_valid_classes(valid_classes_per_instance)
-        b, tmax, d = features.shape
-        dev = features.device
-        lengths_host = lengths.detach().cpu().numpy().astype(np.int64)
-        assert int(lengths_host.max()) == tmax, "one instance must span the padded length (padding_colate)"
-        no_eos = not add_eos
-        self._check_no_eos_lengths(lengths_host, no_eos)
-        tab = self._decode_tables(valid_classes, dev)
-        c = tab['init'].numel()
-        batch = ops.Batch(lengths_host, [c], tab['len'].size(0), c_max=c, t_max=tmax, total_frames=b * tmax, d=d,
-                          no_eos=no_eos)
-        x = features.detach().to(torch.float32).contiguous().view(b * tmax, d)
-        cons = None
-        if constraints is not None:
-            cons = constraints.detach().to(device=dev, dtype=torch.float32).contiguous().view(b * tmax, c)
-        endpen = None if no_eos else self._endpen(valid_classes, additional_allowed_ends_per_instance, b, c, dev)
-        g1 = tab.get('_one_group')
-        if g1 is None:
-            g1 = tab['_one_group'] = tuple(tab[n].unsqueeze(0).contiguous() for n in ('w', 'cst', 'trans', 'init', 'len')) \
-                + (tab['class_map'].view(1, -1),)
-        elp, _ = ops.emission(batch, x, g1[0], g1[1], tab['inv_var'], cons=cons)
-        out = ops.kbest(batch, elp, g1[2], g1[3], g1[4], k, endpen=endpen, class_map=g1[5], want_spans=True,
-                        want_labels=False)
-        spans = out['spans'].cpu()
-        ops.check_decoded(batch, out)
-        if no_eos:
-            spans = spans[:, :, :tmax].contiguous()
-        return spans, out['score']
+        # (no_time_split stays off on this entry point, hard masks or not)
+        batch, x, cons, endpen, tab, g1 = self._stage_padded(
+            features, lengths, self._check_valid_classes(valid_classes_per_instance), additional_allowed_ends_per_instance,
+            constraints, no_eos=not add_eos)
+        return _kbest(_emit(batch, x, cons, endpen, g1, tab['inv_var']), k, want_spans=True)
 
     @torch.no_grad()
     def kbest_packed(self, pc, k):
         """``viterbi_kbest`` for a whole PackedCorpus: one emission launch and one k-best launch.  Returns (labels, scores):
         device int64 k x total_frames (global class ids on the packed frame axis) and fp64 k x n_videos in the order of
         ``pc.video_names``."""
-        x = pc.x
-        self._require_device(x, 'kbest_packed')
-        self.prepare_packed(pc)
-        t = pc.tables
-        elp, _ = ops.emission(pc.batch, x, t['w'], t['cst'], t['inv_var'], cons=pc.cons)
-        out = ops.kbest(pc.batch, elp, t['trans'], t['init'], t['len'], k, endpen=pc.endpen, class_map=t['class_map'],
-                        want_spans=False, want_labels=True)
-        ops.check_decoded(pc.batch, out)
-        return out['labels'], out['score']
+        return _kbest(_emit(*self._packed_stage(pc, 'kbest_packed')), k, want_spans=False)
 
     # ------------------------------------------------------------------ minimum-Bayes-risk decode (smm_mbr_f64)
     @torch.no_grad()
@@ -1002,27 +1013,14 @@ class SemiMarkovModule(nn.Module):
         when a NaN reached the DP.  No autograd."""
         r = self._posterior_launch(features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
                                    constraints, 'mbr_decode', with_backward=True)
-        g = ops.logz_bwd(r['batch'], r['elp'], r['trans'], r['init'], r['len'], r['logz'], endpen=r['endpen'], ws=r['ws'],
-                         with_backward=True)
-        out = ops.mbr(r['batch'], g['elp'], r['trans'], r['init'], endpen=r['endpen'], class_map=r['class_map'], ws=r['ws'],
-                      want_spans=True, want_labels=False)
-        spans = out['spans'].cpu()
-        ops.check_decoded(r['batch'], out)
-        if not add_eos:
-            spans = spans[:, :features.size(1)].contiguous()
-        return spans, out['gain_sum']
+        return _mbr(r, want_spans=True)
 
     @torch.no_grad()
     def mbr_decode_packed(self, pc):
         """``mbr_decode`` for a whole PackedCorpus: one emission, one log Z (both directions), one marginals and one MBR launch.
         Returns (labels, expected_correct): device int64 total_frames (global class ids on the packed frame axis, -1 on frames
         no video covers) and fp64 n_videos in the order of ``pc.video_names``."""
-        t, elp, z, ws = self._packed_posterior_launch(pc, 'mbr_decode_packed', with_backward=True)
-        g = ops.logz_bwd(pc.batch, elp, t['trans'], t['init'], t['len'], z, endpen=pc.endpen, ws=ws, with_backward=True)
-        out = ops.mbr(pc.batch, g['elp'], t['trans'], t['init'], endpen=pc.endpen, class_map=t['class_map'], ws=ws,
-                      want_spans=False, want_labels=True)
-        ops.check_decoded(pc.batch, out)
-        return out['labels'], out['gain_sum']
+        return _mbr(self._packed_posterior_launch(pc, 'mbr_decode_packed', with_backward=True), want_spans=False)
 
     # ------------------------------------------------------------------ forced alignment (smm_align_f64)
     @staticmethod
@@ -1057,30 +1055,12 @@ class SemiMarkovModule(nn.Module):
         if not add_eos:
             raise ValueError("align: add_eos=False is not supported")
         self._require_device(features, 'align')
-        valid_classes = self._check_valid_classes(valid_classes_per_instance)
-        b, tmax, d = features.shape
-        dev = features.device
-        lengths_host = lengths.detach().cpu().numpy().astype(np.int64)
-        assert int(lengths_host.max()) == tmax, "one instance must span the padded length (padding_colate)"
-        tab = self._decode_tables(valid_classes, dev)
-        c = tab['init'].numel()
-        local = self._local_transcripts(transcripts, tab['class_map'].view(1, -1).cpu().numpy(), [c], np.zeros(b, np.int64))
-        batch = ops.Batch(lengths_host, [c], tab['len'].size(0), c_max=c, t_max=tmax, total_frames=b * tmax, d=d)
-        x = features.detach().to(torch.float32).contiguous().view(b * tmax, d)
-        cons = None
-        if constraints is not None:
-            cons = constraints.detach().to(device=dev, dtype=torch.float32).contiguous().view(b * tmax, c)
-        endpen = self._endpen(valid_classes, additional_allowed_ends_per_instance, b, c, dev)
-        g1 = tab.get('_one_group')
-        if g1 is None:
-            g1 = tab['_one_group'] = tuple(tab[n].unsqueeze(0).contiguous() for n in ('w', 'cst', 'trans', 'init', 'len')) \
-                + (tab['class_map'].view(1, -1),)
-        elp, _ = ops.emission(batch, x, g1[0], g1[1], tab['inv_var'], cons=cons)
-        out = ops.align(batch, elp, g1[2], g1[3], g1[4], local, endpen=endpen, class_map=g1[5], want_spans=True,
-                        want_labels=False)
-        spans = out['spans'].cpu()
-        ops.check_decoded(batch, out)
-        return spans, out['best']
+        # (this entry point stages without no_time_split and, having refused add_eos=False above, without the length check)
+        batch, x, cons, endpen, tab, g1 = self._stage_padded(
+            features, lengths, self._check_valid_classes(valid_classes_per_instance), additional_allowed_ends_per_instance,
+            constraints, check_no_eos=False)
+        local = self._local_transcripts(transcripts, g1[5].cpu().numpy(), batch.n_states, np.zeros(batch.b, np.int64))
+        return _align(_emit(batch, x, cons, endpen, g1, tab['inv_var']), local, want_spans=True)
 
     @torch.no_grad()
     def align_packed(self, pc, transcripts):
@@ -1088,19 +1068,13 @@ class SemiMarkovModule(nn.Module):
         GLOBAL class ids per video, in the order of ``pc.video_names``.  Returns (labels, scores): device int64 total_frames
         (global class ids on the packed frame axis, -1 on frames no video covers and on videos without an alignment) and fp64
         n_videos."""
-        x = pc.x
-        self._require_device(x, 'align_packed')
+        self._require_device(pc.x, 'align_packed')
         if pc.batch.no_eos:
             raise ValueError("align_packed: add_eos=False is not supported")
-        self.prepare_packed(pc)
-        t = pc.tables
-        group = pc.batch.group if pc.batch.group is not None else np.zeros(pc.batch.b, np.int64)
-        local = self._local_transcripts(transcripts, t['class_map'].cpu().numpy(), pc.batch.n_states, group)
-        elp, _ = ops.emission(pc.batch, x, t['w'], t['cst'], t['inv_var'], cons=pc.cons)
-        out = ops.align(pc.batch, elp, t['trans'], t['init'], t['len'], local, endpen=pc.endpen, class_map=t['class_map'],
-                        want_spans=False, want_labels=True)
-        ops.check_decoded(pc.batch, out)
-        return out['labels'], out['best']
+        batch, x, cons, endpen, g, inv_var = self._packed_stage(pc, 'align_packed')
+        group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
+        local = self._local_transcripts(transcripts, g[5].cpu().numpy(), batch.n_states, group)
+        return _align(_emit(batch, x, cons, endpen, g, inv_var), local, want_spans=False)
 
     # ------------------------------------------------------------------ packed multi-task decode
     def stacked_tables(self, pc, differentiable=False):
@@ -1337,48 +1311,34 @@ class SemiMarkovModule(nn.Module):
         return total
 
     def _one_group_tables(self, valid_classes, dev):
-        """The fp64 tables of one class set as a stack of one group, with autograd history -> (tables, c, k_rows)."""
+        """The fp64 tables of one class set as a stack of one group, with autograd history."""
         if self.max_k > 1:
             # one-group stack (HIP table kernels for fp32 parameters on the GPU); the index tensors are kept per class set
             cache = self.__dict__.setdefault('_single_group', {})
             key = None if valid_classes is None else tuple(int(v) for v in valid_classes)
             one = cache.get(key)
             if one is None:
-                import types
                 one = cache[key] = types.SimpleNamespace(groups=[dict(valid_classes=valid_classes)])
-            st, n_states, c, k_rows = self._stacked_tables_batched(one, dev)
-        else:
-            tab = self.factor_tables(valid_classes, dev)
-            c, k_rows = tab['init'].numel(), tab['len'].size(0)
-            st = {n: tab[n].unsqueeze(0).contiguous() for n in ('w', 'cst', 'trans', 'init', 'len')}
-            st['inv_var'] = tab['inv_var'].contiguous()
-        return st, c, k_rows
+            return self._stacked_tables_batched(one, dev)[0]
+        tab = self.factor_tables(valid_classes, dev)
+        st = {n: tab[n].unsqueeze(0).contiguous() for n in TABLE_NAMES}
+        st['inv_var'] = tab['inv_var'].contiguous()
+        return st
 
     def _differentiable_tables(self, valid_classes, dev):
         """(w, cst, trans, init, len) of one class set with autograd history: the inputs of _PosteriorValue."""
-        st = self._one_group_tables(valid_classes, dev)[0]
-        return tuple(st[k] for k in ('w', 'cst', 'trans', 'init', 'len'))
+        st = self._one_group_tables(valid_classes, dev)
+        return tuple(st[k] for k in TABLE_NAMES)
 
     def log_partition(self, features, lengths, valid_classes, additional_allowed_ends_per_instance=None,
                       constraints=None, no_eos=False):
         """log Z per instance on the device, differentiable w.r.t. the module's parameters
         (smm_emission_f64 + smm_logz_f64 forward, smm_logz_bwd_f64 backward)."""
         self._require_device(features, 'log_partition')
-        b, tmax, d = features.shape
-        dev = features.device
-        lengths_host = lengths.detach().cpu().numpy().astype(np.int64)
-        assert int(lengths_host.max()) == tmax
-        self._check_no_eos_lengths(lengths_host, no_eos)
-        st, c, k_rows = self._one_group_tables(valid_classes, dev)
-        batch = ops.Batch(lengths_host, [c], k_rows, c_max=c, t_max=tmax, total_frames=b * tmax, d=d, no_eos=no_eos,
-                          no_time_split=self._hard_masks())
-        x = features.detach().to(torch.float32).contiguous().view(b * tmax, d)
-        cons = None
-        if constraints is not None:
-            cons = constraints.detach().to(device=dev, dtype=torch.float32).contiguous().view(b * tmax, c)
-        endpen = None if no_eos else self._endpen(valid_classes, additional_allowed_ends_per_instance, b, c, dev)
-        return _LogPartition.apply(batch, None, x, cons, endpen, st['w'], st['cst'], st['inv_var'], st['trans'],
-                                   st['init'], st['len'])
+        st = self._one_group_tables(valid_classes, features.device)
+        batch, x, cons, endpen, _, _ = self._stage_padded(features, lengths, valid_classes, additional_allowed_ends_per_instance,
+                                                          constraints, no_eos=no_eos, no_time_split=self._hard_masks(), tables=st)
+        return _LogPartition.apply(batch, x, cons, endpen, st['w'], st['cst'], st['inv_var'], st['trans'], st['init'], st['len'])
 
     def log_partition_packed(self, pc):
         """log Z of every video of a PackedCorpus (any number of single-task batches, any mix of tasks) in ONE launch
@@ -1388,8 +1348,8 @@ class SemiMarkovModule(nn.Module):
         self._require_device(pc.x, 'log_partition_packed')
         self.prepare_packed(pc, differentiable=True)
         t = pc.tables
-        return _LogPartition.apply(pc.batch, None, pc.x, pc.cons, pc.endpen, t['w'], t['cst'],
-                                   t['inv_var'], t['trans'], t['init'], t['len'])
+        return _LogPartition.apply(pc.batch, pc.x, pc.cons, pc.endpen, t['w'], t['cst'], t['inv_var'], t['trans'], t['init'],
+                                   t['len'])
 
     def log_likelihood_packed(self, pc):
         """Per source batch the mean log-likelihood the reference's ``log_likelihood(spans=None)`` returns for it
