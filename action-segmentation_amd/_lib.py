@@ -13,6 +13,7 @@ SYMBOLS = [
     "smm_sample_f64", "smm_entropy_f64", "smm_kl_f64", "smm_kbest_workspace_bytes", "smm_kbest_f64",
     "smm_mbr_workspace_bytes", "smm_mbr_f64",
     "smm_align_workspace_bytes", "smm_align_f64",
+    "smm_align_logz_workspace_bytes", "smm_align_logz_f64", "smm_align_logz_bwd_f64",
     "smm_entropy_bwd_scratch_bytes", "smm_entropy_bwd_f64", "smm_kl_bwd_f64",
     "smm_factor_tables_f64", "smm_factor_tables_bwd_f64",
     "smm_dense_workspace_bytes", "smm_dense_dp_f32", "smm_dense_marginals_f32",
@@ -38,6 +39,7 @@ SHAPE_NO_TIME_SPLIT = 4
 KL_BWD_CROSS_ENTROPY = 0
 KL_BWD_KL = 1
 MAX_TRANSCRIPT = 256
+ALIGN_LOGZ_TILE = 768      # positions per tile of the transcript-likelihood kernels (csrc/smm_align_logz.hip: threads x R)
 
 
 class SmmEvalShape(ctypes.Structure):
@@ -89,6 +91,14 @@ def load():
     lib.smm_align_f64.restype = ctypes.c_int
     lib.smm_align_f64.argtypes = [ctypes.POINTER(SmmShape)] + [ctypes.c_void_p] * 17 + [ctypes.c_void_p, ctypes.c_size_t,
                                                                                         ctypes.c_void_p]
+    lib.smm_align_logz_workspace_bytes.restype = ctypes.c_size_t
+    lib.smm_align_logz_workspace_bytes.argtypes = [ctypes.POINTER(SmmShape), ctypes.c_void_p, ctypes.c_void_p]
+    lib.smm_align_logz_f64.restype = ctypes.c_int
+    lib.smm_align_logz_f64.argtypes = [ctypes.POINTER(SmmShape)] + [ctypes.c_void_p] * 13 + [ctypes.c_void_p, ctypes.c_size_t,
+                                                                                             ctypes.c_void_p]
+    lib.smm_align_logz_bwd_f64.restype = ctypes.c_int
+    lib.smm_align_logz_bwd_f64.argtypes = [ctypes.POINTER(SmmShape)] + [ctypes.c_void_p] * 18 + [ctypes.c_void_p, ctypes.c_size_t,
+                                                                                                 ctypes.c_void_p]
     lib.smm_dense_workspace_bytes.restype = ctypes.c_size_t
     lib.smm_dense_workspace_bytes.argtypes = [ctypes.c_int32] * 4
     lib.smm_eval_workspace_bytes.restype = ctypes.c_size_t

@@ -24,62 +24,10 @@
 //     the maximum of that expression over k;
 //   - outputs: every span position and frame finds its segment by bisection over the segment starts in LDS.
 // No atomics, no private segment; NaN / +inf detection on the bits (smm_nan_bits' reasoning).
-#include "smm_device.h"
-#include "smm_launch.h"
-#include "../../include/smmdp.h"
-
 #define SMM_ALIGN_THREADS 256
 #define SMM_ALIGN_R 3                                            // positions per thread (odd: see above)
-#define SMM_ALIGN_P (SMM_ALIGN_THREADS * SMM_ALIGN_R)            // positions per tile
-#define SMM_ALIGN_DMAX ((SMM_MAX_K_ROWS + SMM_ALIGN_R - 1) / SMM_ALIGN_R * SMM_ALIGN_R)   // distances walked, at most
-#define SMM_ALIGN_OFF SMM_ALIGN_DMAX                             // LDS index of the tile's first position
-#define SMM_ALIGN_HS (SMM_ALIGN_OFF + SMM_ALIGN_P + 8)           // h values in LDS: halo | tile | the R ahead
-#define SMM_ALIGN_LEN (SMM_ALIGN_DMAX + 3 * SMM_ALIGN_R)         // length scores in LDS: index k + R, -inf outside 1 .. kp - 1
-
-static_assert(SMM_ALIGN_R % 2 == 1, "an even stride puts a half-wave's h reads on a quarter of the banks");
-static_assert(SMM_MAX_TRANSCRIPT <= SMM_ALIGN_THREADS, "one thread per transcript position checks its tables");
-
-__device__ __forceinline__ double align_max(double a, double b) { return __builtin_fmax(a, b); }
-
-// NaN or +-inf by the bits (exponent all ones)
-__device__ __forceinline__ bool align_nonfinite_bits(double x)
-{
-    int hi = __double2hiint(x);
-    asm volatile("" : "+v"(hi));
-    return (hi & 0x7ff00000) == 0x7ff00000;
-}
-// NaN or +inf: what must not enter the DP (-inf is an ordinary "impossible")
-__device__ __forceinline__ bool align_bad_bits(double x)
-{
-    return smm_nan_bits(x) || (align_nonfinite_bits(x) && __double2hiint(x) >= 0);
-}
-
-__device__ __forceinline__ double align_wave_max(double x)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x = align_max(x, __shfl_xor(x, off));
-    return x;
-}
-
-__device__ __forceinline__ int align_wave_min(int x)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const int y = __shfl_xor(x, off);
-        x = y < x ? y : x;
-    }
-    return x;
-}
-
-// the cells of column m that lie on a complete alignment (lo > hi: none)
-__device__ __forceinline__ void align_range(int m, int M, int T, int kw, int &lo, int &hi)
-{
-    const int rest = M - 1 - m;
-    const int a = m + 1, b = T - rest * kw;
-    const int c = T - rest, d = (m + 1) * kw;
-    lo = a > b ? a : b;
-    hi = c < d ? c : d;
-}
+#include "smm_align_tile.h"                                      // the tile geometry that follows from the two, and the shared phases
+#include "smm_launch.h"
 
 __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_kernel(SmmAlignArgs a)
 {
@@ -138,35 +86,8 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_kernel(SmmAlignAr
         if (bad) s_flag[1] = 1;
     }
 
-    // ---- prefix sums: tiles of `rows` frames through LDS, lane c adds class c serially, cum[c][n] class-major
-    {
-        const int ld = cm + 1;                                 // row stride in LDS: odd, so the transposing reads spread over the banks
-        const int rows = SMM_ALIGN_HS / ld;
-        double run = 0.0;
-        if (tid < C) cum[(size_t)tid * T1] = 0.0;
-        for (int f0 = 0; f0 < T; f0 += rows) {
-            const int nr = T - f0 < rows ? T - f0 : rows;
-            __syncthreads();
-            for (int e = tid; e < nr * cm; e += SMM_ALIGN_THREADS) {
-                const int r = e / cm, c = e - r * cm;
-                s_h[r * ld + c] = elp[(size_t)f0 * cm + e];
-            }
-            __syncthreads();
-            if (tid < C) {
-#pragma unroll 8
-                for (int r = 0; r < nr; ++r) {
-                    run = run + s_h[r * ld + tid];
-                    s_h[r * ld + tid] = run;
-                }
-            }
-            __syncthreads();
-            for (int e = tid; e < nr * C; e += SMM_ALIGN_THREADS) {
-                const int c = e / nr, r = e - c * nr;
-                cum[(size_t)c * T1 + f0 + 1 + r] = s_h[r * ld + c];
-            }
-        }
-        if (tid < C && align_nonfinite_bits(run)) s_flag[1] = 1;
-    }
+    // ---- prefix sums (smm_align_tile.h): tiles of frames through LDS, lane c adds class c serially, cum[c][n] class-major
+    if (align_prefix_sums(elp, cum, C, cm, T, s_h, tid)) s_flag[1] = 1;
     if (tid == 0) hcol[0] = a.init[(size_t)g * cm + s_a[0]];
     __threadfence_block();
     __syncthreads();

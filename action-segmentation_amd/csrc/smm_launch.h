@@ -255,3 +255,30 @@ struct SmmAlignArgs {
     int32_t c_max, k_rows, t_max, b;
 };
 void smm_launch_align(const SmmAlignArgs &a, hipStream_t stream);
+
+// transcript likelihood and its gradient (smm_align_logz.hip).  cum as for the alignment; the columns of video i at
+// cols + hoff[i]: h | gam | q, each [M][T+1]; its part of g_len at part + poff[i]: [min(k_rows, T + 1)][c_max]
+struct SmmAlignLogzArgs {
+    const SmmVideo *videos;
+    const int32_t *order;      // [b] workgroup -> video (most lattice cells first)
+    const int32_t *n_states;
+    const double *elp;         // [total_frames][c_max]
+    const double *trans;       // [g][c_max][c_max]  [to][from]
+    const double *init;        // [g][c_max]
+    const double *len;         // [g][k_rows][c_max]
+    const double *endpen;      // [b][c_max] or null
+    const int32_t *transcript; // [toff[b]] local state ids (caller's; checked against n_states on load)
+    const int64_t *toff;       // [b + 1]
+    const int64_t *hoff;       // [b] doubles
+    const int64_t *poff;       // [b] doubles
+    double *hist;              // the workspace's history area
+    double *cols;              // behind the plan's workspace
+    double *part;              // behind the columns
+    double *logz;              // [b]: the forward launch writes it, the backward launches read it
+    const double *grad;        // [b] or null (= 1)                      (backward only, as the four below)
+    double *g_elp, *g_trans, *g_init, *g_len;   // smm_logz_bwd_f64's layouts; g_elp zero at launch
+    int32_t *err;              // sticky error word
+    int32_t c_max, k_rows, b, n_groups;
+};
+void smm_launch_align_logz_fwd(const SmmAlignLogzArgs &a, hipStream_t stream);
+void smm_launch_align_logz_bwd(const SmmAlignLogzArgs &a, hipStream_t stream);

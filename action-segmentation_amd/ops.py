@@ -710,6 +710,79 @@ def align(batch, elp, trans, init, len_scores, transcripts, endpen=None, class_m
     return dict(spans=spans, labels=labels, best=best, n_segs=n_segs, _err=_err_copy(batch, ws), _keep=(ids_dev, ws))
 
 
+ALIGN_LOGZ_TILE = _lib.ALIGN_LOGZ_TILE
+
+
+def _transcript_offsets(batch, transcript_offset, what):
+    off = np.ascontiguousarray(np.asarray(transcript_offset, dtype=np.int64).reshape(-1))
+    if off.shape[0] != batch.b + 1:
+        raise ValueError("%s: b + 1 transcript offsets expected" % what)
+    return off
+
+
+def align_logz_workspace_bytes(batch, transcript_offset):
+    """Bytes of workspace smm_align_logz_f64 / smm_align_logz_bwd_f64 need for this batch and these transcript offsets (int64
+    [b + 1]; host only)."""
+    off = _transcript_offsets(batch, transcript_offset, 'align_logz_workspace_bytes')
+    n = _lib.load().smm_align_logz_workspace_bytes(ctypes.byref(batch.shape), ctypes.c_void_p(batch.lengths.ctypes.data),
+                                                   ctypes.c_void_p(off.ctypes.data))
+    if n == 0:
+        raise _lib.SmmError("libsmmdp: invalid batch shape or transcript offsets for the transcript likelihood (add_eos=True "
+                            "only, 1..%d entries per video)" % MAX_TRANSCRIPT)
+    return n
+
+
+def _align_logz_inputs(batch, elp, trans, init, len_scores, transcripts, endpen):
+    """The arguments the forward and the backward call share, from the tables on: (ctypes values, what they keep alive).
+    ``transcripts``: per-video sequences of local ids, or the (ids on the device, offsets on the host) pair an earlier call
+    returned as ``transcript``."""
+    f64 = torch.float64
+    if isinstance(transcripts, tuple) and len(transcripts) == 2 and torch.is_tensor(transcripts[0]):
+        ids_dev, off = transcripts
+    else:
+        ids, off = _transcript_arrays(batch, transcripts)
+        ids_dev = torch.from_numpy(ids).to(elp.device)
+    args = (_dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
+            _dev(endpen, f64, 'endpen'), _dev(ids_dev, torch.int32, 'transcript'), ctypes.c_void_p(off.ctypes.data))
+    return args, (ids_dev, off)
+
+
+def align_logz(batch, elp, trans, init, len_scores, transcripts, endpen=None, ws=None):
+    """Transcript likelihood (smm_align_logz_f64): per video log Z_a, the log of the sum over every segmentation whose class
+    sequence is its transcript -- LOCAL state ids, one per segment, consecutive repeats allowed.  -> fp64 [b]: -inf for a
+    video without such a segmentation, NaN (and the error word) when a NaN reached the DP.  ``ws``: a uint8 workspace of at
+    least ``align_logz_workspace_bytes`` -- keep it for ``align_logz_bwd`` (default: a private one, then use ``align_logz_ex``)."""
+    return align_logz_ex(batch, elp, trans, init, len_scores, transcripts, endpen=endpen, ws=ws)['logz']
+
+
+def align_logz_ex(batch, elp, trans, init, len_scores, transcripts, endpen=None, ws=None):
+    """``align_logz`` with what a backward call needs: dict(logz, ws, transcript (ids on the device, offsets on the host),
+    _err (the launch's error words, copied))."""
+    lib = _lib.load()
+    dev = elp.device
+    args, tr = _align_logz_inputs(batch, elp, trans, init, len_scores, transcripts, endpen)
+    ws = _own_workspace(ws, align_logz_workspace_bytes(batch, tr[1]), dev)
+    out = torch.empty(batch.b, dtype=torch.float64, device=dev)
+    _lib.check(lib.smm_align_logz_f64(*batch.head(), *args, _dev(out, torch.float64, 'logz_a'), *_ws_args(ws), _stream()))
+    return dict(logz=out, ws=ws, transcript=tr, _err=_err_copy(batch, ws))
+
+
+def align_logz_bwd(batch, elp, trans, init, len_scores, transcripts, logz_a, grad_logz=None, endpen=None, ws=None):
+    """Gradient of sum_i grad_logz[i] * log Z_a(i) (smm_align_logz_bwd_f64).  Must follow ``align_logz`` for the same batch,
+    tables and transcripts with the same workspace ``ws`` on the same stream; ``logz_a`` = its output.
+    -> dict(elp [total_frames, c_max], trans, init, len) fp64; videos whose log Z_a is -inf or NaN contribute zeros."""
+    lib = _lib.load()
+    f64 = torch.float64
+    args, tr = _align_logz_inputs(batch, elp, trans, init, len_scores, transcripts, endpen)
+    if ws is None or ws.numel() < align_logz_workspace_bytes(batch, tr[1]):
+        raise ValueError("align_logz_bwd: pass the workspace the align_logz call wrote")
+    g = _grad_outputs(elp, trans, init, len_scores)
+    _lib.check(lib.smm_align_logz_bwd_f64(
+        *batch.head(), *args, _dev(logz_a, f64, 'logz_a'), _dev(grad_logz, f64, 'grad_logz'), _dev(g['elp'], f64, 'g_elp'),
+        _dev(g['trans'], f64, 'g_trans'), _dev(g['init'], f64, 'g_init'), _dev(g['len'], f64, 'g_len'), *_ws_args(ws), _stream()))
+    return g
+
+
 _pinned = {}
 
 

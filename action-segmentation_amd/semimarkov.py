@@ -387,6 +387,23 @@ class SemiMarkovModel(object):
         assert lab.size == 0 or int(lab.max()) < self.model.n_classes, "alignments should not contain EOS"
         return {name: lab[off:off + t] for name, off, t in zip(pc.video_names, pc.frame_offset, pc.lengths)}
 
+    def transcript_log_likelihood(self, data, transcripts_by_video, conditional=False, shard=None):
+        """The likelihood of every video's transcript: ``transcripts_by_video[name]`` is the video's class sequence in global
+        class ids, one entry per segment.  Returns ``{video: float}``: log Z_a, the log of the sum over every segmentation with
+        that class sequence (the joint log-likelihood of frames and transcript); ``conditional``: log Z_a - log Z, the
+        log-probability of the transcript given the frames.  -inf for a transcript that cannot be laid over its video.  One
+        emission launch and the DP launches on the packed corpus (``SemiMarkovModule.transcript_scores_packed``)."""
+        self.model.eval()
+        pc = self.prepare(data, shard=shard)
+        if pc.n_videos == 0:
+            return {}
+        missing = [name for name in pc.video_names if name not in transcripts_by_video]
+        if missing:
+            raise ValueError("transcript_log_likelihood: no transcript for video %r" % (missing[0],))
+        z = self.model.transcript_scores_packed(pc, [transcripts_by_video[name] for name in pc.video_names],
+                                                conditional=conditional)
+        return {name: float(v) for name, v in zip(pc.video_names, z.tolist())}
+
     def predict_packed(self, pc):
         import torch
         from . import ops

@@ -172,6 +172,43 @@ class _LogPartition(torch.autograd.Function):
         return None, None, None, None, g_w, g_cst, g_iv, g['trans'], g['init'], g['len']
 
 
+class _TranscriptLogPartition(torch.autograd.Function):
+    """log Z_a of every video of one launch -- the sum over the segmentations whose class sequence is the video's transcript --
+    as a differentiable function of the fp64 factor tables, beside ``_LogPartition``.  Forward: smm_emission_f64 +
+    smm_align_logz_f64 on a private workspace that survives until backward; backward: smm_align_logz_bwd_f64 (the posterior
+    of the alignments) + smm_emission_bwd_f64.  ``local``: the transcripts in local state ids."""
+
+    @staticmethod
+    def forward(ctx, batch, x, cons, endpen, local, w, cst, inv_var, trans, init, len_scores):
+        r = _emit(batch, x, cons, endpen, (w, cst, trans, init, len_scores, None), inv_var)
+        out = ops.align_logz_ex(batch, r['elp'], trans, init, len_scores, local, endpen=endpen)
+        ctx.batch, ctx.endpen, ctx.ws, ctx.transcript = batch, endpen, out['ws'], out['transcript']
+        ctx.save_for_backward(x, r['elp'], trans, init, len_scores, out['logz'])
+        return out['logz']
+
+    @staticmethod
+    def backward(ctx, gz):
+        x, elp, trans, init, len_scores, logz = ctx.saved_tensors
+        g = ops.align_logz_bwd(ctx.batch, elp, trans, init, len_scores, ctx.transcript, logz,
+                               grad_logz=gz.to(torch.float64).contiguous(), endpen=ctx.endpen, ws=ctx.ws)
+        g_w, g_cst, g_iv = ops.emission_bwd(ctx.batch, x, g['elp'], ws=ctx.ws)
+        return None, None, None, None, None, g_w, g_cst, g_iv, g['trans'], g['init'], g['len']
+
+
+def _check_transcript_logz(z, names, what, allow_none=False):
+    """The host's look at a launch's log Z_a (synchronises): SmmError for a NaN, ValueError -- naming the video -- for -inf."""
+    zh = z.detach().cpu()
+    if bool(torch.isnan(zh).any()):
+        raise ops._lib.SmmError("libsmmdp: NaN (or +inf) in the DP inputs of %s" % what)
+    bad = torch.nonzero(torch.isinf(zh)).reshape(-1).tolist()
+    if bad and not allow_none:
+        i = bad[0]
+        raise ValueError("%s: no segmentation of video %r has its transcript (more entries than frames, too few for the span "
+                         "limit, or forbidden by the tables): log Z_a = -inf cannot be trained on"
+                         % (what, i if names is None else names[i]))
+    return zh
+
+
 def _table_grads(batch, x, g, ws):
     """(g_w, g_cst, g_trans, g_init, g_len) from the gradients of the tables and elp: the emission chain rule, one pass over x."""
     g_w, g_cst, _ = ops.emission_bwd(batch, x, g['elp'], ws=ws)
@@ -1076,6 +1113,64 @@ class SemiMarkovModule(nn.Module):
         local = self._local_transcripts(transcripts, g[5].cpu().numpy(), batch.n_states, group)
         return _align(_emit(batch, x, cons, endpen, g, inv_var), local, want_spans=False)
 
+    # ------------------------------------------------------------------ transcript likelihood (smm_align_logz_f64)
+    def transcript_log_partition(self, features, lengths, valid_classes_per_instance, transcripts, add_eos=True,
+                                 additional_allowed_ends_per_instance=None, constraints=None):
+        """log Z_a per video of a zero-padded single-task batch (argument conventions of ``align``): the log of the sum over
+        every segmentation whose class sequence is ``transcripts[i]`` (GLOBAL class ids, one entry per segment, consecutive
+        repeats are two segments) -- the joint log-likelihood of frames and transcript; minus ``log_partition`` it is the
+        conditional likelihood of the transcript.  fp64 b on the device, differentiable w.r.t. the module's parameters
+        (smm_emission_f64 + smm_align_logz_f64 forward, smm_align_logz_bwd_f64 + smm_emission_bwd_f64 backward).
+        ValueError for add_eos=False, an id that is not valid for the video, an empty transcript, and for a video no
+        segmentation of which has its transcript (log Z_a = -inf); SmmError when a NaN reached the DP."""
+        if not add_eos:
+            raise ValueError("transcript_log_partition: add_eos=False is not supported")
+        if len(transcripts) != features.size(0):
+            raise ValueError("transcript_log_partition: %d transcripts for %d videos" % (len(transcripts), features.size(0)))
+        valid_classes = self._check_valid_classes(valid_classes_per_instance)
+        ids = list(range(self.n_classes)) if valid_classes is None else [int(v) for v in valid_classes]
+        local = self._local_transcripts(transcripts, np.array([ids + [self.n_classes]], np.int64), [len(ids)],
+                                        np.zeros(len(transcripts), np.int64))
+        self._require_device(features, 'transcript_log_partition')
+        st = self._one_group_tables(valid_classes, features.device)
+        batch, x, cons, endpen, _, _ = self._stage_padded(features, lengths, valid_classes, additional_allowed_ends_per_instance,
+                                                          constraints, check_no_eos=False, tables=st)
+        z = _TranscriptLogPartition.apply(batch, x, cons, endpen, local, st['w'], st['cst'], st['inv_var'], st['trans'],
+                                          st['init'], st['len'])
+        _check_transcript_logz(z, None, 'transcript_log_partition')
+        return z
+
+    def transcript_log_partition_packed(self, pc, transcripts):
+        """``transcript_log_partition`` for a whole PackedCorpus in one launch of each kernel: ``transcripts`` holds one sequence
+        of GLOBAL class ids per video, in the order of ``pc.video_names``.  fp64 [n_videos], differentiable."""
+        self._require_device(pc.x, 'transcript_log_partition_packed')
+        if pc.batch is not None and pc.batch.no_eos:
+            raise ValueError("transcript_log_partition_packed: add_eos=False is not supported")
+        self.prepare_packed(pc, differentiable=True)
+        t, batch = pc.tables, pc.batch
+        group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
+        local = self._local_transcripts(transcripts, t['class_map'].cpu().numpy(), batch.n_states, group)
+        z = _TranscriptLogPartition.apply(batch, pc.x, pc.cons, pc.endpen, local, t['w'], t['cst'], t['inv_var'], t['trans'],
+                                          t['init'], t['len'])
+        _check_transcript_logz(z, list(pc.video_names), 'transcript_log_partition_packed')
+        return z
+
+    @torch.no_grad()
+    def transcript_scores_packed(self, pc, transcripts, conditional=False):
+        """Without autograd, on the cached decode tables: log Z_a of every video of a PackedCorpus (``conditional``: minus its
+        log Z) as a CPU fp64 tensor; -inf for a video no segmentation of which has its transcript.  One emission launch, then
+        the DP launches.  SmmError when a NaN reached the DP."""
+        if pc.batch is not None and pc.batch.no_eos:
+            raise ValueError("transcript_scores_packed: add_eos=False is not supported")
+        batch, x, cons, endpen, g, inv_var = self._packed_stage(pc, 'transcript_scores_packed')
+        group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
+        local = self._local_transcripts(transcripts, g[5].cpu().numpy(), batch.n_states, group)
+        r = _emit(batch, x, cons, endpen, g, inv_var)
+        z = ops.align_logz(batch, r['elp'], r['trans'], r['init'], r['len'], local, endpen=endpen)
+        if conditional:
+            z = z - ops.logz(batch, r['elp'], r['trans'], r['init'], r['len'], endpen=endpen)
+        return _check_transcript_logz(z, None, 'transcript_scores_packed', allow_none=True)
+
     # ------------------------------------------------------------------ packed multi-task decode
     def stacked_tables(self, pc, differentiable=False):
         """fp64 factor tables of every group of a PackedCorpus stacked to [groups, ...] and zero-padded to c_max columns.
@@ -1378,18 +1473,29 @@ class SemiMarkovModule(nn.Module):
         return torch.mv(mean_of, z)
 
     def log_likelihood(self, features, lengths, valid_classes_per_instance, spans=None, add_eos=True, use_mean_z=False,
-                       additional_allowed_ends_per_instance=None, constraints=None):
+                       additional_allowed_ends_per_instance=None, constraints=None, transcripts=None):
         """(mean log-likelihood, mean log_det) like the reference (:597-658).
 
         spans given: joint score p(x, y) (differentiable), or with --sm_train_discriminatively the conditional
         score - log Z.  spans=None: the log-partition (marginal likelihood) from the HIP forward kernel; its gradient
         (posterior marginals chained into the parameters) comes from the HIP backward kernels.
+        transcripts given (and no spans): only the order of each video's actions is known -- the mean of log Z_a
+        (``transcript_log_partition``), or with --sm_train_discriminatively of log Z_a - log Z.
         """
+        if spans is not None and transcripts is not None:
+            raise ValueError("log_likelihood: give spans (full supervision) or transcripts (the order only), not both")
         no_eos = not add_eos
         valid_classes = self._check_valid_classes(valid_classes_per_instance)
         self.set_z(features, lengths, use_mean=use_mean_z)
         log_det = torch.zeros(features.size(0), device=features.device)
-        if spans is not None:
+        if transcripts is not None:
+            ll = self.transcript_log_partition(features, lengths, valid_classes_per_instance, transcripts, add_eos=add_eos,
+                                               additional_allowed_ends_per_instance=additional_allowed_ends_per_instance,
+                                               constraints=constraints)
+            if getattr(self.args, 'sm_train_discriminatively', False):
+                ll = ll - self.log_partition(features, lengths, valid_classes, additional_allowed_ends_per_instance,
+                                             constraints)
+        elif spans is not None:
             ll = self.gold_score(features, lengths, valid_classes, spans, additional_allowed_ends_per_instance, constraints,
                                  no_eos=no_eos)
             if getattr(self.args, 'sm_train_discriminatively', False):

@@ -26,6 +26,8 @@
  *                              correct frames (the reference has none)
  *   smm_align_f64           <- forced alignment: the best segmentation whose class sequence is a given transcript (the
  *                              reference has none)
+ *   smm_align_logz_f64 /    <- transcript likelihood: the log of the sum over every segmentation with a given transcript,
+ *   smm_align_logz_bwd_f64     and its gradient (the objective and the E-step of transcript supervision; the reference has none)
  *
  * The reference has no FFI: its boundary is the Python call SemiMarkovCRF(scores, lengths) on a dense
  * b x N x K x C x C tensor.  These entry points take the FACTORS of that tensor instead,
@@ -471,6 +473,65 @@ int smm_align_f64(const smm_shape *shape, const int64_t *lengths_host, const int
                   const double *endpen, const int64_t *class_map, const int32_t *transcript,
                   const int64_t *transcript_offset_host, int64_t *spans, int64_t *labels, double *best, int32_t *n_segs,
                   void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Transcript likelihood (csrc/smm_align_logz.hip): per video log Z_a = log sum_{y : classes(y) = a} exp score(y), the sum over
+ * every segmentation whose class sequence is the transcript a[0..M-1], and the gradient of sum_i u_i log Z_a(i).  log Z_a is the
+ * joint log-likelihood of frames and transcript, log Z_a - log Z (smm_logz_f64) the conditional one; the gradient is the E-step
+ * of transcript-supervised training.  Conventions of smm_align_f64: EOS mode only, 1 <= M <= SMM_MAX_TRANSCRIPT local state
+ * ids, consecutive equal ids are two segments, kp the video's span limit, cum the serial prefix sum of elp,
+ * closing = endpen ? endpen[i][a_{M-1}] : 0; lse is log-sum-exp, and an lse over only -inf terms is -inf.
+ *   forward   h[0][0] = init[a_0];  h[0][m>0] = -inf;  h[n>0][0] = -inf
+ *             gam[n][m] = cum[n][a_m] + lse_{k=1..min(kp-1,n)} ( h[n-k][m] + len[k][a_m] )            n = 1..T
+ *             h[n][m]   = gam[n][m-1] + trans[a_m][a_{m-1}] - cum[n][a_m]                             0 < n < T, m >= 1
+ *             logZ_a    = gam[T][M-1] + closing
+ *   backward  bg[T][M-1] = closing;  bg[T][m<M-1] = -inf
+ *             bh[s][m]  = lse_{k=1..min(kp-1,T-s)} ( len[k][a_m] + cum[s+k][a_m] + bg[s+k][m] )       s = 0..T-1
+ *             bg[n][m]  = trans[a_{m+1}][a_m] - cum[n][a_{m+1}] + bh[n][m+1]                          0 < n < T, m < M-1
+ *             (identity: h[0][0] + bh[0][0] = logZ_a)
+ *   marginals S[s][m] = exp(h[s][m] + bh[s][m] - logZ_a)      segment m starts at s   (= E[s][m-1] for m >= 1; S[0][0] = 1)
+ *             E[n][m] = exp(gam[n][m] + bg[n][m] - logZ_a)    segment m ends at n
+ *             occ[t][m] = sum_{s<=t} S[s][m] - sum_{n<=t} E[n][m]                                    frame t lies in segment m
+ *   gradients of sum_i u_i logZ_a(i)   (u = grad_logz, NULL = ones):
+ *             g_elp[t][c]    = u_i * sum_{m: a_m = c} occ[t][m]
+ *             g_len[k][c]    = sum_i u_i * sum_{m: a_m = c} sum_s exp(h[s][m] + len[k][c] + cum[s+k][c] + bg[s+k][m] - logZ_a)
+ *             g_trans[c][c'] = sum_i u_i * #{m >= 1 : a_m = c, a_{m-1} = c'}        (every alignment uses the same transitions)
+ *             g_init[c]      = sum_i u_i * [a_0 = c]
+ * Each lse takes its own maximum as the reference: the differences are formed in fp64, exponentiated in fp32 and summed in
+ * fp64, so the values hold for any dynamic range of the scores (|logZ_a - exact| ~ 1e-7 per column).  Every sum -- over the
+ * videos of a group, the transcript entries, the positions -- is taken in a fixed order without atomics: two calls on the same
+ * inputs give the same bits.
+ *   - A video without a path by counting (M > T or M (kp - 1) < T), or with an id outside [0, n_states), gets logZ_a = -inf
+ *     and contributes exactly zero to every gradient (its g_elp rows are zeros); the error word stays clear and no table is
+ *     read with such an id.
+ *   - A video with a path by counting but none of finite score (-inf table entries, an ordinary "impossible") likewise gets
+ *     -inf and zero gradients.
+ *   - The error word is set, logZ_a is NaN and the gradient contributions are zero under smm_align_f64's conditions: cum[T][c]
+ *     not finite for any state of the video, or a NaN or +inf in a table entry the transcript reads.
+ * smm_align_logz_bwd_f64 must follow smm_align_logz_f64 for the same batch, tables and transcripts on the same workspace and
+ * stream: it reads the cum, h and gam columns the forward call left there (and writes the bg columns and the videos' parts of
+ * g_len beside them); logz_a is the forward call's output.  g_elp, g_trans, g_init, g_len have smm_logz_bwd_f64's layouts and
+ * are overwritten entirely (zero fills are kernels).  The workspace is smm_align_logz_workspace_bytes -- the only size query
+ * these entry points add to -- and the error word sits at smm_error_word_offset; staging the backward call clears the word,
+ * and the backward call sets it again for every video whose logz_a is NaN.  Enqueued on `stream` only; never synchronises;
+ * a video is never split over workgroups.
+ * SMM_ERR_ARG for a NULL required pointer, non-monotone offsets or an empty transcript; SMM_ERR_UNSUPPORTED for
+ * SMM_SHAPE_NO_EOS, a transcript longer than SMM_MAX_TRANSCRIPT, c_max or k_rows beyond the compiled kernels;
+ * SMM_ERR_WORKSPACE below smm_align_logz_workspace_bytes -- all before anything is staged.
+ */
+/* host only; 0 on whatever the calls refuse for the shape, the lengths or the offsets */
+size_t smm_align_logz_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host, const int64_t *transcript_offset_host);
+int smm_align_logz_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                       const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                       const double *elp, const double *trans, const double *init, const double *len_scores,
+                       const double *endpen, const int32_t *transcript, const int64_t *transcript_offset_host,
+                       double *logz_a /* dev [b] */, void *workspace, size_t workspace_bytes, void *stream);
+int smm_align_logz_bwd_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                           const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                           const double *elp, const double *trans, const double *init, const double *len_scores,
+                           const double *endpen, const int32_t *transcript, const int64_t *transcript_offset_host,
+                           const double *logz_a, const double *grad_logz /* nullable */, double *g_elp, double *g_trans,
+                           double *g_init, double *g_len, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Factor tables of every parameter group from the model parameters (training steps), and their chain rule.
