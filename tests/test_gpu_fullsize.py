@@ -287,12 +287,26 @@ def test_split_decode_equals_single_stream_decode_and_the_twin(k, monkeypatch):
     """smm_decode_f32 splits a launch whose few longest videos set the DP's time: those are scored and decoded on the
     caller's stream, the rest on a second stream beside them (smm_api.hip: choose_split).  Same labels, spans and scores
     as the single-stream decode and as the twin."""
+    from action_segmentation_amd import ops
+
+    def decode_and_tags():
+        """decode_both, and the tags of the DP launches its one decode made (ops.dp_timing_read)."""
+        ops.dp_timing_read()
+        ops.dp_timing(True)
+        try:
+            r = decode_both(cp)
+        finally:
+            ops.dp_timing(False)
+        return r, sorted(t for _, t in ops.dp_timing_read(tagged=True))
+
     monkeypatch.setenv('SMM_SPLIT_MIN_US', '0')
     cp = make_corpus(91, [5000, 4800, 4700] + [1200 + 13 * i for i in range(40)], 9, k, rate=(20, 200) if k > 64 else (5, 40))
-    res = decode_both(cp)
+    res, tags = decode_and_tags()
+    assert tags == [1, 2], tags                                   # the split did happen: critical videos | the rest
     check_equivalent(cp, *res)
     monkeypatch.setenv('SMM_NO_SPLIT', '1')
-    one = decode_both(cp)
+    one, tags = decode_and_tags()
+    assert tags == [0], tags
     for key in ('spans', 'labels', 'best', 'n_segs'):
         np.testing.assert_array_equal(res[0][key].cpu().numpy(), one[0][key].cpu().numpy())
 
