@@ -8,7 +8,7 @@ LIB_PATH = os.environ.get("SMM_LIB_PATH") or os.path.join(HERE, "libsmmdp.so")  
 SYMBOLS = [
     "smm_strerror", "smm_last_hip_error", "smm_version", "smm_device_count", "smm_workspace_bytes",
     "smm_error_word_offset", "smm_dp_timing_enable", "smm_dp_timing_read", "smm_dp_timing_read_tagged", "smm_band_frame_ns", "smm_time_split_plan",
-    "smm_env_reload", "smm_release_cached_plans", "smm_cached_plan_bytes",
+    "smm_env_reload", "smm_release_cached_plans", "smm_cached_plan_bytes", "smm_plan_feedback_info", "smm_plan_feedback_plan",
     "smm_emission_f64", "smm_emission_bwd_f64", "smm_viterbi_f64", "smm_viterbi_f32", "smm_decode_f32", "smm_logz_f64", "smm_logz_bwd_f64",
     "smm_sample_f64", "smm_entropy_f64", "smm_kl_f64", "smm_kbest_workspace_bytes", "smm_kbest_f64",
     "smm_mbr_workspace_bytes", "smm_mbr_f64",
@@ -26,6 +26,12 @@ class SmmShape(ctypes.Structure):
     _fields_ = [("b", ctypes.c_int32), ("d", ctypes.c_int32), ("n_groups", ctypes.c_int32),
                 ("c_max", ctypes.c_int32), ("k_rows", ctypes.c_int32), ("t_max", ctypes.c_int32),
                 ("flags", ctypes.c_int32), ("total_frames", ctypes.c_int64)]
+
+
+class SmmPlanFeedbackInfo(ctypes.Structure):
+    _fields_ = [("n_replans", ctypes.c_int32), ("n1_before", ctypes.c_int32), ("n1_after", ctypes.c_int32),
+                ("n_videos", ctypes.c_int32), ("end_before_us", ctypes.c_double), ("end_after_us", ctypes.c_double),
+                ("stamps", ctypes.POINTER(ctypes.c_uint64)), ("order", ctypes.POINTER(ctypes.c_int32))]
 
 
 class SmmTablesShape(ctypes.Structure):
@@ -140,6 +146,11 @@ def load():
     lib.smm_release_cached_plans.argtypes = []
     lib.smm_cached_plan_bytes.restype = ctypes.c_size_t
     lib.smm_cached_plan_bytes.argtypes = []
+    lib.smm_plan_feedback_info.restype = ctypes.c_int
+    lib.smm_plan_feedback_info.argtypes = [ctypes.POINTER(SmmPlanFeedbackInfo)]
+    lib.smm_plan_feedback_plan.restype = ctypes.c_int
+    lib.smm_plan_feedback_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_double] + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_int] \
+        + [ctypes.c_void_p] * 4
     _lib = lib
     return lib
 

@@ -15,6 +15,7 @@
 #include "../../include/smmdp.h"
 #include "smm_device.h"
 #include "smm_launch.h"
+#include "smm_plan_feedback.h"
 
 static thread_local int g_last_hip = 0;
 
@@ -31,6 +32,8 @@ struct SmmEnv {
     int split_margin = 400;
     int plan_cache = 1;       // SMM_PLAN_CACHE=0: no resident plans
     int small_wg = 1;         // SMM_SMALL_WG=0: no four-wave workgroups for <= 16-state videos; 2: wherever they apply, whatever the part's size (tests; same results)
+    int plan_feedback = 1;    // SMM_PLAN_FEEDBACK=0: a resident plan's stream split is never re-planned from measured times; 2: re-planned after the
+                              // first complete measurement whatever the predicted gain (tests; same results)
     int chunk = 1;            // SMM_CHUNK=0: no time-split decode of long videos (same results)
     int chunk_p = 0;          // SMM_CHUNK_P: positions per unit of a time-split decode (0: from the launch's CU-time; tests force small ones)
     int chunk_lmin = 0;       // SMM_CHUNK_LMIN: least own part of a unit (0: SMM_CHUNK_LMIN below; never less than kp - 1 or 130)
@@ -59,7 +62,7 @@ void env_read()
     const Item items[] = {
         {"SMM_SPEC", &e.spec, nullptr}, {"SMM_NO_SPLIT", &e.no_split, nullptr}, {"SMM_SPLIT_MIN_US", nullptr, &e.split_min_us},
         {"SMM_SPLIT_NS", nullptr, &e.split_ns}, {"SMM_SPLIT_MARGIN", &e.split_margin, nullptr},
-        {"SMM_PLAN_CACHE", &e.plan_cache, nullptr}, {"SMM_SMALL_WG", &e.small_wg, nullptr}, {"SMM_CHUNK", &e.chunk, nullptr}, {"SMM_CHUNK_P", &e.chunk_p, nullptr},
+        {"SMM_PLAN_CACHE", &e.plan_cache, nullptr}, {"SMM_SMALL_WG", &e.small_wg, nullptr}, {"SMM_PLAN_FEEDBACK", &e.plan_feedback, nullptr}, {"SMM_CHUNK", &e.chunk, nullptr}, {"SMM_CHUNK_P", &e.chunk_p, nullptr},
         {"SMM_CHUNK_WC", &e.chunk_wc, nullptr}, {"SMM_CHUNK_LMIN", &e.chunk_lmin, nullptr}, {"SMM_NO_BT_WINDOW", &e.no_bt_window, nullptr},
         {"SMM_FIT_GRID", &e.fit_grid, nullptr}, {"SMM_VERBOSE", &e.verbose, nullptr},
 #ifdef SMM_DEV
@@ -353,6 +356,12 @@ struct Staged {
     // the LAST part of the DP launch order (the rest of a stream split, or the whole launch) ends with small_count units of <= 16
     // states that run in four-wave workgroups, two per CU, beside the others (smm_viterbi.hip: smm_launch_viterbi_small); 0: none
     int small_first, small_count;
+    // plan feedback (below, "Plan feedback"): where this call's DP workgroups stamp their start and end (null: nowhere), the
+    // event the call records behind its join, and the resident plan it runs from
+    uint64_t *stamps = nullptr;
+    hipEvent_t done = nullptr;
+    void *fb_entry = nullptr;
+    std::vector<int32_t> order_host, frames_host;   // (stream split, on the way to a new resident plan only: `order` and T by video)
 };
 
 static bool band_mode(int kp_max, int c_need);
@@ -387,6 +396,10 @@ extern "C" double smm_band_frame_ns(int n_states)
     if (n_states < 1 || n_states > SMM_MAX_STATES) return 0.0;
     return SMM_BAND_NS_BASE + SMM_BAND_NS_PER_STATE * n_states;
 }
+
+// Modelled ns per frame of one video on its CU: BAND mode by the library's model, the ring kernels (span limits up to 512: cfg2's
+// 16 states at K = 256 take 199 ns per frame) by theirs.  A DP launch is ordered by T x this, most work first.
+static double dp_frame_ns(bool band, int c) { return band ? smm_band_frame_ns(c) : 150.0 + 3.0 * c; }
 
 static int choose_split(const SmmVideo *hv, int32_t *order, int b, int d, int c_max, int64_t total_frames)
 {
@@ -432,8 +445,36 @@ static int choose_split(const SmmVideo *hv, int32_t *order, int b, int d, int c_
 // call in flight and no captured graph that was captured from one of these calls still to be replayed).  With
 // SMM_PLAN_CACHE=0, past the cap, or when a call with new inputs happens under stream capture (no allocation, no event
 // query there), a call is staged into its workspace as before.
+//
+// Plan feedback.  The stream split of a decode is planned from a model -- (T, states) -> time -- that predicts a video's DP time
+// to +-15 % (BAND mode skips what its bound tests exclude: the time depends on the lattice), and a launch ends with its slowest
+// video.  A resident plan is decoded again and again, so the library MEASURES instead: a call that runs from (or admits) a
+// resident plan with a stream split, no time-split videos and no small-workgroup tail hands the DP kernels a pinned host
+// buffer, [b][2] ticks of the 100 MHz wall clock, and records an event behind its join.  A later call on that plan that
+// finds the event complete (queried, never waited for; nothing of this under stream capture) takes the times and, once its
+// own launches are queued, replays the step from them (smm_plan_feedback.h).  If a first part made of the videos that
+// really are the slowest ends the replayed step at least 2 % sooner, the plan's launch order and emission block table are
+// written into a FRESH region of the plan slabs and the entry's pointers are swapped on the host: the old region stays valid
+// until smm_release_cached_plans(), so a call in flight or a captured graph never sees a buffer change under it.  Only who
+// starts when changes: every video is decoded by the same kernel on the same inputs.  An entry is re-planned at most 4 times
+// and stops measuring at the first measurement that offers no such gain.  SMM_PLAN_FEEDBACK=0: never; 2: tests.
 namespace {
+struct PlanFeedback {
+    uint64_t *stamps = nullptr;              // pinned host memory, [b][2]: the DP workgroups write, the host reads behind `done`
+    hipEvent_t done = nullptr;
+    bool pending = false;                    // a stamping call has been queued and its stamps have not been looked at yet
+    bool have = false;                       // `snap` is a complete measurement nobody has evaluated yet
+    bool busy = false;                       // a thread is evaluating it
+    int evals_left = 5, n_replans = 0;
+    int b = 0, n1_first = 0;
+    double em_us = 0.0, end_before_us = 0.0, end_after_us = 0.0;
+    std::vector<uint64_t> snap, used;        // the latest complete measurement; the one the last evaluation was made from
+    std::vector<int32_t> order, frames;      // host copies: the plan's current launch order, T by video
+};
+constexpr int SMM_FEEDBACK_MAX_REPLANS = 4;
+constexpr double SMM_FEEDBACK_MIN_GAIN = 0.02;
 struct PlanEntry {
+    PlanFeedback *fb = nullptr;
     std::vector<char> key;
     int device = 0;
     char *dev_meta = nullptr;
@@ -453,6 +494,8 @@ struct PlanCache {
     std::unordered_map<uint64_t, std::vector<PlanEntry *>> entries;     // by FNV-1a of the key; compared in full on a hit
     std::unordered_map<uint64_t, uint32_t> seen_once;                   // keys seen once (hash only): admitted at the second sighting
     size_t n = 0, bytes = 0, key_bytes = 0;                            // plans, device bytes, host bytes of their keys
+    size_t pinned_bytes = 0;                                           // pinned host bytes of the plans' stamp buffers
+    uint64_t generation = 1;                                           // bumped by smm_release_cached_plans()
     PlanSlabs slabs[64];
 } g_plans;
 constexpr size_t SMM_PLAN_MAX_BYTES = (size_t)64 << 20, SMM_PLAN_MAX_ENTRIES = 8192, SMM_PLAN_SLAB = (size_t)1 << 20;
@@ -511,6 +554,28 @@ std::vector<char> plan_key(const smm_shape *s, const int64_t *lengths, const int
     return k;
 }
 
+// (cache locked) a call is about to run from resident plan `e`: take a finished measurement, arm the next one
+void feedback_arm(PlanEntry *e, Staged *out)
+{
+    PlanFeedback *fb = e->fb;
+    if (!fb || !env().plan_feedback) return;
+    out->fb_entry = e;
+    if (fb->pending) {
+        if (hipEventQuery(fb->done) != hipSuccess) { (void)hipGetLastError(); return; }      // (still running: this call does not stamp)
+        fb->pending = false;
+        bool complete = !fb->have && !fb->busy;
+        for (int i = 0; complete && i < fb->b; ++i) complete = fb->stamps[2 * i] > 0 && fb->stamps[2 * i + 1] >= fb->stamps[2 * i];
+        if (complete) { fb->snap.assign(fb->stamps, fb->stamps + 2 * (size_t)fb->b); fb->have = true; }
+    }
+    // (a measurement that waits for its evaluation at the end of this call may change the plan: nothing is measured beside it)
+    if (fb->evals_left > 0 && !fb->have && !fb->busy) {
+        std::memset(fb->stamps, 0, sizeof(uint64_t) * 2 * (size_t)fb->b);
+        out->stamps = fb->stamps;
+        out->done = fb->done;
+        fb->pending = true;
+    }
+}
+
 void plan_point(const SmmPlan &p, void *ws, Staged *out)
 {
     char *base = static_cast<char *>(ws);
@@ -562,7 +627,11 @@ static int stage(const smm_shape *s, const int64_t *lengths, const int64_t *fram
     }
     if (hit) {
         if (ws_bytes < hit->plan.total) return SMM_ERR_WORKSPACE;
-        *out = hit->st;
+        {
+            std::lock_guard<std::mutex> lock(g_plans.mu);      // (a re-plan swaps the entry's pointers under this lock)
+            *out = hit->st;
+            if (!capturing && for_viterbi && want_split) feedback_arm(hit, out);
+        }
         plan_point(hit->plan, ws, out);
         char *base = static_cast<char *>(ws);
         SMM_HIP((hipError_t)smm_zero_async(base + hit->plan.o_err, hit->plan.meta_bytes - hit->plan.o_err, stream));
@@ -600,15 +669,52 @@ static int stage(const smm_shape *s, const int64_t *lengths, const int64_t *fram
     e->device = dev;
     e->dev_meta = dev_meta;
     e->plan = plan;
+    PlanFeedback *fb = nullptr;
+    std::vector<int32_t> order_host = std::move(out->order_host), frames_host = std::move(out->frames_host);
+    out->order_host.clear(); out->frames_host.clear();
     e->st = *out;
     e->stream = stream;
+    // plan feedback: this call, the one that admits the plan, is the first to be measured
+    if (for_viterbi && want_split && env().plan_feedback && out->n_split > 0 && out->n_cv == 0 && out->small_count == 0 &&
+        (int)order_host.size() == s->b) {
+        fb = new PlanFeedback;
+        const size_t bytes = sizeof(uint64_t) * 2 * (size_t)s->b;
+        if (hipHostMalloc(reinterpret_cast<void **>(&fb->stamps), bytes, hipHostMallocDefault) != hipSuccess) fb->stamps = nullptr;
+        if (fb->stamps && hipEventCreateWithFlags(&fb->done, hipEventDisableTiming) != hipSuccess) fb->done = nullptr;
+        if (!fb->stamps || !fb->done) {
+            (void)hipGetLastError();
+            if (fb->stamps) (void)hipHostFree(fb->stamps);
+            delete fb;
+            fb = nullptr;
+        } else {
+            fb->b = s->b;
+            fb->n1_first = out->n_split;
+            fb->em_us = (double)s->total_frames * (4.0 * s->d + 8.0 * s->c_max) / 4.0e6;      // choose_split's emission model
+            fb->order = std::move(order_host);
+            fb->frames = std::move(frames_host);
+            std::memset(fb->stamps, 0, bytes);
+            fb->pending = true;
+            out->stamps = fb->stamps;
+            out->done = fb->done;
+        }
+    }
+    e->fb = fb;
+    auto drop_fb = [&]() {
+        if (!fb) return;
+        out->stamps = nullptr; out->done = nullptr;             // (this call then runs unmeasured)
+        (void)hipHostFree(fb->stamps);
+        (void)hipEventDestroy(fb->done);
+        delete fb;
+    };
     if (hipEventCreateWithFlags(&e->ready, hipEventDisableTiming) != hipSuccess || hipEventRecord(e->ready, stream) != hipSuccess) {
         // (cannot tell later whether the upload is through: this call is fine -- same stream -- but the plan is not kept)
         if (e->ready) (void)hipEventDestroy(e->ready);
+        drop_fb();
         delete e;
         return SMM_OK;     // dev_meta stays allocated: this call's kernels read it
     }
     std::lock_guard<std::mutex> lock(g_plans.mu);
+    if (fb) { g_plans.pinned_bytes += sizeof(uint64_t) * 2 * (size_t)s->b; out->fb_entry = e; }
     g_plans.entries[hk].push_back(e);
     g_plans.seen_once.erase(hk);
     g_plans.n += 1;
@@ -630,8 +736,16 @@ extern "C" size_t smm_release_cached_plans(void)
     for (auto &kv : g_plans.entries)
         for (PlanEntry *e : kv.second) {
             if (e->ready) (void)hipEventDestroy(e->ready);
+            if (e->fb) {
+                (void)hipHostFree(e->fb->stamps);
+                (void)hipEventDestroy(e->fb->done);
+                delete e->fb;
+            }
             delete e;
         }
+    freed += g_plans.pinned_bytes;
+    g_plans.pinned_bytes = 0;
+    g_plans.generation += 1;
     g_plans.entries.clear();
     g_plans.seen_once.clear();
     for (int d = 0; d < 64; ++d) {
@@ -649,10 +763,142 @@ extern "C" size_t smm_release_cached_plans(void)
 extern "C" size_t smm_cached_plan_bytes(void)
 {
     std::lock_guard<std::mutex> lock(g_plans.mu);
-    size_t n = 0;
+    size_t n = g_plans.pinned_bytes;                 // (the plans' stamp buffers: pinned host memory)
     for (int d = 0; d < 64; ++d)
         for (auto &ps : g_plans.slabs[d].all) n += ps.second;
     return n;
+}
+
+// ---- plan feedback: the evaluation, at the END of a decode call (its launches are queued: the host work hides behind them)
+namespace {
+struct FeedbackInfo {
+    uint64_t generation = 0;
+    smm_plan_feedback_info_t info{};
+};
+thread_local FeedbackInfo g_fb_info;
+
+void feedback_info_set(const PlanFeedback *fb, int n1_now)        // (cache locked)
+{
+    g_fb_info.generation = g_plans.generation;
+    smm_plan_feedback_info_t &o = g_fb_info.info;
+    o.n_replans = fb->n_replans;
+    o.n1_before = fb->n1_first;
+    o.n1_after = n1_now;
+    o.n_videos = fb->b;
+    o.end_before_us = fb->end_before_us;
+    o.end_after_us = fb->end_after_us;
+    o.stamps = fb->used.empty() ? nullptr : fb->used.data();
+    o.order = fb->order.data();
+}
+
+// st: what the call ran from; stream: the caller's (the new metadata is uploaded behind the call's own work)
+void feedback_evaluate(const Staged &st, hipStream_t stream)
+{
+    PlanEntry *e = static_cast<PlanEntry *>(st.fb_entry);
+    if (!e || !e->fb) return;
+    PlanFeedback *fb = e->fb;
+    std::vector<uint64_t> snap;
+    std::vector<int32_t> order;
+    int n1 = 0;
+    {
+        std::lock_guard<std::mutex> lock(g_plans.mu);
+        if (!fb->have || fb->busy || fb->evals_left <= 0) { feedback_info_set(fb, e->st.n_split); return; }
+        fb->busy = true;
+        snap = fb->snap;
+        order = fb->order;
+        n1 = e->st.n_split;
+    }
+    const SmmEnv &ev = env();
+    const int b = fb->b, n_cu = device_cus();
+    std::vector<double> dur(b);
+    for (int i = 0; i < b; ++i) dur[i] = (double)(snap[2 * i + 1] - snap[2 * i]) * 0.01;       // 100 MHz ticks -> us
+    const bool force = ev.plan_feedback >= 2;
+    // the emission pass's time, measured as well: the rest's first workgroup started (1 - the first part's share of the frames) of
+    // it behind the first part's (the model's 4 TB/s are on the fast side: cfg3 603 us modelled, 690 measured); kept within a
+    // factor of two of the model, so that a launch whose emission is a few microseconds is not planned around launch gaps
+    double em_us = fb->em_us;
+    {
+        uint64_t s1 = ~0ull, s2 = ~0ull;
+        double f1 = 0.0, f_all = 0.0;
+        for (int i = 0; i < b; ++i) {
+            const int v = order[i];
+            (i < n1 ? s1 : s2) = std::min(i < n1 ? s1 : s2, snap[2 * (size_t)v]);
+            f_all += fb->frames[v];
+            if (i < n1) f1 += fb->frames[v];
+        }
+        if (s2 > s1 && f_all > f1) em_us = std::min(2.0 * fb->em_us, std::max(0.5 * fb->em_us, (double)(s2 - s1) * 0.01 * f_all / (f_all - f1)));
+    }
+    const SmmFeedbackPlan plan = smm_feedback_plan(dur.data(), fb->frames.data(), order.data(), b, n1, n_cu, em_us, force);
+    const bool planned = smm_feedback_guards(b, n_cu, plan.n1) && plan.end_chosen_us > 0.0;
+    bool replan = planned && (force || (plan.changed && plan.end_chosen_us <= (1.0 - SMM_FEEDBACK_MIN_GAIN) * plan.end_current_us));
+    // the new metadata: launch order | emission block table, in the DP's new order
+    const size_t o_cum = align_up(sizeof(int32_t) * (size_t)b, 256), bytes = o_cum + align_up(sizeof(int32_t) * ((size_t)b + 1), 256);
+    std::vector<char> host(replan ? bytes : 0, 0);
+    std::vector<int32_t> cum(replan ? b + 1 : 0);
+    if (replan) {
+        int64_t c = 0;
+        for (int i = 0; i < b; ++i) { cum[i] = (int32_t)c; c += smm_emission_blocks(fb->frames[plan.order[i]], st.em_tpw); }
+        cum[b] = (int32_t)c;
+        if (c != st.em_blocks) replan = false;                      // (cannot happen: the same videos)
+        else {
+            std::memcpy(host.data(), plan.order.data(), sizeof(int32_t) * b);
+            std::memcpy(host.data() + o_cum, cum.data(), sizeof(int32_t) * ((size_t)b + 1));
+        }
+    }
+    std::lock_guard<std::mutex> lock(g_plans.mu);
+    fb->busy = false;
+    fb->have = false;
+    fb->evals_left -= 1;
+    fb->used = std::move(snap);
+    if (fb->n_replans == 0) fb->end_before_us = plan.end_current_us;
+    fb->end_after_us = plan.end_current_us;
+    char *dst = nullptr;
+    if (replan && g_plans.bytes + bytes <= SMM_PLAN_MAX_BYTES) dst = plan_alloc(bytes, e->device);
+    if (dst && smm_upload_meta(dst, host.data(), bytes, stream) == (int)hipSuccess && hipEventRecord(e->ready, stream) == hipSuccess) {
+        g_plans.bytes += align_up(bytes, 256);
+        e->st.order = reinterpret_cast<int32_t *>(dst);
+        e->st.em_cum = reinterpret_cast<int32_t *>(dst + o_cum);
+        e->st.em_cum_host = cum;
+        e->st.n_split = plan.n1;
+        e->stream = stream;                                          // (another stream waits for `ready` before it uses the new region)
+        e->settled = false;
+        fb->order = plan.order;
+        fb->n_replans += 1;
+        fb->end_after_us = plan.end_chosen_us;
+        if (force || fb->n_replans >= SMM_FEEDBACK_MAX_REPLANS) fb->evals_left = 0;
+    } else {
+        if (dst) (void)hipGetLastError();
+        fb->evals_left = 0;                                          // nothing to gain (or no room): the plan is final, nothing more is measured
+    }
+    feedback_info_set(fb, e->st.n_split);
+}
+}  // namespace
+
+extern "C" int smm_plan_feedback_info(smm_plan_feedback_info_t *out)
+{
+    if (!out) return SMM_ERR_ARG;
+    std::lock_guard<std::mutex> lock(g_plans.mu);
+    *out = g_fb_info.generation == g_plans.generation ? g_fb_info.info : smm_plan_feedback_info_t{};
+    return SMM_OK;
+}
+
+// The planner alone (smm_plan_feedback.h), for the host tests: no device needed.
+extern "C" int smm_plan_feedback_plan(int b, int n_cu, double em_us, const double *dur_us, const int32_t *frames,
+                                      const int32_t *cur_order, int cur_n1, int force, int32_t *order_out, int32_t *n1_out,
+                                      double *end_current_us, double *end_chosen_us)
+{
+    if (b < 1 || n_cu < 1 || !dur_us || !frames || !cur_order || cur_n1 < 0 || cur_n1 > b) return SMM_ERR_ARG;
+    std::vector<char> seen(b, 0);
+    for (int i = 0; i < b; ++i) {
+        if (cur_order[i] < 0 || cur_order[i] >= b || seen[cur_order[i]]) return SMM_ERR_ARG;
+        seen[cur_order[i]] = 1;
+    }
+    const SmmFeedbackPlan p = smm_feedback_plan(dur_us, frames, cur_order, b, cur_n1, n_cu, em_us, force != 0);
+    if (order_out) std::memcpy(order_out, p.order.data(), sizeof(int32_t) * b);
+    if (n1_out) *n1_out = p.n1;
+    if (end_current_us) *end_current_us = p.end_current_us;
+    if (end_chosen_us) *end_chosen_us = p.end_chosen_us;
+    return p.changed ? 1 : 0;
 }
 
 // Time-split plan of a Viterbi launch (smm_chunk.hip).  A launch lasts as long as its longest video -- one serial chain -- while
@@ -672,8 +918,7 @@ static void plan_chunks_lmin(const smm_shape *s, const SmmVideo *hv, const int32
     if (!ev.chunk || (s->flags & (SMM_SHAPE_NO_EOS | SMM_SHAPE_NO_TIME_SPLIT)) || kp_max <= 64) return;      // (kp <= 64: the window back-trace's launches are left alone)
     const int n_cu = n_cu_given > 0 ? n_cu_given : device_cus();
     if (n_cu <= 0) return;
-    // (the ring kernels, span limits up to 512: cfg2's 16 states at K = 256 take 199 ns per frame; BAND mode: the library's model)
-    auto ns = [&](int c) { return band ? smm_band_frame_ns(c) : 150.0 + 3.0 * c; };
+    auto ns = [&](int c) { return dp_frame_ns(band, c); };
     double t_cu = 0.0, t_long = 0.0;
     for (int i = 0; i < s->b; ++i) {
         const double t = (double)hv[i].T * ns(n_states[hv[i].group]);
@@ -789,14 +1034,15 @@ static int stage_uncached(const smm_shape *s, const int64_t *lengths, const int6
         kp_max = std::max(kp_max, k);
     }
     std::iota(ho, ho + s->b, 0);
-    // most work first, so the tail of the grid is made of short videos
+    out->band_mode = band_mode(kp_max, c_need);
+    // most work first -- by modelled time, T x ns per frame at the video's state count -- so the tail of the grid is made of short videos
+    const bool band = out->band_mode;
     std::stable_sort(ho, ho + s->b, [&](int a, int b) {
-        return (int64_t)hv[a].T * n_states[hv[a].group] > (int64_t)hv[b].T * n_states[hv[b].group];
+        return hv[a].T * dp_frame_ns(band, n_states[hv[a].group]) > hv[b].T * dp_frame_ns(band, n_states[hv[b].group]);
     });
     // (chunk table for the emission chain rule: by group, so that a workgroup's run of chunks rarely changes group)
     if (cum_chunk > 0) std::stable_sort(ho, ho + s->b, [&](int a, int b) { return hv[a].group < hv[b].group; });
     std::memcpy(hn, n_states, sizeof(int32_t) * s->n_groups);
-    out->band_mode = band_mode(kp_max, c_need);
     // time-split plan (Viterbi launches only): the split videos come FIRST in `order` -- with a stream split they are its
     // first part (their emission, the prefix sums at their units' starts and their units' DP on the caller's stream, the
     // rest beside them)
@@ -857,6 +1103,11 @@ static int stage_uncached(const smm_shape *s, const int64_t *lengths, const int6
         hc[s->b] = (int32_t)cum;
         out->em_blocks = (int)cum;
         if (out->n_split > 0) out->em_cum_host.assign(hc, hc + s->b + 1);
+        if (out->n_split > 0 && meta_alloc) {
+            out->order_host.assign(ho, ho + s->b);
+            out->frames_host.resize(s->b);
+            for (int i = 0; i < s->b; ++i) out->frames_host[i] = hv[i].T;
+        }
     }
     // the units' metadata: [videos | units], the DP launch's order over [units (most work first) | unsplit videos (as in `order`)],
     // the split videos' table and -- for the repair launch -- their list
@@ -875,7 +1126,7 @@ static int stage_uncached(const smm_shape *s, const int64_t *lengths, const int6
         std::memcpy(xv + s->b, cp.units.data(), sizeof(SmmVideo) * n_un);
         for (int i = 0; i < n_un; ++i) xo[i] = s->b + i;
         std::stable_sort(xo, xo + n_un, [&](int a, int b) {
-            return (int64_t)xv[a].T * n_states[xv[a].group] > (int64_t)xv[b].T * n_states[xv[b].group];
+            return xv[a].T * dp_frame_ns(band, n_states[xv[a].group]) > xv[b].T * dp_frame_ns(band, n_states[xv[b].group]);
         });
         for (int i = n_cv; i < s->b; ++i) xo[n_un + i - n_cv] = ho[i];
         for (int i = 0; i < n_cv; ++i) {
@@ -1100,6 +1351,7 @@ static int run_viterbi(const smm_shape *s, const Staged &st, const double *elp, 
     SmmDpArgs a = dp_args(s, st, Tables{elp, trans, init, len_scores, endpen, nullptr});
     a.class_map = class_map;
     a.spans = spans; a.labels = labels; a.best = best; a.n_segs = n_segs;
+    a.stamps = st.stamps;
     if (count >= 0) { a.order = st.order + first; a.b = count; }
     // time-split videos (smm_chunk.hip): the launch runs over UNITS -- [the split videos' units | the unsplit videos]; a stream
     // split's first part is exactly the units
@@ -1343,6 +1595,7 @@ extern "C" int smm_decode_f32(const smm_shape *shape, const int64_t *lengths_hos
                               const int64_t *class_map, int64_t *spans, int64_t *labels, double *best, int32_t *n_segs,
                               float *elp32, void *workspace, size_t workspace_bytes, void *stream)
 {
+    g_fb_info = FeedbackInfo{};        // (smm_plan_feedback_info: this thread's last decode call)
     Staged st;
     hipStream_t hs = static_cast<hipStream_t>(stream);
     int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes,
@@ -1359,7 +1612,9 @@ extern "C" int smm_decode_f32(const smm_shape *shape, const int64_t *lengths_hos
     if (!aux) {
         rc = run_emission(shape, st, x, w, cst, inv_var, cons, st.elp, elp32, hs);
         if (rc != SMM_OK) return rc;
-        return run_viterbi(shape, st, st.elp, trans, init, len_scores, endpen, class_map, spans, labels, best, n_segs, hs);
+        rc = run_viterbi(shape, st, st.elp, trans, init, len_scores, endpen, class_map, spans, labels, best, n_segs, hs);
+        if (st.stamps && hipEventRecord(st.done, hs) != hipSuccess) (void)hipGetLastError();
+        return rc;
     }
     // split decode (choose_split): [band tables, emission of the critical videos] on the caller's stream, then their DP
     // there, while the second stream scores and decodes the rest; the caller's stream waits for it at the end
@@ -1386,6 +1641,9 @@ extern "C" int smm_decode_f32(const smm_shape *shape, const int64_t *lengths_hos
     // the join is made even after an error on the way, so that the caller's stream never runs ahead of the second one
     if (hipEventRecord(join, aux) != hipSuccess || hipStreamWaitEvent(hs, join, 0) != hipSuccess) rc2 = SMM_ERR_HIP;
     aux_events_put(dev, fj);
+    // plan feedback: the stamps of this call are whole once `done` is; a measurement taken on the way in is evaluated now
+    if (st.stamps && hipEventRecord(st.done, hs) != hipSuccess) (void)hipGetLastError();
+    if (rc == SMM_OK && rc2 == SMM_OK) feedback_evaluate(st, hs);
     return rc != SMM_OK ? rc : rc2;
 }
 

@@ -71,6 +71,8 @@ struct SmmDpArgs {
     int32_t b_videos;          // ... and the number of real videos (units are entries b_videos.. of `videos`)
     int32_t bt_window;         // Viterbi, kp <= 64: positions per LDS window of the back-trace (0: the general back-trace) ...
     int32_t bt_dyn_bytes;      // ... and the dynamic LDS it needs: (3 W + c + kp) c doubles for the launch's largest c, kp
+    uint64_t *stamps;          // Viterbi, or null: [b][2] wall_clock64() at the start and the end of each video's workgroup, by video
+                               // (the library's pinned host buffer: plan feedback, smm_api.hip)
 };
 
 // One-CU videos on 8 waves: the rank (0..6) that trades places with the chain wave's partner (rank 6, the lightest) so

@@ -458,6 +458,10 @@ smm_viterbi_kernel(SmmDpArgs a)
     __shared__ int sh_guess[SMM_MAX_STATES_DEV + 1];   // back-trace: the predecessor state last seen / expected for each state
 
     if (T <= 0) return;
+    // plan feedback (smm_api.hip): when this video's workgroup started and -- at the kernel's two ends below -- ended, on the
+    // 100 MHz wall clock; one uniform branch per workgroup when nobody asks.  (Here, behind the address arithmetic, and not at the
+    // kernel's first line: a clock read in front of the metadata loads costs every instantiation ten VGPRs.)
+    if (a.stamps && threadIdx.x == 0) a.stamps[2 * (size_t)vid] = wall_clock64();
     if (spans)
         for (int i = threadIdx.x; i <= a.t_max; i += blockDim.x) spans[i] = -1;
     if (threadIdx.x < SMM_MAX_STATES_DEV) {
@@ -1558,6 +1562,7 @@ smm_viterbi_kernel(SmmDpArgs a)
                 }
             }
             if (a.n_segs && threadIdx.x == 0) a.n_segs[vid] = nseg + (no_eos ? 1 : 0);
+            if (a.stamps && threadIdx.x == 0) a.stamps[2 * (size_t)vid + 1] = wall_clock64();
             return;
         }
     }
@@ -1683,6 +1688,7 @@ smm_viterbi_kernel(SmmDpArgs a)
     }
 #endif
     if (a.n_segs && threadIdx.x == 0) a.n_segs[vid] = nseg + (no_eos ? 1 : 0);
+    if (a.stamps && threadIdx.x == 0) a.stamps[2 * (size_t)vid + 1] = wall_clock64();   // (behind the back-trace and this thread's label stores)
 #ifdef SMM_PROFILE_END   // diagnostic build: when did each video's (leader) workgroup finish?  (100 MHz wall clock into best[])
     if (a.best && threadIdx.x == 0) a.best[vid] = (double)wall_clock64();
 #endif

@@ -963,6 +963,42 @@ def dp_timing_read(cap=4096, tagged=False):
     return [float(buf[i]) for i in range(min(n, cap))]
 
 
+def plan_feedback_info():
+    """What plan feedback (smmdp.h: smm_plan_feedback_info) has done to the resident plan the last decode call of this thread ran
+    from: re-plans, the first part's size before and now, the replayed ends (us), the measured (start, end) ticks of each video's
+    DP workgroup -- int64 [b, 2], 100 MHz, or None -- and the plan's launch order.  Copies: they outlive the plan."""
+    import numpy as np
+    info = _lib.SmmPlanFeedbackInfo()
+    _lib.check(_lib.load().smm_plan_feedback_info(ctypes.byref(info)))
+    n = int(info.n_videos)
+    stamps = np.ctypeslib.as_array(info.stamps, shape=(n, 2)).astype(np.int64) if n > 0 and info.stamps else None
+    order = np.ctypeslib.as_array(info.order, shape=(n,)).copy() if n > 0 and info.order else None
+    return {'n_replans': int(info.n_replans), 'n1_before': int(info.n1_before), 'n1_after': int(info.n1_after), 'n_videos': n,
+            'end_before_us': float(info.end_before_us), 'end_after_us': float(info.end_after_us), 'stamps': stamps, 'order': order}
+
+
+def plan_feedback_plan(dur_us, frames, cur_order, cur_n1, n_cu, em_us, force=False):
+    """The feedback planner alone, on the host (smmdp.h: smm_plan_feedback_plan) -> (changed, order, n1, replayed end of the
+    current plan, of the chosen one; us)."""
+    import numpy as np
+    dur = np.ascontiguousarray(dur_us, dtype=np.float64)
+    fr = np.ascontiguousarray(frames, dtype=np.int32)
+    cur = np.ascontiguousarray(cur_order, dtype=np.int32)
+    b = len(dur)
+    if len(fr) != b or len(cur) != b:
+        raise ValueError("dur_us, frames and cur_order must have one entry per video")
+    order = np.zeros(b, dtype=np.int32)
+    n1 = ctypes.c_int32(0)
+    e0, e1 = ctypes.c_double(0.0), ctypes.c_double(0.0)
+    ptr = lambda a: ctypes.c_void_p(a.ctypes.data)
+    rc = _lib.load().smm_plan_feedback_plan(b, int(n_cu), float(em_us), ptr(dur), ptr(fr), ptr(cur), int(cur_n1), 1 if force else 0,
+                                            ptr(order), ctypes.cast(ctypes.byref(n1), ctypes.c_void_p),
+                                            ctypes.cast(ctypes.byref(e0), ctypes.c_void_p), ctypes.cast(ctypes.byref(e1), ctypes.c_void_p))
+    if rc < 0:
+        _lib.check(rc)
+    return bool(rc), order, int(n1.value), float(e0.value), float(e1.value)
+
+
 def time_split_plan(batch, n_cu=256):
     """The time-split plan the library would make for this batch's Viterbi launch on a GPU of ``n_cu`` compute units (host logic
     only: include/smmdp.h, smm_time_split_plan) -> list of (video, first position, positions, positions in front of its own part)."""

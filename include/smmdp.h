@@ -55,6 +55,8 @@
  * State (all of it released by smm_release_cached_plans(); none of it changes a result)
  *   - resident plans: the staged, immutable metadata of a call whose inputs have been seen twice, in library-owned device
  *     memory (at most 64 MB per process; the entry points that take lengths_host / frame_offset_host stage through it);
+ *   - measured times per resident plan of a split smm_decode_f32 ("Plan feedback" below): 16 bytes of pinned host memory
+ *     per video and one event per plan;
  *   - one low-priority stream per device for smm_decode_f32's split decode, and pooled events around it;
  *   - the SMM_* tuning switches, read from the environment once, at first use (smm_env_reload() reads them again);
  *   - smm_dp_timing_*: the event pairs of the measurement aid while it is enabled.
@@ -179,15 +181,53 @@ double smm_band_frame_ns(int n_states);
  * Library state (see "State" above).  smm_release_cached_plans frees every resident plan (all devices), the split
  * decode's second streams and all pooled events, and returns the device bytes it gave back.  The caller's promise: no
  * libsmmdp call is in flight on any stream, and no hipGraph captured from a call will be replayed afterwards (a captured
- * call points at its plan's buffer).  smm_cached_plan_bytes: device bytes currently held by resident plans.
+ * call points at its plan's buffer).  smm_cached_plan_bytes: device bytes currently held by resident plans, plus the
+ * pinned host bytes of their measured times (both are given back, and counted in smm_release_cached_plans' result).
  * smm_env_reload: read the SMM_* tuning switches from the environment again (they are read once, at first use:
- * SMM_SPEC, SMM_NO_SPLIT, SMM_SPLIT_MIN_US / _NS / _MARGIN, SMM_PLAN_CACHE, SMM_NO_BT_WINDOW, SMM_FIT_GRID, SMM_SMALL_WG,
+ * SMM_SPEC, SMM_NO_SPLIT, SMM_SPLIT_MIN_US / _NS / _MARGIN, SMM_PLAN_CACHE, SMM_PLAN_FEEDBACK, SMM_NO_BT_WINDOW, SMM_FIT_GRID, SMM_SMALL_WG,
  * SMM_CHUNK, SMM_CHUNK_P / _WC / _LMIN, SMM_VERBOSE --
  * none of them changes a result; switches that do exist only in -DSMM_DEV builds of the library).
  */
 size_t smm_release_cached_plans(void);
 size_t smm_cached_plan_bytes(void);
 void smm_env_reload(void);
+
+/*
+ * Plan feedback (smm_decode_f32; not part of the reference's interface).  A split decode runs the launch's slowest videos
+ * first, on the caller's stream, and everything else beside them.  Which videos are the slowest the library first takes
+ * from a model of (frames, states); for a RESIDENT plan -- a launch it has seen twice and will see again -- it then measures:
+ * the DP workgroups of a call that runs from (or admits) such a plan write their start and end, ticks of the 100 MHz wall
+ * clock, into pinned host memory the library owns, the call records an event behind its last work, and a later call on the
+ * plan that finds the event complete (it is queried, never waited for) replays the step from the measured times and, where
+ * that ends at least 2 % sooner, moves videos between the two parts and re-orders them -- at most 4 times per plan.  The
+ * plan's new metadata goes into a fresh buffer and the old one stays valid until smm_release_cached_plans, so a call in
+ * flight and a captured graph are never touched; under stream capture nothing is measured and nothing re-planned; plans
+ * with videos split in time or a four-wave tail are left alone.  Results do not change: every video is decoded by the same
+ * kernel on the same inputs, only who starts when differs.  SMM_PLAN_FEEDBACK=0 switches it off (2: re-plan after the
+ * first complete measurement whatever the predicted gain -- tests).
+ *
+ * smm_plan_feedback_info: what feedback has done to the plan the LAST smm_decode_f32 call of the calling thread ran from (all
+ * zero when it ran from none, or since smm_release_cached_plans).  The pointers stay valid until smm_release_cached_plans.
+ */
+typedef struct smm_plan_feedback_info_t {
+    int32_t n_replans;           /* times the plan has been re-planned */
+    int32_t n1_before, n1_after; /* videos of the first part: as first planned, and now */
+    int32_t n_videos;
+    double end_before_us;        /* replayed end of the step under the first plan, from the first measurement */
+    double end_after_us;         /* ... under the current plan: as predicted at the last re-plan, or as replayed from a later measurement */
+    const uint64_t *stamps;      /* [n_videos][2] start and end of each video's workgroup, 100 MHz ticks: the measurement the last
+                                    evaluation was made from (NULL: none yet) */
+    const int32_t *order;        /* [n_videos] the plan's launch order: the first n1_after are the first part */
+} smm_plan_feedback_info_t;
+int smm_plan_feedback_info(smm_plan_feedback_info_t *out);
+
+/* The planner alone, on the host (tests): measured times dur_us[b] and frames[b] by video, the current plan (cur_order[b], its
+ * first cur_n1 videos the first part), the GPU's CU count and the emission pass's time em_us -> the plan feedback would make
+ * (order_out[b], *n1_out) and the replayed ends of both; force != 0: the best plan of the planner's own form even where the
+ * current one replays no later.  Returns 1 when the plan changes, 0 when it stays, or a negative smm_status. */
+int smm_plan_feedback_plan(int b, int n_cu, double em_us, const double *dur_us, const int32_t *frames, const int32_t *cur_order,
+                           int cur_n1, int force, int32_t *order_out, int32_t *n1_out, double *end_current_us,
+                           double *end_chosen_us);
 
 /*
  * Emission scorer.  elp[t][c] = cst[g][c] + sum_d x[t][d]*w[g][c][d] - 0.5*sum_d x[t][d]^2*inv_var[d] (+ cons[t][c])
