@@ -92,15 +92,16 @@ def _entropy_of_scores(scores):
     return float(-(p[keep] * lp[keep]).sum()), lz
 
 
-def _twin_entropy(elp, lengths, trans, init, lens, endpen=None):
+def _twin_entropy(elp, lengths, trans, init, lens, endpen=None, tmax=None):
     """log Z - E[score] per video from the C twin's exact fp64 marginals (EOS mode).  E[score] sums every marginal times its
     potential; the closing term is the last frame's occupancy times the end penalty.  Terms of zero marginal are skipped, and
     so are masked potentials (<= -1e8): their exact marginal is exp(-1e9) = 0, but the twin's occupancies are differences of
-    sums, whose rounding residue (~1e-17) times the mask would add ~1e-8 nats."""
+    sums, whose rounding residue (~1e-17) times the mask would add ~1e-8 nats.  `tmax`: each video keeps that many frames of
+    its padded row, so that the span limit is min(K, tmax) as in its batch (default: its own length)."""
     out = []
     for i, t in enumerate(lengths):
         ep = None if endpen is None else endpen[i:i + 1]
-        e = elp[i:i + 1, :t]
+        e = elp[i:i + 1, :max(t, tmax or t)]
         z, g = F.logz(e, np.array([t]), trans, init, lens, endpen=ep, grad=True)
         kp = g['len'].shape[0]
 

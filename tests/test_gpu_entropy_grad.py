@@ -4,12 +4,18 @@ ops.kl_bwd, SemiMarkovModule.entropy / entropy_packed / cross_entropy / kl_diver
 References are computed here: torch fp64 autograd through -sum p log p, -sum p log q and sum p log(p / q) over every
 segmentation of small lattices (tests/entropy_grad_ref.py), central differences of the C twin's fp64 entropy at real sizes,
 exact invariants of the occurrence counts, closed forms (the uniform lattice, bit-identical sides) and Monte Carlo.  Every seed
-is fixed."""
+is fixed.  Every gradient entry is compared with a reference in two regimes: on the enumerable lattices (3 states, K <= 4, T <= 7:
+each kernel's work split in its first lane, slab, block and slice only) and at the mid sizes (up to 32 states, 300 length rows
+and 330 frames, packed groups: every split crossed, against the forward recursion of tests/entropy_grad_dp_ref.py, which
+tests/test_entropy_grad_dp_ref_host.py pins on the CPU); the real sizes are covered by invariants, values and one directional
+derivative per table."""
 import numpy as np
 import pytest
 import torch
 
+import entropy_grad_cases as C
 import entropy_grad_ref as R
+from entropy_grad_cases import SMALL, _small_case
 from oracle import dense_ref as O
 from oracle import factored as F
 from test_gpu_entropy import _batch_tables, _corpus, _features, _module, _ref_params, _twin_entropy
@@ -59,62 +65,6 @@ def _close(got, ref, what, bar=1e-4):
 
 
 # ----------------------------------------------------------------------------------------------- 1. enumerable lattices
-SMALL = [
-    # (K, add_eos, masks, extra allowed ends, narration constraints)
-    (2, True, False, False, False),
-    (4, True, False, False, False),
-    (4, False, False, False, False),
-    (2, False, False, False, False),
-    (4, True, True, False, False),
-    (4, False, True, False, False),
-    (4, True, True, True, False),
-    (4, True, False, False, True),
-    (3, False, True, False, True),
-]
-
-
-def _small_tables(k, add_eos, masked, additional, narration, seed, like=None, shift=None):
-    """One small padded batch of 3 states and 3 videos: (elp_bt, lengths, trans, init, lens, endpen) as numpy.  `like` with
-    `shift`: the same tables with elp moved by shift x N(0, 1) (a q near p); `like` alone: the same masks, other values."""
-    rng = np.random.default_rng(seed)
-    c, lengths = 3, [7, 5, 6]
-    b, tmax = len(lengths), max(lengths)
-    if like is not None and shift is not None:
-        elp = like[0] + shift * rng.normal(size=like[0].shape) * (like[0] > -1e8)
-        return (elp,) + tuple(like[1:])
-    lsm = lambda a, ax: a - np.log(np.exp(a - a.max(ax, keepdims=True)).sum(ax, keepdims=True)) - a.max(ax, keepdims=True)
-    trans = lsm(rng.normal(size=(c, c)), 0)
-    init = lsm(rng.normal(size=c), 0)
-    lens = np.zeros((k, c))
-    lens[1:] = lsm(rng.normal(size=(k - 1, c)), 0)
-    elp = rng.normal(size=(b, tmax, c)) * 1.5
-    for i, t in enumerate(lengths):
-        elp[i, t:] = 0.0
-    if masked:
-        trans[2, 0] = trans[0, 2] = -1e9
-        init[2] = -1e9
-    if narration:
-        elp[0, 2, 1] = -1e9
-        elp[1, 0:2, 2] = -1e9
-    ep = None
-    if add_eos and (masked or additional):
-        ep = np.zeros((b, c))
-        ep[:, 0] = -1e9
-        if additional:
-            ep[1, 0] = 0.0
-    return elp, lengths, trans, init, lens, ep
-
-
-def _small_case(k, add_eos, masked, additional, narration, q_kind):
-    seed = 500 + k + 10 * add_eos + 20 * masked + 40 * additional + 80 * narration
-    p = _small_tables(k, add_eos, masked, additional, narration, seed)
-    if q_kind == 'draw':
-        q = _small_tables(k, add_eos, masked, additional, narration, seed + 1)
-    else:
-        q = _small_tables(k, add_eos, masked, additional, narration, seed + 2, like=p, shift=1e-3)
-    return p, q
-
-
 @pytest.mark.parametrize('q_kind', ['draw', 'near'])
 @pytest.mark.parametrize('k,add_eos,masked,additional,narration', SMALL)
 def test_exact_on_enumerable_lattices(k, add_eos, masked, additional, narration, q_kind):
@@ -142,6 +92,128 @@ def test_exact_on_enumerable_lattices(k, add_eos, masked, additional, narration,
         assert np.isfinite(v).all()
         np.testing.assert_allclose(v[:, 0], vals, rtol=1e-6, atol=1e-6)
         np.testing.assert_allclose(v[:, 1], vals, rtol=1e-6, atol=1e-6)
+
+
+# ------------------------------------------------------------------------------------ 1b. mid sizes, entry by entry
+# The bar is the stated accuracy of the log-partition path whose histories (smm_logz_kernel, fp32 sums) the gradient is read
+# from: 1e-4, _close's default.  Measured on one MI355X, worst |error| / max(1, max |ref|) over the four tables, p's side (the
+# kernels) / q's side (mu_q - mu_p), for entropy, cross-entropy, KL:
+#   k_trips            2.9e-6        3.4e-6 / 3.9e-6    1.9e-6 / 3.9e-6
+#   k_blocks           5.5e-6        6.6e-6 / 1.1e-5    1.5e-5 / 1.1e-5
+#   states_32          3.3e-6        2.0e-6 / 1.7e-6    1.0e-6 / 1.7e-6
+#   states_23_no_eos   6.4e-7        2.4e-7 / 7.0e-7    4.6e-7 / 7.0e-7
+#   packed_groups      1.2e-6        3.0e-6 / 4.3e-6    4.2e-6 / 4.3e-6
+# (smm_logz_bwd_f64's marginals alone against the C twin's on the same lattices: 1.2e-6, 4.0e-6, 1.5e-6, 5.8e-7, 8.0e-7; the
+# kernel's two values are within 1.8e-7 of the reference value, smm_entropy_f64 / smm_kl_f64 within 2.9e-6.)  No case needs a
+# bar of its own.
+MID_BAR = 1e-4
+
+
+def _mid_launch(case, side):
+    """(Batch, elp, trans, init, len, endpen) on the device and the rows of each video's frames in the kernels' elp layout: a
+    padded single-group batch without per-video arguments, or (packed_groups) ops.Batch with frame_offset, group and kp."""
+    from action_segmentation_amd import ops
+    elp, trans, init, lens, ep = case[side]
+    lengths, off = case['lengths'], case['frame_offset']
+    if case['single']:
+        b, tmax, c = len(lengths), max(lengths), case['c_max']
+        pad = np.zeros((b, tmax, c))
+        for i, t in enumerate(lengths):
+            pad[i, :t] = elp[off[i]:off[i] + t]
+        rows = [np.arange(i * tmax, i * tmax + t) for i, t in enumerate(lengths)]
+        return _batch_tables(pad, lengths, trans[0], init[0], lens[0], ep, no_eos=case['no_eos']), rows
+    batch = ops.Batch(lengths, case['n_states'], case['k'], c_max=case['c_max'], frame_offset=off, group=case['group'],
+                      kp=case['kp'], total_frames=case['total_frames'], no_eos=case['no_eos'])
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64).to(DEV).contiguous()
+    return (batch, t(elp), t(trans), t(init), t(lens), None if ep is None else t(ep)), [np.arange(o, o + n) for o, n in
+                                                                                         zip(off, lengths)]
+
+
+def _entries(got, ref, case, rows, what, bar, failures):
+    """Every entry of every table: |got - ref| <= bar max(1, max |ref|); a table beyond it adds a line to `failures` that names
+    its worst entry's index (elp: video, frame, state; the tables: group, [row,] state).  Returns the worst ratio."""
+    worst = 0.0
+    for k in TABLES:
+        a = got[k].detach().double().cpu()
+        if k == 'elp':
+            r = torch.cat([ref[k][o:o + n] for o, n in zip(case['frame_offset'], case['lengths'])])
+            a = a.reshape(-1, r.shape[1])[np.concatenate(rows)]
+        else:
+            r = ref[k]
+            a = a.reshape(r.shape)
+        err = (a - r).abs()
+        scale = max(1.0, float(r.abs().max()))
+        at = np.unravel_index(int(err.argmax()), err.shape)
+        where = tuple(int(v) for v in at)
+        if k == 'elp':
+            ends = np.cumsum(case['lengths'])
+            vid = int(np.searchsorted(ends, where[0], side='right'))
+            where = (vid, where[0] - int(ends[vid] - case['lengths'][vid]), where[1])
+        ratio = float(err.max()) / scale
+        worst = max(worst, ratio)
+        if not ratio <= bar:
+            failures.append('%s: g_%s%s is %.12g, reference %.12g: |error| / max(1, max |ref|) %.3g > %.3g' % (
+                what, k, list(where), float(a[at]), float(r[at]), ratio, bar))
+    return worst
+
+
+def _padding_is_zero(g, case, rows, what):
+    """Exactly 0.0: frames no video covers, the states a group does not have (columns of elp, init and len, rows and columns of
+    trans), len's row 0 and its rows from the group's largest span limit on, the frames of a video of upstream weight 0."""
+    cm = case['c_max']
+    ge = g['elp'].detach().cpu().reshape(-1, cm)
+    covered = np.zeros(ge.shape[0], bool)
+    covered[np.concatenate(rows)] = True
+    assert (ge[~covered] == 0.0).all(), (what, 'elp rows of no video')
+    for i, r in enumerate(rows):
+        c = case['n_states'][case['group'][i]]
+        assert (ge[r][:, c:] == 0.0).all(), (what, 'elp', i, 'padded states')
+        if case['up'][i] == 0.0:
+            assert (ge[r] == 0.0).all(), (what, 'elp', i, 'upstream weight 0')
+    for gi, c in enumerate(case['n_states']):
+        tr, ini, ln = (g[k].detach().cpu()[gi] for k in ('trans', 'init', 'len'))
+        assert (tr[c:] == 0.0).all() and (tr[:, c:] == 0.0).all(), (what, 'trans', gi)
+        assert (ini[c:] == 0.0).all(), (what, 'init', gi)
+        kmax = max(kp for kp, gv in zip(case['kp'], case['group']) if gv == gi)
+        assert (ln[:, c:] == 0.0).all() and (ln[0] == 0.0).all() and (ln[kmax:] == 0.0).all(), (what, 'len', gi)
+
+
+@pytest.mark.parametrize('name', list(C.MID))
+def test_entry_by_entry_at_mid_sizes(name):
+    """Every mode, both sides, every entry against the fp64 forward recursion of tests/entropy_grad_dp_ref.py at sizes that
+    cross each kernel's work split (entropy_grad_cases.MID says which): <= MID_BAR = 1e-4 max(1, max |ref|) per table; the kernel's
+    two values within 1e-6, smm_entropy_f64 / smm_kl_f64 within 1e-4 of the reference value; padding exactly 0."""
+    from action_segmentation_amd import ops
+    case, ref = C.mid_case(name), C.mid_reference(name)
+    (batch, *tp), rows = _mid_launch(case, 'p')
+    (_, *tq), _ = _mid_launch(case, 'q')
+    upd = torch.tensor(case['up'], dtype=torch.float64, device=DEV)
+    failures = []
+    for mode in ('entropy', 'cross_entropy', 'kl'):
+        vals, rp, rq = ref[mode]
+        P, Q = _side(batch, *tp), _side(batch, *tq, both=False)
+        if mode == 'entropy':
+            direct = ops.entropy(batch, *tp[:4], P[5], endpen=tp[4], ws=P[6], with_backward=True)
+        else:
+            kl, xe = ops.kl(batch, P, Q, with_backward=True, want_cross_entropy=True)
+            direct = xe if mode == 'cross_entropy' else kl
+        g, gq = _grads(batch, P, Q, mode, upd)
+        assert ops.error_flag(batch, ws=P[6]) == 0
+        v, direct = g['value'].cpu().numpy(), direct.cpu().numpy()
+        scale = np.maximum(1.0, np.abs(vals))
+        rv = max(float((np.abs(v[:, j] - vals) / scale).max()) for j in (0, 1))
+        rd = float((np.abs(direct - vals) / scale).max())
+        print('mid %s %s: value %s; value_out off by %.3g, the value kernel by %.3g' % (name, mode, vals, rv, rd))
+        w = _entries(g, rp, case, rows, (name, mode, 'p'), MID_BAR, failures)
+        wq = 0.0 if gq is None else _entries(gq, rq, case, rows, (name, mode, 'q'), MID_BAR, failures)
+        WORST[('mid', name, mode)] = (w, wq)
+        print('mid %s %s: worst |error| / max(1, max |ref|) %.3g (p), %.3g (q)' % (name, mode, w, wq))
+        if not (np.isfinite(v).all() and rv <= 1e-6):
+            failures.append('%s %s: value_out %s, reference %s: off by %.3g > 1e-6' % (name, mode, v.tolist(), vals, rv))
+        if not rd <= 1e-4:
+            failures.append('%s %s: the value kernel gives %s, reference %s: off by %.3g > 1e-4' % (name, mode, direct, vals, rd))
+        _padding_is_zero(g, case, rows, (name, mode))
+    assert not failures, '\n'.join(failures)
 
 
 # ------------------------------------------------------------------------------------------------------- 2. closed forms
