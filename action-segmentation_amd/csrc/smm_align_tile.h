@@ -1,7 +1,8 @@
-// smm_align_tile.h -- what the two transcript kernels share (smm_align.hip: the best alignment; smm_align_logz.hip: the sum over
-// all alignments): the tile geometry of a column, the cells of a column that lie on a complete alignment, the prefix-sum phase,
-// and the tests on the bits.  The including unit chooses its tile: SMM_ALIGN_THREADS threads, SMM_ALIGN_R positions per thread
-// (odd: the threads' h reads are R doubles apart, which spreads a half-wave over all 64 banks).
+// smm_align_tile.h -- what the transcript kernels share (smm_align.hip: the best alignment; smm_align_opt.hip: the same with
+// optional entries; smm_align_logz.hip: the sum over all alignments): the tile geometry of a column, the cells of a column
+// that lie on a complete alignment, the prefix-sum phase, and the tests on the bits.  The including unit chooses its tile:
+// SMM_ALIGN_THREADS threads, SMM_ALIGN_R positions per thread (odd: the threads' h reads are R doubles apart, which spreads a
+// half-wave over all 64 banks).
 #pragma once
 #include "smm_device.h"
 #include "../../include/smmdp.h"

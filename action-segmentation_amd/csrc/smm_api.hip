@@ -2029,13 +2029,14 @@ extern "C" int smm_mbr_f64(const smm_shape *shape, const int64_t *lengths_host, 
 
 // ------------------------------------------------------------------------------------------------ forced alignment
 // Behind the plan's workspace: the transcript offsets, the offsets of the videos' h columns and the launch order (uploaded
-// per call: they are no part of a resident plan), then the h columns, M (T + 1) doubles per video.  cum uses the history area.
+// per call: they are no part of a resident plan), then the columns, (M + extra) (T + 1) doubles per video: M h columns, and
+// for the alignment with optional entries c_max columns of running maxima.  cum uses the history area.
 struct AlignLayout {
     size_t o_toff, o_hoff, o_order, meta_end, o_hcols, total;
 };
 
 // SMM_OK, or the refusal; everything here is host arithmetic on the caller's arrays
-static int align_layout(const smm_shape *s, const int64_t *lengths, const int64_t *toff, AlignLayout *lo)
+static int align_layout(const smm_shape *s, const int64_t *lengths, const int64_t *toff, size_t extra, AlignLayout *lo)
 {
     if (!shape_ok(s) || !lengths || !toff) return SMM_ERR_ARG;
     if ((s->flags & SMM_SHAPE_NO_EOS) || !limits_ok(s)) return SMM_ERR_UNSUPPORTED;
@@ -2046,7 +2047,7 @@ static int align_layout(const smm_shape *s, const int64_t *lengths, const int64_
         const int64_t m = toff[i + 1] - toff[i];
         if (m < 1) return SMM_ERR_ARG;                      // non-monotone offsets, or an empty transcript
         too_long |= m > SMM_MAX_TRANSCRIPT;
-        cells += (size_t)m * (size_t)(lengths[i] + 1);
+        cells += ((size_t)m + extra) * (size_t)(lengths[i] + 1);
     }
     if (too_long) return SMM_ERR_UNSUPPORTED;
     const size_t b = (size_t)s->b;
@@ -2060,29 +2061,24 @@ static int align_layout(const smm_shape *s, const int64_t *lengths, const int64_
     return SMM_OK;
 }
 
-extern "C" size_t smm_align_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host,
-                                            const int64_t *transcript_offset_host)
-{
-    AlignLayout lo;
-    return align_layout(shape, lengths_host, transcript_offset_host, &lo) == SMM_OK ? lo.total : 0;
-}
-
-extern "C" int smm_align_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
-                             const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
-                             const double *elp, const double *trans, const double *init, const double *len_scores,
-                             const double *endpen, const int64_t *class_map, const int32_t *transcript,
-                             const int64_t *transcript_offset_host, int64_t *spans, int64_t *labels, double *best,
-                             int32_t *n_segs, void *workspace, size_t workspace_bytes, void *stream)
+// Both alignment entry points up to their launch: the refusals, the staging, this call's metadata, the kernel arguments.
+// `extra`: columns per video behind its h columns.
+static int align_prepare(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                         const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                         const double *elp, const double *trans, const double *init, const double *len_scores,
+                         const double *endpen, const int64_t *class_map, const int32_t *transcript,
+                         const int64_t *transcript_offset_host, int64_t *spans, int64_t *labels, double *best,
+                         int32_t *n_segs, void *workspace, size_t workspace_bytes, hipStream_t hs, size_t extra,
+                         SmmAlignArgs *out)
 {
     if (!shape_ok(shape) || !lengths_host || !frame_offset_host || !n_states_host || !transcript_offset_host) return SMM_ERR_ARG;
     if (!elp || !trans || !init || !len_scores || !transcript || !workspace) return SMM_ERR_ARG;
     if (!spans && !labels && !best && !n_segs) return SMM_ERR_ARG;
     AlignLayout lo;
-    int rc = align_layout(shape, lengths_host, transcript_offset_host, &lo);
+    int rc = align_layout(shape, lengths_host, transcript_offset_host, extra, &lo);
     if (rc != SMM_OK) return rc;
     if (workspace_bytes < lo.total) return SMM_ERR_WORKSPACE;
     Staged st;
-    hipStream_t hs = static_cast<hipStream_t>(stream);
     rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes, hs, &st);
     if (rc != SMM_OK) return rc;
     // this call's own metadata: offsets, and the launch order -- most lattice cells (T x M x span limit) first
@@ -2098,7 +2094,7 @@ extern "C" int smm_align_f64(const smm_shape *shape, const int64_t *lengths_host
         const int k = kp_host ? kp_host[i] : std::min<int>(shape->k_rows, shape->t_max);
         h_toff[i] = transcript_offset_host[i];
         h_hoff[i] = cells;
-        cells += m * (lengths_host[i] + 1);
+        cells += (m + (int64_t)extra) * (lengths_host[i] + 1);
         work[i] = (double)m * (double)lengths_host[i] * (double)std::min<int64_t>(k, lengths_host[i]);
     }
     h_toff[b] = transcript_offset_host[b];
@@ -2116,7 +2112,61 @@ extern "C" int smm_align_f64(const smm_shape *shape, const int64_t *lengths_host
     a.hist = st.hist; a.hcols = reinterpret_cast<double *>(base + lo.o_hcols);
     a.spans = spans; a.labels = labels; a.best = best; a.n_segs = n_segs; a.err = st.err;
     a.c_max = shape->c_max; a.k_rows = shape->k_rows; a.t_max = shape->t_max; a.b = b;
+    *out = a;
+    return SMM_OK;
+}
+
+extern "C" size_t smm_align_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host,
+                                            const int64_t *transcript_offset_host)
+{
+    AlignLayout lo;
+    return align_layout(shape, lengths_host, transcript_offset_host, 0, &lo) == SMM_OK ? lo.total : 0;
+}
+
+extern "C" int smm_align_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                             const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                             const double *elp, const double *trans, const double *init, const double *len_scores,
+                             const double *endpen, const int64_t *class_map, const int32_t *transcript,
+                             const int64_t *transcript_offset_host, int64_t *spans, int64_t *labels, double *best,
+                             int32_t *n_segs, void *workspace, size_t workspace_bytes, void *stream)
+{
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    SmmAlignArgs a;
+    const int rc = align_prepare(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp, trans, init,
+                                 len_scores, endpen, class_map, transcript, transcript_offset_host, spans, labels, best, n_segs,
+                                 workspace, workspace_bytes, hs, 0, &a);
+    if (rc != SMM_OK) return rc;
     smm_launch_align(a, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
+// ... with optional entries (smm_align_opt.hip): the running maxima take c_max columns per video more
+extern "C" size_t smm_align_opt_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host,
+                                                const int64_t *transcript_offset_host)
+{
+    AlignLayout lo;
+    if (!shape_ok(shape)) return 0;
+    return align_layout(shape, lengths_host, transcript_offset_host, (size_t)shape->c_max, &lo) == SMM_OK ? lo.total : 0;
+}
+
+extern "C" int smm_align_opt_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                 const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                 const double *elp, const double *trans, const double *init, const double *len_scores,
+                                 const double *endpen, const int64_t *class_map, const int32_t *transcript,
+                                 const uint8_t *optional, const int64_t *transcript_offset_host, int64_t *spans,
+                                 int64_t *labels, double *best, int32_t *n_segs, int32_t *used, void *workspace,
+                                 size_t workspace_bytes, void *stream)
+{
+    if (!optional) return SMM_ERR_ARG;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    SmmAlignArgs a;
+    const int rc = align_prepare(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp, trans, init,
+                                 len_scores, endpen, class_map, transcript, transcript_offset_host, spans, labels, best, n_segs,
+                                 workspace, workspace_bytes, hs, shape_ok(shape) ? (size_t)shape->c_max : 0, &a);
+    if (rc != SMM_OK) return rc;
+    a.optional = optional; a.used = used;
+    smm_launch_align_opt(a, hs);
     SMM_HIP(hipGetLastError());
     return SMM_OK;
 }

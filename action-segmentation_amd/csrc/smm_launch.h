@@ -230,8 +230,9 @@ struct SmmMbrArgs {
 };
 void smm_launch_mbr(const SmmMbrArgs &a, hipStream_t stream);
 
-// forced alignment to a given transcript (smm_align.hip).  cum sits class-major [C][T+1] at the video's hist_off; the h columns
-// [M][T+1] of video i at hcols + hoff[i]
+// forced alignment to a given transcript (smm_align.hip; with optional entries: smm_align_opt.hip).  cum sits class-major
+// [C][T+1] at the video's hist_off; the h columns [M][T+1] of video i at hcols + hoff[i], smm_align_opt's running maxima
+// [c_max][T+1] behind them
 struct SmmAlignArgs {
     const SmmVideo *videos;
     const int32_t *order;      // [b] workgroup -> video (most lattice cells first)
@@ -243,6 +244,7 @@ struct SmmAlignArgs {
     const double *endpen;      // [b][c_max] or null
     const int64_t *class_map;  // [g][c_max+1] or null
     const int32_t *transcript; // [toff[b]] local state ids (caller's; checked against n_states on load)
+    const uint8_t *optional;   // [toff[b]] non-zero: the entry may be left out            (smm_align_opt only, as `used`)
     const int64_t *toff;       // [b + 1]
     const int64_t *hoff;       // [b] doubles
     double *hist;              // the workspace's history area
@@ -251,10 +253,12 @@ struct SmmAlignArgs {
     int64_t *labels;           // [total_frames] or null
     double *best;              // [b] or null
     int32_t *n_segs;           // [b] or null
+    int32_t *used;             // [toff[b]] or null: 1 for an entry that got a segment
     int32_t *err;              // sticky error word
     int32_t c_max, k_rows, t_max, b;
 };
 void smm_launch_align(const SmmAlignArgs &a, hipStream_t stream);
+void smm_launch_align_opt(const SmmAlignArgs &a, hipStream_t stream);
 
 // transcript likelihood and its gradient (smm_align_logz.hip).  cum as for the alignment; the columns of video i at
 // cols + hoff[i]: h | gam | q, each [M][T+1]; its part of g_len at part + poff[i]: [min(k_rows, T + 1)][c_max]

@@ -683,6 +683,66 @@ def align_workspace_bytes(batch, transcript_offset):
     return n
 
 
+def align_opt_workspace_bytes(batch, transcript_offset):
+    """Bytes of workspace smm_align_opt_f64 needs for this batch and these transcript offsets (int64 [b + 1]; host only)."""
+    off = np.ascontiguousarray(np.asarray(transcript_offset, dtype=np.int64).reshape(-1))
+    if off.shape[0] != batch.b + 1:
+        raise ValueError("align_opt_workspace_bytes: b + 1 transcript offsets expected")
+    n = _lib.load().smm_align_opt_workspace_bytes(ctypes.byref(batch.shape), ctypes.c_void_p(batch.lengths.ctypes.data),
+                                                  ctypes.c_void_p(off.ctypes.data))
+    if n == 0:
+        raise _lib.SmmError("libsmmdp: invalid batch shape or transcript offsets for the alignment (add_eos=True only, "
+                            "1..%d entries per video)" % MAX_TRANSCRIPT)
+    return n
+
+
+def _optional_flags(off, optional):
+    """One boolean sequence per video, as long as its transcript -> uint8 [sum M] on the host."""
+    b = off.shape[0] - 1
+    if len(optional) != b:
+        raise ValueError("align: %d sequences of optional flags for %d videos" % (len(optional), b))
+    flags = [np.asarray(f.detach().cpu() if torch.is_tensor(f) else f).reshape(-1) != 0 for f in optional]
+    for i, f in enumerate(flags):
+        if f.size != off[i + 1] - off[i]:
+            raise ValueError("align: %d optional flags for the %d transcript entries of video %d" % (f.size, off[i + 1] - off[i], i))
+    return np.ascontiguousarray(np.concatenate(flags).astype(np.uint8))
+
+
+def _align_call(batch, elp, trans, init, len_scores, transcripts, flags, endpen, class_map, ws, want_spans, want_labels,
+                want_used, staged=None):
+    """smm_align_f64 (``flags`` None) or smm_align_opt_f64 (``flags``: one boolean sequence per video).  ``staged``: the ids and
+    flags on the device, from an earlier call."""
+    lib = _lib.load()
+    dev = elp.device
+    f64 = torch.float64
+    ids, off = _transcript_arrays(batch, transcripts)
+    flags = None if flags is None else _optional_flags(off, flags)
+    need = align_workspace_bytes(batch, off) if flags is None else align_opt_workspace_bytes(batch, off)
+    spans, labels, best, n_segs = _device_outputs(batch, dev, want_spans, want_labels)
+    ws = _own_workspace(ws, need, dev)
+    ids_dev = torch.from_numpy(ids).to(dev) if staged is None else staged[0]
+    tables = (_dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
+              _dev(endpen, f64, 'endpen'), _dev(class_map, torch.int64, 'class_map'), _dev(ids_dev, torch.int32, 'transcript'))
+    outs = (_dev(spans, torch.int64, 'spans'), _dev(labels, torch.int64, 'labels'), _dev(best, f64, 'best'),
+            _dev(n_segs, torch.int32, 'n_segs'))
+    if flags is None:
+        _lib.check(lib.smm_align_f64(*batch.head(), *tables, ctypes.c_void_p(off.ctypes.data), *outs, *_ws_args(ws), _stream()))
+        return dict(spans=spans, labels=labels, best=best, n_segs=n_segs, _err=_err_copy(batch, ws), _keep=(ids_dev, ws))
+    if staged is not None:
+        flags_dev = staged[1]
+        if staged[0].shape[0] != ids.shape[0] or flags_dev.shape[0] != flags.shape[0]:
+            raise ValueError("align_optional: staged ids and flags of another transcript")
+    else:
+        flags_dev = torch.from_numpy(flags).to(dev)
+    used = torch.empty(ids.shape[0], dtype=torch.int32, device=dev) if want_used else None
+    _lib.check(lib.smm_align_opt_f64(*batch.head(), *tables, _dev(flags_dev, torch.uint8, 'optional'),
+                                     ctypes.c_void_p(off.ctypes.data), *outs, _dev(used, torch.int32, 'used'), *_ws_args(ws),
+                                     _stream()))
+    return dict(spans=spans, labels=labels, best=best, n_segs=n_segs,
+                used=None if used is None else list(torch.split(used, np.diff(off).tolist())),
+                _err=_err_copy(batch, ws), _staged=(ids_dev, flags_dev), _keep=(ws,))
+
+
 def align(batch, elp, trans, init, len_scores, transcripts, endpen=None, class_map=None, ws=None, want_spans=True,
           want_labels=True):
     """Forced alignment (smm_align_f64): per video the best segmentation whose class sequence is its transcript -- a sequence
@@ -692,22 +752,25 @@ def align(batch, elp, trans, init, len_scores, transcripts, endpen=None, class_m
     (global ids, -1 on frames no video covers) or None, best fp64 [b], n_segs int32 [b] (the transcript's length)).  A video
     whose transcript cannot be laid over its frames (more entries than frames, too few for the span limit, an id that is no
     state of the video) gets best -inf, n_segs 0, spans and labels -1.  ``ws``: a uint8 workspace of at least
-    ``align_workspace_bytes`` (default: a private one for this call)."""
-    lib = _lib.load()
-    dev = elp.device
-    f64 = torch.float64
-    ids, off = _transcript_arrays(batch, transcripts)
-    need = align_workspace_bytes(batch, off)
-    spans, labels, best, n_segs = _device_outputs(batch, dev, want_spans, want_labels)
-    ws = _own_workspace(ws, need, dev)
-    ids_dev = torch.from_numpy(ids).to(dev)
-    _lib.check(lib.smm_align_f64(
-        *batch.head(), _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'),
-        _dev(len_scores, f64, 'len_scores'), _dev(endpen, f64, 'endpen'), _dev(class_map, torch.int64, 'class_map'),
-        _dev(ids_dev, torch.int32, 'transcript'), ctypes.c_void_p(off.ctypes.data), _dev(spans, torch.int64, 'spans'),
-        _dev(labels, torch.int64, 'labels'), _dev(best, f64, 'best'), _dev(n_segs, torch.int32, 'n_segs'),
-        *_ws_args(ws), _stream()))
-    return dict(spans=spans, labels=labels, best=best, n_segs=n_segs, _err=_err_copy(batch, ws), _keep=(ids_dev, ws))
+    ``align_workspace_bytes`` (default: a private one for this call).  Optional entries: ``align_optional``."""
+    return _align_call(batch, elp, trans, init, len_scores, transcripts, None, endpen, class_map, ws, want_spans, want_labels,
+                       False)
+
+
+def align_optional(batch, elp, trans, init, len_scores, transcripts, optional, endpen=None, class_map=None, ws=None,
+                   want_spans=True, want_labels=True, want_used=False, staged=None):
+    """``align`` with optional transcript entries (smm_align_opt_f64, also when no flag is set): ``optional`` is one boolean
+    sequence per video, as long as its transcript; the flagged entries may be left out, and the result is the best over every
+    subset of them.  ValueError when their count or a length differs from the transcripts'.  Returns ``align``'s dict, n_segs
+    counting the entries that got a segment, plus ``used``: None, or with ``want_used`` a list of per-video int32 views of one
+    device tensor, 1 for an entry that has a segment, else 0.  More MANDATORY entries than frames is what leaves no alignment.
+    ``ws``: at least ``align_opt_workspace_bytes``.  ``staged``: the ``_staged`` entry of an earlier call's result for the same
+    transcripts and flags -- the ids and flags on the device: the call then copies nothing from the host itself and can be
+    captured into a graph (keep that earlier result alive as long as the graph)."""
+    if optional is None:
+        raise ValueError("align_optional: one sequence of flags per video expected (no flags: align)")
+    return _align_call(batch, elp, trans, init, len_scores, transcripts, optional, endpen, class_map, ws, want_spans, want_labels,
+                       want_used, staged)
 
 
 ALIGN_LOGZ_TILE = _lib.ALIGN_LOGZ_TILE

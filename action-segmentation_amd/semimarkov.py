@@ -370,11 +370,18 @@ class SemiMarkovModel(object):
                 assert self.model.n_classes not in predictions[video], "predictions should not contain EOS"
         return predictions
 
-    def align(self, data, transcripts_by_video, shard=None):
+    def align(self, data, transcripts_by_video, shard=None, *, optional_by_video=None, optional_classes=None):
         """Forced alignment of every video of ``data`` to its transcript: ``transcripts_by_video[name]`` is the video's class
         sequence in global class ids, one entry per segment.  Returns what ``predict`` returns, ``{video: int64[T]}``: the frame
         labels of the best segmentation with that class sequence (-1 on a video whose transcript cannot be laid over its
-        frames).  One emission launch and one alignment launch on the packed corpus (``SemiMarkovModule.align_packed``)."""
+        frames).  One emission launch and one alignment launch on the packed corpus (``SemiMarkovModule.align_packed``).
+
+        Entries may be optional: the result is then the best segmentation whose class sequence is the transcript with any
+        subset of the optional entries left out.  ``optional_by_video[name]``: one boolean per entry of the video's
+        transcript; or ``optional_classes``: an iterable of global class ids, every entry of such a class being optional
+        (a CrossTask task ``bg, step_1, bg, ...``: pass the background ids).  ValueError when both are given."""
+        if optional_by_video is not None and optional_classes is not None:
+            raise ValueError("align: give optional_by_video or optional_classes, not both")
         self.model.eval()
         pc = self.prepare(data, shard=shard)
         if pc.n_videos == 0:
@@ -382,7 +389,18 @@ class SemiMarkovModel(object):
         missing = [name for name in pc.video_names if name not in transcripts_by_video]
         if missing:
             raise ValueError("align: no transcript for video %r" % (missing[0],))
-        labels, _ = self.model.align_packed(pc, [transcripts_by_video[name] for name in pc.video_names])
+        transcripts = [transcripts_by_video[name] for name in pc.video_names]
+        optional = None
+        if optional_classes is not None:
+            classes = np.array(sorted(set(int(c) for c in optional_classes)), np.int64)
+            optional = [np.isin(np.asarray(t.cpu() if torch.is_tensor(t) else t, dtype=np.int64).reshape(-1), classes)
+                        for t in transcripts]
+        elif optional_by_video is not None:
+            missing = [name for name in pc.video_names if name not in optional_by_video]
+            if missing:
+                raise ValueError("align: no optional flags for video %r" % (missing[0],))
+            optional = [optional_by_video[name] for name in pc.video_names]
+        labels, _ = self.model.align_packed(pc, transcripts, optional=optional)
         lab = labels.cpu().numpy()
         assert lab.size == 0 or int(lab.max()) < self.model.n_classes, "alignments should not contain EOS"
         return {name: lab[off:off + t] for name, off, t in zip(pc.video_names, pc.frame_offset, pc.lengths)}

@@ -141,9 +141,12 @@ def _kbest(r, k, want_spans):
     return _paths(r['batch'], out, want_spans), out['score']
 
 
-def _align(r, local, want_spans):
-    out = ops.align(r['batch'], r['elp'], r['trans'], r['init'], r['len'], local, endpen=r['endpen'], class_map=r['class_map'],
-                    want_spans=want_spans, want_labels=not want_spans)
+def _align(r, local, want_spans, optional=None):
+    kw = dict(endpen=r['endpen'], class_map=r['class_map'], want_spans=want_spans, want_labels=not want_spans)
+    if optional is None:
+        out = ops.align(r['batch'], r['elp'], r['trans'], r['init'], r['len'], local, **kw)
+    else:
+        out = ops.align_optional(r['batch'], r['elp'], r['trans'], r['init'], r['len'], local, optional, **kw)
     return _paths(r['batch'], out, want_spans), out['best']
 
 
@@ -1080,7 +1083,7 @@ class SemiMarkovModule(nn.Module):
 
     @torch.no_grad()
     def align(self, features, lengths, valid_classes_per_instance, transcripts, add_eos=True,
-              additional_allowed_ends_per_instance=None, constraints=None):
+              additional_allowed_ends_per_instance=None, constraints=None, optional=None):
         """Forced alignment of a zero-padded single-task batch (argument conventions of ``viterbi``): ``transcripts[i]`` is the
         class sequence of video i in GLOBAL class ids, one entry per segment (consecutive repeats are two segments); the result
         is the best segmentation with exactly that sequence.  One emission launch, one alignment launch (smm_align_f64).
@@ -1088,7 +1091,11 @@ class SemiMarkovModule(nn.Module):
         Returns (pred_spans, scores): pred_spans CPU int64 b x (Tmax+1) in ``viterbi``'s format, scores fp64 b on the device.
         A transcript that cannot be laid over its video (more entries than frames, or too few for the span limit) gives a row
         of -1 and score -inf.  ValueError for an id that is not valid for the video, an empty transcript or add_eos=False.
-        Raises SmmError when a NaN reached the DP.  No autograd."""
+        Raises SmmError when a NaN reached the DP.  No autograd.
+
+        ``optional``: one boolean sequence per video, as long as its transcript; the flagged entries may be left out and the
+        result is the best over every subset of them (smm_align_opt_f64; ``ops.align_optional``).  ValueError when their count or a
+        length differs from the transcripts'."""
         if not add_eos:
             raise ValueError("align: add_eos=False is not supported")
         self._require_device(features, 'align')
@@ -1097,21 +1104,21 @@ class SemiMarkovModule(nn.Module):
             features, lengths, self._check_valid_classes(valid_classes_per_instance), additional_allowed_ends_per_instance,
             constraints, check_no_eos=False)
         local = self._local_transcripts(transcripts, g1[5].cpu().numpy(), batch.n_states, np.zeros(batch.b, np.int64))
-        return _align(_emit(batch, x, cons, endpen, g1, tab['inv_var']), local, want_spans=True)
+        return _align(_emit(batch, x, cons, endpen, g1, tab['inv_var']), local, want_spans=True, optional=optional)
 
     @torch.no_grad()
-    def align_packed(self, pc, transcripts):
+    def align_packed(self, pc, transcripts, optional=None):
         """``align`` for a whole PackedCorpus: one emission launch and one alignment launch.  ``transcripts``: one sequence of
         GLOBAL class ids per video, in the order of ``pc.video_names``.  Returns (labels, scores): device int64 total_frames
         (global class ids on the packed frame axis, -1 on frames no video covers and on videos without an alignment) and fp64
-        n_videos."""
+        n_videos.  ``optional``: as in ``align``."""
         self._require_device(pc.x, 'align_packed')
         if pc.batch.no_eos:
             raise ValueError("align_packed: add_eos=False is not supported")
         batch, x, cons, endpen, g, inv_var = self._packed_stage(pc, 'align_packed')
         group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
         local = self._local_transcripts(transcripts, g[5].cpu().numpy(), batch.n_states, group)
-        return _align(_emit(batch, x, cons, endpen, g, inv_var), local, want_spans=False)
+        return _align(_emit(batch, x, cons, endpen, g, inv_var), local, want_spans=False, optional=optional)
 
     # ------------------------------------------------------------------ transcript likelihood (smm_align_logz_f64)
     def transcript_log_partition(self, features, lengths, valid_classes_per_instance, transcripts, add_eos=True,

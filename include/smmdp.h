@@ -26,6 +26,8 @@
  *                              correct frames (the reference has none)
  *   smm_align_f64           <- forced alignment: the best segmentation whose class sequence is a given transcript (the
  *                              reference has none)
+ *   smm_align_opt_f64       <- ... with optional transcript entries: the best over every subset of them left out (a CrossTask
+ *                              task "bg, step, bg, ..." whose backgrounds or steps may be missing; the reference has none)
  *   smm_align_logz_f64 /    <- transcript likelihood: the log of the sum over every segmentation with a given transcript,
  *   smm_align_logz_bwd_f64     and its gradient (the objective and the E-step of transcript supervision; the reference has none)
  *
@@ -513,6 +515,50 @@ int smm_align_f64(const smm_shape *shape, const int64_t *lengths_host, const int
                   const double *endpen, const int64_t *class_map, const int32_t *transcript,
                   const int64_t *transcript_offset_host, int64_t *spans, int64_t *labels, double *best, int32_t *n_segs,
                   void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Forced alignment with optional transcript entries (csrc/smm_align_opt.hip): per video, the best segmentation whose class
+ * sequence is the transcript a[0..M-1] with any subset of its optional entries left out.  opt[0..M-1] flags the entries
+ * (0 = mandatory, non-zero = optional); kw = kp - 1.  With
+ *   pred(m)  = the entries that may directly precede entry m: j = m-1, m-2, ... down to and including the nearest mandatory
+ *              entry (down to 0 when no mandatory entry lies before m),
+ *   first(m) = every entry before m is optional (entry m may be the first segment),
+ *   end(j)   = every entry after j is optional (entry j may be the last segment),
+ *   nb(m) / na(m) = the number of mandatory entries before / after m,
+ * every + and - one IEEE fp64 operation in this association:
+ *   cum as in smm_align_f64
+ *   h[0][m]   = init[a_m] if first(m), else -inf
+ *   h[n][m]   = max_{j in pred(m)} ( gam[n][j] + trans[a_m][a_j] ) - cum[n][a_m]              0 < n < T
+ *   gam[n][m] = cum[n][a_m] + max_{k=1..min(kw,n)} ( h[n-k][m] + len[k][a_m] )                n = 1..T
+ *   best      = max_{j : end(j)} ( gam[T][j] + closing_j )                  closing_j = endpen ? endpen[i][a_j] : 0.0
+ * Back-trace: start from n = T with the candidates {j : end(j)} and the weights w_j = closing_j.  Among all (k, j) take the
+ * smallest k, then the smallest j, whose (cum[n][a_j] + (h[n-k][j] + len[k][a_j])) + w_j equals the maximum of that
+ * expression; the segment is entry j on [n-k, n); continue from n - k with the candidates pred(j) and w_i = trans[a_j][a_i];
+ * stop at n = 0.  This is smm_oracle_viterbi_ex on the expanded lattice -- states = transcript positions,
+ * trans'[m][j] = trans[a_m][a_j] for j in pred(m), init'[m] = init[a_m] for first(m), endpen'[j] = closing_j for end(j), every
+ * other entry -1e9 -- bit for bit, the tie rule being the twin's "shortest segment, then smallest source state".
+ * Only the cells max(nb(m)+1, T - (M-1-m) kw) <= n <= min(T - na(m), (m+1) kw) of column m lie on a complete alignment; the
+ * kernel evaluates those.
+ *   optional   dev uint8 [transcript_offset_host[b]], laid out like `transcript`                                   (required)
+ *   used       dev int32, laid out like `transcript`: 1 for an entry that has a segment, else 0                     (nullable)
+ *   spans, labels, best as smm_align_f64; n_segs = the number of entries that got a segment; every other argument as
+ *   smm_align_f64.  With every flag 0 the results are bit-identical to smm_align_f64's.
+ * A video whose mandatory entries outnumber its frames, or with M kw < T, kw < 1, or an id outside [0, n_states), gets
+ * best = -inf, n_segs = 0, spans and labels -1, used 0; the error word stays clear.  The error word is set (best NaN, n_segs 0,
+ * spans and labels -1, used 0) as by smm_align_f64: a prefix sum cum[T][c] of any state of the video that is not finite, or a
+ * NaN or +inf in a table entry the recursion reads -- init[a_m] for first(m), trans[a_m][a_j] for j in pred(m), len[k][a_m]
+ * for k < kp, endpen[a_j] for end(j); -inf there is an ordinary "impossible", -1e9 an ordinary finite score.
+ * The workspace is smm_align_opt_workspace_bytes (smm_align_workspace_bytes plus c_max (T + 1) doubles per video: the running
+ * maxima per class that keep a column's cost independent of the length of an optional run).  Refusals as smm_align_f64's,
+ * plus SMM_ERR_ARG for a NULL `optional` -- all before anything is staged.
+ */
+size_t smm_align_opt_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host, const int64_t *transcript_offset_host);
+int smm_align_opt_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                      const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                      const double *elp, const double *trans, const double *init, const double *len_scores,
+                      const double *endpen, const int64_t *class_map, const int32_t *transcript, const uint8_t *optional,
+                      const int64_t *transcript_offset_host, int64_t *spans, int64_t *labels, double *best, int32_t *n_segs,
+                      int32_t *used, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Transcript likelihood (csrc/smm_align_logz.hip): per video log Z_a = log sum_{y : classes(y) = a} exp score(y), the sum over
