@@ -30,15 +30,6 @@
 #include "smm_align_tile.h"
 #include "smm_launch.h"
 
-// the cells of column m that lie on a complete alignment (lo > hi: none); nb / na: mandatory entries before / after m
-__device__ __forceinline__ void align_opt_range(int m, int M, int T, int kw, int nb, int na, int &lo, int &hi)
-{
-    const int a = nb + 1, b = T - (M - 1 - m) * kw;
-    const int c = T - na, d = (m + 1) * kw;
-    lo = a > b ? a : b;
-    hi = c < d ? c : d;
-}
-
 __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_kernel(SmmAlignArgs a)
 {
     __shared__ double s_h[SMM_ALIGN_HS];

@@ -1,5 +1,5 @@
 // smm_align_tile.h -- what the transcript kernels share (smm_align.hip: the best alignment; smm_align_opt.hip: the same with
-// optional entries; smm_align_logz.hip: the sum over all alignments): the tile geometry of a column, the cells of a column
+// optional entries; smm_align_logz.hip, smm_align_opt_logz.hip: the sums over all alignments): the tile geometry of a column, the cells of a column
 // that lie on a complete alignment, the prefix-sum phase, and the tests on the bits.  The including unit chooses its tile:
 // SMM_ALIGN_THREADS threads, SMM_ALIGN_R positions per thread (odd: the threads' h reads are R doubles apart, which spreads a
 // half-wave over all 64 banks).
@@ -66,6 +66,15 @@ __device__ __forceinline__ void align_start_range(int m, int M, int T, int kw, i
 {
     lo = hi = 0;
     if (m > 0) align_range(m - 1, M, T, kw, lo, hi);
+}
+
+// ... with optional entries (smm_align_opt.hip, smm_align_opt_logz.hip): nb / na: mandatory entries before / after m
+__device__ __forceinline__ void align_opt_range(int m, int M, int T, int kw, int nb, int na, int &lo, int &hi)
+{
+    const int a = nb + 1, b = T - (M - 1 - m) * kw;
+    const int c = T - na, d = (m + 1) * kw;
+    lo = a > b ? a : b;
+    hi = c < d ? c : d;
 }
 
 // Prefix sums of one video: tiles of `rows` frames through LDS (s_h: SMM_ALIGN_HS doubles), lane c adds class c serially,

@@ -2311,6 +2311,152 @@ extern "C" int smm_align_logz_bwd_f64(const smm_shape *shape, const int64_t *len
     return SMM_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ ... with optional entries
+// As above; per video the columns' ranges (3 M doubles), the h, gam, q and bh columns, 4 M (T + 1) doubles, and c_max columns
+// of running per-class sums; the parts hold g_len's rows, then c_max^2 + c_max doubles of g_trans and g_init and the
+// backward pass's own logZ_o.
+static size_t align_opt_logz_cells(int64_t m, int64_t t, int c_max) { return (size_t)(3 * m + (4 * m + c_max) * (t + 1)); }
+static size_t align_opt_logz_part(const smm_shape *s, int64_t t)
+{
+    return (size_t)(std::min<int64_t>(s->k_rows, t + 1) * s->c_max + (int64_t)s->c_max * s->c_max + s->c_max + 1);
+}
+
+static int align_opt_logz_layout(const smm_shape *s, const int64_t *lengths, const int64_t *toff, AlignLogzLayout *lo)
+{
+    if (!shape_ok(s) || !lengths || !toff) return SMM_ERR_ARG;
+    if ((s->flags & SMM_SHAPE_NO_EOS) || !limits_ok(s)) return SMM_ERR_UNSUPPORTED;
+    if (toff[0] < 0 || !lengths_ok(s, lengths)) return SMM_ERR_ARG;
+    size_t cells = 0, part = 0;
+    bool too_long = false;
+    for (int i = 0; i < s->b; ++i) {
+        const int64_t m = toff[i + 1] - toff[i];
+        if (m < 1) return SMM_ERR_ARG;                      // non-monotone offsets, or an empty transcript
+        too_long |= m > SMM_MAX_TRANSCRIPT;
+        cells += align_opt_logz_cells(m, lengths[i], s->c_max);
+        part += align_opt_logz_part(s, lengths[i]);
+    }
+    if (too_long) return SMM_ERR_UNSUPPORTED;
+    const size_t b = (size_t)s->b;
+    Carver c{align_up(make_plan(s, lengths).total, 256)};
+    lo->o_toff = c.packed(sizeof(int64_t) * (b + 1));      // (the four arrays go up in one upload)
+    lo->o_hoff = c.packed(sizeof(int64_t) * b);
+    lo->o_poff = c.packed(sizeof(int64_t) * b);
+    lo->o_order = c.take(sizeof(int32_t) * b);
+    lo->meta_end = lo->o_order + sizeof(int32_t) * b;
+    lo->o_cols = c.take(sizeof(double) * cells);
+    lo->o_part = c.packed(sizeof(double) * part);
+    lo->total = c.cur;
+    return SMM_OK;
+}
+
+extern "C" size_t smm_align_opt_logz_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host,
+                                                     const int64_t *transcript_offset_host)
+{
+    AlignLogzLayout lo;
+    return align_opt_logz_layout(shape, lengths_host, transcript_offset_host, &lo) == SMM_OK ? lo.total : 0;
+}
+
+// what the forward and the backward call share: the refusals, staging, this call's own metadata, the launch arguments
+static int align_opt_logz_stage(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                const int64_t *transcript_offset_host, void *workspace, size_t workspace_bytes, hipStream_t hs,
+                                SmmAlignOptLogzArgs *a)
+{
+    AlignLogzLayout lo;
+    int rc = align_opt_logz_layout(shape, lengths_host, transcript_offset_host, &lo);
+    if (rc != SMM_OK) return rc;
+    if (workspace_bytes < lo.total) return SMM_ERR_WORKSPACE;
+    Staged st;
+    rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes, hs, &st);
+    if (rc != SMM_OK) return rc;
+    // offsets, and the launch order -- most lattice cells (T x M x span limit) first
+    const int b = shape->b;
+    std::vector<char> host(lo.meta_end - lo.o_toff, 0);
+    int64_t *h_toff = reinterpret_cast<int64_t *>(host.data());
+    int64_t *h_hoff = reinterpret_cast<int64_t *>(host.data() + (lo.o_hoff - lo.o_toff));
+    int64_t *h_poff = reinterpret_cast<int64_t *>(host.data() + (lo.o_poff - lo.o_toff));
+    int32_t *h_order = reinterpret_cast<int32_t *>(host.data() + (lo.o_order - lo.o_toff));
+    std::vector<double> work(b);
+    int64_t cells = 0, part = 0;
+    for (int i = 0; i < b; ++i) {
+        const int64_t m = transcript_offset_host[i + 1] - transcript_offset_host[i];
+        const int k = kp_host ? kp_host[i] : std::min<int>(shape->k_rows, shape->t_max);
+        h_toff[i] = transcript_offset_host[i];
+        h_hoff[i] = cells;
+        h_poff[i] = part;
+        cells += (int64_t)align_opt_logz_cells(m, lengths_host[i], shape->c_max);
+        part += (int64_t)align_opt_logz_part(shape, lengths_host[i]);
+        work[i] = (double)m * (double)lengths_host[i] * (double)std::min<int64_t>(k, lengths_host[i]);
+    }
+    h_toff[b] = transcript_offset_host[b];
+    std::iota(h_order, h_order + b, 0);
+    std::stable_sort(h_order, h_order + b, [&](int x, int y) { return work[x] > work[y]; });
+    char *base = static_cast<char *>(workspace);
+    SMM_HIP((hipError_t)smm_upload_meta(base + lo.o_toff, host.data(), host.size(), hs));
+    *a = SmmAlignOptLogzArgs{};
+    a->videos = st.videos; a->n_states = st.n_states;
+    a->order = reinterpret_cast<const int32_t *>(base + lo.o_order);
+    a->toff = reinterpret_cast<const int64_t *>(base + lo.o_toff);
+    a->hoff = reinterpret_cast<const int64_t *>(base + lo.o_hoff);
+    a->poff = reinterpret_cast<const int64_t *>(base + lo.o_poff);
+    a->hist = st.hist;
+    a->cols = reinterpret_cast<double *>(base + lo.o_cols);
+    a->part = reinterpret_cast<double *>(base + lo.o_part);
+    a->err = st.err;
+    a->c_max = shape->c_max; a->k_rows = shape->k_rows; a->b = b; a->n_groups = shape->n_groups;
+    return SMM_OK;
+}
+
+extern "C" int smm_align_opt_logz_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                      const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                      const double *elp, const double *trans, const double *init, const double *len_scores,
+                                      const double *endpen, const int32_t *transcript, const uint8_t *optional,
+                                      const int64_t *transcript_offset_host, double *logz_o, void *workspace,
+                                      size_t workspace_bytes, void *stream)
+{
+    if (!shape_ok(shape) || !lengths_host || !frame_offset_host || !n_states_host || !transcript_offset_host) return SMM_ERR_ARG;
+    if (!elp || !trans || !init || !len_scores || !transcript || !optional || !logz_o || !workspace) return SMM_ERR_ARG;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    SmmAlignOptLogzArgs a;
+    const int rc = align_opt_logz_stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host,
+                                        transcript_offset_host, workspace, workspace_bytes, hs, &a);
+    if (rc != SMM_OK) return rc;
+    a.elp = elp; a.trans = trans; a.init = init; a.len = len_scores; a.endpen = endpen; a.transcript = transcript;
+    a.optional = optional;
+    a.logz = logz_o;
+    smm_launch_align_opt_logz_fwd(a, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
+extern "C" int smm_align_opt_logz_bwd_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                          const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                          const double *elp, const double *trans, const double *init, const double *len_scores,
+                                          const double *endpen, const int32_t *transcript, const uint8_t *optional,
+                                          const int64_t *transcript_offset_host, const double *logz_o, const double *grad_logz,
+                                          double *g_elp, double *g_trans, double *g_init, double *g_len, double *p_used,
+                                          void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!shape_ok(shape) || !lengths_host || !frame_offset_host || !n_states_host || !transcript_offset_host) return SMM_ERR_ARG;
+    if (!elp || !trans || !init || !len_scores || !transcript || !optional || !logz_o || !workspace) return SMM_ERR_ARG;
+    if (!g_elp || !g_trans || !g_init || !g_len) return SMM_ERR_ARG;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    SmmAlignOptLogzArgs a;
+    const int rc = align_opt_logz_stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host,
+                                        transcript_offset_host, workspace, workspace_bytes, hs, &a);
+    if (rc != SMM_OK) return rc;
+    a.elp = elp; a.trans = trans; a.init = init; a.len = len_scores; a.endpen = endpen; a.transcript = transcript;
+    a.optional = optional;
+    a.logz = const_cast<double *>(logz_o);                      // (the backward launches only read it)
+    a.grad = grad_logz;
+    a.g_elp = g_elp; a.g_trans = g_trans; a.g_init = g_init; a.g_len = g_len; a.p_used = p_used;
+    // g_elp: frames no video covers and the rows of skipped videos stay zero; the others are written whole by their kernels
+    SMM_HIP((hipError_t)smm_zero_async(g_elp, sizeof(double) * (size_t)shape->total_frames * shape->c_max, hs));
+    smm_launch_align_opt_logz_bwd(a, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ dense boundary
 struct DenseLayout {
     size_t o_len, o_alpha, o_beta, o_bp_from, o_bp_k, o_rmsg, total;

@@ -846,6 +846,120 @@ def align_logz_bwd(batch, elp, trans, init, len_scores, transcripts, logz_a, gra
     return g
 
 
+def align_opt_logz_workspace_bytes(batch, transcript_offset):
+    """Bytes of workspace smm_align_opt_logz_f64 / smm_align_opt_logz_bwd_f64 need for this batch and these transcript offsets
+    (int64 [b + 1]; host only)."""
+    off = _transcript_offsets(batch, transcript_offset, 'align_opt_logz_workspace_bytes')
+    n = _lib.load().smm_align_opt_logz_workspace_bytes(ctypes.byref(batch.shape), ctypes.c_void_p(batch.lengths.ctypes.data),
+                                                       ctypes.c_void_p(off.ctypes.data))
+    if n == 0:
+        raise _lib.SmmError("libsmmdp: invalid batch shape or transcript offsets for the transcript likelihood (add_eos=True "
+                            "only, 1..%d entries per video)" % MAX_TRANSCRIPT)
+    return n
+
+
+def _align_opt_logz_inputs(batch, elp, trans, init, len_scores, transcripts, optional, endpen, staged, what):
+    """The arguments the forward and the backward call share, from the tables on: (ctypes values, offsets, (ids, flags) on the
+    device).  Every check on the host arrays comes before a device is touched."""
+    if optional is None:
+        raise ValueError("%s: one sequence of flags per video expected (no flags: align_logz)" % what)
+    f64 = torch.float64
+    ids, off = _transcript_arrays(batch, transcripts)
+    flags = _optional_flags(off, optional)
+    if staged is not None:
+        ids_dev, flags_dev = staged
+        if ids_dev.shape[0] != ids.shape[0] or flags_dev.shape[0] != flags.shape[0]:
+            raise ValueError("%s: staged ids and flags of another transcript" % what)
+    else:
+        ids_dev, flags_dev = torch.from_numpy(ids).to(elp.device), torch.from_numpy(flags).to(elp.device)
+    args = (_dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
+            _dev(endpen, f64, 'endpen'), _dev(ids_dev, torch.int32, 'transcript'), _dev(flags_dev, torch.uint8, 'optional'),
+            ctypes.c_void_p(off.ctypes.data))
+    return args, off, (ids_dev, flags_dev)
+
+
+def align_opt_logz(batch, elp, trans, init, len_scores, transcripts, optional, endpen=None, ws=None, staged=None):
+    """Transcript likelihood with optional entries (smm_align_opt_logz_f64, also when no flag is set): per video log Z_o, the
+    log of the sum over every ALIGNMENT -- which of the flagged entries get a segment, and where the boundaries lie.  Where no
+    two subsets of the flagged entries give the same class sequence (``transcript_is_ambiguous``) that is the likelihood of
+    the set of class sequences; else a segmentation counts once per subset that yields its class sequence.  ``transcripts``
+    and ``optional`` as in ``align_optional``.  -> dict(logz fp64 [b] (-inf: no alignment; NaN and the error word: a NaN
+    reached the DP), ws (keep it for ``align_opt_logz_bwd``), _staged (ids and flags on the device), _err).  ``ws``: at least
+    ``align_opt_logz_workspace_bytes``.  ``staged``: the ``_staged`` entry of an earlier call for the same transcripts and
+    flags: the call then copies nothing from the host itself and can be captured into a graph."""
+    lib = _lib.load()
+    args, off, st = _align_opt_logz_inputs(batch, elp, trans, init, len_scores, transcripts, optional, endpen, staged,
+                                           'align_opt_logz')
+    ws = _own_workspace(ws, align_opt_logz_workspace_bytes(batch, off), elp.device)
+    out = torch.empty(batch.b, dtype=torch.float64, device=elp.device)
+    _lib.check(lib.smm_align_opt_logz_f64(*batch.head(), *args, _dev(out, torch.float64, 'logz_o'), *_ws_args(ws), _stream()))
+    return dict(logz=out, ws=ws, _staged=st, _err=_err_copy(batch, ws))
+
+
+def align_opt_logz_bwd(batch, elp, trans, init, len_scores, transcripts, optional, logz_o, grad_logz=None, endpen=None, ws=None,
+                       staged=None, want_entry_prob=False):
+    """Gradient of sum_i grad_logz[i] * log Z_o(i) (smm_align_opt_logz_bwd_f64).  Must follow ``align_opt_logz`` for the same
+    batch, tables, transcripts and flags with the same workspace ``ws`` on the same stream; ``logz_o`` = its output.
+    -> dict(elp [total_frames, c_max], trans, init, len) fp64, plus with ``want_entry_prob`` entry_prob: a list of per-video
+    fp64 views of one device tensor, the posterior probability that the entry has a segment (1 for a mandatory entry).  Videos
+    whose log Z_o is -inf or NaN contribute zeros."""
+    lib = _lib.load()
+    f64 = torch.float64
+    args, off, st = _align_opt_logz_inputs(batch, elp, trans, init, len_scores, transcripts, optional, endpen, staged,
+                                           'align_opt_logz_bwd')
+    if ws is None or ws.numel() < align_opt_logz_workspace_bytes(batch, off):
+        raise ValueError("align_opt_logz_bwd: pass the workspace the align_opt_logz call wrote")
+    g = _grad_outputs(elp, trans, init, len_scores)
+    used = torch.empty(int(off[-1]), dtype=f64, device=elp.device) if want_entry_prob else None
+    _lib.check(lib.smm_align_opt_logz_bwd_f64(
+        *batch.head(), *args, _dev(logz_o, f64, 'logz_o'), _dev(grad_logz, f64, 'grad_logz'), _dev(g['elp'], f64, 'g_elp'),
+        _dev(g['trans'], f64, 'g_trans'), _dev(g['init'], f64, 'g_init'), _dev(g['len'], f64, 'g_len'),
+        _dev(used, f64, 'p_used'), *_ws_args(ws), _stream()))
+    if want_entry_prob:
+        g['entry_prob'] = list(torch.split(used, np.diff(off).tolist()))
+    g['_keep'] = st
+    return g
+
+
+def transcript_is_ambiguous(ids, optional):
+    """Host only: True when two different subsets of the optional entries of this transcript give the same non-empty class
+    sequence -- ``align_opt_logz`` then counts the segmentations with that class sequence once per subset.  Exact: over the
+    pairs (i, j) with ids[i] == ids[j], `reach` says that a kept-entry path ending in i and one ending in j spell the same
+    labels, `diff` that two such paths differ somewhere; each is one rectangle query on a 2-D prefix sum over
+    pred(i) x pred(j), O(M^2) in all."""
+    a = np.asarray(ids.detach().cpu() if torch.is_tensor(ids) else ids, dtype=np.int64).reshape(-1)
+    opt = np.asarray(optional.detach().cpu() if torch.is_tensor(optional) else optional).reshape(-1) != 0
+    M = a.shape[0]
+    if opt.shape[0] != M:
+        raise ValueError("transcript_is_ambiguous: %d flags for %d entries" % (opt.shape[0], M))
+    if M == 0:
+        return False
+    plo, head = np.zeros(M, np.int64), 0
+    for m in range(M):
+        plo[m] = head
+        if not opt[m]:
+            head = m
+    first = [bool(opt[:m].all()) for m in range(M)]
+    end = [bool(opt[m + 1:].all()) for m in range(M)]
+    reach = np.zeros((M + 1, M + 1), np.int64)      # 2-D inclusive prefix sums, shifted by one
+    diff = np.zeros((M + 1, M + 1), np.int64)
+
+    def rect(p, i0, i1, j0, j1):                    # the sum over [i0, i1) x [j0, j1)
+        return p[i1, j1] - p[i0, j1] - p[i1, j0] + p[i0, j0]
+
+    for i in range(M):
+        for j in range(M):
+            r = d = 0
+            if a[i] == a[j]:
+                r = int((first[i] and first[j]) or rect(reach, plo[i], i, plo[j], j) > 0)
+                d = int(r and (i != j or rect(diff, plo[i], i, plo[j], j) > 0))
+                if d and end[i] and end[j]:
+                    return True
+            reach[i + 1, j + 1] = r + reach[i, j + 1] + reach[i + 1, j] - reach[i, j]
+            diff[i + 1, j + 1] = d + diff[i, j + 1] + diff[i + 1, j] - diff[i, j]
+    return False
+
+
 _pinned = {}
 
 

@@ -380,8 +380,7 @@ class SemiMarkovModel(object):
         subset of the optional entries left out.  ``optional_by_video[name]``: one boolean per entry of the video's
         transcript; or ``optional_classes``: an iterable of global class ids, every entry of such a class being optional
         (a CrossTask task ``bg, step_1, bg, ...``: pass the background ids).  ValueError when both are given."""
-        if optional_by_video is not None and optional_classes is not None:
-            raise ValueError("align: give optional_by_video or optional_classes, not both")
+        self._one_kind_of_flags(optional_by_video, optional_classes, 'align')
         self.model.eval()
         pc = self.prepare(data, shard=shard)
         if pc.n_videos == 0:
@@ -390,27 +389,67 @@ class SemiMarkovModel(object):
         if missing:
             raise ValueError("align: no transcript for video %r" % (missing[0],))
         transcripts = [transcripts_by_video[name] for name in pc.video_names]
-        optional = None
-        if optional_classes is not None:
-            classes = np.array(sorted(set(int(c) for c in optional_classes)), np.int64)
-            optional = [np.isin(np.asarray(t.cpu() if torch.is_tensor(t) else t, dtype=np.int64).reshape(-1), classes)
-                        for t in transcripts]
-        elif optional_by_video is not None:
-            missing = [name for name in pc.video_names if name not in optional_by_video]
-            if missing:
-                raise ValueError("align: no optional flags for video %r" % (missing[0],))
-            optional = [optional_by_video[name] for name in pc.video_names]
+        optional = self._optional_flags(pc, transcripts, optional_by_video, optional_classes, 'align')
         labels, _ = self.model.align_packed(pc, transcripts, optional=optional)
         lab = labels.cpu().numpy()
         assert lab.size == 0 or int(lab.max()) < self.model.n_classes, "alignments should not contain EOS"
         return {name: lab[off:off + t] for name, off, t in zip(pc.video_names, pc.frame_offset, pc.lengths)}
 
-    def transcript_log_likelihood(self, data, transcripts_by_video, conditional=False, shard=None):
+    @staticmethod
+    def _one_kind_of_flags(optional_by_video, optional_classes, what):
+        if optional_by_video is not None and optional_classes is not None:
+            raise ValueError("%s: give optional_by_video or optional_classes, not both" % what)
+
+    @staticmethod
+    def _refuse_ambiguous(transcripts_by_video, optional_by_video, optional_classes, ambiguous, what):
+        """ambiguous='raise', on the host before the corpus is prepared: ValueError naming the first video two subsets of whose
+        optional entries give the same class sequence."""
+        from . import ops
+        if ambiguous not in ('raise', 'allow'):
+            raise ValueError("%s: ambiguous must be 'raise' or 'allow'" % what)
+        if ambiguous == 'allow' or (optional_by_video is None and optional_classes is None):
+            return
+        classes = None if optional_classes is None else np.array(sorted(set(int(c) for c in optional_classes)), np.int64)
+        for name, t in transcripts_by_video.items():
+            ids = np.asarray(t.cpu() if torch.is_tensor(t) else t, dtype=np.int64).reshape(-1)
+            if classes is not None:
+                flags = np.isin(ids, classes)
+            elif name in optional_by_video:
+                f = optional_by_video[name]
+                flags = np.asarray(f.cpu() if torch.is_tensor(f) else f).reshape(-1) != 0
+            else:
+                continue
+            if flags.size == ids.size and ops.transcript_is_ambiguous(ids, flags):
+                raise ValueError("%s: two subsets of the optional entries of video %r give the same class sequence; pass "
+                                 "ambiguous='allow' for the sum over alignments" % (what, name))
+
+    @staticmethod
+    def _optional_flags(pc, transcripts, optional_by_video, optional_classes, what):
+        """The two ways to flag optional entries -> one boolean sequence per video of ``pc`` (None: no flags)."""
+        if optional_classes is not None:
+            classes = np.array(sorted(set(int(c) for c in optional_classes)), np.int64)
+            return [np.isin(np.asarray(t.cpu() if torch.is_tensor(t) else t, dtype=np.int64).reshape(-1), classes)
+                    for t in transcripts]
+        if optional_by_video is not None:
+            missing = [name for name in pc.video_names if name not in optional_by_video]
+            if missing:
+                raise ValueError("%s: no optional flags for video %r" % (what, missing[0]))
+            return [optional_by_video[name] for name in pc.video_names]
+        return None
+
+    def transcript_log_likelihood(self, data, transcripts_by_video, conditional=False, shard=None, *, optional_by_video=None,
+                                  optional_classes=None, ambiguous='raise'):
         """The likelihood of every video's transcript: ``transcripts_by_video[name]`` is the video's class sequence in global
         class ids, one entry per segment.  Returns ``{video: float}``: log Z_a, the log of the sum over every segmentation with
         that class sequence (the joint log-likelihood of frames and transcript); ``conditional``: log Z_a - log Z, the
         log-probability of the transcript given the frames.  -inf for a transcript that cannot be laid over its video.  One
-        emission launch and the DP launches on the packed corpus (``SemiMarkovModule.transcript_scores_packed``)."""
+        emission launch and the DP launches on the packed corpus (``SemiMarkovModule.transcript_scores_packed``).
+
+        ``optional_by_video`` / ``optional_classes`` (as in ``align``): entries that may be missing; the value is then log Z_o,
+        the sum over every alignment with any subset of them left out.  ``ambiguous``: 'raise' -- ValueError naming the first
+        video two subsets of whose optional entries give the same class sequence -- or 'allow'."""
+        self._one_kind_of_flags(optional_by_video, optional_classes, 'transcript_log_likelihood')
+        self._refuse_ambiguous(transcripts_by_video, optional_by_video, optional_classes, ambiguous, 'transcript_log_likelihood')
         self.model.eval()
         pc = self.prepare(data, shard=shard)
         if pc.n_videos == 0:
@@ -418,9 +457,31 @@ class SemiMarkovModel(object):
         missing = [name for name in pc.video_names if name not in transcripts_by_video]
         if missing:
             raise ValueError("transcript_log_likelihood: no transcript for video %r" % (missing[0],))
-        z = self.model.transcript_scores_packed(pc, [transcripts_by_video[name] for name in pc.video_names],
-                                                conditional=conditional)
+        transcripts = [transcripts_by_video[name] for name in pc.video_names]
+        optional = self._optional_flags(pc, transcripts, optional_by_video, optional_classes, 'transcript_log_likelihood')
+        z = self.model.transcript_scores_packed(pc, transcripts, conditional=conditional, optional=optional, ambiguous=ambiguous)
         return {name: float(v) for name, v in zip(pc.video_names, z.tolist())}
+
+    def transcript_entry_posteriors(self, data, transcripts_by_video, shard=None, *, optional_by_video=None, optional_classes=None,
+                                    ambiguous='raise'):
+        """``{video: fp64 array}``: per entry of the video's transcript the posterior probability that it has a segment, given
+        the frames and the transcript with its optional entries (flagged as in ``align``; 1 for a mandatory entry, zeros for a
+        video without an alignment).  ``SemiMarkovModule.transcript_entry_posteriors_packed`` on the packed corpus."""
+        self._one_kind_of_flags(optional_by_video, optional_classes, 'transcript_entry_posteriors')
+        if optional_by_video is None and optional_classes is None:
+            raise ValueError("transcript_entry_posteriors: give optional_by_video or optional_classes")
+        self._refuse_ambiguous(transcripts_by_video, optional_by_video, optional_classes, ambiguous, 'transcript_entry_posteriors')
+        self.model.eval()
+        pc = self.prepare(data, shard=shard)
+        if pc.n_videos == 0:
+            return {}
+        missing = [name for name in pc.video_names if name not in transcripts_by_video]
+        if missing:
+            raise ValueError("transcript_entry_posteriors: no transcript for video %r" % (missing[0],))
+        transcripts = [transcripts_by_video[name] for name in pc.video_names]
+        optional = self._optional_flags(pc, transcripts, optional_by_video, optional_classes, 'transcript_entry_posteriors')
+        post = self.model.transcript_entry_posteriors_packed(pc, transcripts, optional, ambiguous=ambiguous)
+        return dict(zip(pc.video_names, post))
 
     def predict_packed(self, pc):
         import torch

@@ -198,6 +198,50 @@ class _TranscriptLogPartition(torch.autograd.Function):
         return None, None, None, None, None, g_w, g_cst, g_iv, g['trans'], g['init'], g['len']
 
 
+class _TranscriptOptLogPartition(torch.autograd.Function):
+    """log Z_o of every video of one launch -- the sum over every alignment to the video's transcript with any subset of its
+    optional entries left out -- beside ``_TranscriptLogPartition``.  Forward: smm_emission_f64 + smm_align_opt_logz_f64 on a
+    private workspace that survives until backward; backward: smm_align_opt_logz_bwd_f64 + smm_emission_bwd_f64.  ``local``:
+    the transcripts in local state ids, ``optional``: one boolean sequence per video."""
+
+    @staticmethod
+    def forward(ctx, batch, x, cons, endpen, local, optional, w, cst, inv_var, trans, init, len_scores):
+        r = _emit(batch, x, cons, endpen, (w, cst, trans, init, len_scores, None), inv_var)
+        out = ops.align_opt_logz(batch, r['elp'], trans, init, len_scores, local, optional, endpen=endpen)
+        ctx.batch, ctx.endpen, ctx.ws, ctx.local, ctx.optional, ctx.staged = batch, endpen, out['ws'], local, optional, out['_staged']
+        ctx.save_for_backward(x, r['elp'], trans, init, len_scores, out['logz'])
+        return out['logz']
+
+    @staticmethod
+    def backward(ctx, gz):
+        x, elp, trans, init, len_scores, logz = ctx.saved_tensors
+        g = ops.align_opt_logz_bwd(ctx.batch, elp, trans, init, len_scores, ctx.local, ctx.optional, logz,
+                                   grad_logz=gz.to(torch.float64).contiguous(), endpen=ctx.endpen, ws=ctx.ws, staged=ctx.staged)
+        g_w, g_cst, g_iv = ops.emission_bwd(ctx.batch, x, g['elp'], ws=ctx.ws)
+        return None, None, None, None, None, None, g_w, g_cst, g_iv, g['trans'], g['init'], g['len']
+
+
+def _checked_optional(transcripts, optional, ambiguous, names, what):
+    """The flags of a launch as boolean arrays, checked on the host before a device is touched (``transcripts`` in global or
+    local ids: the map between them is one-to-one within a video): one sequence per video, as long as its transcript; ``ambiguous='raise'``: ValueError naming the first video two subsets of whose optional entries give the
+    same class sequence (``ops.transcript_is_ambiguous``), ``'allow'``: the sum over alignments as defined."""
+    if ambiguous not in ('raise', 'allow'):
+        raise ValueError("%s: ambiguous must be 'raise' or 'allow'" % what)
+    if len(optional) != len(transcripts):
+        raise ValueError("%s: %d sequences of optional flags for %d videos" % (what, len(optional), len(transcripts)))
+    flags = [np.asarray(f.detach().cpu() if torch.is_tensor(f) else f).reshape(-1) != 0 for f in optional]
+    ids = [np.asarray(a.detach().cpu() if torch.is_tensor(a) else a, dtype=np.int64).reshape(-1) for a in transcripts]
+    for i, (a, f) in enumerate(zip(ids, flags)):
+        if f.size != len(a):
+            raise ValueError("%s: %d optional flags for the %d transcript entries of video %r"
+                             % (what, f.size, len(a), i if names is None else names[i]))
+        if ambiguous == 'raise' and ops.transcript_is_ambiguous(a, f):
+            raise ValueError("%s: two subsets of the optional entries of video %r give the same class sequence, so its "
+                             "segmentations would be counted once per subset; pass ambiguous='allow' for that sum over "
+                             "alignments" % (what, i if names is None else names[i]))
+    return flags
+
+
 def _check_transcript_logz(z, names, what, allow_none=False):
     """The host's look at a launch's log Z_a (synchronises): SmmError for a NaN, ValueError -- naming the video -- for -inf."""
     zh = z.detach().cpu()
@@ -1122,14 +1166,20 @@ class SemiMarkovModule(nn.Module):
 
     # ------------------------------------------------------------------ transcript likelihood (smm_align_logz_f64)
     def transcript_log_partition(self, features, lengths, valid_classes_per_instance, transcripts, add_eos=True,
-                                 additional_allowed_ends_per_instance=None, constraints=None):
+                                 additional_allowed_ends_per_instance=None, constraints=None, optional=None, ambiguous='raise'):
         """log Z_a per video of a zero-padded single-task batch (argument conventions of ``align``): the log of the sum over
         every segmentation whose class sequence is ``transcripts[i]`` (GLOBAL class ids, one entry per segment, consecutive
         repeats are two segments) -- the joint log-likelihood of frames and transcript; minus ``log_partition`` it is the
         conditional likelihood of the transcript.  fp64 b on the device, differentiable w.r.t. the module's parameters
         (smm_emission_f64 + smm_align_logz_f64 forward, smm_align_logz_bwd_f64 + smm_emission_bwd_f64 backward).
         ValueError for add_eos=False, an id that is not valid for the video, an empty transcript, and for a video no
-        segmentation of which has its transcript (log Z_a = -inf); SmmError when a NaN reached the DP."""
+        segmentation of which has its transcript (log Z_a = -inf); SmmError when a NaN reached the DP.
+
+        ``optional`` (``align``'s conventions: one boolean sequence per video, as long as its transcript): the flagged entries
+        may be missing, and the value is log Z_o, the sum over every alignment with any subset of them left out
+        (smm_align_opt_logz_f64 / _bwd_f64) -- the likelihood of the set of class sequences when no two subsets give the same
+        one.  ``ambiguous``: 'raise' (ValueError naming the first video with two such subsets) or 'allow' (the sum over
+        alignments as defined, a segmentation counted once per subset that yields its class sequence)."""
         if not add_eos:
             raise ValueError("transcript_log_partition: add_eos=False is not supported")
         if len(transcripts) != features.size(0):
@@ -1138,18 +1188,27 @@ class SemiMarkovModule(nn.Module):
         ids = list(range(self.n_classes)) if valid_classes is None else [int(v) for v in valid_classes]
         local = self._local_transcripts(transcripts, np.array([ids + [self.n_classes]], np.int64), [len(ids)],
                                         np.zeros(len(transcripts), np.int64))
+        if optional is not None:
+            optional = _checked_optional(local, optional, ambiguous, None, 'transcript_log_partition')
         self._require_device(features, 'transcript_log_partition')
         st = self._one_group_tables(valid_classes, features.device)
         batch, x, cons, endpen, _, _ = self._stage_padded(features, lengths, valid_classes, additional_allowed_ends_per_instance,
                                                           constraints, check_no_eos=False, tables=st)
-        z = _TranscriptLogPartition.apply(batch, x, cons, endpen, local, st['w'], st['cst'], st['inv_var'], st['trans'],
-                                          st['init'], st['len'])
+        if optional is None:
+            z = _TranscriptLogPartition.apply(batch, x, cons, endpen, local, st['w'], st['cst'], st['inv_var'], st['trans'],
+                                              st['init'], st['len'])
+        else:
+            z = _TranscriptOptLogPartition.apply(batch, x, cons, endpen, local, optional, st['w'], st['cst'], st['inv_var'],
+                                                 st['trans'], st['init'], st['len'])
         _check_transcript_logz(z, None, 'transcript_log_partition')
         return z
 
-    def transcript_log_partition_packed(self, pc, transcripts):
+    def transcript_log_partition_packed(self, pc, transcripts, optional=None, ambiguous='raise'):
         """``transcript_log_partition`` for a whole PackedCorpus in one launch of each kernel: ``transcripts`` holds one sequence
-        of GLOBAL class ids per video, in the order of ``pc.video_names``.  fp64 [n_videos], differentiable."""
+        of GLOBAL class ids per video, in the order of ``pc.video_names``.  fp64 [n_videos], differentiable.  ``optional``,
+        ``ambiguous``: as in ``transcript_log_partition``."""
+        if optional is not None:
+            optional = _checked_optional(transcripts, optional, ambiguous, list(pc.video_names), 'transcript_log_partition_packed')
         self._require_device(pc.x, 'transcript_log_partition_packed')
         if pc.batch is not None and pc.batch.no_eos:
             raise ValueError("transcript_log_partition_packed: add_eos=False is not supported")
@@ -1157,26 +1216,57 @@ class SemiMarkovModule(nn.Module):
         t, batch = pc.tables, pc.batch
         group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
         local = self._local_transcripts(transcripts, t['class_map'].cpu().numpy(), batch.n_states, group)
-        z = _TranscriptLogPartition.apply(batch, pc.x, pc.cons, pc.endpen, local, t['w'], t['cst'], t['inv_var'], t['trans'],
-                                          t['init'], t['len'])
+        if optional is None:
+            z = _TranscriptLogPartition.apply(batch, pc.x, pc.cons, pc.endpen, local, t['w'], t['cst'], t['inv_var'], t['trans'],
+                                              t['init'], t['len'])
+        else:
+            z = _TranscriptOptLogPartition.apply(batch, pc.x, pc.cons, pc.endpen, local, optional, t['w'], t['cst'], t['inv_var'],
+                                                 t['trans'], t['init'], t['len'])
         _check_transcript_logz(z, list(pc.video_names), 'transcript_log_partition_packed')
         return z
 
     @torch.no_grad()
-    def transcript_scores_packed(self, pc, transcripts, conditional=False):
+    def transcript_scores_packed(self, pc, transcripts, conditional=False, optional=None, ambiguous='raise'):
         """Without autograd, on the cached decode tables: log Z_a of every video of a PackedCorpus (``conditional``: minus its
         log Z) as a CPU fp64 tensor; -inf for a video no segmentation of which has its transcript.  One emission launch, then
-        the DP launches.  SmmError when a NaN reached the DP."""
+        the DP launches.  SmmError when a NaN reached the DP.  ``optional``, ``ambiguous``: as in ``transcript_log_partition``
+        (log Z_o in place of log Z_a)."""
         if pc.batch is not None and pc.batch.no_eos:
             raise ValueError("transcript_scores_packed: add_eos=False is not supported")
+        if optional is not None:
+            optional = _checked_optional(transcripts, optional, ambiguous, list(pc.video_names), 'transcript_scores_packed')
         batch, x, cons, endpen, g, inv_var = self._packed_stage(pc, 'transcript_scores_packed')
         group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
         local = self._local_transcripts(transcripts, g[5].cpu().numpy(), batch.n_states, group)
         r = _emit(batch, x, cons, endpen, g, inv_var)
-        z = ops.align_logz(batch, r['elp'], r['trans'], r['init'], r['len'], local, endpen=endpen)
+        if optional is None:
+            z = ops.align_logz(batch, r['elp'], r['trans'], r['init'], r['len'], local, endpen=endpen)
+        else:
+            z = ops.align_opt_logz(batch, r['elp'], r['trans'], r['init'], r['len'], local, optional, endpen=endpen)['logz']
         if conditional:
             z = z - ops.logz(batch, r['elp'], r['trans'], r['init'], r['len'], endpen=endpen)
         return _check_transcript_logz(z, None, 'transcript_scores_packed', allow_none=True)
+
+    @torch.no_grad()
+    def transcript_entry_posteriors_packed(self, pc, transcripts, optional, ambiguous='raise'):
+        """Per video of a PackedCorpus the posterior probability that each entry of its transcript has a segment, given the
+        frames and the transcript with its ``optional`` flags (p_used of smm_align_opt_logz_bwd_f64: 1 for a mandatory entry):
+        a list of fp64 CPU arrays in the order of ``pc.video_names``; zeros for a video without an alignment.  One emission
+        launch, then the forward and the backward launches.  SmmError when a NaN reached the DP."""
+        if pc.batch is not None and pc.batch.no_eos:
+            raise ValueError("transcript_entry_posteriors_packed: add_eos=False is not supported")
+        if optional is None:
+            raise ValueError("transcript_entry_posteriors_packed: one sequence of optional flags per video expected")
+        optional = _checked_optional(transcripts, optional, ambiguous, list(pc.video_names), 'transcript_entry_posteriors_packed')
+        batch, x, cons, endpen, g, inv_var = self._packed_stage(pc, 'transcript_entry_posteriors_packed')
+        group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
+        local = self._local_transcripts(transcripts, g[5].cpu().numpy(), batch.n_states, group)
+        r = _emit(batch, x, cons, endpen, g, inv_var)
+        out = ops.align_opt_logz(batch, r['elp'], r['trans'], r['init'], r['len'], local, optional, endpen=endpen)
+        grads = ops.align_opt_logz_bwd(batch, r['elp'], r['trans'], r['init'], r['len'], local, optional, out['logz'],
+                                       endpen=endpen, ws=out['ws'], staged=out['_staged'], want_entry_prob=True)
+        _check_transcript_logz(out['logz'], None, 'transcript_entry_posteriors_packed', allow_none=True)
+        return [p.cpu().numpy() for p in grads['entry_prob']]
 
     # ------------------------------------------------------------------ packed multi-task decode
     def stacked_tables(self, pc, differentiable=False):
@@ -1480,17 +1570,20 @@ class SemiMarkovModule(nn.Module):
         return torch.mv(mean_of, z)
 
     def log_likelihood(self, features, lengths, valid_classes_per_instance, spans=None, add_eos=True, use_mean_z=False,
-                       additional_allowed_ends_per_instance=None, constraints=None, transcripts=None):
+                       additional_allowed_ends_per_instance=None, constraints=None, transcripts=None, transcript_optional=None):
         """(mean log-likelihood, mean log_det) like the reference (:597-658).
 
         spans given: joint score p(x, y) (differentiable), or with --sm_train_discriminatively the conditional
         score - log Z.  spans=None: the log-partition (marginal likelihood) from the HIP forward kernel; its gradient
         (posterior marginals chained into the parameters) comes from the HIP backward kernels.
         transcripts given (and no spans): only the order of each video's actions is known -- the mean of log Z_a
-        (``transcript_log_partition``), or with --sm_train_discriminatively of log Z_a - log Z.
+        (``transcript_log_partition``), or with --sm_train_discriminatively of log Z_a - log Z.  ``transcript_optional``: one
+        boolean sequence per transcript, the flagged entries may be missing (log Z_o; ValueError for an ambiguous transcript).
         """
         if spans is not None and transcripts is not None:
             raise ValueError("log_likelihood: give spans (full supervision) or transcripts (the order only), not both")
+        if transcript_optional is not None and transcripts is None:
+            raise ValueError("log_likelihood: transcript_optional goes with transcripts")
         no_eos = not add_eos
         valid_classes = self._check_valid_classes(valid_classes_per_instance)
         self.set_z(features, lengths, use_mean=use_mean_z)
@@ -1498,7 +1591,7 @@ class SemiMarkovModule(nn.Module):
         if transcripts is not None:
             ll = self.transcript_log_partition(features, lengths, valid_classes_per_instance, transcripts, add_eos=add_eos,
                                                additional_allowed_ends_per_instance=additional_allowed_ends_per_instance,
-                                               constraints=constraints)
+                                               constraints=constraints, optional=transcript_optional)
             if getattr(self.args, 'sm_train_discriminatively', False):
                 ll = ll - self.log_partition(features, lengths, valid_classes, additional_allowed_ends_per_instance,
                                              constraints)

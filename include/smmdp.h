@@ -30,6 +30,8 @@
  *                              task "bg, step, bg, ..." whose backgrounds or steps may be missing; the reference has none)
  *   smm_align_logz_f64 /    <- transcript likelihood: the log of the sum over every segmentation with a given transcript,
  *   smm_align_logz_bwd_f64     and its gradient (the objective and the E-step of transcript supervision; the reference has none)
+ *   smm_align_opt_logz_f64 / <- ... with optional transcript entries: the sum over every alignment, any subset of them left
+ *   smm_align_opt_logz_bwd_f64   out, its gradient and each entry's posterior of being used (the reference has none)
  *
  * The reference has no FFI: its boundary is the Python call SemiMarkovCRF(scores, lengths) on a dense
  * b x N x K x C x C tensor.  These entry points take the FACTORS of that tensor instead,
@@ -618,6 +620,77 @@ int smm_align_logz_bwd_f64(const smm_shape *shape, const int64_t *lengths_host, 
                            const double *endpen, const int32_t *transcript, const int64_t *transcript_offset_host,
                            const double *logz_a, const double *grad_logz /* nullable */, double *g_elp, double *g_trans,
                            double *g_init, double *g_len, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Transcript likelihood with optional entries (csrc/smm_align_opt_logz.hip): the log-semiring counterpart of smm_align_opt_f64,
+ * with its gradient.  Per video log Z_o = log of the sum of exp score over every ALIGNMENT of the video to the transcript
+ * a[0..M-1]: a choice of which optional entries get a segment, and of the boundaries.  Definitions of smm_align_opt_f64 (pred,
+ * first, end, nb, na; closing_j = endpen ? endpen[i][a_j] : 0) and conventions of smm_align_logz_f64 (EOS mode only, local
+ * state ids, kw = kp - 1, cum the serial prefix sum, lse of only -inf terms is -inf); succ(j) = { m : j in pred(m) }, that is
+ * j+1, j+2, ... up to and including the next mandatory entry (to M-1 when there is none).
+ *   forward   h[0][m]   = init[a_m] if first(m), else -inf
+ *             h[n][m]   = lse_{j in pred(m)} ( gam[n][j] + trans[a_m][a_j] ) - cum[n][a_m]            0 < n < T
+ *             gam[n][m] = cum[n][a_m] + lse_{k=1..min(kw,n)} ( h[n-k][m] + len[k][a_m] )              n = 1..T
+ *             logZ_o    = lse_{j : end(j)} ( gam[T][j] + closing_j )
+ *   backward  bg[T][j]  = closing_j if end(j), else -inf
+ *             bh[s][m]  = lse_{k=1..min(kw,T-s)} ( len[k][a_m] + cum[s+k][a_m] + bg[s+k][m] )         s = 0..T-1
+ *             bg[n][j]  = lse_{m in succ(j)} ( trans[a_m][a_j] - cum[n][a_m] + bh[n][m] )             0 < n < T
+ *             (identity: lse_{m : first(m)} ( h[0][m] + bh[0][m] ) = logZ_o)
+ *   marginals S[s][m]   = exp(h[s][m] + bh[s][m] - logZ_o)          entry m has a segment that starts at s
+ *             E[n][m]   = exp(gam[n][m] + bg[n][m] - logZ_o)        ... that ends at n
+ *             occ[t][m] = sum_{s<=t} S[s][m] - sum_{n<=t} E[n][m]   frame t lies in the segment of entry m
+ *             p_used[m] = sum_n E[n][m]                             entry m has a segment at all (1 for a mandatory entry)
+ *   gradients of sum_i u_i logZ_o(i)   (u = grad_logz, NULL = ones):
+ *             g_elp[t][c]    = u_i sum_{m: a_m=c} occ[t][m]
+ *             g_len[k][c]    = sum_i u_i sum_{m: a_m=c} sum_s exp(h[s][m] + len[k][c] + cum[s+k][c] + bg[s+k][m] - logZ_o)
+ *             g_trans[c][c'] = sum_i u_i sum_{m: a_m=c} sum_{j in pred(m): a_j=c'} sum_{0<n<T}
+ *                                      exp(gam[n][j] + trans[c][c'] - cum[n][c] + bh[n][m] - logZ_o)
+ *             g_init[c]      = sum_i u_i sum_{m: first(m), a_m=c} S[0][m]
+ *   g_trans and g_init are sums of posteriors here, not counts; there is no gradient for endpen.
+ * What is summed: alignments, not class sequences.  Where no two subsets of the optional entries give the same class sequence
+ * logZ_o is the log-likelihood of the SET of class sequences the transcript stands for.  Where two subsets do -- [x?, y?, x?]
+ * without y, either x -- the segmentations with that class sequence are counted once per subset.  Whether a transcript is of
+ * that kind is host arithmetic on the ids and the flags (the Python layer ships the predicate: ops.transcript_is_ambiguous).
+ * With no flag set this is smm_align_logz_f64's value (the h, gam and bg columns are formed in its association).
+ * What the structure decides is returned exactly, as smm_align_logz_bwd_f64 returns counts: p_used of a mandatory entry is 1;
+ * where pred(m) = {m-1} and succ(m-1) = {m}, S[.][m] is taken as E[.][m-1] and the transition's posterior as p_used[m-1]; the
+ * start posteriors S[0][m] are normalised by their own total (the identity's left side), so g_init adds up to u_i.
+ * Numerics of smm_align_logz_f64 for the span sums; a sum over pred(m) or succ(j) is a running per-class log-sum kept as an fp64
+ * logarithm (max + log1p(exp(min - max))), then one lse over at most n_states classes in fp64: exact for any dynamic range.
+ * Every sum is taken in a fixed order without atomics: two calls on the same inputs give the same bits.
+ *   - A video whose MANDATORY entries outnumber its frames, or with M kw < T, kw < 1, or an id outside [0, n_states), gets
+ *     logZ_o = -inf, zero gradient contributions and p_used 0; the error word stays clear and no table is read with such an id.
+ *   - A video with a path by counting but none of finite score (-inf table entries) likewise gets -inf, zeros and p_used 0.
+ *   - The error word is set, logZ_o is NaN, the gradient contributions and p_used are zero under smm_align_opt_f64's
+ *     conditions: cum[T][c] not finite for any state of the video, or a NaN or +inf in a table entry the recursion reads:
+ *     init[a_m] for first(m), trans[a_m][a_j] for j in pred(m), len[k][a_m] for k < kp, endpen[i][a_j] for end(j).
+ * smm_align_opt_logz_bwd_f64 must follow smm_align_opt_logz_f64 for the same batch, tables, transcripts and flags on the same
+ * workspace and stream: it reads the cum, h and gam columns and the columns' ranges the forward call left there.  g_elp,
+ * g_trans, g_init, g_len have smm_logz_bwd_f64's layouts and are overwritten entirely (zero fills are kernels); p_used
+ * (nullable) is laid out like `transcript` and written for every entry.  The workspace is smm_align_opt_logz_workspace_bytes
+ * (more than smm_align_logz_workspace_bytes: a fourth column per entry and n_states columns of running sums per video); the
+ * error word sits at smm_error_word_offset; staging the backward call clears the word, and the backward call sets it again
+ * for every video whose logz_o is NaN.  Enqueued on `stream` only; never synchronises; a video is never split over workgroups.
+ * SMM_ERR_ARG for a NULL required pointer (`optional` is one), non-monotone offsets or an empty transcript;
+ * SMM_ERR_UNSUPPORTED for SMM_SHAPE_NO_EOS, a transcript longer than SMM_MAX_TRANSCRIPT, c_max or k_rows beyond the compiled
+ * kernels; SMM_ERR_WORKSPACE below smm_align_opt_logz_workspace_bytes -- all before anything is staged.
+ */
+/* host only; 0 on whatever the calls refuse for the shape, the lengths or the offsets */
+size_t smm_align_opt_logz_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host, const int64_t *transcript_offset_host);
+int smm_align_opt_logz_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                           const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                           const double *elp, const double *trans, const double *init, const double *len_scores,
+                           const double *endpen, const int32_t *transcript, const uint8_t *optional /* dev, required */,
+                           const int64_t *transcript_offset_host, double *logz_o /* dev [b] */, void *workspace,
+                           size_t workspace_bytes, void *stream);
+int smm_align_opt_logz_bwd_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                               const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                               const double *elp, const double *trans, const double *init, const double *len_scores,
+                               const double *endpen, const int32_t *transcript, const uint8_t *optional,
+                               const int64_t *transcript_offset_host, const double *logz_o, const double *grad_logz /* nullable */,
+                               double *g_elp, double *g_trans, double *g_init, double *g_len,
+                               double *p_used /* dev double, laid out like transcript, nullable */, void *workspace,
+                               size_t workspace_bytes, void *stream);
 
 /*
  * Factor tables of every parameter group from the model parameters (training steps), and their chain rule.
