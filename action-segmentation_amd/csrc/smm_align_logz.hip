@@ -32,23 +32,9 @@
 #define SMM_ALIGN_R 3                                            // positions per thread (odd: smm_align_tile.h)
 #include "smm_align_tile.h"
 #include "smm_align_lse.h"
-#include "smm_launch.h"
 
 #define SMM_ALOGZ_OCC_THREADS 128
 #define SMM_ALOGZ_OCC_LD (SMM_MAX_STATES_DEV + 1)               // doubles per frame row in LDS: odd, one row per thread
-
-__device__ __forceinline__ bool alogz_load_transcript(const SmmAlignLogzArgs &a, int vid, int C, int M, int64_t t0, int *s_a,
-                                                      int *s_flag, int tid, int nthreads)
-{
-    for (int m = tid; m < M; m += nthreads) {
-        const int id = a.transcript[t0 + m];
-        const bool ok = id >= 0 && id < C;
-        s_a[m] = ok ? id : 0;                                  // (never used as an index when the flag is up)
-        if (!ok) s_flag[0] = 1;
-    }
-    __syncthreads();
-    return s_flag[0] == 0;
-}
 
 __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_logz_fwd_kernel(SmmAlignLogzArgs a)
 {
@@ -60,44 +46,30 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_logz_fwd_kernel(S
 
     const int tid = threadIdx.x;
     const int vid = a.order[blockIdx.x];
-    const SmmVideo mv = a.videos[vid];
-    const int T = mv.T, g = mv.group, cm = a.c_max, kw = mv.kp - 1;
-    const int C = a.n_states[g];
-    const int64_t t0 = a.toff[vid];
-    const int M = (int)(a.toff[vid + 1] - t0);
-    const double *elp = a.elp + (size_t)mv.frame_off * cm;
-    const double *trans = a.trans + (size_t)g * cm * cm;
-    const double *len = a.len + (size_t)g * a.k_rows * cm;
-    const size_t T1 = (size_t)T + 1;
-    double *cum = a.hist + mv.hist_off;                        // [C][T+1]
+    const AlignVideo v = align_video(a, vid);
+    const int T = v.T, cm = v.cm, kw = v.kw, M = v.M;
+    const double *trans = v.trans, *len = v.len, *cum = v.cum;
+    const size_t T1 = v.T1;
     double *hcol = a.cols + a.hoff[vid];                       // [M][T+1]
     double *gcol = hcol + (size_t)M * T1;                      // [M][T+1]
 
     if (tid < 2) s_flag[tid] = 0;
     __syncthreads();
-    const bool ids_ok = alogz_load_transcript(a, vid, C, M, t0, s_a, s_flag, tid, SMM_ALIGN_THREADS);
     // no alignment by counting (M segments of 1 .. kp - 1 frames each), or an id that is no state of this video
-    if (!ids_ok || M > T || kw < 1 || (int64_t)M * kw < T) {
+    if (!align_ids_ok(a, v, s_a, s_flag, tid, SMM_ALIGN_THREADS) || M > T || kw < 1 || (int64_t)M * kw < T) {
         if (tid == 0) a.logz[vid] = SMM_NEG_INF;
         return;
     }
 
-    // ---- the tables this transcript reads: a NaN or +inf among them reaches the DP
-    if (tid < M) {
-        const int c = s_a[tid];
-        double v = tid == 0 ? a.init[(size_t)g * cm + c] : trans[(size_t)c * cm + s_a[tid - 1]];
-        bool bad = align_bad_bits(v);
-        if (tid == M - 1 && a.endpen) bad |= align_bad_bits(a.endpen[(size_t)vid * cm + c]);
-        if (bad) s_flag[1] = 1;
-    }
-    if (align_prefix_sums(elp, cum, C, cm, T, s_h, tid)) s_flag[1] = 1;
-    if (tid == 0) hcol[0] = a.init[(size_t)g * cm + s_a[0]];
+    if (align_tables_bad(v, s_a, tid)) s_flag[1] = 1;
+    if (align_prefix_sums(v.elp, v.cum, v.C, cm, T, s_h, tid)) s_flag[1] = 1;
+    if (tid == 0) hcol[0] = v.init[s_a[0]];
     __threadfence_block();
     __syncthreads();
 
     // ---- columns
     int slo = 0, shi = 0;                                      // the positions of column m's sources (h[.][m])
-    const int d_all = (kw + 1 + SMM_ALIGN_R - 1) / SMM_ALIGN_R * SMM_ALIGN_R;   // distances -R .. d_all - 1 cover k = 1 .. kw
+    const int d_all = align_d_all(kw);
     for (int m = 0; m < M; ++m) {
         const int c = s_a[m];
         const bool last = m == M - 1;
@@ -109,11 +81,11 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_logz_fwd_kernel(S
         int lo, hi;
         align_range(m, M, T, kw, lo, hi);
         __syncthreads();                                       // the previous column's readers of s_len, s_h
-        if (alogz_stage_len(len, cm, c, kw, d_all, s_len, tid)) s_flag[1] = 1;
+        if (align_stage_len(len, cm, c, kw, d_all, s_len, tid)) s_flag[1] = 1;
         alogz_column(lo, hi, slo, shi, d_all, s_h, s_len, tid,
                      [&](int s) { return hm[s]; },
-                     [&](int n, double v) {
-                         const double gam = cumc[n] + v;
+                     [&](int n, double lse) {
+                         const double gam = cumc[n] + lse;
                          gm[n] = gam;
                          if (last) s_gam = gam;                // (the last column is the one cell n = T)
                          else hn[n] = (gam + tr) - cumn[n];
@@ -125,7 +97,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_logz_fwd_kernel(S
     __syncthreads();
 
     if (tid == 0) {
-        const double w_end = a.endpen ? a.endpen[(size_t)vid * cm + s_a[M - 1]] : 0.0;
+        const double w_end = v.endpen ? v.endpen[s_a[M - 1]] : 0.0;
         const double z = s_gam + w_end;
         const bool bad = s_flag[1] != 0 || align_bad_bits(z);
         if (bad) a.err[0] = 1;
@@ -147,30 +119,26 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_logz_bwd_kernel(S
         if (tid == 0 && smm_nan_bits(lz)) a.err[0] = 1;        // (staging cleared the word the forward call had set)
         return;
     }
-    const SmmVideo mv = a.videos[vid];
-    const int T = mv.T, g = mv.group, cm = a.c_max, kw = mv.kp - 1;
-    const int C = a.n_states[g];
-    const int64_t t0 = a.toff[vid];
-    const int M = (int)(a.toff[vid + 1] - t0);
-    const double *trans = a.trans + (size_t)g * cm * cm;
-    const double *len = a.len + (size_t)g * a.k_rows * cm;
-    const size_t T1 = (size_t)T + 1;
-    const double *cum = a.hist + mv.hist_off;                  // [C][T+1], the forward call's
+    const AlignVideo v = align_video(a, vid);
+    const int T = v.T, cm = v.cm, kw = v.kw, M = v.M;
+    const double *trans = v.trans, *len = v.len;
+    const size_t T1 = v.T1;
+    const double *cum = v.cum;                                 // [C][T+1], the forward call's
     double *qcol = a.cols + a.hoff[vid] + 2 * (size_t)M * T1;  // [M][T+1]
 
     if (tid < 2) s_flag[tid] = 0;
     __syncthreads();
-    if (!alogz_load_transcript(a, vid, C, M, t0, s_a, s_flag, tid, SMM_ALIGN_THREADS)) return;   // (a finite logZ_a had valid ids)
+    if (!align_ids_ok(a, v, s_a, s_flag, tid, SMM_ALIGN_THREADS)) return;   // (a finite logZ_a had valid ids)
     if (tid == 0) {
         const int c = s_a[M - 1];
-        const double w_end = a.endpen ? a.endpen[(size_t)vid * cm + c] : 0.0;
+        const double w_end = v.endpen ? v.endpen[c] : 0.0;
         qcol[(size_t)(M - 1) * T1 + T] = cum[(size_t)c * T1 + T] + w_end;
     }
     __threadfence_block();
     __syncthreads();
 
     // ---- columns M - 1 .. 0 in the walk coordinate p = T - n: the targets are the starts of segment m, the sources its ends
-    const int d_all = (kw + 1 + SMM_ALIGN_R - 1) / SMM_ALIGN_R * SMM_ALIGN_R;
+    const int d_all = align_d_all(kw);
     for (int m = M - 1; m >= 0; --m) {
         const int c = s_a[m];
         const int cp = m > 0 ? s_a[m - 1] : c;
@@ -181,7 +149,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_logz_bwd_kernel(S
         align_range(m, M, T, kw, lo, hi);
         align_start_range(m, M, T, kw, sl, sh);
         __syncthreads();                                       // the previous column's readers of s_len, s_h
-        alogz_stage_len(len, cm, c, kw, d_all, s_len, tid);
+        align_stage_len(len, cm, c, kw, d_all, s_len, tid);
         alogz_column(T - sh, T - sl, T - hi, T - lo, d_all, s_h, s_len, tid,
                      [&](int p) { return qm[T - p]; },
                      [&](int p, double bh) {
@@ -203,25 +171,22 @@ __global__ void __launch_bounds__(SMM_ALOGZ_OCC_THREADS) smm_align_logz_occ_kern
     __shared__ int s_a[SMM_MAX_TRANSCRIPT];
     __shared__ int s_flag[2];
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int vid = a.order[blockIdx.x];
     const double lz = a.logz[vid];
     if (align_nonfinite_bits(lz)) return;
-    const SmmVideo mv = a.videos[vid];
-    const int T = mv.T, g = mv.group, cm = a.c_max, kw = mv.kp - 1;
-    const int C = a.n_states[g];
-    const int64_t t0 = a.toff[vid];
-    const int M = (int)(a.toff[vid + 1] - t0);
-    const size_t T1 = (size_t)T + 1;
-    const double *cum = a.hist + mv.hist_off;
+    const AlignVideo v = align_video(a, vid);
+    const int T = v.T, cm = v.cm, kw = v.kw, C = v.C, M = v.M;
+    const size_t T1 = v.T1;
+    const double *cum = v.cum;
     const double *gcol = a.cols + a.hoff[vid] + (size_t)M * T1;
     const double *qcol = gcol + (size_t)M * T1;
     const double u = a.grad ? a.grad[vid] : 1.0;
-    double *g_elp = a.g_elp + (size_t)mv.frame_off * cm;
+    double *g_elp = a.g_elp + (size_t)v.frame_off * cm;
 
     if (tid < 2) s_flag[tid] = 0;
     __syncthreads();
-    if (!alogz_load_transcript(a, vid, C, M, t0, s_a, s_flag, tid, SMM_ALOGZ_OCC_THREADS)) return;
+    if (!align_ids_ok(a, v, s_a, s_flag, tid, SMM_ALOGZ_OCC_THREADS)) return;
     for (int m = tid; m < M; m += SMM_ALOGZ_OCC_THREADS) s_carry[m] = 0.0;
     __syncthreads();
 
@@ -240,29 +205,15 @@ __global__ void __launch_bounds__(SMM_ALOGZ_OCC_THREADS) smm_align_logz_occ_kern
                 const size_t i = (size_t)m * T1 + t;
                 e = exp((gcol[i] + (qcol[i] - cum[(size_t)c * T1 + t])) - lz);
             }
-            const double carry = s_carry[m];
-            // inclusive scan over the tile: within the wave by shuffles, the waves before this one through LDS
-            double x = e;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const double y = __shfl_up(x, off);
-                if (lane >= off) x = x + y;
-            }
-            if (lane == 63) s_wave[m & 1][wave] = x;
-            __syncthreads();
-            double before = carry;
-            for (int w = 0; w < wave; ++w) before = before + s_wave[m & 1][w];
-            const double p = before + x;
+            // inclusive scan over the tile on top of the entry's running total
+            const double p = align_block_scan(e, s_carry[m], s_wave[m & 1], tid);
             if (tid == SMM_ALOGZ_OCC_THREADS - 1) s_carry[m] = p;
             row[c] = row[c] + (prev - p);
             prev = p;
         }
         __syncthreads();
         const int nr = T - f0 < SMM_ALOGZ_OCC_THREADS ? T - f0 : SMM_ALOGZ_OCC_THREADS;
-        for (int e = tid; e < nr * cm; e += SMM_ALOGZ_OCC_THREADS) {
-            const int r = e / cm, c = e - r * cm;
-            g_elp[(size_t)f0 * cm + e] = c < C ? u * s_acc[r * SMM_ALOGZ_OCC_LD + c] : 0.0;
-        }
+        align_store_rows(g_elp + (size_t)f0 * cm, s_acc, SMM_ALOGZ_OCC_LD, nr, cm, C, u, tid, SMM_ALOGZ_OCC_THREADS);
         __syncthreads();
     }
 }
@@ -280,23 +231,20 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_logz_glen_kernel(
     const int vid = a.order[blockIdx.x];
     const double lz = a.logz[vid];
     if (align_nonfinite_bits(lz)) return;                      // (the reduction skips this video's part)
-    const SmmVideo mv = a.videos[vid];
-    const int T = mv.T, g = mv.group, cm = a.c_max;
-    const int kw = mv.kp - 1 < T ? mv.kp - 1 : T;              // (a segment is no longer than the video)
-    const int kw_cone = mv.kp - 1;
-    const int C = a.n_states[g];
-    const int64_t t0 = a.toff[vid];
-    const int M = (int)(a.toff[vid + 1] - t0);
+    const AlignVideo v = align_video(a, vid);
+    const int T = v.T, cm = v.cm, M = v.M;
+    const int kw = v.kw < T ? v.kw : T;                        // (a segment is no longer than the video)
+    const int kw_cone = v.kw;
     const int rows = a.k_rows < T + 1 ? a.k_rows : T + 1;
-    const double *len = a.len + (size_t)g * a.k_rows * cm;
-    const size_t T1 = (size_t)T + 1;
+    const double *len = v.len;
+    const size_t T1 = v.T1;
     const double *hcol = a.cols + a.hoff[vid];
     const double *qcol = hcol + 2 * (size_t)M * T1;
     double *part = a.part + a.poff[vid];
 
     if (tid < 2) s_flag[tid] = 0;
     __syncthreads();
-    if (!alogz_load_transcript(a, vid, C, M, t0, s_a, s_flag, tid, SMM_ALIGN_THREADS)) return;
+    if (!align_ids_ok(a, v, s_a, s_flag, tid, SMM_ALIGN_THREADS)) return;
     for (int e = tid; e < rows * cm; e += SMM_ALIGN_THREADS) part[e] = 0.0;
     __threadfence_block();
     __syncthreads();

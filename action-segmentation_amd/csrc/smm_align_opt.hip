@@ -10,7 +10,8 @@
 // Every add is one IEEE fp64 add in this association (max is exact): the twin's Viterbi on the lattice whose states are the
 // transcript positions, with trans'[m][j] = trans[a_m][a_j] for j in pred(m).
 //
-// smm_align_opt_kernel: one workgroup per video, smm_align_kernel's phases (smm_align.hip) and its span loop; what differs:
+// smm_align_opt_kernel: one workgroup per video, smm_align_kernel's phases (smm_align.hip) and its span loop, both from
+// smm_align_tile.h; what differs:
 //   - the cells of column m that lie on a complete alignment count the mandatory entries before (nb) and after (na) it:
 //       max(nb + 1, T - (M-1-m)(kp-1)) <= n <= min(T - na, (m+1)(kp-1));
 //     an optional entry has none when the mandatory ones fill the video;
@@ -28,7 +29,6 @@
 #define SMM_ALIGN_THREADS 256
 #define SMM_ALIGN_R 3                                            // positions per thread (odd: smm_align_tile.h)
 #include "smm_align_tile.h"
-#include "smm_launch.h"
 
 __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_kernel(SmmAlignArgs a)
 {
@@ -50,87 +50,42 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_kernel(SmmAli
 
     const int tid = threadIdx.x;
     const int vid = a.order[blockIdx.x];
-    const SmmVideo mv = a.videos[vid];
-    const int T = mv.T, g = mv.group, cm = a.c_max, kw = mv.kp - 1;
-    const int C = a.n_states[g];
-    const int64_t t0 = a.toff[vid];
-    const int M = (int)(a.toff[vid + 1] - t0);
-    const double *elp = a.elp + (size_t)mv.frame_off * cm;
-    const double *trans = a.trans + (size_t)g * cm * cm;
-    const double *len = a.len + (size_t)g * a.k_rows * cm;
-    const double *endpen = a.endpen ? a.endpen + (size_t)vid * cm : nullptr;
-    const int64_t *cmap = a.class_map ? a.class_map + (size_t)g * (cm + 1) : nullptr;
-    const size_t T1 = (size_t)T + 1;
-    double *cum = a.hist + mv.hist_off;                        // [C][T+1]
+    const AlignVideo v = align_video(a, vid);
+    const int T = v.T, cm = v.cm, kw = v.kw, M = v.M;
+    const double *trans = v.trans, *len = v.len, *endpen = v.endpen, *cum = v.cum;
+    const size_t T1 = v.T1;
     double *hcol = a.hcols + a.hoff[vid];                      // [M][T+1]
     double *G = hcol + (size_t)M * T1;                         // [C][T+1]
-    int64_t *spans = a.spans ? a.spans + (size_t)vid * (a.t_max + 1) : nullptr;
-    int64_t *labels = a.labels ? a.labels + mv.frame_off : nullptr;
-    int32_t *used = a.used ? a.used + t0 : nullptr;
+    int32_t *used = a.used ? a.used + v.t0 : nullptr;
 
     if (tid < 2) s_flag[tid] = 0;
     if (tid < SMM_MAX_STATES_DEV) { s_glo[tid] = 1; s_ghi[tid] = 0; }
     if (tid == 0) s_nact = 0;
-    __syncthreads();
     for (int m = tid; m < M; m += SMM_ALIGN_THREADS) {
-        const int id = a.transcript[t0 + m];
-        const bool ok = id >= 0 && id < C;
-        s_a[m] = ok ? id : 0;                                  // (never used as an index when the flag is up)
-        s_opt[m] = a.optional[t0 + m] != 0;
         s_gamT[m] = SMM_NEG_INF;
         s_used[m] = 0;
-        if (!ok) s_flag[0] = 1;
     }
     __syncthreads();
-    if (tid == 0) {
-        int nb = 0, head = 0;
-        for (int m = 0; m < M; ++m) {
-            s_nb[m] = nb;
-            s_plo[m] = head;
-            if (!s_opt[m]) { ++nb; head = m; }
-        }
-        s_nb[M] = nb;
-        s_plo[M] = head;
-    }
-    __syncthreads();
+    const bool ids_ok = align_load_opt(a, v, s_a, s_opt, s_nb, s_plo, s_flag, tid, SMM_ALIGN_THREADS);
     const int mand = s_nb[M];
     // no alignment by counting (the mandatory entries need a frame each; M segments of at most kp - 1 frames), or an id that is
     // no state of this video
-    if (s_flag[0] || mand > T || kw < 1 || (int64_t)M * kw < T) {
-        if (spans)
-            for (int q = tid; q <= a.t_max; q += SMM_ALIGN_THREADS) spans[q] = -1;
-        if (labels)
-            for (int f = tid; f < T; f += SMM_ALIGN_THREADS) labels[f] = -1;
+    if (!ids_ok || mand > T || kw < 1 || (int64_t)M * kw < T) {
+        align_write_none(a, v, vid, tid);
         if (used && tid < M) used[tid] = 0;
-        if (tid == 0) {
-            if (a.best) a.best[vid] = SMM_NEG_INF;
-            if (a.n_segs) a.n_segs[vid] = 0;
-        }
         return;
     }
 
-    // ---- the tables this transcript reads: a NaN or +inf among them reaches the DP
-    if (tid < M) {
-        const int c = s_a[tid];
-        bool bad = false;
-        if (s_nb[tid] == 0) {                                  // first(m)
-            const double v = a.init[(size_t)g * cm + c];
-            hcol[(size_t)tid * T1] = v;
-            bad |= align_bad_bits(v);
-        }
-        for (int j = s_plo[tid]; j < tid; ++j) bad |= align_bad_bits(trans[(size_t)c * cm + s_a[j]]);
-        if (endpen && tid >= s_plo[M]) bad |= align_bad_bits(endpen[c]);   // end(m)
-        if (bad) s_flag[1] = 1;
-    }
-
+    if (align_opt_tables_bad(v, s_a, s_nb, s_plo, tid)) s_flag[1] = 1;
+    if (tid < M && s_nb[tid] == 0) hcol[(size_t)tid * T1] = v.init[s_a[tid]];   // first(m)
     // ---- prefix sums (smm_align_tile.h): tiles of frames through LDS, lane c adds class c serially, cum[c][n] class-major
-    if (align_prefix_sums(elp, cum, C, cm, T, s_h, tid)) s_flag[1] = 1;
+    if (align_prefix_sums(v.elp, v.cum, v.C, cm, T, s_h, tid)) s_flag[1] = 1;
     __threadfence_block();
     __syncthreads();
 
     // ---- columns
     int ulo = 1, uhi = 0;                                      // the hull of the cones of pred(m): column m's sources besides 0
-    const int d_all = (kw + 1 + SMM_ALIGN_R - 1) / SMM_ALIGN_R * SMM_ALIGN_R;   // distances -R .. d_all - 1 cover k = 1 .. kw
+    const int d_all = align_d_all(kw);
     for (int m = 0; m < M; ++m) {
         const int c = s_a[m];
         const bool optm = s_opt[m] != 0, has_next = m + 1 < M, first = s_nb[m] == 0;
@@ -151,95 +106,38 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_kernel(SmmAli
         const int glo = optm ? s_glo[c] : 1, ghi = optm ? s_ghi[c] : 0;
         if (tid == 0) { s_slo[m] = ulo; s_shi[m] = uhi; }
         if (lo > hi || (!first && ulo > uhi)) continue;        // an optional entry the mandatory ones leave no frame for
-        for (int j = tid; j < d_all + 3 * SMM_ALIGN_R; j += SMM_ALIGN_THREADS) {
-            const int k = j - SMM_ALIGN_R;
-            double v = SMM_NEG_INF;
-            if (k >= 1 && k <= kw) {
-                v = len[(size_t)k * cm + c];
-                if (align_bad_bits(v)) s_flag[1] = 1;
-            }
-            s_len[j] = v;
-        }
+        if (align_stage_len(len, cm, c, kw, d_all, s_len, tid)) s_flag[1] = 1;
         if (m > 0 && s_opt[m - 1] && ulo <= uhi) {
             // ---- h[.][m] from the running maxima of the run before it
             if (tid < nact) s_tr[tid] = trans[(size_t)c * cm + s_act[tid]];
             __syncthreads();
-            for (int n = ulo + tid; n <= uhi; n += SMM_ALIGN_THREADS) {
-                double v = SMM_NEG_INF;
-                for (int i = 0; i < nact; ++i) {
-                    const int cc = s_act[i];
-                    if (n >= s_glo[cc] && n <= s_ghi[cc]) v = align_max(v, G[(size_t)cc * T1 + n] + s_tr[i]);
-                }
-                hm[n] = v - cumc[n];
-            }
+            for (int n = ulo + tid; n <= uhi; n += SMM_ALIGN_THREADS)
+                hm[n] = align_class_max(G, T1, n, nact, s_act, s_glo, s_ghi, s_tr) - cumc[n];
             __threadfence_block();
         }
-        const int s_lo = ulo <= uhi ? ulo : 0, s_hi = ulo <= uhi ? uhi : 0;
-        for (int tb = lo; tb <= hi; tb += SMM_ALIGN_P) {
-            // distances that can meet a source: tb - shi <= d <= tb + P - R - slo; whole steps of R, from -R (cell r at d has k = d + r)
-            const int slo = first && tb <= kw ? 0 : s_lo;
-            const int x = tb - s_hi, y = tb + SMM_ALIGN_P - SMM_ALIGN_R - slo + 1;
-            const int d_first = x <= 0 ? -SMM_ALIGN_R : x / SMM_ALIGN_R * SMM_ALIGN_R;
-            const int y_up = (y + SMM_ALIGN_R - 1) / SMM_ALIGN_R * SMM_ALIGN_R;
-            const int d_end = y_up < d_all ? y_up : d_all;
-            // LDS index i <-> position tb - OFF + i, for the positions tb - (d_end - 1) .. tb + P - R - d_first
-            const int i_first = SMM_ALIGN_OFF - (d_end - 1), i_last = SMM_ALIGN_OFF + SMM_ALIGN_P - SMM_ALIGN_R - d_first;
-            __syncthreads();                                   // the previous tile's readers; h[.][m] formed above
-            if (d_first < d_end)
-                for (int i = i_first + tid; i <= i_last; i += SMM_ALIGN_THREADS) {
-                    const int s = tb - SMM_ALIGN_OFF + i;
-                    s_h[i] = ((s >= ulo && s <= uhi) || (first && s == 0)) ? hm[s] : SMM_NEG_INF;
-                }
-            __syncthreads();
-            const int n0 = tb + tid * SMM_ALIGN_R;
-            if (n0 <= hi) {
-                double acc[SMM_ALIGN_R], lw[SMM_ALIGN_R];
+        align_tiles(lo, hi, first ? 0 : ulo, ulo <= uhi ? uhi : 0, d_all, s_h, tid,
+                    [&](int s) { return ((s >= ulo && s <= uhi) || (first && s == 0)) ? hm[s] : SMM_NEG_INF; },
+                    [&](int n0, int d_first, int d_end, const double *hp) {
+                        double acc[SMM_ALIGN_R];
+                        // (d_first >= d_end: no source is in reach of this tile, its cells are -inf)
+                        align_sweep_max(d_first < d_end ? d_first : d_end, d_end, hp, s_len, acc);
 #pragma unroll
-                for (int r = 0; r < SMM_ALIGN_R; ++r) acc[r] = SMM_NEG_INF;
-                if (d_first < d_end) {                         // (else no source is in reach of this tile: its cells are -inf)
-                    // lw[(d + r) % R] = len[d + r]; d_first is a multiple of R
-#pragma unroll
-                    for (int q = 0; q < SMM_ALIGN_R - 1; ++q) lw[q] = s_len[d_first + q + SMM_ALIGN_R];
-                    const double *hp = s_h + SMM_ALIGN_OFF + tid * SMM_ALIGN_R;
-                    for (int d0 = d_first; d0 < d_end; d0 += SMM_ALIGN_R) {
-#pragma unroll
-                        for (int j = 0; j < SMM_ALIGN_R; ++j) {
-                            const int d = d0 + j;
-                            const double hv = hp[-d];
-                            lw[(j + SMM_ALIGN_R - 1) % SMM_ALIGN_R] = s_len[d + 2 * SMM_ALIGN_R - 1];
-#pragma unroll
-                            for (int r = 0; r < SMM_ALIGN_R; ++r)
-                                acc[r] = align_max(acc[r], hv + lw[(j + r) % SMM_ALIGN_R]);
+                        for (int r = 0; r < SMM_ALIGN_R; ++r) {
+                            const int n = n0 + r;
+                            if (n <= hi) {
+                                const double gam = cumc[n] + acc[r];
+                                if (n == T) s_gamT[m] = gam;   // (read for end(m) only)
+                                if (direct) hn[n] = (gam + tr) - cumn[n];
+                                if (to_g) gc[n] = (n >= glo && n <= ghi) ? align_max(gc[n], gam) : gam;
+                            }
                         }
-                    }
-                }
-#pragma unroll
-                for (int r = 0; r < SMM_ALIGN_R; ++r) {
-                    const int n = n0 + r;
-                    if (n <= hi) {
-                        const double gam = cumc[n] + acc[r];
-                        if (n == T) s_gamT[m] = gam;           // (read for end(m) only)
-                        if (direct) hn[n] = (gam + tr) - cumn[n];
-                        if (to_g) gc[n] = (n >= glo && n <= ghi) ? align_max(gc[n], gam) : gam;
-                    }
-                }
-            }
-        }
+                    });
         if (to_g) {
             // the positions between this class's last cone and this one hold no cell
             if (glo <= ghi)
                 for (int n = ghi + 1 + tid; n < lo; n += SMM_ALIGN_THREADS) gc[n] = SMM_NEG_INF;
             __syncthreads();                                   // every reader of G's ranges in this column
-            if (tid == 0) {
-                int na2 = nact;
-                if (!optm) {
-                    for (int i = 0; i < nact; ++i) { s_glo[s_act[i]] = 1; s_ghi[s_act[i]] = 0; }
-                    na2 = 0;
-                }
-                if (glo > ghi) { s_act[na2++] = c; s_glo[c] = lo; }
-                s_ghi[c] = hi;
-                s_nact = na2;
-            }
+            if (tid == 0) align_hull(s_glo, s_ghi, s_act, &s_nact, !optm, c, lo, hi);
         }
         if (!optm || ulo > uhi) ulo = lo;
         uhi = hi;
@@ -275,9 +173,9 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_kernel(SmmAli
                     if (s == 0 ? nbi != 0 : (s < s_slo[i] || s > s_shi[i])) continue;
                     const int c = s_a[i];
                     const double w = cur < M ? trow[c] : (endpen ? endpen[c] : 0.0);
-                    const double v = (cum[(size_t)c * T1 + n] + (hcol[(size_t)i * T1 + s] + len[(size_t)k * cm + c])) + w;
+                    const double val = (cum[(size_t)c * T1 + n] + (hcol[(size_t)i * T1 + s] + len[(size_t)k * cm + c])) + w;
                     const int kk = k * SMM_MAX_TRANSCRIPT + i;
-                    if (v > mx || (v == mx && kk < key)) { mx = v; key = kk; }
+                    if (val > mx || (val == mx && kk < key)) { mx = val; key = kk; }
                 }
                 const double top = align_wave_max(mx);
                 key = align_wave_min(mx == top ? key : 0x7fffffff);
@@ -298,33 +196,10 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_kernel(SmmAli
     const bool failed = s_flag[1] != 0 || align_bad_bits(best);
     const bool empty = failed || align_nonfinite_bits(best);
 
-    // ---- outputs: the segment of position q is the last one that starts at or before it
+    // ---- outputs (smm_align_tile.h): the recorded segments carry the entries that got one
     const int seg0 = empty ? M : s_first_seg;
-    const int64_t eos = cmap ? cmap[C] : (int64_t)C;
-    const int q_end = a.t_max > T - 1 ? a.t_max : T - 1;
-    for (int q = tid; q <= q_end; q += SMM_ALIGN_THREADS) {
-        int64_t sp = -1, lb = -1;
-        if (!empty && q < T) {
-            int l = seg0, r = M - 1;                           // s_start[seg0] = 0 <= q
-            while (l < r) {
-                const int mid = (l + r + 1) >> 1;
-                if (s_start[mid] <= q) l = mid; else r = mid - 1;
-            }
-            const int id = s_a[s_entry[l]];
-            lb = cmap ? cmap[id] : (int64_t)id;
-            if (s_start[l] == q) sp = lb;
-        } else if (!empty && q == T) {
-            sp = eos;
-        }
-        if (spans && q <= a.t_max) spans[q] = sp;
-        if (labels && q < T) labels[q] = lb;
-    }
+    align_write_result(a, v, vid, s_start, [&](int l) { return s_a[s_entry[l]]; }, seg0, failed, empty, best, tid);
     if (used && tid < M) used[tid] = empty ? 0 : s_used[tid];
-    if (tid == 0) {
-        if (failed) a.err[0] = 1;
-        if (a.best) a.best[vid] = failed ? __builtin_nan("") : best;
-        if (a.n_segs) a.n_segs[vid] = empty ? 0 : M - seg0;
-    }
 }
 
 void smm_launch_align_opt(const SmmAlignArgs &a, hipStream_t stream)

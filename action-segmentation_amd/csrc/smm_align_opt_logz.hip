@@ -45,7 +45,6 @@
 #define SMM_ALIGN_R 3                                            // positions per thread (odd: smm_align_tile.h)
 #include "smm_align_tile.h"
 #include "smm_align_lse.h"
-#include "smm_launch.h"
 
 #define SMM_AOL_OCC_THREADS 128
 #define SMM_AOL_OCC_LD (SMM_MAX_STATES_DEV + 1)                 // doubles per frame row in LDS: odd, one row per thread
@@ -57,33 +56,6 @@ __device__ __forceinline__ double aol_add(double a, double b)
     const double hi = align_max(a, b), lo = __builtin_fmin(a, b);
     if (align_nonfinite_bits(hi)) return hi;
     return hi + log1p(exp(lo - hi));
-}
-
-// ids, flags, nb (mandatory entries before m; [M]: all of them) and plo (the first entry of pred(m); [M]: of the entries that
-// may end) of one video -> LDS; false where an id is no state of the video
-__device__ __forceinline__ bool aol_load(const SmmAlignOptLogzArgs &a, int C, int M, int64_t t0, int *s_a, int *s_opt, int *s_nb,
-                                         int *s_plo, int *s_flag, int tid, int nthreads)
-{
-    for (int m = tid; m < M; m += nthreads) {
-        const int id = a.transcript[t0 + m];
-        const bool ok = id >= 0 && id < C;
-        s_a[m] = ok ? id : 0;                                  // (never used as an index when the flag is up)
-        s_opt[m] = a.optional[t0 + m] != 0;
-        if (!ok) s_flag[0] = 1;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int nb = 0, head = 0;
-        for (int m = 0; m < M; ++m) {
-            s_nb[m] = nb;
-            s_plo[m] = head;
-            if (!s_opt[m]) { ++nb; head = m; }
-        }
-        s_nb[M] = nb;
-        s_plo[M] = head;
-    }
-    __syncthreads();
-    return s_flag[0] == 0;
 }
 
 // Add val(n), n in [lo, hi], to the running log-sum gc[.] of one class, whose values so far sit at [glo, ghi] (glo > ghi:
@@ -101,36 +73,11 @@ __device__ __forceinline__ void aol_fold(double *gc, int glo, int ghi, int lo, i
     }
 }
 
-// one thread: the classes' hulls after a fold of [lo, hi] into class c (lo > hi: nothing was added); reset: emptied first
-__device__ __forceinline__ void aol_hull(int *s_glo, int *s_ghi, int *s_act, int *s_nact, bool reset, int c, int lo, int hi)
-{
-    int n = *s_nact;
-    if (reset) {
-        for (int i = 0; i < n; ++i) { s_glo[s_act[i]] = 1; s_ghi[s_act[i]] = 0; }
-        n = 0;
-    }
-    if (lo <= hi) {
-        if (s_glo[c] > s_ghi[c]) {
-            s_act[n++] = c;
-            s_glo[c] = lo;
-            s_ghi[c] = hi;
-        } else {
-            s_glo[c] = lo < s_glo[c] ? lo : s_glo[c];
-            s_ghi[c] = hi > s_ghi[c] ? hi : s_ghi[c];
-        }
-    }
-    *s_nact = n;
-}
-
 // lse_i ( G[act_i][n] + tr[i] ) over the classes whose hull holds n
 __device__ __forceinline__ double aol_class_lse(const double *G, size_t T1, int n, int nact, const int *s_act, const int *s_glo,
                                                 const int *s_ghi, const double *s_tr)
 {
-    double mx = SMM_NEG_INF;
-    for (int i = 0; i < nact; ++i) {
-        const int cc = s_act[i];
-        if (n >= s_glo[cc] && n <= s_ghi[cc]) mx = align_max(mx, G[(size_t)cc * T1 + n] + s_tr[i]);
-    }
+    const double mx = align_class_max(G, T1, n, nact, s_act, s_glo, s_ghi, s_tr);
     const double ref = align_nonfinite_bits(mx) ? 0.0 : mx;
     double sum = 0.0;
     for (int i = 0; i < nact; ++i) {
@@ -153,7 +100,7 @@ __device__ __forceinline__ double aol_block_sum(double x, double *s_red, int tid
     return s;
 }
 
-__global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_logz_fwd_kernel(SmmAlignOptLogzArgs a)
+__global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_logz_fwd_kernel(SmmAlignLogzArgs a)
 {
     __shared__ double s_h[SMM_ALIGN_HS];
     __shared__ double s_len[SMM_ALIGN_LEN];
@@ -169,17 +116,10 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_logz_fwd_kern
 
     const int tid = threadIdx.x;
     const int vid = a.order[blockIdx.x];
-    const SmmVideo mv = a.videos[vid];
-    const int T = mv.T, g = mv.group, cm = a.c_max, kw = mv.kp - 1;
-    const int C = a.n_states[g];
-    const int64_t t0 = a.toff[vid];
-    const int M = (int)(a.toff[vid + 1] - t0);
-    const double *elp = a.elp + (size_t)mv.frame_off * cm;
-    const double *trans = a.trans + (size_t)g * cm * cm;
-    const double *len = a.len + (size_t)g * a.k_rows * cm;
-    const double *endpen = a.endpen ? a.endpen + (size_t)vid * cm : nullptr;
-    const size_t T1 = (size_t)T + 1;
-    double *cum = a.hist + mv.hist_off;                        // [C][T+1]
+    const AlignVideo v = align_video(a, vid);
+    const int T = v.T, cm = v.cm, kw = v.kw, M = v.M;
+    const double *trans = v.trans, *len = v.len, *endpen = v.endpen, *cum = v.cum;
+    const size_t T1 = v.T1;
     int *rng = reinterpret_cast<int *>(a.cols + a.hoff[vid]);  // [M][SMM_AOL_RNG], in 3 M doubles
     double *hcol = a.cols + a.hoff[vid] + 3 * (size_t)M;       // [M][T+1]
     double *gcol = hcol + (size_t)M * T1;                      // [M][T+1]
@@ -190,7 +130,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_logz_fwd_kern
     if (tid == 0) s_nact = 0;
     for (int m = tid; m < M; m += SMM_ALIGN_THREADS) s_gamT[m] = SMM_NEG_INF;
     __syncthreads();
-    const bool ids_ok = aol_load(a, C, M, t0, s_a, s_opt, s_nb, s_plo, s_flag, tid, SMM_ALIGN_THREADS);
+    const bool ids_ok = align_load_opt(a, v, s_a, s_opt, s_nb, s_plo, s_flag, tid, SMM_ALIGN_THREADS);
     const int mand = s_nb[M];
     // no alignment by counting (the mandatory entries need a frame each; M segments of at most kp - 1 frames), or an id that is
     // no state of this video
@@ -199,26 +139,15 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_logz_fwd_kern
         return;
     }
 
-    // ---- the tables this transcript reads: a NaN or +inf among them reaches the DP
-    if (tid < M) {
-        const int c = s_a[tid];
-        bool bad = false;
-        if (s_nb[tid] == 0) {                                  // first(m)
-            const double v = a.init[(size_t)g * cm + c];
-            hcol[(size_t)tid * T1] = v;
-            bad |= align_bad_bits(v);
-        }
-        for (int j = s_plo[tid]; j < tid; ++j) bad |= align_bad_bits(trans[(size_t)c * cm + s_a[j]]);
-        if (endpen && tid >= s_plo[M]) bad |= align_bad_bits(endpen[c]);   // end(m)
-        if (bad) s_flag[1] = 1;
-    }
-    if (align_prefix_sums(elp, cum, C, cm, T, s_h, tid)) s_flag[1] = 1;
+    if (align_opt_tables_bad(v, s_a, s_nb, s_plo, tid)) s_flag[1] = 1;
+    if (tid < M && s_nb[tid] == 0) hcol[(size_t)tid * T1] = v.init[s_a[tid]];   // first(m)
+    if (align_prefix_sums(v.elp, v.cum, v.C, cm, T, s_h, tid)) s_flag[1] = 1;
     __threadfence_block();
     __syncthreads();
 
     // ---- columns
     int ulo = 1, uhi = 0;                                      // the hull of the cones of pred(m): column m's sources besides 0
-    const int d_all = (kw + 1 + SMM_ALIGN_R - 1) / SMM_ALIGN_R * SMM_ALIGN_R;   // distances -R .. d_all - 1 cover k = 1 .. kw
+    const int d_all = align_d_all(kw);
     for (int m = 0; m < M; ++m) {
         const int c = s_a[m];
         const bool optm = s_opt[m] != 0, has_next = m + 1 < M, first = s_nb[m] == 0;
@@ -246,7 +175,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_logz_fwd_kern
             r[4] = active && first ? 1 : 0;
         }
         if (!active) continue;
-        if (alogz_stage_len(len, cm, c, kw, d_all, s_len, tid)) s_flag[1] = 1;
+        if (align_stage_len(len, cm, c, kw, d_all, s_len, tid)) s_flag[1] = 1;
         if (m > 0 && s_opt[m - 1] && ulo <= uhi) {
             // ---- h[.][m] from the running sums of the run before it
             if (tid < nact) s_tr[tid] = trans[(size_t)c * cm + s_act[tid]];
@@ -257,8 +186,8 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_logz_fwd_kern
         }
         alogz_column(lo, hi, first ? 0 : ulo, ulo <= uhi ? uhi : 0, d_all, s_h, s_len, tid,
                      [&](int s) { return ((s >= ulo && s <= uhi) || (first && s == 0)) ? hm[s] : SMM_NEG_INF; },
-                     [&](int n, double v) {
-                         const double gam = cumc[n] + v;
+                     [&](int n, double lse) {
+                         const double gam = cumc[n] + lse;
                          gm[n] = gam;
                          if (n == T) s_gamT[m] = gam;          // (read for end(m) only)
                          if (direct) hn[n] = (gam + tr) - cumn[n];
@@ -267,7 +196,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_logz_fwd_kern
             __threadfence_block();
             __syncthreads();                                   // the column's gam; every reader of G's hulls in this column
             aol_fold(G + (size_t)c * T1, glo, ghi, lo, hi, tid, [&](int n) { return gm[n]; });
-            if (tid == 0) aol_hull(s_glo, s_ghi, s_act, &s_nact, !optm, c, lo, hi);
+            if (tid == 0) align_hull(s_glo, s_ghi, s_act, &s_nact, !optm, c, lo, hi);
         }
         if (!optm || ulo > uhi) ulo = lo;
         uhi = hi;
@@ -289,7 +218,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_logz_fwd_kern
     }
 }
 
-__global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_logz_bwd_kernel(SmmAlignOptLogzArgs a)
+__global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_logz_bwd_kernel(SmmAlignLogzArgs a)
 {
     __shared__ double s_h[SMM_ALIGN_HS];
     __shared__ double s_len[SMM_ALIGN_LEN];
@@ -314,14 +243,11 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_logz_bwd_kern
             for (int m = tid; m < M; m += SMM_ALIGN_THREADS) a.p_used[t0 + m] = 0.0;
         return;
     }
-    const SmmVideo mv = a.videos[vid];
-    const int T = mv.T, g = mv.group, cm = a.c_max, kw = mv.kp - 1;
-    const int C = a.n_states[g];
-    const double *trans = a.trans + (size_t)g * cm * cm;
-    const double *len = a.len + (size_t)g * a.k_rows * cm;
-    const double *endpen = a.endpen ? a.endpen + (size_t)vid * cm : nullptr;
-    const size_t T1 = (size_t)T + 1;
-    const double *cum = a.hist + mv.hist_off;                  // [C][T+1], the forward call's
+    const AlignVideo v = align_video(a, vid);
+    const int T = v.T, cm = v.cm, kw = v.kw;
+    const double *trans = v.trans, *len = v.len, *endpen = v.endpen;
+    const size_t T1 = v.T1;
+    const double *cum = v.cum;                                 // [C][T+1], the forward call's
     const int *rng = reinterpret_cast<const int *>(a.cols + a.hoff[vid]);
     const double *hcol = a.cols + a.hoff[vid] + 3 * (size_t)M;
     const double *gcol = hcol + (size_t)M * T1;
@@ -338,12 +264,12 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_logz_bwd_kern
     if (tid == 0) s_nact = 0;
     for (int e = tid; e < cm * cm + cm; e += SMM_ALIGN_THREADS) tpart[e] = 0.0;
     __syncthreads();
-    if (!aol_load(a, C, M, t0, s_a, s_opt, s_nb, s_plo, s_flag, tid, SMM_ALIGN_THREADS)) return;   // (a finite logZ_o had valid ids)
+    if (!align_load_opt(a, v, s_a, s_opt, s_nb, s_plo, s_flag, tid, SMM_ALIGN_THREADS)) return;   // (a finite logZ_o had valid ids)
     __threadfence_block();
     __syncthreads();
 
     // ---- columns M - 1 .. 0 in the walk coordinate p = T - n: the targets are the starts of entry m, the sources its ends
-    const int d_all = (kw + 1 + SMM_ALIGN_R - 1) / SMM_ALIGN_R * SMM_ALIGN_R;
+    const int d_all = align_d_all(kw);
     for (int m = M - 1; m >= 0; --m) {
         const int *r = rng + SMM_AOL_RNG * m;
         const int elo = r[0], ehi = r[1], ulo = r[2], uhi = r[3], z = r[4];
@@ -369,10 +295,10 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_logz_bwd_kern
             if (tid < nact) s_tr[tid] = trans[(size_t)s_act[tid] * cm + c];
             __syncthreads();
             for (int n = elo + tid; n <= ehi; n += SMM_ALIGN_THREADS) {
-                double v;
-                if (n == T) v = endm ? (endpen ? endpen[c] : 0.0) : SMM_NEG_INF;
-                else v = aol_class_lse(B, T1, n, nact, s_act, s_glo, s_ghi, s_tr);
-                qm[n] = cumc[n] + v;
+                double bg;
+                if (n == T) bg = endm ? (endpen ? endpen[c] : 0.0) : SMM_NEG_INF;
+                else bg = aol_class_lse(B, T1, n, nact, s_act, s_glo, s_ghi, s_tr);
+                qm[n] = cumc[n] + bg;
             }
             for (int i = 0; i < nact; ++i) {
                 const int cc = s_act[i];
@@ -401,7 +327,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_logz_bwd_kern
         }
         // ---- bh[.][m]
         const int smin = z ? 0 : ulo, smax = ulo <= uhi ? uhi : 0;
-        alogz_stage_len(len, cm, c, kw, d_all, s_len, tid);
+        align_stage_len(len, cm, c, kw, d_all, s_len, tid);
         alogz_column(T - smax, T - smin, T - ehi, T - elo, d_all, s_h, s_len, tid,
                      [&](int p) { return qm[T - p]; },
                      [&](int p, double bh) {
@@ -420,7 +346,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_logz_bwd_kern
             const int glo = optm ? s_glo[c] : 1, ghi = optm ? s_ghi[c] : 0;
             if (ulo <= uhi) aol_fold(B + (size_t)c * T1, glo, ghi, ulo, uhi, tid, [&](int n) { return bhm[n] - cumc[n]; });
             __syncthreads();                                   // every reader of B's hulls in this column
-            if (tid == 0) aol_hull(s_glo, s_ghi, s_act, &s_nact, !optm, c, ulo, uhi);
+            if (tid == 0) align_hull(s_glo, s_ghi, s_act, &s_nact, !optm, c, ulo, uhi);
         }
         __threadfence_block();
     }
@@ -445,7 +371,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_logz_bwd_kern
 // g_elp of one video.  Thread j of a tile owns frame t = f0 + j and an LDS row of class sums; per transcript entry one block scan
 // of S[t][m] - E[t][m] over the tile on top of the entry's running total gives occ[t][m], which goes to the row's class a_m.
 // Frames beside the video's and the rows of a skipped video keep the zeros of the call's zero fill.
-__global__ void __launch_bounds__(SMM_AOL_OCC_THREADS) smm_align_opt_logz_occ_kernel(SmmAlignOptLogzArgs a)
+__global__ void __launch_bounds__(SMM_AOL_OCC_THREADS) smm_align_opt_logz_occ_kernel(SmmAlignLogzArgs a)
 {
     __shared__ double s_acc[SMM_AOL_OCC_THREADS * SMM_AOL_OCC_LD];
     __shared__ double s_carry[SMM_MAX_TRANSCRIPT];
@@ -453,33 +379,29 @@ __global__ void __launch_bounds__(SMM_AOL_OCC_THREADS) smm_align_opt_logz_occ_ke
     __shared__ int s_a[SMM_MAX_TRANSCRIPT];
     __shared__ int s_dir[SMM_MAX_TRANSCRIPT];                  // pred(m) = {m-1} and succ(m-1) = {m}: S[.][m] is E[.][m-1]
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int vid = a.order[blockIdx.x];
     const double lz = a.logz[vid];
     if (align_nonfinite_bits(lz)) return;
-    const SmmVideo mv = a.videos[vid];
-    const int T = mv.T, g = mv.group, cm = a.c_max;
-    const int C = a.n_states[g];
-    const int64_t t0 = a.toff[vid];
-    const int M = (int)(a.toff[vid + 1] - t0);
-    const size_t T1 = (size_t)T + 1;
-    const double *cum = a.hist + mv.hist_off;
+    const AlignVideo v = align_video(a, vid);
+    const int T = v.T, cm = v.cm, C = v.C, M = v.M;
+    const int64_t t0 = v.t0;
+    const size_t T1 = v.T1;
+    const double *cum = v.cum;
     const int *rng = reinterpret_cast<const int *>(a.cols + a.hoff[vid]);
     const double *hcol = a.cols + a.hoff[vid] + 3 * (size_t)M;
     const double *gcol = hcol + (size_t)M * T1;
     const double *qcol = gcol + (size_t)M * T1;
     const double *bhcol = qcol + (size_t)M * T1;
     const double u = a.grad ? a.grad[vid] : 1.0;
-    double *g_elp = a.g_elp + (size_t)mv.frame_off * cm;
+    double *g_elp = a.g_elp + (size_t)v.frame_off * cm;
     const int rows = a.k_rows < T + 1 ? a.k_rows : T + 1;
     const double lzb = a.part[a.poff[vid] + (size_t)rows * cm + (size_t)cm * cm + cm];   // the backward kernel's
 
-    for (int m = tid; m < M; m += SMM_AOL_OCC_THREADS) {
-        const int id = a.transcript[t0 + m];
-        s_a[m] = (id >= 0 && id < C) ? id : 0;                 // (a finite logZ_o had valid ids)
+    align_load_ids(a, v, s_a, tid, SMM_AOL_OCC_THREADS, [&](int m, bool) {   // (a finite logZ_o had valid ids)
         s_dir[m] = m > 0 && a.optional[t0 + m] == 0 && (m == 1 || a.optional[t0 + m - 1] == 0);
         s_carry[m] = 0.0;
-    }
+    });
     __syncthreads();
 
     double *row = s_acc + tid * SMM_AOL_OCC_LD;
@@ -502,28 +424,14 @@ __global__ void __launch_bounds__(SMM_AOL_OCC_THREADS) smm_align_opt_logz_occ_ke
                 }
                 if (t >= elo && t <= ehi) e = e - exp((gcol[i] + (qcol[i] - cum[(size_t)c * T1 + t])) - lz);
             }
-            const double carry = s_carry[m];
-            // inclusive scan over the tile: within the wave by shuffles, the waves before this one through LDS
-            double x = e;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const double y = __shfl_up(x, off);
-                if (lane >= off) x = x + y;
-            }
-            if (lane == 63) s_wave[m & 1][wave] = x;
-            __syncthreads();
-            double before = carry;
-            for (int w = 0; w < wave; ++w) before = before + s_wave[m & 1][w];
-            const double p = before + x;
+            // inclusive scan over the tile on top of the entry's running total
+            const double p = align_block_scan(e, s_carry[m], s_wave[m & 1], tid);
             if (tid == SMM_AOL_OCC_THREADS - 1) s_carry[m] = p;
             row[c] = row[c] + p;
         }
         __syncthreads();
         const int nr = T - f0 < SMM_AOL_OCC_THREADS ? T - f0 : SMM_AOL_OCC_THREADS;
-        for (int e = tid; e < nr * cm; e += SMM_AOL_OCC_THREADS) {
-            const int r = e / cm, c = e - r * cm;
-            g_elp[(size_t)f0 * cm + e] = c < C ? u * s_acc[r * SMM_AOL_OCC_LD + c] : 0.0;
-        }
+        align_store_rows(g_elp + (size_t)f0 * cm, s_acc, SMM_AOL_OCC_LD, nr, cm, C, u, tid, SMM_AOL_OCC_THREADS);
         __syncthreads();
     }
 }
@@ -531,7 +439,7 @@ __global__ void __launch_bounds__(SMM_AOL_OCC_THREADS) smm_align_opt_logz_occ_ke
 // The video's part of g_len, [rows][c_max] at part + poff[vid] with rows = min(k_rows, T + 1), without the factor u:
 //   part[k][c] = sum_{m: a_m = c} sum_s exp( h[s][m] + len[k][c] + q[s+k][m] - logZ_o )
 // Thread k owns row k (k = tid + 1, + THREADS, ...): the entries in order, the starts in order (0 first).
-__global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_logz_glen_kernel(SmmAlignOptLogzArgs a)
+__global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_logz_glen_kernel(SmmAlignLogzArgs a)
 {
     __shared__ int s_a[SMM_MAX_TRANSCRIPT];
 
@@ -539,24 +447,18 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_logz_glen_ker
     const int vid = a.order[blockIdx.x];
     const double lz = a.logz[vid];
     if (align_nonfinite_bits(lz)) return;                      // (the reduction skips this video's part)
-    const SmmVideo mv = a.videos[vid];
-    const int T = mv.T, g = mv.group, cm = a.c_max;
-    const int kw = mv.kp - 1 < T ? mv.kp - 1 : T;              // (a segment is no longer than the video)
-    const int C = a.n_states[g];
-    const int64_t t0 = a.toff[vid];
-    const int M = (int)(a.toff[vid + 1] - t0);
+    const AlignVideo v = align_video(a, vid);
+    const int T = v.T, cm = v.cm, M = v.M;
+    const int kw = v.kw < T ? v.kw : T;                        // (a segment is no longer than the video)
     const int rows = a.k_rows < T + 1 ? a.k_rows : T + 1;
-    const double *len = a.len + (size_t)g * a.k_rows * cm;
-    const size_t T1 = (size_t)T + 1;
+    const double *len = v.len;
+    const size_t T1 = v.T1;
     const int *rng = reinterpret_cast<const int *>(a.cols + a.hoff[vid]);
     const double *hcol = a.cols + a.hoff[vid] + 3 * (size_t)M;
     const double *qcol = hcol + 2 * (size_t)M * T1;
     double *part = a.part + a.poff[vid];
 
-    for (int m = tid; m < M; m += SMM_ALIGN_THREADS) {
-        const int id = a.transcript[t0 + m];
-        s_a[m] = (id >= 0 && id < C) ? id : 0;                 // (a finite logZ_o had valid ids)
-    }
+    align_load_ids(a, v, s_a, tid, SMM_ALIGN_THREADS, [](int, bool) {});   // (a finite logZ_o had valid ids)
     for (int e = tid; e < rows * cm; e += SMM_ALIGN_THREADS) part[e] = 0.0;
     __threadfence_block();
     __syncthreads();
@@ -582,7 +484,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_opt_logz_glen_ker
 
 // g_len[g][k][c], g_trans[g][c][c'], g_init[g][c] = sum over the group's videos, in video order, of u_i * the video's part;
 // rows a video does not have add nothing.  One thread per element: k_rows c_max of g_len, then c_max^2, then c_max.
-__global__ void __launch_bounds__(256) smm_align_opt_logz_reduce_kernel(SmmAlignOptLogzArgs a)
+__global__ void __launch_bounds__(256) smm_align_opt_logz_reduce_kernel(SmmAlignLogzArgs a)
 {
     const int cm = a.c_max, g = blockIdx.y;
     const int n_len = a.k_rows * cm, n_tab = cm * cm + cm;
@@ -606,12 +508,12 @@ __global__ void __launch_bounds__(256) smm_align_opt_logz_reduce_kernel(SmmAlign
     else a.g_init[(size_t)g * cm + (e - n_len - cm * cm)] = sum;
 }
 
-void smm_launch_align_opt_logz_fwd(const SmmAlignOptLogzArgs &a, hipStream_t stream)
+void smm_launch_align_opt_logz_fwd(const SmmAlignLogzArgs &a, hipStream_t stream)
 {
     hipLaunchKernelGGL(smm_align_opt_logz_fwd_kernel, dim3((unsigned)a.b), dim3(SMM_ALIGN_THREADS), 0, stream, a);
 }
 
-void smm_launch_align_opt_logz_bwd(const SmmAlignOptLogzArgs &a, hipStream_t stream)
+void smm_launch_align_opt_logz_bwd(const SmmAlignLogzArgs &a, hipStream_t stream)
 {
     hipLaunchKernelGGL(smm_align_opt_logz_bwd_kernel, dim3((unsigned)a.b), dim3(SMM_ALIGN_THREADS), 0, stream, a);
     hipLaunchKernelGGL(smm_align_opt_logz_occ_kernel, dim3((unsigned)a.b), dim3(SMM_AOL_OCC_THREADS), 0, stream, a);

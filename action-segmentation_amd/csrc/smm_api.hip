@@ -2028,73 +2028,106 @@ extern "C" int smm_mbr_f64(const smm_shape *shape, const int64_t *lengths_host, 
 }
 
 // ------------------------------------------------------------------------------------------------ forced alignment
-// Behind the plan's workspace: the transcript offsets, the offsets of the videos' h columns and the launch order (uploaded
-// per call: they are no part of a resident plan), then the columns, (M + extra) (T + 1) doubles per video: M h columns, and
-// for the alignment with optional entries c_max columns of running maxima.  cum uses the history area.
+// The transcript entry points (alignment, alignment with optional entries, transcript likelihood, the same with optional
+// entries) share one layout behind the plan's workspace: the transcript offsets, the offsets of the videos' columns and, where
+// the family has parts, of their parts, and the launch order (uploaded per call: they are no part of a resident plan), then the
+// videos' columns, then their parts.  cum uses the history area.  A family says how many doubles a video takes:
+struct AlignFamily {
+    size_t (*cells)(const smm_shape *s, int64_t m, int64_t t);   // the columns of a video with m entries and t frames
+    size_t (*part)(const smm_shape *s, int64_t t);               // its parts of the gradients; null: the family has none
+};
+static size_t glen_part(const smm_shape *s, int64_t t) { return (size_t)(std::min<int64_t>(s->k_rows, t + 1) * s->c_max); }
+// alignment: M h columns; with optional entries c_max columns of running maxima more
+static const AlignFamily ALIGN = {[](const smm_shape *, int64_t m, int64_t t) { return (size_t)(m * (t + 1)); }, nullptr};
+static const AlignFamily ALIGN_OPT = {[](const smm_shape *s, int64_t m, int64_t t) { return (size_t)((m + s->c_max) * (t + 1)); },
+                                      nullptr};
+// likelihood: the h, gam and q columns; the parts are g_len's rows, min(k_rows, T + 1) c_max doubles
+static const AlignFamily ALIGN_LOGZ = {[](const smm_shape *, int64_t m, int64_t t) { return (size_t)(3 * m * (t + 1)); }, glen_part};
+// ... with optional entries: the columns' ranges (3 M doubles), the h, gam, q and bh columns and c_max columns of running
+// per-class sums; the parts hold g_len's rows, then c_max^2 + c_max doubles of g_trans and g_init and the backward pass's own
+// logZ_o
+static const AlignFamily ALIGN_OPT_LOGZ = {
+    [](const smm_shape *s, int64_t m, int64_t t) { return (size_t)(3 * m + (4 * m + s->c_max) * (t + 1)); },
+    [](const smm_shape *s, int64_t t) { return glen_part(s, t) + (size_t)((int64_t)s->c_max * s->c_max + s->c_max + 1); }};
+
 struct AlignLayout {
-    size_t o_toff, o_hoff, o_order, meta_end, o_hcols, total;
+    size_t o_toff, o_hoff, o_poff, o_order, meta_end, o_cols, o_part, total;
 };
 
 // SMM_OK, or the refusal; everything here is host arithmetic on the caller's arrays
-static int align_layout(const smm_shape *s, const int64_t *lengths, const int64_t *toff, size_t extra, AlignLayout *lo)
+static int align_layout(const AlignFamily &f, const smm_shape *s, const int64_t *lengths, const int64_t *toff, AlignLayout *lo)
 {
     if (!shape_ok(s) || !lengths || !toff) return SMM_ERR_ARG;
     if ((s->flags & SMM_SHAPE_NO_EOS) || !limits_ok(s)) return SMM_ERR_UNSUPPORTED;
     if (toff[0] < 0 || !lengths_ok(s, lengths)) return SMM_ERR_ARG;
-    size_t cells = 0;
+    size_t cells = 0, part = 0;
     bool too_long = false;
     for (int i = 0; i < s->b; ++i) {
         const int64_t m = toff[i + 1] - toff[i];
         if (m < 1) return SMM_ERR_ARG;                      // non-monotone offsets, or an empty transcript
         too_long |= m > SMM_MAX_TRANSCRIPT;
-        cells += ((size_t)m + extra) * (size_t)(lengths[i] + 1);
+        cells += f.cells(s, m, lengths[i]);
+        if (f.part) part += f.part(s, lengths[i]);
     }
     if (too_long) return SMM_ERR_UNSUPPORTED;
     const size_t b = (size_t)s->b;
     Carver c{align_up(make_plan(s, lengths).total, 256)};
-    lo->o_toff = c.packed(sizeof(int64_t) * (b + 1));      // (the three arrays go up in one upload)
+    lo->o_toff = c.packed(sizeof(int64_t) * (b + 1));      // (the arrays up to meta_end go up in one upload)
     lo->o_hoff = c.packed(sizeof(int64_t) * b);
+    lo->o_poff = c.packed(f.part ? sizeof(int64_t) * b : 0);
     lo->o_order = c.take(sizeof(int32_t) * b);
     lo->meta_end = lo->o_order + sizeof(int32_t) * b;
-    lo->o_hcols = c.packed(sizeof(double) * cells);
+    lo->o_cols = c.packed(sizeof(double) * cells);
+    if (f.part) c.cur = align_up(c.cur, 256);
+    lo->o_part = c.packed(sizeof(double) * part);
     lo->total = c.cur;
     return SMM_OK;
 }
 
-// Both alignment entry points up to their launch: the refusals, the staging, this call's metadata, the kernel arguments.
-// `extra`: columns per video behind its h columns.
-static int align_prepare(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
-                         const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
-                         const double *elp, const double *trans, const double *init, const double *len_scores,
-                         const double *endpen, const int64_t *class_map, const int32_t *transcript,
-                         const int64_t *transcript_offset_host, int64_t *spans, int64_t *labels, double *best,
-                         int32_t *n_segs, void *workspace, size_t workspace_bytes, hipStream_t hs, size_t extra,
-                         SmmAlignArgs *out)
+static size_t align_workspace_bytes(const AlignFamily &f, const smm_shape *s, const int64_t *lengths, const int64_t *toff)
 {
-    if (!shape_ok(shape) || !lengths_host || !frame_offset_host || !n_states_host || !transcript_offset_host) return SMM_ERR_ARG;
-    if (!elp || !trans || !init || !len_scores || !transcript || !workspace) return SMM_ERR_ARG;
-    if (!spans && !labels && !best && !n_segs) return SMM_ERR_ARG;
     AlignLayout lo;
-    int rc = align_layout(shape, lengths_host, transcript_offset_host, extra, &lo);
+    return align_layout(f, s, lengths, toff, &lo) == SMM_OK ? lo.total : 0;
+}
+
+// what every transcript entry point has staged when it fills its kernel arguments
+struct AlignStaged {
+    Staged st;
+    const int32_t *order;      // [b] most lattice cells (T x M x span limit) first
+    const int64_t *toff, *hoff, *poff;   // poff: null in a family without parts
+    double *cols, *part;
+};
+
+// The refusals of the layout and of the workspace size, the staging, and this call's own metadata
+static int align_stage(const AlignFamily &f, const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                       const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                       const int64_t *transcript_offset_host, void *workspace, size_t workspace_bytes, hipStream_t hs,
+                       AlignStaged *out)
+{
+    AlignLayout lo;
+    int rc = align_layout(f, shape, lengths_host, transcript_offset_host, &lo);
     if (rc != SMM_OK) return rc;
     if (workspace_bytes < lo.total) return SMM_ERR_WORKSPACE;
-    Staged st;
-    rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes, hs, &st);
+    rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes, hs, &out->st);
     if (rc != SMM_OK) return rc;
-    // this call's own metadata: offsets, and the launch order -- most lattice cells (T x M x span limit) first
     const int b = shape->b;
     std::vector<char> host(lo.meta_end - lo.o_toff, 0);
     int64_t *h_toff = reinterpret_cast<int64_t *>(host.data());
     int64_t *h_hoff = reinterpret_cast<int64_t *>(host.data() + (lo.o_hoff - lo.o_toff));
+    int64_t *h_poff = reinterpret_cast<int64_t *>(host.data() + (lo.o_poff - lo.o_toff));
     int32_t *h_order = reinterpret_cast<int32_t *>(host.data() + (lo.o_order - lo.o_toff));
     std::vector<double> work(b);
-    int64_t cells = 0;
+    int64_t cells = 0, part = 0;
     for (int i = 0; i < b; ++i) {
         const int64_t m = transcript_offset_host[i + 1] - transcript_offset_host[i];
         const int k = kp_host ? kp_host[i] : std::min<int>(shape->k_rows, shape->t_max);
         h_toff[i] = transcript_offset_host[i];
         h_hoff[i] = cells;
-        cells += (m + (int64_t)extra) * (lengths_host[i] + 1);
+        cells += (int64_t)f.cells(shape, m, lengths_host[i]);
+        if (f.part) {
+            h_poff[i] = part;
+            part += (int64_t)f.part(shape, lengths_host[i]);
+        }
         work[i] = (double)m * (double)lengths_host[i] * (double)std::min<int64_t>(k, lengths_host[i]);
     }
     h_toff[b] = transcript_offset_host[b];
@@ -2102,16 +2135,37 @@ static int align_prepare(const smm_shape *shape, const int64_t *lengths_host, co
     std::stable_sort(h_order, h_order + b, [&](int x, int y) { return work[x] > work[y]; });
     char *base = static_cast<char *>(workspace);
     SMM_HIP((hipError_t)smm_upload_meta(base + lo.o_toff, host.data(), host.size(), hs));
+    out->order = reinterpret_cast<const int32_t *>(base + lo.o_order);
+    out->toff = reinterpret_cast<const int64_t *>(base + lo.o_toff);
+    out->hoff = reinterpret_cast<const int64_t *>(base + lo.o_hoff);
+    out->poff = f.part ? reinterpret_cast<const int64_t *>(base + lo.o_poff) : nullptr;
+    out->cols = reinterpret_cast<double *>(base + lo.o_cols);
+    out->part = reinterpret_cast<double *>(base + lo.o_part);
+    return SMM_OK;
+}
+
+// Both alignment entry points up to their launch: the refusals, the staging, the kernel arguments
+static int align_prepare(const AlignFamily &f, const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                         const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                         const double *elp, const double *trans, const double *init, const double *len_scores,
+                         const double *endpen, const int64_t *class_map, const int32_t *transcript,
+                         const int64_t *transcript_offset_host, int64_t *spans, int64_t *labels, double *best,
+                         int32_t *n_segs, void *workspace, size_t workspace_bytes, hipStream_t hs, SmmAlignArgs *out)
+{
+    if (!shape_ok(shape) || !lengths_host || !frame_offset_host || !n_states_host || !transcript_offset_host) return SMM_ERR_ARG;
+    if (!elp || !trans || !init || !len_scores || !transcript || !workspace) return SMM_ERR_ARG;
+    if (!spans && !labels && !best && !n_segs) return SMM_ERR_ARG;
+    AlignStaged sg;
+    const int rc = align_stage(f, shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host,
+                               transcript_offset_host, workspace, workspace_bytes, hs, &sg);
+    if (rc != SMM_OK) return rc;
     SmmAlignArgs a{};
-    a.videos = st.videos; a.n_states = st.n_states;
-    a.order = reinterpret_cast<const int32_t *>(base + lo.o_order);
-    a.toff = reinterpret_cast<const int64_t *>(base + lo.o_toff);
-    a.hoff = reinterpret_cast<const int64_t *>(base + lo.o_hoff);
+    a.videos = sg.st.videos; a.n_states = sg.st.n_states; a.order = sg.order; a.toff = sg.toff; a.hoff = sg.hoff;
     a.elp = elp; a.trans = trans; a.init = init; a.len = len_scores; a.endpen = endpen; a.class_map = class_map;
     a.transcript = transcript;
-    a.hist = st.hist; a.hcols = reinterpret_cast<double *>(base + lo.o_hcols);
-    a.spans = spans; a.labels = labels; a.best = best; a.n_segs = n_segs; a.err = st.err;
-    a.c_max = shape->c_max; a.k_rows = shape->k_rows; a.t_max = shape->t_max; a.b = b;
+    a.hist = sg.st.hist; a.hcols = sg.cols;
+    a.spans = spans; a.labels = labels; a.best = best; a.n_segs = n_segs; a.err = sg.st.err;
+    a.c_max = shape->c_max; a.k_rows = shape->k_rows; a.t_max = shape->t_max; a.b = shape->b;
     *out = a;
     return SMM_OK;
 }
@@ -2119,8 +2173,7 @@ static int align_prepare(const smm_shape *shape, const int64_t *lengths_host, co
 extern "C" size_t smm_align_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host,
                                             const int64_t *transcript_offset_host)
 {
-    AlignLayout lo;
-    return align_layout(shape, lengths_host, transcript_offset_host, 0, &lo) == SMM_OK ? lo.total : 0;
+    return align_workspace_bytes(ALIGN, shape, lengths_host, transcript_offset_host);
 }
 
 extern "C" int smm_align_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
@@ -2132,22 +2185,20 @@ extern "C" int smm_align_f64(const smm_shape *shape, const int64_t *lengths_host
 {
     hipStream_t hs = static_cast<hipStream_t>(stream);
     SmmAlignArgs a;
-    const int rc = align_prepare(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp, trans, init,
-                                 len_scores, endpen, class_map, transcript, transcript_offset_host, spans, labels, best, n_segs,
-                                 workspace, workspace_bytes, hs, 0, &a);
+    const int rc = align_prepare(ALIGN, shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp, trans,
+                                 init, len_scores, endpen, class_map, transcript, transcript_offset_host, spans, labels, best,
+                                 n_segs, workspace, workspace_bytes, hs, &a);
     if (rc != SMM_OK) return rc;
     smm_launch_align(a, hs);
     SMM_HIP(hipGetLastError());
     return SMM_OK;
 }
 
-// ... with optional entries (smm_align_opt.hip): the running maxima take c_max columns per video more
+// ... with optional entries (smm_align_opt.hip).  (The family reads shape->c_max behind the layout's shape_ok only.)
 extern "C" size_t smm_align_opt_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host,
                                                 const int64_t *transcript_offset_host)
 {
-    AlignLayout lo;
-    if (!shape_ok(shape)) return 0;
-    return align_layout(shape, lengths_host, transcript_offset_host, (size_t)shape->c_max, &lo) == SMM_OK ? lo.total : 0;
+    return align_workspace_bytes(ALIGN_OPT, shape, lengths_host, transcript_offset_host);
 }
 
 extern "C" int smm_align_opt_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
@@ -2161,9 +2212,9 @@ extern "C" int smm_align_opt_f64(const smm_shape *shape, const int64_t *lengths_
     if (!optional) return SMM_ERR_ARG;
     hipStream_t hs = static_cast<hipStream_t>(stream);
     SmmAlignArgs a;
-    const int rc = align_prepare(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp, trans, init,
-                                 len_scores, endpen, class_map, transcript, transcript_offset_host, spans, labels, best, n_segs,
-                                 workspace, workspace_bytes, hs, shape_ok(shape) ? (size_t)shape->c_max : 0, &a);
+    const int rc = align_prepare(ALIGN_OPT, shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp,
+                                 trans, init, len_scores, endpen, class_map, transcript, transcript_offset_host, spans, labels,
+                                 best, n_segs, workspace, workspace_bytes, hs, &a);
     if (rc != SMM_OK) return rc;
     a.optional = optional; a.used = used;
     smm_launch_align_opt(a, hs);
@@ -2172,97 +2223,47 @@ extern "C" int smm_align_opt_f64(const smm_shape *shape, const int64_t *lengths_
 }
 
 // ------------------------------------------------------------------------------------------------ transcript likelihood
-// Behind the plan's workspace: the transcript offsets, the offsets of the videos' columns and of their parts of g_len, the launch
-// order (uploaded per call), then per video the h, gam and q columns, 3 M (T + 1) doubles, then the parts of g_len,
-// min(k_rows, T + 1) c_max doubles per video.  cum uses the history area.
-struct AlignLogzLayout {
-    size_t o_toff, o_hoff, o_poff, o_order, meta_end, o_cols, o_part, total;
-};
-
-static int align_logz_layout(const smm_shape *s, const int64_t *lengths, const int64_t *toff, AlignLogzLayout *lo)
+// What the four likelihood entry points (forward and backward, exact and with optional entries) share up to their launch:
+// the refusals, the staging, the kernel arguments but for `optional` and what the backward call adds
+static int align_logz_prepare(const AlignFamily &f, const smm_shape *shape, const int64_t *lengths_host,
+                              const int64_t *frame_offset_host, const int32_t *group_host, const int32_t *kp_host,
+                              const int32_t *n_states_host, const double *elp, const double *trans, const double *init,
+                              const double *len_scores, const double *endpen, const int32_t *transcript,
+                              const int64_t *transcript_offset_host, const double *logz, void *workspace, size_t workspace_bytes,
+                              hipStream_t hs, SmmAlignLogzArgs *a)
 {
-    if (!shape_ok(s) || !lengths || !toff) return SMM_ERR_ARG;
-    if ((s->flags & SMM_SHAPE_NO_EOS) || !limits_ok(s)) return SMM_ERR_UNSUPPORTED;
-    if (toff[0] < 0 || !lengths_ok(s, lengths)) return SMM_ERR_ARG;
-    size_t cells = 0, part = 0;
-    bool too_long = false;
-    for (int i = 0; i < s->b; ++i) {
-        const int64_t m = toff[i + 1] - toff[i];
-        if (m < 1) return SMM_ERR_ARG;                      // non-monotone offsets, or an empty transcript
-        too_long |= m > SMM_MAX_TRANSCRIPT;
-        cells += 3 * (size_t)m * (size_t)(lengths[i] + 1);
-        part += (size_t)std::min<int64_t>(s->k_rows, lengths[i] + 1) * (size_t)s->c_max;
-    }
-    if (too_long) return SMM_ERR_UNSUPPORTED;
-    const size_t b = (size_t)s->b;
-    Carver c{align_up(make_plan(s, lengths).total, 256)};
-    lo->o_toff = c.packed(sizeof(int64_t) * (b + 1));      // (the four arrays go up in one upload)
-    lo->o_hoff = c.packed(sizeof(int64_t) * b);
-    lo->o_poff = c.packed(sizeof(int64_t) * b);
-    lo->o_order = c.take(sizeof(int32_t) * b);
-    lo->meta_end = lo->o_order + sizeof(int32_t) * b;
-    lo->o_cols = c.take(sizeof(double) * cells);
-    lo->o_part = c.packed(sizeof(double) * part);
-    lo->total = c.cur;
+    if (!shape_ok(shape) || !lengths_host || !frame_offset_host || !n_states_host || !transcript_offset_host) return SMM_ERR_ARG;
+    if (!elp || !trans || !init || !len_scores || !transcript || !logz || !workspace) return SMM_ERR_ARG;
+    AlignStaged sg;
+    const int rc = align_stage(f, shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host,
+                               transcript_offset_host, workspace, workspace_bytes, hs, &sg);
+    if (rc != SMM_OK) return rc;
+    *a = SmmAlignLogzArgs{};
+    a->videos = sg.st.videos; a->n_states = sg.st.n_states; a->order = sg.order;
+    a->toff = sg.toff; a->hoff = sg.hoff; a->poff = sg.poff;
+    a->elp = elp; a->trans = trans; a->init = init; a->len = len_scores; a->endpen = endpen; a->transcript = transcript;
+    a->hist = sg.st.hist; a->cols = sg.cols; a->part = sg.part;
+    a->logz = const_cast<double *>(logz);                       // (the backward launches only read it)
+    a->err = sg.st.err;
+    a->c_max = shape->c_max; a->k_rows = shape->k_rows; a->b = shape->b; a->n_groups = shape->n_groups;
+    return SMM_OK;
+}
+
+// ... and the backward calls behind it: the gradients' arguments, and g_elp's zeros -- frames no video covers and the rows of
+// skipped videos stay zero; the other gradients are written whole by their kernels
+static int align_logz_bwd_outputs(const smm_shape *shape, const double *grad_logz, double *g_elp, double *g_trans, double *g_init,
+                                  double *g_len, hipStream_t hs, SmmAlignLogzArgs *a)
+{
+    a->grad = grad_logz;
+    a->g_elp = g_elp; a->g_trans = g_trans; a->g_init = g_init; a->g_len = g_len;
+    SMM_HIP((hipError_t)smm_zero_async(g_elp, sizeof(double) * (size_t)shape->total_frames * shape->c_max, hs));
     return SMM_OK;
 }
 
 extern "C" size_t smm_align_logz_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host,
                                                  const int64_t *transcript_offset_host)
 {
-    AlignLogzLayout lo;
-    return align_logz_layout(shape, lengths_host, transcript_offset_host, &lo) == SMM_OK ? lo.total : 0;
-}
-
-// what the forward and the backward call share: the refusals, staging, this call's own metadata, the launch arguments
-static int align_logz_stage(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
-                            const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
-                            const int64_t *transcript_offset_host, void *workspace, size_t workspace_bytes, hipStream_t hs,
-                            SmmAlignLogzArgs *a)
-{
-    AlignLogzLayout lo;
-    int rc = align_logz_layout(shape, lengths_host, transcript_offset_host, &lo);
-    if (rc != SMM_OK) return rc;
-    if (workspace_bytes < lo.total) return SMM_ERR_WORKSPACE;
-    Staged st;
-    rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes, hs, &st);
-    if (rc != SMM_OK) return rc;
-    // offsets, and the launch order -- most lattice cells (T x M x span limit) first
-    const int b = shape->b;
-    std::vector<char> host(lo.meta_end - lo.o_toff, 0);
-    int64_t *h_toff = reinterpret_cast<int64_t *>(host.data());
-    int64_t *h_hoff = reinterpret_cast<int64_t *>(host.data() + (lo.o_hoff - lo.o_toff));
-    int64_t *h_poff = reinterpret_cast<int64_t *>(host.data() + (lo.o_poff - lo.o_toff));
-    int32_t *h_order = reinterpret_cast<int32_t *>(host.data() + (lo.o_order - lo.o_toff));
-    std::vector<double> work(b);
-    int64_t cells = 0, part = 0;
-    for (int i = 0; i < b; ++i) {
-        const int64_t m = transcript_offset_host[i + 1] - transcript_offset_host[i];
-        const int k = kp_host ? kp_host[i] : std::min<int>(shape->k_rows, shape->t_max);
-        h_toff[i] = transcript_offset_host[i];
-        h_hoff[i] = cells;
-        h_poff[i] = part;
-        cells += 3 * m * (lengths_host[i] + 1);
-        part += std::min<int64_t>(shape->k_rows, lengths_host[i] + 1) * shape->c_max;
-        work[i] = (double)m * (double)lengths_host[i] * (double)std::min<int64_t>(k, lengths_host[i]);
-    }
-    h_toff[b] = transcript_offset_host[b];
-    std::iota(h_order, h_order + b, 0);
-    std::stable_sort(h_order, h_order + b, [&](int x, int y) { return work[x] > work[y]; });
-    char *base = static_cast<char *>(workspace);
-    SMM_HIP((hipError_t)smm_upload_meta(base + lo.o_toff, host.data(), host.size(), hs));
-    *a = SmmAlignLogzArgs{};
-    a->videos = st.videos; a->n_states = st.n_states;
-    a->order = reinterpret_cast<const int32_t *>(base + lo.o_order);
-    a->toff = reinterpret_cast<const int64_t *>(base + lo.o_toff);
-    a->hoff = reinterpret_cast<const int64_t *>(base + lo.o_hoff);
-    a->poff = reinterpret_cast<const int64_t *>(base + lo.o_poff);
-    a->hist = st.hist;
-    a->cols = reinterpret_cast<double *>(base + lo.o_cols);
-    a->part = reinterpret_cast<double *>(base + lo.o_part);
-    a->err = st.err;
-    a->c_max = shape->c_max; a->k_rows = shape->k_rows; a->b = b; a->n_groups = shape->n_groups;
-    return SMM_OK;
+    return align_workspace_bytes(ALIGN_LOGZ, shape, lengths_host, transcript_offset_host);
 }
 
 extern "C" int smm_align_logz_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
@@ -2271,15 +2272,12 @@ extern "C" int smm_align_logz_f64(const smm_shape *shape, const int64_t *lengths
                                   const double *endpen, const int32_t *transcript, const int64_t *transcript_offset_host,
                                   double *logz_a, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!shape_ok(shape) || !lengths_host || !frame_offset_host || !n_states_host || !transcript_offset_host) return SMM_ERR_ARG;
-    if (!elp || !trans || !init || !len_scores || !transcript || !logz_a || !workspace) return SMM_ERR_ARG;
     hipStream_t hs = static_cast<hipStream_t>(stream);
     SmmAlignLogzArgs a;
-    const int rc = align_logz_stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host,
-                                    transcript_offset_host, workspace, workspace_bytes, hs, &a);
+    const int rc = align_logz_prepare(ALIGN_LOGZ, shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp,
+                                      trans, init, len_scores, endpen, transcript, transcript_offset_host, logz_a, workspace,
+                                      workspace_bytes, hs, &a);
     if (rc != SMM_OK) return rc;
-    a.elp = elp; a.trans = trans; a.init = init; a.len = len_scores; a.endpen = endpen; a.transcript = transcript;
-    a.logz = logz_a;
     smm_launch_align_logz_fwd(a, hs);
     SMM_HIP(hipGetLastError());
     return SMM_OK;
@@ -2292,119 +2290,24 @@ extern "C" int smm_align_logz_bwd_f64(const smm_shape *shape, const int64_t *len
                                       const double *logz_a, const double *grad_logz, double *g_elp, double *g_trans,
                                       double *g_init, double *g_len, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!shape_ok(shape) || !lengths_host || !frame_offset_host || !n_states_host || !transcript_offset_host) return SMM_ERR_ARG;
-    if (!elp || !trans || !init || !len_scores || !transcript || !logz_a || !workspace) return SMM_ERR_ARG;
     if (!g_elp || !g_trans || !g_init || !g_len) return SMM_ERR_ARG;
     hipStream_t hs = static_cast<hipStream_t>(stream);
     SmmAlignLogzArgs a;
-    const int rc = align_logz_stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host,
-                                    transcript_offset_host, workspace, workspace_bytes, hs, &a);
+    int rc = align_logz_prepare(ALIGN_LOGZ, shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp,
+                                trans, init, len_scores, endpen, transcript, transcript_offset_host, logz_a, workspace,
+                                workspace_bytes, hs, &a);
+    if (rc == SMM_OK) rc = align_logz_bwd_outputs(shape, grad_logz, g_elp, g_trans, g_init, g_len, hs, &a);
     if (rc != SMM_OK) return rc;
-    a.elp = elp; a.trans = trans; a.init = init; a.len = len_scores; a.endpen = endpen; a.transcript = transcript;
-    a.logz = const_cast<double *>(logz_a);                      // (the backward launches only read it)
-    a.grad = grad_logz;
-    a.g_elp = g_elp; a.g_trans = g_trans; a.g_init = g_init; a.g_len = g_len;
-    // g_elp: frames no video covers and the rows of skipped videos stay zero; the other three are written whole by their kernels
-    SMM_HIP((hipError_t)smm_zero_async(g_elp, sizeof(double) * (size_t)shape->total_frames * shape->c_max, hs));
     smm_launch_align_logz_bwd(a, hs);
     SMM_HIP(hipGetLastError());
     return SMM_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ ... with optional entries
-// As above; per video the columns' ranges (3 M doubles), the h, gam, q and bh columns, 4 M (T + 1) doubles, and c_max columns
-// of running per-class sums; the parts hold g_len's rows, then c_max^2 + c_max doubles of g_trans and g_init and the
-// backward pass's own logZ_o.
-static size_t align_opt_logz_cells(int64_t m, int64_t t, int c_max) { return (size_t)(3 * m + (4 * m + c_max) * (t + 1)); }
-static size_t align_opt_logz_part(const smm_shape *s, int64_t t)
-{
-    return (size_t)(std::min<int64_t>(s->k_rows, t + 1) * s->c_max + (int64_t)s->c_max * s->c_max + s->c_max + 1);
-}
-
-static int align_opt_logz_layout(const smm_shape *s, const int64_t *lengths, const int64_t *toff, AlignLogzLayout *lo)
-{
-    if (!shape_ok(s) || !lengths || !toff) return SMM_ERR_ARG;
-    if ((s->flags & SMM_SHAPE_NO_EOS) || !limits_ok(s)) return SMM_ERR_UNSUPPORTED;
-    if (toff[0] < 0 || !lengths_ok(s, lengths)) return SMM_ERR_ARG;
-    size_t cells = 0, part = 0;
-    bool too_long = false;
-    for (int i = 0; i < s->b; ++i) {
-        const int64_t m = toff[i + 1] - toff[i];
-        if (m < 1) return SMM_ERR_ARG;                      // non-monotone offsets, or an empty transcript
-        too_long |= m > SMM_MAX_TRANSCRIPT;
-        cells += align_opt_logz_cells(m, lengths[i], s->c_max);
-        part += align_opt_logz_part(s, lengths[i]);
-    }
-    if (too_long) return SMM_ERR_UNSUPPORTED;
-    const size_t b = (size_t)s->b;
-    Carver c{align_up(make_plan(s, lengths).total, 256)};
-    lo->o_toff = c.packed(sizeof(int64_t) * (b + 1));      // (the four arrays go up in one upload)
-    lo->o_hoff = c.packed(sizeof(int64_t) * b);
-    lo->o_poff = c.packed(sizeof(int64_t) * b);
-    lo->o_order = c.take(sizeof(int32_t) * b);
-    lo->meta_end = lo->o_order + sizeof(int32_t) * b;
-    lo->o_cols = c.take(sizeof(double) * cells);
-    lo->o_part = c.packed(sizeof(double) * part);
-    lo->total = c.cur;
-    return SMM_OK;
-}
-
 extern "C" size_t smm_align_opt_logz_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host,
                                                      const int64_t *transcript_offset_host)
 {
-    AlignLogzLayout lo;
-    return align_opt_logz_layout(shape, lengths_host, transcript_offset_host, &lo) == SMM_OK ? lo.total : 0;
-}
-
-// what the forward and the backward call share: the refusals, staging, this call's own metadata, the launch arguments
-static int align_opt_logz_stage(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
-                                const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
-                                const int64_t *transcript_offset_host, void *workspace, size_t workspace_bytes, hipStream_t hs,
-                                SmmAlignOptLogzArgs *a)
-{
-    AlignLogzLayout lo;
-    int rc = align_opt_logz_layout(shape, lengths_host, transcript_offset_host, &lo);
-    if (rc != SMM_OK) return rc;
-    if (workspace_bytes < lo.total) return SMM_ERR_WORKSPACE;
-    Staged st;
-    rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes, hs, &st);
-    if (rc != SMM_OK) return rc;
-    // offsets, and the launch order -- most lattice cells (T x M x span limit) first
-    const int b = shape->b;
-    std::vector<char> host(lo.meta_end - lo.o_toff, 0);
-    int64_t *h_toff = reinterpret_cast<int64_t *>(host.data());
-    int64_t *h_hoff = reinterpret_cast<int64_t *>(host.data() + (lo.o_hoff - lo.o_toff));
-    int64_t *h_poff = reinterpret_cast<int64_t *>(host.data() + (lo.o_poff - lo.o_toff));
-    int32_t *h_order = reinterpret_cast<int32_t *>(host.data() + (lo.o_order - lo.o_toff));
-    std::vector<double> work(b);
-    int64_t cells = 0, part = 0;
-    for (int i = 0; i < b; ++i) {
-        const int64_t m = transcript_offset_host[i + 1] - transcript_offset_host[i];
-        const int k = kp_host ? kp_host[i] : std::min<int>(shape->k_rows, shape->t_max);
-        h_toff[i] = transcript_offset_host[i];
-        h_hoff[i] = cells;
-        h_poff[i] = part;
-        cells += (int64_t)align_opt_logz_cells(m, lengths_host[i], shape->c_max);
-        part += (int64_t)align_opt_logz_part(shape, lengths_host[i]);
-        work[i] = (double)m * (double)lengths_host[i] * (double)std::min<int64_t>(k, lengths_host[i]);
-    }
-    h_toff[b] = transcript_offset_host[b];
-    std::iota(h_order, h_order + b, 0);
-    std::stable_sort(h_order, h_order + b, [&](int x, int y) { return work[x] > work[y]; });
-    char *base = static_cast<char *>(workspace);
-    SMM_HIP((hipError_t)smm_upload_meta(base + lo.o_toff, host.data(), host.size(), hs));
-    *a = SmmAlignOptLogzArgs{};
-    a->videos = st.videos; a->n_states = st.n_states;
-    a->order = reinterpret_cast<const int32_t *>(base + lo.o_order);
-    a->toff = reinterpret_cast<const int64_t *>(base + lo.o_toff);
-    a->hoff = reinterpret_cast<const int64_t *>(base + lo.o_hoff);
-    a->poff = reinterpret_cast<const int64_t *>(base + lo.o_poff);
-    a->hist = st.hist;
-    a->cols = reinterpret_cast<double *>(base + lo.o_cols);
-    a->part = reinterpret_cast<double *>(base + lo.o_part);
-    a->err = st.err;
-    a->c_max = shape->c_max; a->k_rows = shape->k_rows; a->b = b; a->n_groups = shape->n_groups;
-    return SMM_OK;
+    return align_workspace_bytes(ALIGN_OPT_LOGZ, shape, lengths_host, transcript_offset_host);
 }
 
 extern "C" int smm_align_opt_logz_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
@@ -2414,16 +2317,14 @@ extern "C" int smm_align_opt_logz_f64(const smm_shape *shape, const int64_t *len
                                       const int64_t *transcript_offset_host, double *logz_o, void *workspace,
                                       size_t workspace_bytes, void *stream)
 {
-    if (!shape_ok(shape) || !lengths_host || !frame_offset_host || !n_states_host || !transcript_offset_host) return SMM_ERR_ARG;
-    if (!elp || !trans || !init || !len_scores || !transcript || !optional || !logz_o || !workspace) return SMM_ERR_ARG;
+    if (!optional) return SMM_ERR_ARG;
     hipStream_t hs = static_cast<hipStream_t>(stream);
-    SmmAlignOptLogzArgs a;
-    const int rc = align_opt_logz_stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host,
-                                        transcript_offset_host, workspace, workspace_bytes, hs, &a);
+    SmmAlignLogzArgs a;
+    const int rc = align_logz_prepare(ALIGN_OPT_LOGZ, shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host,
+                                      elp, trans, init, len_scores, endpen, transcript, transcript_offset_host, logz_o, workspace,
+                                      workspace_bytes, hs, &a);
     if (rc != SMM_OK) return rc;
-    a.elp = elp; a.trans = trans; a.init = init; a.len = len_scores; a.endpen = endpen; a.transcript = transcript;
     a.optional = optional;
-    a.logz = logz_o;
     smm_launch_align_opt_logz_fwd(a, hs);
     SMM_HIP(hipGetLastError());
     return SMM_OK;
@@ -2437,21 +2338,15 @@ extern "C" int smm_align_opt_logz_bwd_f64(const smm_shape *shape, const int64_t 
                                           double *g_elp, double *g_trans, double *g_init, double *g_len, double *p_used,
                                           void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!shape_ok(shape) || !lengths_host || !frame_offset_host || !n_states_host || !transcript_offset_host) return SMM_ERR_ARG;
-    if (!elp || !trans || !init || !len_scores || !transcript || !optional || !logz_o || !workspace) return SMM_ERR_ARG;
-    if (!g_elp || !g_trans || !g_init || !g_len) return SMM_ERR_ARG;
+    if (!optional || !g_elp || !g_trans || !g_init || !g_len) return SMM_ERR_ARG;
     hipStream_t hs = static_cast<hipStream_t>(stream);
-    SmmAlignOptLogzArgs a;
-    const int rc = align_opt_logz_stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host,
-                                        transcript_offset_host, workspace, workspace_bytes, hs, &a);
+    SmmAlignLogzArgs a;
+    int rc = align_logz_prepare(ALIGN_OPT_LOGZ, shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp,
+                                trans, init, len_scores, endpen, transcript, transcript_offset_host, logz_o, workspace,
+                                workspace_bytes, hs, &a);
+    if (rc == SMM_OK) rc = align_logz_bwd_outputs(shape, grad_logz, g_elp, g_trans, g_init, g_len, hs, &a);
     if (rc != SMM_OK) return rc;
-    a.elp = elp; a.trans = trans; a.init = init; a.len = len_scores; a.endpen = endpen; a.transcript = transcript;
-    a.optional = optional;
-    a.logz = const_cast<double *>(logz_o);                      // (the backward launches only read it)
-    a.grad = grad_logz;
-    a.g_elp = g_elp; a.g_trans = g_trans; a.g_init = g_init; a.g_len = g_len; a.p_used = p_used;
-    // g_elp: frames no video covers and the rows of skipped videos stay zero; the others are written whole by their kernels
-    SMM_HIP((hipError_t)smm_zero_async(g_elp, sizeof(double) * (size_t)shape->total_frames * shape->c_max, hs));
+    a.optional = optional; a.p_used = p_used;
     smm_launch_align_opt_logz_bwd(a, hs);
     SMM_HIP(hipGetLastError());
     return SMM_OK;

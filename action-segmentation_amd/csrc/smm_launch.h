@@ -260,8 +260,11 @@ struct SmmAlignArgs {
 void smm_launch_align(const SmmAlignArgs &a, hipStream_t stream);
 void smm_launch_align_opt(const SmmAlignArgs &a, hipStream_t stream);
 
-// transcript likelihood and its gradient (smm_align_logz.hip).  cum as for the alignment; the columns of video i at
-// cols + hoff[i]: h | gam | q, each [M][T+1]; its part of g_len at part + poff[i]: [min(k_rows, T + 1)][c_max]
+// transcript likelihood and its gradient (smm_align_logz.hip; with optional entries: smm_align_opt_logz.hip).  cum as for the
+// alignment.  smm_align_logz: the columns of video i at cols + hoff[i]: h | gam | q, each [M][T+1]; its part of g_len at
+// part + poff[i]: [min(k_rows, T + 1)][c_max].  smm_align_opt_logz: the block of video i at cols + hoff[i]: the columns' ranges
+// (3 M doubles), then h | gam | q | bh, each [M][T+1], then the running per-class sums [c_max][T+1]; its parts at
+// part + poff[i]: g_len [min(k_rows, T + 1)][c_max], g_trans [c_max][c_max], g_init [c_max], then the backward pass's logZ_o
 struct SmmAlignLogzArgs {
     const SmmVideo *videos;
     const int32_t *order;      // [b] workgroup -> video (most lattice cells first)
@@ -272,36 +275,7 @@ struct SmmAlignLogzArgs {
     const double *len;         // [g][k_rows][c_max]
     const double *endpen;      // [b][c_max] or null
     const int32_t *transcript; // [toff[b]] local state ids (caller's; checked against n_states on load)
-    const int64_t *toff;       // [b + 1]
-    const int64_t *hoff;       // [b] doubles
-    const int64_t *poff;       // [b] doubles
-    double *hist;              // the workspace's history area
-    double *cols;              // behind the plan's workspace
-    double *part;              // behind the columns
-    double *logz;              // [b]: the forward launch writes it, the backward launches read it
-    const double *grad;        // [b] or null (= 1)                      (backward only, as the four below)
-    double *g_elp, *g_trans, *g_init, *g_len;   // smm_logz_bwd_f64's layouts; g_elp zero at launch
-    int32_t *err;              // sticky error word
-    int32_t c_max, k_rows, b, n_groups;
-};
-void smm_launch_align_logz_fwd(const SmmAlignLogzArgs &a, hipStream_t stream);
-void smm_launch_align_logz_bwd(const SmmAlignLogzArgs &a, hipStream_t stream);
-
-// transcript likelihood with optional entries and its gradient (smm_align_opt_logz.hip).  cum as for the alignment; the block
-// of video i at cols + hoff[i]: the columns' ranges (3 M doubles), then h | gam | q | bh, each [M][T+1], then the running
-// per-class sums [c_max][T+1]; its parts at part + poff[i]: g_len [min(k_rows, T + 1)][c_max], g_trans [c_max][c_max], g_init [c_max], then the
-// backward pass's logZ_o
-struct SmmAlignOptLogzArgs {
-    const SmmVideo *videos;
-    const int32_t *order;      // [b] workgroup -> video (most lattice cells first)
-    const int32_t *n_states;
-    const double *elp;         // [total_frames][c_max]
-    const double *trans;       // [g][c_max][c_max]  [to][from]
-    const double *init;        // [g][c_max]
-    const double *len;         // [g][k_rows][c_max]
-    const double *endpen;      // [b][c_max] or null
-    const int32_t *transcript; // [toff[b]] local state ids (caller's; checked against n_states on load)
-    const uint8_t *optional;   // [toff[b]] non-zero: the entry may be left out
+    const uint8_t *optional;   // [toff[b]] non-zero: the entry may be left out            (smm_align_opt_logz only, as `p_used`)
     const int64_t *toff;       // [b + 1]
     const int64_t *hoff;       // [b] doubles
     const int64_t *poff;       // [b] doubles
@@ -315,5 +289,7 @@ struct SmmAlignOptLogzArgs {
     int32_t *err;              // sticky error word
     int32_t c_max, k_rows, b, n_groups;
 };
-void smm_launch_align_opt_logz_fwd(const SmmAlignOptLogzArgs &a, hipStream_t stream);
-void smm_launch_align_opt_logz_bwd(const SmmAlignOptLogzArgs &a, hipStream_t stream);
+void smm_launch_align_logz_fwd(const SmmAlignLogzArgs &a, hipStream_t stream);
+void smm_launch_align_logz_bwd(const SmmAlignLogzArgs &a, hipStream_t stream);
+void smm_launch_align_opt_logz_fwd(const SmmAlignLogzArgs &a, hipStream_t stream);
+void smm_launch_align_opt_logz_bwd(const SmmAlignLogzArgs &a, hipStream_t stream);

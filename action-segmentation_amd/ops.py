@@ -670,30 +670,32 @@ def _transcript_arrays(batch, transcripts):
     return np.ascontiguousarray(np.concatenate(seqs).astype(np.int32)), off
 
 
-def align_workspace_bytes(batch, transcript_offset):
-    """Bytes of workspace smm_align_f64 needs for this batch and these transcript offsets (int64 [b + 1]; host only)."""
+def _transcript_offsets(batch, transcript_offset, what):
     off = np.ascontiguousarray(np.asarray(transcript_offset, dtype=np.int64).reshape(-1))
     if off.shape[0] != batch.b + 1:
-        raise ValueError("align_workspace_bytes: b + 1 transcript offsets expected")
-    n = _lib.load().smm_align_workspace_bytes(ctypes.byref(batch.shape), ctypes.c_void_p(batch.lengths.ctypes.data),
-                                              ctypes.c_void_p(off.ctypes.data))
+        raise ValueError("%s: b + 1 transcript offsets expected" % what)
+    return off
+
+
+def _transcript_workspace_bytes(batch, transcript_offset, what, of):
+    """The four ``*_workspace_bytes`` below: libsmmdp's ``smm_<what>`` on the checked offsets; 0 is its refusal."""
+    off = _transcript_offsets(batch, transcript_offset, what)
+    n = getattr(_lib.load(), 'smm_' + what)(ctypes.byref(batch.shape), ctypes.c_void_p(batch.lengths.ctypes.data),
+                                            ctypes.c_void_p(off.ctypes.data))
     if n == 0:
-        raise _lib.SmmError("libsmmdp: invalid batch shape or transcript offsets for the alignment (add_eos=True only, "
-                            "1..%d entries per video)" % MAX_TRANSCRIPT)
+        raise _lib.SmmError("libsmmdp: invalid batch shape or transcript offsets for the %s (add_eos=True only, 1..%d entries "
+                            "per video)" % (of, MAX_TRANSCRIPT))
     return n
+
+
+def align_workspace_bytes(batch, transcript_offset):
+    """Bytes of workspace smm_align_f64 needs for this batch and these transcript offsets (int64 [b + 1]; host only)."""
+    return _transcript_workspace_bytes(batch, transcript_offset, 'align_workspace_bytes', 'alignment')
 
 
 def align_opt_workspace_bytes(batch, transcript_offset):
     """Bytes of workspace smm_align_opt_f64 needs for this batch and these transcript offsets (int64 [b + 1]; host only)."""
-    off = np.ascontiguousarray(np.asarray(transcript_offset, dtype=np.int64).reshape(-1))
-    if off.shape[0] != batch.b + 1:
-        raise ValueError("align_opt_workspace_bytes: b + 1 transcript offsets expected")
-    n = _lib.load().smm_align_opt_workspace_bytes(ctypes.byref(batch.shape), ctypes.c_void_p(batch.lengths.ctypes.data),
-                                                  ctypes.c_void_p(off.ctypes.data))
-    if n == 0:
-        raise _lib.SmmError("libsmmdp: invalid batch shape or transcript offsets for the alignment (add_eos=True only, "
-                            "1..%d entries per video)" % MAX_TRANSCRIPT)
-    return n
+    return _transcript_workspace_bytes(batch, transcript_offset, 'align_opt_workspace_bytes', 'alignment')
 
 
 def _optional_flags(off, optional):
@@ -776,23 +778,10 @@ def align_optional(batch, elp, trans, init, len_scores, transcripts, optional, e
 ALIGN_LOGZ_TILE = _lib.ALIGN_LOGZ_TILE
 
 
-def _transcript_offsets(batch, transcript_offset, what):
-    off = np.ascontiguousarray(np.asarray(transcript_offset, dtype=np.int64).reshape(-1))
-    if off.shape[0] != batch.b + 1:
-        raise ValueError("%s: b + 1 transcript offsets expected" % what)
-    return off
-
-
 def align_logz_workspace_bytes(batch, transcript_offset):
     """Bytes of workspace smm_align_logz_f64 / smm_align_logz_bwd_f64 need for this batch and these transcript offsets (int64
     [b + 1]; host only)."""
-    off = _transcript_offsets(batch, transcript_offset, 'align_logz_workspace_bytes')
-    n = _lib.load().smm_align_logz_workspace_bytes(ctypes.byref(batch.shape), ctypes.c_void_p(batch.lengths.ctypes.data),
-                                                   ctypes.c_void_p(off.ctypes.data))
-    if n == 0:
-        raise _lib.SmmError("libsmmdp: invalid batch shape or transcript offsets for the transcript likelihood (add_eos=True "
-                            "only, 1..%d entries per video)" % MAX_TRANSCRIPT)
-    return n
+    return _transcript_workspace_bytes(batch, transcript_offset, 'align_logz_workspace_bytes', 'transcript likelihood')
 
 
 def _align_logz_inputs(batch, elp, trans, init, len_scores, transcripts, endpen):
@@ -849,13 +838,7 @@ def align_logz_bwd(batch, elp, trans, init, len_scores, transcripts, logz_a, gra
 def align_opt_logz_workspace_bytes(batch, transcript_offset):
     """Bytes of workspace smm_align_opt_logz_f64 / smm_align_opt_logz_bwd_f64 need for this batch and these transcript offsets
     (int64 [b + 1]; host only)."""
-    off = _transcript_offsets(batch, transcript_offset, 'align_opt_logz_workspace_bytes')
-    n = _lib.load().smm_align_opt_logz_workspace_bytes(ctypes.byref(batch.shape), ctypes.c_void_p(batch.lengths.ctypes.data),
-                                                       ctypes.c_void_p(off.ctypes.data))
-    if n == 0:
-        raise _lib.SmmError("libsmmdp: invalid batch shape or transcript offsets for the transcript likelihood (add_eos=True "
-                            "only, 1..%d entries per video)" % MAX_TRANSCRIPT)
-    return n
+    return _transcript_workspace_bytes(batch, transcript_offset, 'align_opt_logz_workspace_bytes', 'transcript likelihood')
 
 
 def _align_opt_logz_inputs(batch, elp, trans, init, len_scores, transcripts, optional, endpen, staged, what):
