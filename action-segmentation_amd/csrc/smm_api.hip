@@ -1235,6 +1235,17 @@ static SmmDpArgs dp_args(const smm_shape *s, const Staged &st, const Tables &t)
     return a;
 }
 
+// what the posterior launches repeat (smm_launch.h): the head from the shape and the staged videos ...
+static SmmPostHead post_head(const smm_shape *s, const Staged &st)
+{
+    return {st.videos, st.n_states, st.err, s->c_max, s->k_rows, s->b, (s->flags & SMM_SHAPE_NO_EOS) ? 1 : 0};
+}
+// ... and one side from the workspace its histories are in and its tables: endpen is null without EOS
+static SmmPostSide post_side(int no_eos, const double *hist, const Tables &t)
+{
+    return {hist, t.elp, t.trans, t.init, t.len, no_eos ? nullptr : t.endpen, t.logz};
+}
+
 // The `tabs` area of a plan as the time-reversed recursion uses it
 struct ReversedTabs {
     double *trans_t;       // [g][cm][cm] transposed
@@ -1718,15 +1729,9 @@ extern "C" int smm_sample_f64(const smm_shape *shape, const int64_t *lengths_hos
                    hs, &st);
     if (rc != SMM_OK) return rc;
     if (!elp || !trans || !init || !len_scores || !logz) return SMM_ERR_ARG;
-    const bool no_eos = (shape->flags & SMM_SHAPE_NO_EOS) != 0;
-    SmmSampleArgs a{};
-    a.videos = st.videos; a.n_states = st.n_states; a.hist = st.hist;
-    a.elp = elp; a.trans = trans; a.init = init; a.len = len_scores; a.endpen = no_eos ? nullptr : endpen;
-    a.class_map = class_map; a.logz = logz;
-    a.spans = spans_out; a.labels = labels_out; a.logp = logp_out; a.err = st.err;
-    a.total_frames = shape->total_frames; a.seed = seed;
-    a.c_max = shape->c_max; a.k_rows = shape->k_rows; a.t_max = shape->t_max; a.b = shape->b; a.n_samples = n_samples;
-    a.no_eos = no_eos ? 1 : 0;
+    const SmmPostHead h = post_head(shape, st);
+    const SmmSampleArgs a{h, post_side(h.no_eos, st.hist, Tables{elp, trans, init, len_scores, endpen, logz}), class_map,
+                          spans_out, labels_out, logp_out, shape->total_frames, seed, shape->t_max, n_samples};
     smm_launch_sample(a, hs);
     SMM_HIP(hipGetLastError());
     return SMM_OK;
@@ -1744,15 +1749,11 @@ extern "C" int smm_entropy_f64(const smm_shape *shape, const int64_t *lengths_ho
     int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes,
                    hs, &st);
     if (rc != SMM_OK) return rc;
-    const bool no_eos = (shape->flags & SMM_SHAPE_NO_EOS) != 0;
-    rc = run_reversed(shape, st, st.hist, st.tabs, Tables{elp, trans, init, len_scores, endpen, logz}, hs);
+    const Tables p{elp, trans, init, len_scores, endpen, logz};
+    rc = run_reversed(shape, st, st.hist, st.tabs, p, hs);
     if (rc != SMM_OK) return rc;
-    SmmEntropyArgs e{};
-    e.videos = st.videos; e.n_states = st.n_states; e.hist = st.hist;
-    e.elp = elp; e.trans = trans; e.len = len_scores; e.endpen = no_eos ? nullptr : endpen; e.logz = logz;
-    e.entropy = entropy_out; e.err = st.err;
-    e.c_max = shape->c_max; e.k_rows = shape->k_rows; e.b = shape->b; e.no_eos = no_eos ? 1 : 0;
-    smm_launch_entropy(e, shape->t_max, hs);
+    const SmmPostHead h = post_head(shape, st);
+    smm_launch_entropy(SmmEntropyArgs{h, post_side(h.no_eos, st.hist, p), entropy_out}, shape->t_max, hs);
     SMM_HIP(hipGetLastError());
     return SMM_OK;
 }
@@ -1786,17 +1787,12 @@ extern "C" int smm_kl_f64(const smm_shape *shape, const int64_t *lengths_host, c
     hipStream_t hs = static_cast<hipStream_t>(stream);
     int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, ws_p, ws_p_bytes, hs, &st);
     if (rc != SMM_OK) return rc;
-    const bool no_eos = (shape->flags & SMM_SHAPE_NO_EOS) != 0;
-    rc = run_reversed(shape, st, st.hist, st.tabs, Tables{elp_p, trans_p, init_p, len_p, endpen_p, logz_p}, hs);   // (p's side only)
+    const Tables p{elp_p, trans_p, init_p, len_p, endpen_p, logz_p}, q{elp_q, trans_q, init_q, len_q, endpen_q, logz_q};
+    rc = run_reversed(shape, st, st.hist, st.tabs, p, hs);          // (p's side only)
     if (rc != SMM_OK) return rc;
-    SmmKlArgs k{};
-    k.videos = st.videos; k.n_states = st.n_states; k.hist_p = st.hist; k.hist_q = sq.hist;
-    k.elp_p = elp_p; k.elp_q = elp_q; k.trans_p = trans_p; k.trans_q = trans_q; k.len_p = len_p; k.len_q = len_q;
-    k.endpen_p = no_eos ? nullptr : endpen_p; k.endpen_q = no_eos ? nullptr : endpen_q;
-    k.logz_p = logz_p; k.logz_q = logz_q;
-    k.kl = kl_out; k.xent = xent_out; k.err = st.err;
-    k.c_max = shape->c_max; k.k_rows = shape->k_rows; k.b = shape->b; k.no_eos = no_eos ? 1 : 0;
-    smm_launch_kl(k, shape->t_max, hs);
+    const SmmPostHead h = post_head(shape, st);
+    smm_launch_kl(SmmKlArgs{h, post_side(h.no_eos, st.hist, p), post_side(h.no_eos, sq.hist, q), kl_out, xent_out}, shape->t_max,
+                  hs);
     SMM_HIP(hipGetLastError());
     return SMM_OK;
 }
@@ -1828,24 +1824,15 @@ static int ebwd_run(const smm_shape *shape, const int64_t *lengths_host, const S
 {
     size_t pv_base = 0, tot = 0;
     ebwd_layout(shape, lengths_host, &pv_base, &tot);
-    const size_t g = shape->n_groups, cm = shape->c_max;
-    const bool no_eos = (shape->flags & SMM_SHAPE_NO_EOS) != 0;
     double *sc = static_cast<double *>(scratch);
     {
         void *const zp[2] = {g_elp, sc + pv_base};
-        const size_t zb[2] = {sizeof(double) * (size_t)shape->total_frames * cm, sizeof(double) * (tot - pv_base)};
+        const size_t zb[2] = {sizeof(double) * (size_t)shape->total_frames * shape->c_max, sizeof(double) * (tot - pv_base)};
         SMM_HIP((hipError_t)smm_zero_multi_async(zp, zb, 2, hs));
     }
-    SmmEntBwdArgs e{};
-    e.videos = st.videos; e.n_states = st.n_states; e.hist_p = st.hist; e.hist_r = hist_r;
-    e.elp_p = p.elp; e.elp_r = r.elp; e.trans_p = p.trans; e.trans_r = r.trans; e.init_p = p.init; e.init_r = r.init;
-    e.len_p = p.len; e.len_r = r.len;
-    e.endpen_p = no_eos ? nullptr : p.endpen; e.endpen_r = no_eos ? nullptr : r.endpen;
-    e.logz_p = p.logz; e.logz_r = r.logz; e.grad_out = grad_out;
-    e.g_elp = g_elp; e.g_trans = g_trans; e.g_init = g_init; e.g_len = g_len; e.value = value_out;
-    e.scratch = sc; e.pv_base = (int64_t)pv_base; e.err = st.err;
-    e.c_max = shape->c_max; e.k_rows = shape->k_rows; e.b = shape->b; e.n_groups = (int32_t)g; e.no_eos = no_eos ? 1 : 0;
-    e.kl = kl;
+    const SmmPostHead h = post_head(shape, st);
+    const SmmEntBwdArgs e{h, post_side(h.no_eos, st.hist, p), post_side(h.no_eos, hist_r, r), grad_out, g_elp, g_trans, g_init,
+                          g_len, value_out, sc, (int64_t)pv_base, shape->n_groups, kl};
     smm_launch_entropy_bwd(e, shape->t_max, st.kp_max, hs);
     SMM_HIP(hipGetLastError());
     return SMM_OK;

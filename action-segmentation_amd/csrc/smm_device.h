@@ -96,6 +96,33 @@ __device__ __forceinline__ double smm_readlane(double x, int lane)
     return smm_pack(lo, hi);
 }
 
+// Butterfly max / sum / or over groups of W consecutive lanes (W a power of two, <= 64); every lane of the group receives the
+// result, the same bits in each.  fmax() here is the NaN-dropping one: units with other max semantics (smm_viterbi.hip,
+// smm_logz.hip, smm_chunk.hip, smm_mbr.hip) keep their own.
+template <int W>
+__device__ __forceinline__ double smm_group_max(double x)
+{
+#pragma unroll
+    for (int off = W / 2; off >= 1; off >>= 1) x = fmax(x, __shfl_xor(x, off));
+    return x;
+}
+
+template <int W>
+__device__ __forceinline__ double smm_group_sum(double x)
+{
+#pragma unroll
+    for (int off = W / 2; off >= 1; off >>= 1) x += __shfl_xor(x, off);
+    return x;
+}
+
+template <int W>
+__device__ __forceinline__ int smm_group_or(int x)
+{
+#pragma unroll
+    for (int off = W / 2; off >= 1; off >>= 1) x |= __shfl_xor(x, off);
+    return x;
+}
+
 // DPP move of a double; lanes whose source is out of range keep their own value (bound_ctrl = 0, old = src).
 template <int CTRL, int ROW_MASK = 0xf>
 __device__ __forceinline__ double smm_dpp(double x)

@@ -271,13 +271,6 @@ __global__ void __launch_bounds__(64 * SMM_KB_WAVES) smm_kbest_fwd_kernel(SmmKbe
 
 __device__ __forceinline__ int64_t kb_gid(const int64_t *cmap, int c) { return cmap ? cmap[c] : (int64_t)c; }
 
-__device__ __forceinline__ double kb_wave_sum(double x)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-
 __device__ void smm_kbest_one(const SmmKbestArgs &a, int vid, int rank, int lane)
 {
     const SmmVideo mv = a.videos[vid];
@@ -342,7 +335,7 @@ __device__ void smm_kbest_one(const SmmKbestArgs &a, int vid, int rank, int lane
             es += elp[(size_t)f * cm + j];
             if (lab) lab[f] = gid;
         }
-        lp += kb_wave_sum(es);
+        lp += smm_group_sum<64>(es);
         if (sp && lane == (s & 63)) sp[s] = gid;
         s += l;
         jprev = j;

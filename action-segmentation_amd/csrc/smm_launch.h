@@ -100,25 +100,35 @@ void smm_launch_dense(const SmmDenseArgs &a, bool log_semiring, hipStream_t stre
 // posterior edge marginals (x upstream gradient) from the beta a LogSemiring smm_launch_dense left in a.beta and a.v
 void smm_launch_dense_marginals(const SmmDenseArgs &a, double *rmsg, const double *grad_v, float *out, hipStream_t stream);
 
-// posterior sampling (smm_sample.hip): after smm_launch_logz on the same workspace (forward histories)
-struct SmmSampleArgs {
+// What the posterior units' argument structs repeat.  The head: the staged videos, the error word, the sizes, add_eos=False
+struct SmmPostHead {
     const SmmVideo *videos;
     const int32_t *n_states;
-    const double *hist;        // per video: F_cum, F_h, F_g, ... each [T+1][c_max] (smm_logz_bwd.hip)
+    int32_t *err;              // sticky error word (p's workspace)
+    int32_t c_max, k_rows, b, no_eos;
+};
+// ... and one side (one posterior): its histories in a workspace smm_launch_logz ran on, its tables, its log Z
+struct SmmPostSide {
+    const double *hist;        // per video: F_cum, F_h, F_g, B_cum, B_h, B_g, (scratch) hT0, hT1; each [T+1][c_max] (smm_logz_bwd.hip)
     const double *elp;         // [total_frames][c_max]
     const double *trans;       // [g][c_max][c_max]  [to][from]
     const double *init;        // [g][c_max]
     const double *len;         // [g][k_rows][c_max]
-    const double *endpen;      // [b][c_max] or null (EOS mode only)
-    const int64_t *class_map;  // [g][c_max+1] or null
+    const double *endpen;      // [b][c_max] or null (null without EOS)
     const double *logz;        // [b]
+};
+
+// posterior sampling (smm_sample.hip): after smm_launch_logz on the same workspace (forward histories)
+struct SmmSampleArgs {
+    SmmPostHead h;             // (err: a decision without a finite candidate)
+    SmmPostSide p;
+    const int64_t *class_map;  // [g][c_max+1] or null
     int64_t *spans;            // [n_samples][b][t_max+1] or null
     int64_t *labels;           // [n_samples][total_frames] or null
     double *logp;              // [n_samples][b] or null
-    int32_t *err;              // sticky error word (a decision without a finite candidate)
     int64_t total_frames;
     uint64_t seed;
-    int32_t c_max, k_rows, t_max, b, n_samples, no_eos;
+    int32_t t_max, n_samples;
 };
 void smm_launch_sample(const SmmSampleArgs &a, hipStream_t stream);
 
@@ -151,58 +161,33 @@ void smm_launch_kbest(const SmmKbestArgs &a, hipStream_t stream);
 
 // exact posterior entropy (smm_entropy.hip): after smm_launch_logz forward AND time-reversed on the same workspace
 struct SmmEntropyArgs {
-    const SmmVideo *videos;
-    const int32_t *n_states;
-    const double *hist;        // per video: F_cum, F_h, F_g, B_cum, B_h, B_g, (scratch) hT0, hT1; each [T+1][c_max]
-    const double *elp;         // [total_frames][c_max]   (no_eos only: the closing label's emission)
-    const double *trans;       // [g][c_max][c_max]  [to][from]
-    const double *len;         // [g][k_rows][c_max]
-    const double *endpen;      // [b][c_max] or null (EOS mode only)
-    const double *logz;        // [b]
+    SmmPostHead h;
+    SmmPostSide p;
     double *entropy;           // [b] nats
-    int32_t *err;              // sticky error word
-    int32_t c_max, k_rows, b, no_eos;
 };
 void smm_launch_entropy(const SmmEntropyArgs &a, int t_max, hipStream_t stream);
 
 // KL divergence and cross-entropy between two posteriors of one lattice (smm_kl.hip): after smm_launch_logz forward AND
 // time-reversed on p's workspace and forward on q's (the same shape and metadata, so the same history offsets)
 struct SmmKlArgs {
-    const SmmVideo *videos;
-    const int32_t *n_states;
-    const double *hist_p;      // p's per video: F_cum, F_h, F_g, B_cum, B_h, B_g, (scratch) hT0, hT1; each [T+1][c_max]
-    const double *hist_q;      // q's: F_cum, F_h, F_g (forward only)
-    const double *elp_p, *elp_q;          // [total_frames][c_max]   (no_eos only: the closing label's emission)
-    const double *trans_p, *trans_q;      // [g][c_max][c_max]  [to][from]
-    const double *len_p, *len_q;          // [g][k_rows][c_max]
-    const double *endpen_p, *endpen_q;    // [b][c_max] or null (EOS mode only)
-    const double *logz_p, *logz_q;        // [b]
+    SmmPostHead h;
+    SmmPostSide p, q;          // (q: forward histories only)
     double *kl;                // [b] nats
     double *xent;              // [b] nats, or null
-    int32_t *err;              // sticky error word (p's workspace)
-    int32_t c_max, k_rows, b, no_eos;
 };
 void smm_launch_kl(const SmmKlArgs &a, int t_max, hipStream_t stream);
 
 // gradients of the entropy, cross-entropy and KL with respect to p's tables (smm_entropy_bwd.hip): after smm_launch_logz forward
-// AND time-reversed on p's workspace and on r's (r = q; for the entropy r = p, the same pointers)
+// AND time-reversed on p's workspace and on r's (r = q; for the entropy r = p again)
 struct SmmEntBwdArgs {
-    const SmmVideo *videos;
-    const int32_t *n_states;
-    const double *hist_p, *hist_r;        // per video: F_cum, F_h, F_g, B_cum, B_h, B_g, ...; each [T+1][c_max]
-    const double *elp_p, *elp_r;          // [total_frames][c_max]   (no_eos only: the closing label's emission)
-    const double *trans_p, *trans_r;      // [g][c_max][c_max]  [to][from]
-    const double *init_p, *init_r;        // [g][c_max]
-    const double *len_p, *len_r;          // [g][k_rows][c_max]
-    const double *endpen_p, *endpen_r;    // [b][c_max] or null (EOS mode only)
-    const double *logz_p, *logz_r;        // [b]
+    SmmPostHead h;
+    SmmPostSide p, r;
     const double *grad_out;               // [b] or null (= 1)
     double *g_elp, *g_trans, *g_init, *g_len;   // smm_logz_bwd_f64's layouts; g_elp zero at launch
     double *value;                        // [b][2] or null: the value by the two decompositions
     double *scratch;                      // caller's: per video 6 [T+1][c_max] blocks at 6/8 of hist_off, then the fixed parts
     int64_t pv_base;                      // doubles in front of the fixed parts (zero at launch)
-    int32_t *err;                         // sticky error word (p's workspace)
-    int32_t c_max, k_rows, b, n_groups, no_eos, kl;
+    int32_t n_groups, kl;
 };
 size_t smm_entropy_bwd_fixed_doubles(int c_max, int k_rows);   // the fixed part of one video
 void smm_launch_entropy_bwd(const SmmEntBwdArgs &a, int t_max, int kp_max, hipStream_t stream);

@@ -41,6 +41,7 @@ __device__ __forceinline__ double mbr_max(double a, double b) { return __builtin
 // the binary table entry of the substituted inputs: SMM_BIG_NEG for a forbidden term (-inf included), else 0
 __device__ __forceinline__ double mbr_mask(double x) { return x <= SMM_BIG_NEG / 2 ? SMM_BIG_NEG : 0.0; }
 
+// (not smm_device.h's smm_group_max<64>: that one's fmax() is not mbr_max)
 __device__ __forceinline__ double mbr_wave_max(double x)
 {
 #pragma unroll

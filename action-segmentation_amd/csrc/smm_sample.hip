@@ -4,7 +4,7 @@
 //   F_cum[n][c] = cumE,   F_h[s][c] = start[s][c] - cumE[s][c]  (start: log-weight of "a span of c starts at s", init at 0),
 //   F_g[n][c]   = gamma   (log-weight of "a span of c ends at n").
 // One walk per (video, sample), from the end (oracle/smm_oracle.c: smm_oracle_logz has the plain statement of the weights):
-//   last label   EOS:    j ~ exp(gamma[T][j] + wend[j]),  wend[j] = LSE(endpen[j], LSE_to(trans[to][j]) - 1e9)
+//   last label   EOS:    j ~ exp(gamma[T][j] + wend[j]),  wend[j] = LSE(endpen[j], LSE_to(trans[to][j]) - 1e9)  (smm_post_wend)
 //                no EOS: to ~ exp(LSE_c(gamma[T][c] + trans[to][c]) + elp[T][to]), then its predecessor as below
 //   span start   a span of j that ends at n starts at n - k,  k ~ exp(F_h[n-k][j] + len[k][j]),  k = 1 .. min(kp-1, n)
 //                (cumE[n][j] is the same for every k)
@@ -19,8 +19,7 @@
 //
 // Random numbers: Philox4x32-10 keyed by the seed; counter = (decision number, sample, video, 0).  A sample's draws depend on
 // (seed, video, sample) only: not on the grid, on n_samples or on the order the waves run in.  u takes 53 random bits.
-#include "smm_device.h"
-#include "smm_launch.h"
+#include "smm_posterior.h"
 #include "../../include/smmdp.h"
 
 #define SMM_SAMPLE_NI 16           // candidates per lane: 16 x 64 >= SMM_MAX_K_ROWS - 1
@@ -48,27 +47,6 @@ __device__ __forceinline__ double smm_uniform53(uint64_t seed, int vid, int smp,
     const SmmPhilox r = smm_philox4x32_10(dec, (uint32_t)smp, (uint32_t)vid, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
     const uint64_t bits = ((uint64_t)(r.v[0] >> 5) << 26) | (uint64_t)(r.v[1] >> 6);
     return (double)bits * 0x1.0p-53;
-}
-
-__device__ __forceinline__ double smm_lse2_exact(double a, double b)
-{
-    const double m = fmax(a, b);
-    if (m == SMM_NEG_INF) return m;
-    return m + log(exp(a - m) + exp(b - m));
-}
-
-__device__ __forceinline__ double smm_wave_max(double x)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x = fmax(x, __shfl_xor(x, off));
-    return x;
-}
-
-__device__ __forceinline__ double smm_wave_sum(double x)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-    return x;
 }
 
 // lane i <- lane i - n of its row of 16, 0 where that lies outside the row
@@ -102,7 +80,7 @@ __device__ __forceinline__ int smm_draw(const double (&w)[NI], double u, int lan
     double m = w[0];
 #pragma unroll
     for (int i = 1; i < NI; ++i) m = fmax(m, w[i]);
-    m = smm_wave_max(m);
+    m = smm_group_max<64>(m);
     if (!(m > SMM_NEG_INF) || m == -SMM_NEG_INF) return -1;
     double e[NI], ls = 0.0;
 #pragma unroll
@@ -139,34 +117,32 @@ __device__ __forceinline__ int64_t smm_gid(const int64_t *cmap, int c) { return 
 
 __device__ void smm_sample_one(const SmmSampleArgs &a, int vid, int smp, int lane)
 {
-    const SmmVideo mv = a.videos[vid];
-    const int Tf = mv.T, T = mv.T - a.no_eos, g = mv.group, cm = a.c_max;
-    const int C = a.n_states[g];
-    const size_t blk = (size_t)cm * (T + 1);
-    const double *F_h = a.hist + mv.hist_off + blk, *F_g = F_h + blk;
-    const double *trans = a.trans + (size_t)g * cm * cm;
-    const double *len = a.len + (size_t)g * a.k_rows * cm;
-    const double *elp = a.elp + (size_t)mv.frame_off * cm;
+    const SmmVideo mv = a.h.videos[vid];
+    const int Tf = mv.T, T = mv.T - a.h.no_eos, g = mv.group, cm = a.h.c_max;
+    const int C = a.h.n_states[g];
+    const SmmHistDir F = smm_hist_dir(a.p.hist, mv, cm, T, 0);
+    const double *F_h = F.h, *F_g = F.g;
+    const double *trans = a.p.trans + (size_t)g * cm * cm;
+    const double *len = a.p.len + (size_t)g * a.h.k_rows * cm;
+    const double *elp = a.p.elp + (size_t)mv.frame_off * cm;
     const int64_t *cmap = a.class_map ? a.class_map + (size_t)g * (cm + 1) : nullptr;
-    int64_t *sp = a.spans ? a.spans + ((size_t)smp * a.b + vid) * (size_t)(a.t_max + 1) : nullptr;
+    int64_t *sp = a.spans ? a.spans + ((size_t)smp * a.h.b + vid) * (size_t)(a.t_max + 1) : nullptr;
     int64_t *lab = a.labels ? a.labels + (size_t)smp * a.total_frames + mv.frame_off : nullptr;
     // every span position is written by lane (position & 63): the -1 filler and the labels that follow are one thread's stores
     if (sp)
         for (int q = lane; q <= a.t_max; q += 64) sp[q] = -1;
     if (T <= 0 || C <= 0) {
-        if (lane == 0) atomicExch(a.err, 1);
+        if (lane == 0) atomicExch(a.h.err, 1);
         return;
     }
     uint32_t dec = 0;
     double lp = 0.0;               // (wave-uniform)
     bool ok = true;
     int j, n = T;
-    if (!a.no_eos) {
+    if (!a.h.no_eos) {
         double w[1] = {SMM_NEG_INF}, wend = SMM_NEG_INF;
         if (lane < C) {
-            double alt = SMM_NEG_INF;
-            for (int to = 0; to < C; ++to) alt = smm_lse2_exact(alt, trans[(size_t)to * cm + lane]);
-            wend = smm_lse2_exact(a.endpen ? a.endpen[(size_t)vid * cm + lane] : 0.0, alt + SMM_BIG_NEG);
+            wend = smm_post_wend(trans, a.p.endpen ? a.p.endpen + (size_t)vid * cm : nullptr, cm, C, lane);
             w[0] = F_g[(size_t)T * cm + lane] + wend;
         }
         j = smm_draw<1>(w, smm_uniform53(a.seed, vid, smp, dec++), lane);
@@ -215,10 +191,10 @@ __device__ void smm_sample_one(const SmmSampleArgs &a, int vid, int smp, int lan
             es += elp[(size_t)f * cm + j];
             if (lab) lab[f] = gid;
         }
-        lp += len[(size_t)k * cm + j] + smm_wave_sum(es);
+        lp += len[(size_t)k * cm + j] + smm_group_sum<64>(es);
         if (sp && lane == (s & 63)) sp[s] = gid;
         if (s == 0) {
-            lp += a.init[(size_t)g * cm + j];
+            lp += a.p.init[(size_t)g * cm + j];
             break;
         }
         // the span in front of it
@@ -229,14 +205,14 @@ __device__ void smm_sample_one(const SmmSampleArgs &a, int vid, int smp, int lan
         j = jp;
         n = s;
     }
-    if (!ok && lane == 0) atomicExch(a.err, 1);
-    if (a.logp && lane == 0) a.logp[(size_t)smp * a.b + vid] = ok ? lp - a.logz[vid] : __builtin_nan("");
+    if (!ok && lane == 0) atomicExch(a.h.err, 1);
+    if (a.logp && lane == 0) a.logp[(size_t)smp * a.h.b + vid] = ok ? lp - a.p.logz[vid] : __builtin_nan("");
 }
 
 __global__ void __launch_bounds__(256) smm_sample_kernel(SmmSampleArgs a)
 {
     const int lane = threadIdx.x & 63;
-    const int64_t n_pairs = (int64_t)a.b * a.n_samples;
+    const int64_t n_pairs = (int64_t)a.h.b * a.n_samples;
     const int64_t stride = (int64_t)gridDim.x * (blockDim.x >> 6);
     for (int64_t p = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); p < n_pairs; p += stride) {
         const int vid = __builtin_amdgcn_readfirstlane((int)(p / a.n_samples));
@@ -247,7 +223,7 @@ __global__ void __launch_bounds__(256) smm_sample_kernel(SmmSampleArgs a)
 
 void smm_launch_sample(const SmmSampleArgs &a, hipStream_t stream)
 {
-    const int64_t waves = (int64_t)a.b * a.n_samples;
+    const int64_t waves = (int64_t)a.h.b * a.n_samples;
     const int64_t blocks = (waves + 3) / 4;
     hipLaunchKernelGGL(smm_sample_kernel, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, stream, a);
 }

@@ -35,20 +35,6 @@ struct SmmTabArgs {
     int32_t n, d, g, cm, k_rows, allow_self;
 };
 
-__device__ __forceinline__ double smm_wave_max(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-
-__device__ __forceinline__ double smm_wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 __device__ __forceinline__ void smm_tab_atomic(double *p, double v)
 {
     __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -71,12 +57,12 @@ __global__ void __launch_bounds__(256) smm_tables_kernel(SmmTabArgs a)
             const bool masked = on && a.init_cons && a.init_cons[cls];
             if (!BWD) {
                 const double x = on ? (masked ? SMM_BIG_NEG : (double)a.init_logits[cls]) : SMM_NEG_INF;
-                const double m = smm_wave_max(x);
-                const double s = smm_wave_sum(on ? exp(x - m) : 0.0);
+                const double m = smm_group_max<64>(x);
+                const double s = smm_group_sum<64>(on ? exp(x - m) : 0.0);
                 if (tid < cm) a.init[(size_t)g * cm + tid] = on ? (x - m) - log(s) : 0.0;
             } else if (a.g_init) {
                 const double gi = on ? a.g_init[(size_t)g * cm + tid] : 0.0;
-                const double tot = smm_wave_sum(gi);
+                const double tot = smm_group_sum<64>(gi);
                 if (on && !masked) smm_tab_atomic(a.g_init_logits + cls, gi - exp(a.init[(size_t)g * cm + tid]) * tot);
             }
         }
@@ -124,7 +110,7 @@ __global__ void __launch_bounds__(256) smm_tables_kernel(SmmTabArgs a)
             {
                 double lv = 0.0;
                 for (int d = tid; d < D; d += 256) lv += log((double)a.cov[(size_t)d * (D + 1)]);
-                lv = smm_wave_sum(lv);
+                lv = smm_group_sum<64>(lv);
                 if ((tid & 63) == 0) s_lv[tid >> 6] = lv;
                 const int c = tid & 31, r = tid >> 5;
                 double s = 0.0;
