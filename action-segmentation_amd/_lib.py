@@ -13,6 +13,7 @@ SYMBOLS = [
     "smm_sample_f64", "smm_entropy_f64", "smm_kl_f64", "smm_kbest_workspace_bytes", "smm_kbest_f64",
     "smm_mbr_workspace_bytes", "smm_mbr_f64",
     "smm_align_workspace_bytes", "smm_align_f64", "smm_align_opt_workspace_bytes", "smm_align_opt_f64",
+    "smm_align_graph_workspace_bytes", "smm_align_graph_f64",
     "smm_align_logz_workspace_bytes", "smm_align_logz_f64", "smm_align_logz_bwd_f64",
     "smm_align_opt_logz_workspace_bytes", "smm_align_opt_logz_f64", "smm_align_opt_logz_bwd_f64",
     "smm_entropy_bwd_scratch_bytes", "smm_entropy_bwd_f64", "smm_kl_bwd_f64",
@@ -103,6 +104,11 @@ def load():
     lib.smm_align_opt_f64.restype = ctypes.c_int
     lib.smm_align_opt_f64.argtypes = [ctypes.POINTER(SmmShape)] + [ctypes.c_void_p] * 19 + [ctypes.c_void_p, ctypes.c_size_t,
                                                                                             ctypes.c_void_p]
+    lib.smm_align_graph_workspace_bytes.restype = ctypes.c_size_t
+    lib.smm_align_graph_workspace_bytes.argtypes = [ctypes.POINTER(SmmShape), ctypes.c_void_p, ctypes.c_void_p]
+    lib.smm_align_graph_f64.restype = ctypes.c_int
+    lib.smm_align_graph_f64.argtypes = [ctypes.POINTER(SmmShape)] + [ctypes.c_void_p] * 20 + [ctypes.c_void_p, ctypes.c_size_t,
+                                                                                              ctypes.c_void_p]
     lib.smm_align_logz_workspace_bytes.restype = ctypes.c_size_t
     lib.smm_align_logz_workspace_bytes.argtypes = [ctypes.POINTER(SmmShape), ctypes.c_void_p, ctypes.c_void_p]
     lib.smm_align_logz_f64.restype = ctypes.c_int

@@ -1,5 +1,6 @@
 // smm_align_tile.h -- what the transcript kernels share (smm_align.hip: the best alignment; smm_align_opt.hip: the same with
-// optional entries; smm_align_logz.hip, smm_align_opt_logz.hip: the sums over all alignments): a video's header, its transcript
+// optional entries; smm_align_graph.hip: the same over the paths of a transcript graph, which keeps its structure to itself;
+// smm_align_logz.hip, smm_align_opt_logz.hip: the sums over all alignments): a video's header, its transcript
 // in LDS, the tests on the bits and on the tables, the prefix-sum phase, the cells of a column that lie on a complete alignment,
 // the tile walk of a column and the sweep of a thread's cells over the distances, the hulls of the per-class running values,
 // the alignment's output phase, and the block scan and row store of the g_elp kernels.  What is log-semiring only is in
@@ -323,7 +324,7 @@ __device__ __forceinline__ double align_class_max(const double *G, size_t T1, in
     return mx;
 }
 
-// ---- the alignment's outputs (smm_align.hip, smm_align_opt.hip)
+// ---- the alignment's outputs (smm_align.hip, smm_align_opt.hip, smm_align_graph.hip)
 // a video without an alignment by counting, or with an id that is no state of it: no spans, no labels, best -inf
 __device__ __forceinline__ void align_write_none(const SmmAlignArgs &a, const AlignVideo &v, int vid, int tid)
 {

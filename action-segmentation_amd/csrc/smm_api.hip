@@ -2028,6 +2028,8 @@ static size_t glen_part(const smm_shape *s, int64_t t) { return (size_t)(std::mi
 static const AlignFamily ALIGN = {[](const smm_shape *, int64_t m, int64_t t) { return (size_t)(m * (t + 1)); }, nullptr};
 static const AlignFamily ALIGN_OPT = {[](const smm_shape *s, int64_t m, int64_t t) { return (size_t)((m + s->c_max) * (t + 1)); },
                                       nullptr};
+// to a transcript graph: the h columns and, for the pull over the edges, the gam columns
+static const AlignFamily ALIGN_GRAPH = {[](const smm_shape *, int64_t m, int64_t t) { return (size_t)(2 * m * (t + 1)); }, nullptr};
 // likelihood: the h, gam and q columns; the parts are g_len's rows, min(k_rows, T + 1) c_max doubles
 static const AlignFamily ALIGN_LOGZ = {[](const smm_shape *, int64_t m, int64_t t) { return (size_t)(3 * m * (t + 1)); }, glen_part};
 // ... with optional entries: the columns' ranges (3 M doubles), the h, gam, q and bh columns and c_max columns of running
@@ -2205,6 +2207,34 @@ extern "C" int smm_align_opt_f64(const smm_shape *shape, const int64_t *lengths_
     if (rc != SMM_OK) return rc;
     a.optional = optional; a.used = used;
     smm_launch_align_opt(a, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
+// ... to a transcript graph (smm_align_graph.hip): the nodes stand where the transcript's entries do
+extern "C" size_t smm_align_graph_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host,
+                                                  const int64_t *node_offset_host)
+{
+    return align_workspace_bytes(ALIGN_GRAPH, shape, lengths_host, node_offset_host);
+}
+
+extern "C" int smm_align_graph_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                   const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                   const double *elp, const double *trans, const double *init, const double *len_scores,
+                                   const double *endpen, const int64_t *class_map, const int32_t *node_class,
+                                   const uint32_t *pred_mask, const uint8_t *node_flags, const int64_t *node_offset_host,
+                                   int64_t *spans, int64_t *labels, double *best, int32_t *n_segs, int32_t *used,
+                                   void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!pred_mask || !node_flags) return SMM_ERR_ARG;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    SmmAlignArgs a;
+    const int rc = align_prepare(ALIGN_GRAPH, shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp,
+                                 trans, init, len_scores, endpen, class_map, node_class, node_offset_host, spans, labels, best,
+                                 n_segs, workspace, workspace_bytes, hs, &a);
+    if (rc != SMM_OK) return rc;
+    a.pred_mask = pred_mask; a.node_flags = node_flags; a.used = used;
+    smm_launch_align_graph(a, hs);
     SMM_HIP(hipGetLastError());
     return SMM_OK;
 }

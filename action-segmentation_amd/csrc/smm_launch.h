@@ -215,9 +215,10 @@ struct SmmMbrArgs {
 };
 void smm_launch_mbr(const SmmMbrArgs &a, hipStream_t stream);
 
-// forced alignment to a given transcript (smm_align.hip; with optional entries: smm_align_opt.hip).  cum sits class-major
-// [C][T+1] at the video's hist_off; the h columns [M][T+1] of video i at hcols + hoff[i], smm_align_opt's running maxima
-// [c_max][T+1] behind them
+// forced alignment to a given transcript (smm_align.hip; with optional entries: smm_align_opt.hip; to a transcript graph:
+// smm_align_graph.hip, whose nodes stand where the transcript's entries do).  cum sits class-major [C][T+1] at the video's
+// hist_off; the h columns [M][T+1] of video i at hcols + hoff[i], smm_align_opt's running maxima [c_max][T+1] behind them, or
+// smm_align_graph's gam columns [M][T+1]
 struct SmmAlignArgs {
     const SmmVideo *videos;
     const int32_t *order;      // [b] workgroup -> video (most lattice cells first)
@@ -229,7 +230,9 @@ struct SmmAlignArgs {
     const double *endpen;      // [b][c_max] or null
     const int64_t *class_map;  // [g][c_max+1] or null
     const int32_t *transcript; // [toff[b]] local state ids (caller's; checked against n_states on load)
-    const uint8_t *optional;   // [toff[b]] non-zero: the entry may be left out            (smm_align_opt only, as `used`)
+    const uint8_t *optional;   // [toff[b]] non-zero: the entry may be left out            (smm_align_opt only)
+    const uint32_t *pred_mask; // [8 * toff[b]] bit j of node m's 8 words: j may directly precede m   (smm_align_graph only)
+    const uint8_t *node_flags; // [toff[b]] bit 0: may be the first segment, bit 1: the last          (smm_align_graph only)
     const int64_t *toff;       // [b + 1]
     const int64_t *hoff;       // [b] doubles
     double *hist;              // the workspace's history area
@@ -238,12 +241,13 @@ struct SmmAlignArgs {
     int64_t *labels;           // [total_frames] or null
     double *best;              // [b] or null
     int32_t *n_segs;           // [b] or null
-    int32_t *used;             // [toff[b]] or null: 1 for an entry that got a segment
+    int32_t *used;             // [toff[b]] or null: 1 for an entry that got a segment   (smm_align_opt, smm_align_graph)
     int32_t *err;              // sticky error word
     int32_t c_max, k_rows, t_max, b;
 };
 void smm_launch_align(const SmmAlignArgs &a, hipStream_t stream);
 void smm_launch_align_opt(const SmmAlignArgs &a, hipStream_t stream);
+void smm_launch_align_graph(const SmmAlignArgs &a, hipStream_t stream);
 
 // transcript likelihood and its gradient (smm_align_logz.hip; with optional entries: smm_align_opt_logz.hip).  cum as for the
 // alignment.  smm_align_logz: the columns of video i at cols + hoff[i]: h | gam | q, each [M][T+1]; its part of g_len at

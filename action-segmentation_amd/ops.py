@@ -775,6 +775,191 @@ def align_optional(batch, elp, trans, init, len_scores, transcripts, optional, e
                        want_used, staged)
 
 
+class TranscriptGraph:
+    """What smm_align_graph_f64 aligns a video to: a DAG whose nodes carry a class id, numbered in topological order.
+    ``ids`` int64 [M]; ``pred`` bool [M, M], strictly lower triangular: pred[m, j] -- node j may directly precede node m;
+    ``start`` / ``end`` bool [M]: the node may be the first / the last segment.  The allowed class sequences are those of the
+    start -> end paths.  ``pred`` may also be given as a list of predecessor lists.  ``end_candidate`` int64 [M]: for a graph
+    from ``from_candidates`` the lowest index of a candidate that ends at the node, else -1.  ValueError for no node or more
+    than ``MAX_TRANSCRIPT`` of them, an edge j >= m, no start node or no end node."""
+
+    def __init__(self, ids, pred, start, end, end_candidate=None):
+        ids = np.asarray(ids.detach().cpu() if torch.is_tensor(ids) else ids, dtype=np.int64).reshape(-1)
+        M = ids.size
+        if M < 1 or M > MAX_TRANSCRIPT:
+            raise ValueError("TranscriptGraph: %d nodes (1 to %d)" % (M, MAX_TRANSCRIPT))
+        if isinstance(pred, (list, tuple)):                 # predecessor lists (an array or a tensor: the matrix)
+            if len(pred) != M:
+                raise ValueError("TranscriptGraph: %d predecessor lists for %d nodes" % (len(pred), M))
+            p = np.zeros((M, M), bool)
+            for m, js in enumerate(pred):
+                for j in js:
+                    if not 0 <= int(j) < m:
+                        raise ValueError("TranscriptGraph: edge %d -> %d (the numbering must be topological: j < m)" % (int(j), m))
+                    p[m, int(j)] = True
+        else:
+            p = np.asarray(pred.detach().cpu() if torch.is_tensor(pred) else pred) != 0
+            if p.shape != (M, M):
+                raise ValueError("TranscriptGraph: pred must be [M, M] or M predecessor lists")
+            if np.triu(p).any():
+                m, j = (int(x) for x in np.argwhere(np.triu(p))[0])
+                raise ValueError("TranscriptGraph: edge %d -> %d (the numbering must be topological: j < m)" % (j, m))
+        start = np.asarray(start.detach().cpu() if torch.is_tensor(start) else start).reshape(-1) != 0
+        end = np.asarray(end.detach().cpu() if torch.is_tensor(end) else end).reshape(-1) != 0
+        if start.size != M or end.size != M:
+            raise ValueError("TranscriptGraph: start and end take one flag per node")
+        if not start.any():
+            raise ValueError("TranscriptGraph: no start node")
+        if not end.any():
+            raise ValueError("TranscriptGraph: no end node")
+        self.ids, self.pred, self.start, self.end = ids, p, start, end
+        self.end_candidate = (np.full(M, -1, np.int64) if end_candidate is None
+                              else np.asarray(end_candidate, dtype=np.int64).reshape(-1))
+        if self.end_candidate.size != M:
+            raise ValueError("TranscriptGraph: end_candidate takes one index per node")
+
+    def __len__(self):
+        return int(self.ids.size)
+
+    @classmethod
+    def chain(cls, ids):
+        """A plain transcript: pred(m) = {m - 1}, start = {0}, end = {M - 1} (smm_align_f64's results)."""
+        ids = np.asarray(ids.detach().cpu() if torch.is_tensor(ids) else ids, dtype=np.int64).reshape(-1)
+        M = ids.size
+        return cls(ids, np.eye(M, k=-1, dtype=bool), np.arange(M) == 0, np.arange(M) == M - 1)
+
+    @classmethod
+    def from_optional(cls, ids, optional):
+        """A transcript with optional entries: pred(m) = m-1, m-2, ... down to and including the nearest mandatory entry;
+        start(m): every entry before m is optional; end(m): every entry after it is (smm_align_opt_f64's results)."""
+        ids = np.asarray(ids.detach().cpu() if torch.is_tensor(ids) else ids, dtype=np.int64).reshape(-1)
+        opt = np.asarray(optional.detach().cpu() if torch.is_tensor(optional) else optional).reshape(-1) != 0
+        M = ids.size
+        if opt.size != M:
+            raise ValueError("TranscriptGraph.from_optional: %d flags for %d entries" % (opt.size, M))
+        pred = np.zeros((M, M), bool)
+        head = 0
+        for m in range(M):
+            pred[m, head:m] = True
+            if not opt[m]:
+                head = m
+        start = np.array([opt[:m].all() for m in range(M)], bool)
+        end = np.array([opt[m + 1:].all() for m in range(M)], bool)
+        return cls(ids, pred, start, end)
+
+    @classmethod
+    def from_candidates(cls, candidates):
+        """"One of these transcripts": the prefix trie of the candidates (sequences of class ids, none empty).  Nodes are
+        created in insertion order, which is topological; candidates with a common prefix share its nodes, identical
+        candidates collapse.  ``end_candidate[m]``: the lowest index of a candidate that ends at node m."""
+        ids, parent, endc, child = [], [], [], {}
+        for ci, cand in enumerate(candidates):
+            seq = np.asarray(cand.detach().cpu() if torch.is_tensor(cand) else cand, dtype=np.int64).reshape(-1)
+            if seq.size == 0:
+                raise ValueError("TranscriptGraph.from_candidates: candidate %d is empty" % ci)
+            at = -1
+            for c in seq.tolist():
+                nxt = child.get((at, c))
+                if nxt is None:
+                    nxt = len(ids)
+                    child[(at, c)] = nxt
+                    ids.append(c)
+                    parent.append(at)
+                    endc.append(-1)
+                at = nxt
+            if endc[at] < 0:
+                endc[at] = ci
+        M = len(ids)
+        if M < 1 or M > MAX_TRANSCRIPT:
+            raise ValueError("TranscriptGraph.from_candidates: the trie has %d nodes (1 to %d)" % (M, MAX_TRANSCRIPT))
+        par = np.array(parent, np.int64)
+        pred = np.zeros((M, M), bool)
+        inner = np.flatnonzero(par >= 0)
+        pred[inner, par[inner]] = True
+        endc = np.array(endc, np.int64)
+        return cls(ids, pred, par < 0, endc >= 0, end_candidate=endc)
+
+    @staticmethod
+    def trie_nodes(candidates):
+        """The number of nodes ``from_candidates`` would create."""
+        seen = set()
+        for cand in candidates:
+            seq = np.asarray(cand.detach().cpu() if torch.is_tensor(cand) else cand, dtype=np.int64).reshape(-1).tolist()
+            seen.update(tuple(seq[:n]) for n in range(1, len(seq) + 1))
+        return len(seen)
+
+    def with_ids(self, ids):
+        """The same structure over other class ids (global -> local)."""
+        return TranscriptGraph(ids, self.pred, self.start, self.end, self.end_candidate)
+
+    def packed_masks(self):
+        """-> uint32 [M, 8]: bit j of node m's 256-bit mask (word j // 32, bit j % 32) is pred[m, j]."""
+        M = len(self)
+        bits = np.zeros((M, MAX_TRANSCRIPT), np.uint8)
+        bits[:, :M] = self.pred
+        return np.ascontiguousarray(np.packbits(bits, axis=1, bitorder='little')).view('<u4').astype(np.uint32)
+
+    def node_flags(self):
+        """-> uint8 [M]: bit 0 = start, bit 1 = end."""
+        return (self.start.astype(np.uint8) | (self.end.astype(np.uint8) << 1)).astype(np.uint8)
+
+    def candidate_of(self, used):
+        """The candidate an alignment chose: ``end_candidate`` of the last used node (``used``: the call's per-node flags of
+        this video); -1 without an alignment."""
+        u = np.flatnonzero(np.asarray(used.detach().cpu() if torch.is_tensor(used) else used).reshape(-1) != 0)
+        return int(self.end_candidate[u[-1]]) if u.size else -1
+
+
+def align_graph_workspace_bytes(batch, node_offset):
+    """Bytes of workspace smm_align_graph_f64 needs for this batch and these node offsets (int64 [b + 1]; host only)."""
+    return _transcript_workspace_bytes(batch, node_offset, 'align_graph_workspace_bytes', 'graph alignment')
+
+
+def align_graph(batch, elp, trans, init, len_scores, graphs, endpen=None, class_map=None, ws=None, want_spans=True,
+                want_labels=True, want_used=False, staged=None):
+    """Forced alignment to a transcript graph (smm_align_graph_f64): per video the best segmentation whose class sequence is
+    a start -> end path of its ``TranscriptGraph`` (LOCAL state ids) -- a candidate set as its trie, alternatives, a free
+    order, long skips; a chain gives ``align``'s results and ``TranscriptGraph.from_optional`` gives ``align_optional``'s, bit
+    for bit.  Returns ``align_optional``'s dict: n_segs counts the nodes of the path, ``used`` (with ``want_used``) is a list
+    of per-video int32 views of one device tensor, 1 for the nodes of the path.  A video no path of whose graph can be laid
+    over its frames gets best -inf, n_segs 0, spans and labels -1.  ValueError when the number of graphs differs from the
+    videos'.  ``ws``: at least ``align_graph_workspace_bytes``.  ``staged``: the ``_staged`` entry of an earlier call's result
+    for the same graphs -- classes, masks and flags on the device -- as in ``align_optional``."""
+    lib = _lib.load()
+    dev = elp.device
+    f64 = torch.float64
+    if len(graphs) != batch.b:
+        raise ValueError("align_graph: %d graphs for %d videos" % (len(graphs), batch.b))
+    if batch.no_eos:
+        raise ValueError("align_graph: add_eos=False is not supported")
+    off = np.zeros(batch.b + 1, np.int64)
+    np.cumsum([len(g) for g in graphs], out=off[1:])
+    need = align_graph_workspace_bytes(batch, off)
+    spans, labels, best, n_segs = _device_outputs(batch, dev, want_spans, want_labels)
+    ws = _own_workspace(ws, need, dev)
+    if staged is not None:
+        ids_dev, masks_dev, flags_dev = staged
+        if ids_dev.shape[0] != off[-1]:
+            raise ValueError("align_graph: staged classes, masks and flags of other graphs")
+    else:
+        ids = np.ascontiguousarray(np.concatenate([g.ids for g in graphs]).astype(np.int32))
+        masks = np.ascontiguousarray(np.concatenate([g.packed_masks() for g in graphs]).reshape(-1))
+        ids_dev = torch.from_numpy(ids).to(dev)
+        masks_dev = torch.from_numpy(masks.view(np.int32)).to(dev)   # (the bits of the uint32 words)
+        flags_dev = torch.from_numpy(np.ascontiguousarray(np.concatenate([g.node_flags() for g in graphs]))).to(dev)
+    used = torch.empty(int(off[-1]), dtype=torch.int32, device=dev) if want_used else None
+    _lib.check(lib.smm_align_graph_f64(
+        *batch.head(), _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'),
+        _dev(len_scores, f64, 'len_scores'), _dev(endpen, f64, 'endpen'), _dev(class_map, torch.int64, 'class_map'),
+        _dev(ids_dev, torch.int32, 'node_class'), _dev(masks_dev, torch.int32, 'pred_mask'),
+        _dev(flags_dev, torch.uint8, 'node_flags'), ctypes.c_void_p(off.ctypes.data), _dev(spans, torch.int64, 'spans'),
+        _dev(labels, torch.int64, 'labels'), _dev(best, f64, 'best'), _dev(n_segs, torch.int32, 'n_segs'),
+        _dev(used, torch.int32, 'used'), *_ws_args(ws), _stream()))
+    return dict(spans=spans, labels=labels, best=best, n_segs=n_segs,
+                used=None if used is None else list(torch.split(used, np.diff(off).tolist())),
+                _err=_err_copy(batch, ws), _staged=(ids_dev, masks_dev, flags_dev), _keep=(ws,))
+
+
 ALIGN_LOGZ_TILE = _lib.ALIGN_LOGZ_TILE
 
 

@@ -395,6 +395,66 @@ class SemiMarkovModel(object):
         assert lab.size == 0 or int(lab.max()) < self.model.n_classes, "alignments should not contain EOS"
         return {name: lab[off:off + t] for name, off, t in zip(pc.video_names, pc.frame_offset, pc.lengths)}
 
+    def align_candidates(self, data, candidates_by_video, shard=None):
+        """"The video follows one of these transcripts": ``candidates_by_video[name]`` is a list of class sequences in global
+        class ids.  Returns ``({video: int64[T] frame labels}, {video: index of the chosen candidate})``: the best segmentation
+        over every candidate, and which one it follows; labels -1 and index -1 where no candidate can be laid over the video.
+        The candidates of a video go to the GPU as their prefix trie (``ops.TranscriptGraph.from_candidates``,
+        ``SemiMarkovModule.align_graph_packed``): one launch scores all of them, shared prefixes once.  A list whose trie would
+        exceed ``ops.MAX_TRANSCRIPT`` nodes is split into consecutive tries, packed greedily in candidate order, each aligned
+        by its own launch on the same prepared corpus; a strictly better score replaces the earlier one on the device, so a
+        tie keeps the earlier chunk.  ValueError for a video without candidates or a single candidate longer than
+        ``ops.MAX_TRANSCRIPT``.  Under an exact tie between different candidates the chosen index is deterministic but
+        otherwise unspecified."""
+        from . import ops
+        self.model.eval()
+        pc = self.prepare(data, shard=shard)
+        if pc.n_videos == 0:
+            return {}, {}
+        chunks = []                                         # per video: [(first candidate index, its candidates)]
+        for name in pc.video_names:
+            cands = candidates_by_video.get(name)
+            if not cands:
+                raise ValueError("align_candidates: no candidates for video %r" % (name,))
+            mine, first, cur, seen = [], 0, [], set()
+            for ci, cand in enumerate(cands):
+                seq = tuple(int(c) for c in np.asarray(cand.cpu() if torch.is_tensor(cand) else cand, dtype=np.int64).reshape(-1))
+                if len(seq) > ops.MAX_TRANSCRIPT:
+                    raise ValueError("align_candidates: candidate %d of video %r has %d entries (at most %d)"
+                                     % (ci, name, len(seq), ops.MAX_TRANSCRIPT))
+                new = {seq[:n] for n in range(1, len(seq) + 1)} - seen
+                if cur and len(seen) + len(new) > ops.MAX_TRANSCRIPT:
+                    mine.append((first, cur))
+                    first, cur, seen, new = ci, [], set(), {seq[:n] for n in range(1, len(seq) + 1)}
+                cur.append(seq)
+                seen |= new
+            mine.append((first, cur))
+            chunks.append(mine)
+        labels = scores = None
+        chosen = np.full(pc.n_videos, -1, np.int64)
+        for r in range(max(len(c) for c in chunks)):
+            # a video with fewer chunks repeats its last one: the same score never replaces
+            part = [c[min(r, len(c) - 1)] for c in chunks]
+            graphs = [ops.TranscriptGraph.from_candidates(cands) for _, cands in part]
+            lab, sc, used = self.model.align_graph_packed(pc, graphs)
+            within = np.array([g.candidate_of(u.cpu().numpy()) for g, u in zip(graphs, used)], np.int64)
+            idx = np.where(within >= 0, within + np.array([first for first, _ in part], np.int64), -1)
+            if labels is None:
+                labels, scores, chosen = lab, sc, idx
+                # the packed frame axis: which video a covered frame belongs to
+                where = torch.cat([torch.arange(off, off + t, device=lab.device) for off, t in zip(pc.frame_offset, pc.lengths)])
+                video = torch.repeat_interleave(torch.arange(pc.n_videos, device=lab.device),
+                                                torch.as_tensor(np.asarray(pc.lengths, np.int64), device=lab.device))
+                continue
+            better = sc > scores                            # (strictly: a tie keeps the earlier chunk)
+            labels[where] = torch.where(better[video], lab[where], labels[where])
+            scores = torch.where(better, sc, scores)
+            chosen = np.where(better.cpu().numpy(), idx, chosen)
+        lab = labels.cpu().numpy()
+        assert lab.size == 0 or int(lab.max()) < self.model.n_classes, "alignments should not contain EOS"
+        return ({name: lab[off:off + t] for name, off, t in zip(pc.video_names, pc.frame_offset, pc.lengths)},
+                {name: int(c) for name, c in zip(pc.video_names, chosen)})
+
     @staticmethod
     def _one_kind_of_flags(optional_by_video, optional_classes, what):
         if optional_by_video is not None and optional_classes is not None:

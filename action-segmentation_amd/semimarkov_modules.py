@@ -141,8 +141,13 @@ def _kbest(r, k, want_spans):
     return _paths(r['batch'], out, want_spans), out['score']
 
 
-def _align(r, local, want_spans, optional=None):
+def _align(r, local, want_spans, optional=None, graphs=False):
+    """``local``: transcripts in local state ids; with ``graphs`` one ``ops.TranscriptGraph`` per video, and the per-video
+    ``used`` flags of the nodes as a third result."""
     kw = dict(endpen=r['endpen'], class_map=r['class_map'], want_spans=want_spans, want_labels=not want_spans)
+    if graphs:
+        out = ops.align_graph(r['batch'], r['elp'], r['trans'], r['init'], r['len'], local, want_used=True, **kw)
+        return _paths(r['batch'], out, want_spans), out['best'], out['used']
     if optional is None:
         out = ops.align(r['batch'], r['elp'], r['trans'], r['init'], r['len'], local, **kw)
     else:
@@ -1163,6 +1168,53 @@ class SemiMarkovModule(nn.Module):
         group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
         local = self._local_transcripts(transcripts, g[5].cpu().numpy(), batch.n_states, group)
         return _align(_emit(batch, x, cons, endpen, g, inv_var), local, want_spans=False, optional=optional)
+
+    # ------------------------------------------------------------------ alignment to a transcript graph (smm_align_graph_f64)
+    @staticmethod
+    def _local_graphs(graphs, class_map_host, n_states, group):
+        """Graphs in GLOBAL class ids -> local state ids, as ``_local_transcripts`` maps transcripts; a class that is no valid
+        class of the video becomes -1, which leaves that video without an alignment."""
+        if len(graphs) != len(group):
+            raise ValueError("align_graph: %d graphs for %d videos" % (len(graphs), len(group)))
+        lookup = [{int(c): j for j, c in reversed(list(enumerate(class_map_host[g, :n_states[g]])))} for g in range(len(n_states))]
+        return [gr.with_ids([lookup[int(group[i])].get(int(c), -1) for c in gr.ids]) for i, gr in enumerate(graphs)]
+
+    @torch.no_grad()
+    def align_graph(self, features, lengths, valid_classes_per_instance, graphs, add_eos=True,
+                    additional_allowed_ends_per_instance=None, constraints=None):
+        """Alignment of a zero-padded single-task batch to transcript graphs (argument conventions of ``align``):
+        ``graphs[i]`` is an ``ops.TranscriptGraph`` in GLOBAL class ids -- a candidate set as its trie, alternatives, a free
+        order, long skips -- and the result is the best segmentation whose class sequence is one of its start -> end paths.
+        One emission launch, one alignment launch (smm_align_graph_f64).
+
+        Returns (pred_spans, scores, used): ``align``'s pair and a list of per-video int32 device tensors, 1 for the nodes of
+        the path (``graph.candidate_of(used[i])`` names the candidate of a trie).  A video none of whose paths can be laid over
+        it, or whose graph names a class that is not valid for it, gives a row of -1, score -inf and no used node.  ValueError
+        for a wrong number of graphs or add_eos=False; SmmError when a NaN reached the DP.  No autograd."""
+        if not add_eos:
+            raise ValueError("align_graph: add_eos=False is not supported")
+        if len(graphs) != len(lengths):
+            raise ValueError("align_graph: %d graphs for %d videos" % (len(graphs), len(lengths)))
+        self._require_device(features, 'align_graph')
+        batch, x, cons, endpen, tab, g1 = self._stage_padded(
+            features, lengths, self._check_valid_classes(valid_classes_per_instance), additional_allowed_ends_per_instance,
+            constraints, check_no_eos=False)
+        local = self._local_graphs(graphs, g1[5].cpu().numpy(), batch.n_states, np.zeros(batch.b, np.int64))
+        return _align(_emit(batch, x, cons, endpen, g1, tab['inv_var']), local, want_spans=True, graphs=True)
+
+    @torch.no_grad()
+    def align_graph_packed(self, pc, graphs):
+        """``align_graph`` for a whole PackedCorpus: one emission launch and one alignment launch.  ``graphs``: one
+        ``ops.TranscriptGraph`` in GLOBAL class ids per video, in the order of ``pc.video_names``.  Returns (labels, scores,
+        used): device int64 total_frames (-1 on frames no video covers and on videos without an alignment), fp64 n_videos and
+        the per-video flags of the nodes on the path."""
+        self._require_device(pc.x, 'align_graph_packed')
+        if pc.batch.no_eos:
+            raise ValueError("align_graph_packed: add_eos=False is not supported")
+        batch, x, cons, endpen, g, inv_var = self._packed_stage(pc, 'align_graph_packed')
+        group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
+        local = self._local_graphs(graphs, g[5].cpu().numpy(), batch.n_states, group)
+        return _align(_emit(batch, x, cons, endpen, g, inv_var), local, want_spans=False, graphs=True)
 
     # ------------------------------------------------------------------ transcript likelihood (smm_align_logz_f64)
     def transcript_log_partition(self, features, lengths, valid_classes_per_instance, transcripts, add_eos=True,

@@ -28,6 +28,9 @@
  *                              reference has none)
  *   smm_align_opt_f64       <- ... with optional transcript entries: the best over every subset of them left out (a CrossTask
  *                              task "bg, step, bg, ..." whose backgrounds or steps may be missing; the reference has none)
+ *   smm_align_graph_f64     <- ... to a transcript graph: the best segmentation whose class sequence is a start -> end path of a
+ *                              DAG of classes (candidate sets as a trie, alternatives, free order, long skips; the reference
+ *                              has none)
  *   smm_align_logz_f64 /    <- transcript likelihood: the log of the sum over every segmentation with a given transcript,
  *   smm_align_logz_bwd_f64     and its gradient (the objective and the E-step of transcript supervision; the reference has none)
  *   smm_align_opt_logz_f64 / <- ... with optional transcript entries: the sum over every alignment, any subset of them left
@@ -561,6 +564,62 @@ int smm_align_opt_f64(const smm_shape *shape, const int64_t *lengths_host, const
                       const double *endpen, const int64_t *class_map, const int32_t *transcript, const uint8_t *optional,
                       const int64_t *transcript_offset_host, int64_t *spans, int64_t *labels, double *best, int32_t *n_segs,
                       int32_t *used, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Forced alignment to a transcript graph (csrc/smm_align_graph.hip): per video, the best segmentation whose class sequence is
+ * a start -> end path of a DAG whose nodes carry a class.  A set of candidate transcripts is their prefix trie, "a or b" two
+ * nodes with the same neighbours, a free order two branches, a long skip one more edge; a plain transcript is a chain and a
+ * transcript with optional entries a special DAG.  A video's nodes are numbered 0..M-1 in TOPOLOGICAL order,
+ * 1 <= M <= SMM_MAX_TRANSCRIPT; a_m is node m's local state id; pred(m) = the nodes that may directly precede node m, every
+ * one of them < m; start(m) / end(m): node m may be the first / the last segment; kw = kp - 1.  Every + and - one IEEE fp64
+ * operation in this association:
+ *   cum as in smm_align_f64
+ *   h[0][m]   = init[a_m] if start(m), else -inf
+ *   h[n][m]   = max_{j in pred(m)} ( gam[n][j] + trans[a_m][a_j] ) - cum[n][a_m]              0 < n < T  (-inf for an empty pred(m))
+ *   gam[n][m] = cum[n][a_m] + max_{k=1..min(kw,n)} ( h[n-k][m] + len[k][a_m] )                n = 1..T
+ *   best      = max_{j : end(j)} ( gam[T][j] + closing_j )                  closing_j = endpen ? endpen[i][a_j] : 0.0
+ * Back-trace: smm_align_opt_f64's.  Start from n = T with the candidates {j : end(j)} and the weights w_j = closing_j.  Among
+ * all (k, j) take the smallest k, then the smallest j, whose (cum[n][a_j] + (h[n-k][j] + len[k][a_j])) + w_j equals the maximum
+ * of that expression; the segment is node j on [n-k, n); continue from n - k with the candidates pred(j) and
+ * w_i = trans[a_j][a_i]; stop at n = 0, where the node is a start node.  This is smm_oracle_viterbi_ex on the expanded lattice
+ * -- states = nodes, trans'[m][j] = trans[a_m][a_j] for j in pred(m), init'[m] = init[a_m] for start(m), endpen'[j] = closing_j
+ * for end(j), every other entry -1e9 -- bit for bit.
+ *   With pred(m) = {m-1}, start = {0} and end = {M-1}, every output equals smm_align_f64's, bit for bit.
+ *   With pred / start / end as smm_align_opt_f64 derives them from optional flags (start = its first), every output equals
+ *   smm_align_opt_f64's, bit for bit, `used` included.
+ * With bmin(m) / bmax(m) the fewest / most nodes before m on a path from a start node and amin(m) / amax(m) the fewest / most
+ * after it on a path to an end node, only the cells max(bmin+1, T - amax kw) <= n <= min(T - amin, (bmax+1) kw) of column m
+ * lie on a complete alignment; the kernel evaluates those (smm_align_opt_f64's cells for a graph built from flags).
+ *   node_class        dev int32 [node_offset_host[b]]: video i's nodes at [offset[i], offset[i+1])              (required)
+ *   pred_mask         dev uint32 [8 * node_offset_host[b]]: 8 words per node, laid out like node_class; bit j of node m's
+ *                     256-bit mask (word j / 32, bit j % 32) is set when j is in pred(m)                         (required)
+ *   node_flags        dev uint8, laid out like node_class: bit 0 = start(m), bit 1 = end(m)                      (required)
+ *   node_offset_host  host int64 [b + 1], non-decreasing; every video has at least one node
+ *   used              dev int32, laid out like node_class: 1 for the nodes of the path, else 0; the path is the used nodes
+ *                     in index order                                                                            (nullable)
+ *   spans, labels, best as smm_align_f64; n_segs = the number of nodes on the path; every other argument as smm_align_f64.
+ * With Lmin / Lmax the fewest / most nodes on any start -> end path: a video without such a path, or with Lmin > T, kw < 1,
+ * Lmax kw < T, an id outside [0, n_states) or a mask bit j >= m, gets best = -inf, n_segs = 0, spans and labels -1, used 0; the
+ * error word stays clear and no table is read (for a graph built from optional flags this is smm_align_opt_f64's rule).  A
+ * video that passes this rule but has no alignment of finite score (path lengths the graph skips, -inf table entries) gets
+ * the same.  The error word is set (best NaN, n_segs 0, spans and labels -1, used 0) under smm_align_opt_f64's conditions read
+ * structurally: a prefix sum cum[T][c] of any state of the video that is not finite, or a NaN or +inf in a table entry the
+ * recursion reads -- init[a_m] for start(m), trans[a_m][a_j] for every edge, len[k][a_m] for k < kp and every node,
+ * endpen[a_j] for end(j) -- every node and every edge, on a start -> end path or not.
+ * Enqueued on `stream` only; never synchronises; a video is never split; the error word sits at smm_error_word_offset.
+ * The workspace is smm_align_graph_workspace_bytes = smm_align_workspace_bytes(shape, lengths_host, node_offset_host)
+ * + 8 * sum_i M_i (T_i + 1) bytes: the gam columns, which a column reads over its edges, behind the h columns.
+ * SMM_ERR_ARG for a NULL required pointer, every output NULL, non-monotone offsets or a video without nodes;
+ * SMM_ERR_UNSUPPORTED for SMM_SHAPE_NO_EOS, more than SMM_MAX_TRANSCRIPT nodes in a video, c_max or k_rows beyond the compiled
+ * kernels; SMM_ERR_WORKSPACE below smm_align_graph_workspace_bytes -- all before anything is staged.
+ */
+size_t smm_align_graph_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host, const int64_t *node_offset_host);
+int smm_align_graph_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                        const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                        const double *elp, const double *trans, const double *init, const double *len_scores,
+                        const double *endpen, const int64_t *class_map, const int32_t *node_class, const uint32_t *pred_mask,
+                        const uint8_t *node_flags, const int64_t *node_offset_host, int64_t *spans, int64_t *labels,
+                        double *best, int32_t *n_segs, int32_t *used, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Transcript likelihood (csrc/smm_align_logz.hip): per video log Z_a = log sum_{y : classes(y) = a} exp score(y), the sum over
