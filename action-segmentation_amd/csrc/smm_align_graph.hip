@@ -12,7 +12,8 @@
 //
 // smm_align_graph_kernel: one workgroup per video, smm_align_opt_kernel's phases (smm_align_opt.hip) and its span loop, both
 // from smm_align_tile.h; what differs:
-//   - the structure sits in LDS: classes, flags and the 8-word masks.  Wave 0 walks the nodes once up and once down for the
+//   - the structure sits in LDS (this item and the next: smm_align_graph.h, shared with smm_align_graph_logz.hip): classes,
+//     flags and the 8-word masks.  Wave 0 walks the nodes once up and once down for the
 //     fewest / most nodes before a node on a path from a start node (bmin, bmax) and after it on a path to an end node (amin,
 //     amax); Lmin and Lmax, the count rule's path lengths, come from the same walk.  A node no start -> end path crosses has no
 //     cells;
@@ -33,26 +34,9 @@
 #define SMM_ALIGN_THREADS 256
 #define SMM_ALIGN_R 3                                            // positions per thread (odd: smm_align_tile.h)
 #include "smm_align_tile.h"
+#include "smm_align_graph.h"
 
-#define SMM_GRAPH_WORDS (SMM_MAX_TRANSCRIPT / 32)                // mask words per node
-#define SMM_GRAPH_FAR 0x3fffffff                                 // "no path": more nodes than any path has
 #define SMM_GRAPH_U 4                                            // positions per thread and round when h is formed
-
-static_assert(SMM_MAX_TRANSCRIPT == SMM_ALIGN_THREADS, "thread j stands for node j when a column lists its predecessors");
-
-// node j may directly precede node m
-__device__ __forceinline__ bool graph_edge(const uint32_t *s_mask, int m, int j)
-{
-    return (s_mask[m * SMM_GRAPH_WORDS + (j >> 5)] >> (j & 31)) & 1u;
-}
-
-__device__ __forceinline__ int graph_wave_max(int x) { return -align_wave_min(-x); }
-
-// this lane's slot among the set lanes of a ballot
-__device__ __forceinline__ int graph_rank(unsigned long long ballot, int lane)
-{
-    return __popcll(ballot & ((1ull << lane) - 1ull));
-}
 
 __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_kernel(SmmAlignArgs a)
 {
@@ -72,10 +56,10 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_kernel(SmmA
     __shared__ int s_start[SMM_MAX_TRANSCRIPT], s_entry[SMM_MAX_TRANSCRIPT];   // the segments, filled from the top down
     __shared__ int s_used[SMM_MAX_TRANSCRIPT];
     __shared__ int s_wcnt[4], s_wlo[4], s_whi[4];              // per wave: predecessors with cells, the hull of their cells
-    __shared__ int s_lmin, s_lmax, s_first_seg;
+    __shared__ int s_len2[2], s_first_seg;                     // [0], [1]: the fewest and most nodes on a start -> end path
     __shared__ int s_flag[2];                                  // [0] an id or a mask bit out of range, [1] a NaN / +inf reached the DP
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int vid = a.order[blockIdx.x];
     const AlignVideo v = align_video(a, vid);
     const int T = v.T, cm = v.cm, kw = v.kw, M = v.M;
@@ -87,22 +71,9 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_kernel(SmmA
 
     if (tid < 2) s_flag[tid] = 0;
     __syncthreads();
-    // ---- the structure -> LDS: an id must be a state of the video, a mask may name earlier nodes only
+    // ---- the structure -> LDS (smm_align_graph.h)
+    graph_load(a, v, s_a, s_fl, s_mask, s_flag, tid);
     if (tid < M) {
-        const int id = a.transcript[v.t0 + tid];
-        bool ok = id >= 0 && id < v.C;
-        s_a[tid] = ok ? id : 0;
-        s_fl[tid] = a.node_flags[v.t0 + tid] & 3;
-        const uint32_t *mask = a.pred_mask + (size_t)(v.t0 + tid) * SMM_GRAPH_WORDS;
-#pragma unroll
-        for (int w = 0; w < SMM_GRAPH_WORDS; ++w) {
-            const uint32_t word = mask[w];
-            const int below = tid - 32 * w;                    // bits of this word that name a node before tid
-            const uint32_t allowed = below <= 0 ? 0u : below >= 32 ? 0xffffffffu : (1u << below) - 1u;
-            ok &= (word & ~allowed) == 0;
-            s_mask[tid * SMM_GRAPH_WORDS + w] = word;
-        }
-        if (!ok) s_flag[0] = 1;
         s_gamT[tid] = SMM_NEG_INF;
         s_used[tid] = 0;
     }
@@ -113,88 +84,19 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_kernel(SmmA
         return;
     }
 
-    // ---- path lengths (wave 0, serially in topological order; the fences order a lane's writes before the other lanes' reads)
-    if (tid < 64) {
-        for (int m = 0; m < M; ++m) {
-            int mn = SMM_GRAPH_FAR, mx = -1;
-            for (int j = tid; j < m; j += 64) {
-                const int bj = s_bmax[j];
-                if (bj >= 0 && graph_edge(s_mask, m, j)) {
-                    const int t = s_bmin[j] + 1;
-                    mn = t < mn ? t : mn;
-                    mx = bj + 1 > mx ? bj + 1 : mx;
-                }
-            }
-            mn = align_wave_min(mn);
-            mx = graph_wave_max(mx);
-            if (s_fl[m] & 1) { mn = 0; mx = mx > 0 ? mx : 0; }
-            if (tid == 0) { s_bmin[m] = mn; s_bmax[m] = mx; }  // bmax < 0: no start node reaches m
-            __threadfence_block();
-        }
-        for (int j = tid; j < M; j += 64) {
-            const bool e = (s_fl[j] & 2) != 0;
-            s_amin[j] = e ? 0 : SMM_GRAPH_FAR;
-            s_amax[j] = e ? 0 : -1;                            // amax < 0: m reaches no end node
-        }
-        __threadfence_block();
-        for (int m = M - 1; m > 0; --m) {                      // every successor of m has pushed: m is final, and pushes
-            const int an = s_amin[m], ax = s_amax[m];
-            if (ax >= 0)
-                for (int j = tid; j < m; j += 64)
-                    if (graph_edge(s_mask, m, j)) {
-                        if (an + 1 < s_amin[j]) s_amin[j] = an + 1;
-                        if (ax + 1 > s_amax[j]) s_amax[j] = ax + 1;
-                    }
-            __threadfence_block();
-        }
-        int lmin = SMM_GRAPH_FAR, lmax = -1;                   // nodes on a start -> end path, fewest and most
-        for (int j = tid; j < M; j += 64)
-            if ((s_fl[j] & 2) && s_bmax[j] >= 0) {
-                lmin = s_bmin[j] + 1 < lmin ? s_bmin[j] + 1 : lmin;
-                lmax = s_bmax[j] + 1 > lmax ? s_bmax[j] + 1 : lmax;
-            }
-        lmin = align_wave_min(lmin);
-        lmax = graph_wave_max(lmax);
-        if (tid == 0) { s_lmin = lmin; s_lmax = lmax; }
-    }
+    // ---- path lengths (wave 0), the columns' cells, the count rule
+    if (tid < 64) graph_path_lengths(s_mask, s_fl, M, s_bmin, s_bmax, s_amin, s_amax, s_len2, tid);
     __syncthreads();
-    if (tid < M) {
-        int lo = 1, hi = 0;
-        if (s_bmax[tid] >= 0 && s_amax[tid] >= 0) {
-            const int p = s_bmin[tid] + 1, q = T - s_amax[tid] * kw;
-            const int r = T - s_amin[tid], s = (s_bmax[tid] + 1) * kw;
-            lo = p > q ? p : q;
-            hi = r < s ? r : s;
-            if (lo > hi) { lo = 1; hi = 0; }
-        }
-        s_lo[tid] = lo;
-        s_hi[tid] = hi;
-    }
-    // no alignment by counting: no start -> end path, the shortest needs more frames than there are, the longest at the span
-    // limit does not reach T
-    if (s_lmax < 0 || s_lmin > T || (int64_t)s_lmax * kw < T) {
+    graph_cells(M, T, kw, s_bmin, s_bmax, s_amin, s_amax, s_lo, s_hi, tid);
+    if (graph_no_path(s_len2, T, kw)) {
         align_write_none(a, v, vid, tid);
         if (used && tid < M) used[tid] = 0;
         return;
     }
 
-    // ---- the tables the structure reads, on a start -> end path or not: init where start(m), the transition of every edge,
-    // the closing score where end(m) (the length scores: as their column stages them)
-    if (tid < M) {
-        const int c = s_a[tid];
-        bool bad = (s_fl[tid] & 1) && align_bad_bits(v.init[c]);
-        for (int w = 0; w * 32 < tid; ++w) {
-            uint32_t word = s_mask[tid * SMM_GRAPH_WORDS + w];
-            while (word) {
-                const int j = w * 32 + __builtin_ctz(word);
-                word &= word - 1;
-                bad |= align_bad_bits(trans[(size_t)c * cm + s_a[j]]);
-            }
-        }
-        if (endpen && (s_fl[tid] & 2)) bad |= align_bad_bits(endpen[c]);
-        if (bad) s_flag[1] = 1;
-        if (s_fl[tid] & 1) hcol[(size_t)tid * T1] = v.init[c];
-    }
+    // ---- the tables the structure reads; h[0][m] of the start nodes
+    if (graph_tables_bad(v, s_a, s_fl, s_mask, tid)) s_flag[1] = 1;
+    if (tid < M && (s_fl[tid] & 1)) hcol[(size_t)tid * T1] = v.init[s_a[tid]];
     // ---- prefix sums (smm_align_tile.h): tiles of frames through LDS, lane c adds class c serially, cum[c][n] class-major
     if (align_prefix_sums(v.elp, v.cum, v.C, cm, T, s_h, tid)) s_flag[1] = 1;
     __threadfence_block();
@@ -217,24 +119,11 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_kernel(SmmA
         if (align_stage_len(len, cm, c, kw, d_all, s_len, tid)) s_flag[1] = 1;
         // ---- the predecessors that have cells -> s_pl, their transitions -> s_tr; the hull of their cells
         const bool is = tid < m && graph_edge(s_mask, m, tid) && s_lo[tid] <= s_hi[tid];
-        const unsigned long long ballot = __ballot(is);
-        {
-            const int wl = align_wave_min(is ? s_lo[tid] : SMM_GRAPH_FAR), wh = graph_wave_max(is ? s_hi[tid] : 0);
-            if (lane == 0) { s_wcnt[wave] = __popcll(ballot); s_wlo[wave] = wl; s_whi[wave] = wh; }
-        }
-        __syncthreads();
-        int np = 0, before = 0, ulo = SMM_GRAPH_FAR, uhi = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            if (w < wave) before += s_wcnt[w];
-            np += s_wcnt[w];
-            ulo = s_wlo[w] < ulo ? s_wlo[w] : ulo;
-            uhi = s_whi[w] > uhi ? s_whi[w] : uhi;
-        }
+        int slot, np, ulo, uhi;
+        graph_compact(is, is ? s_lo[tid] : 0, is ? s_hi[tid] : 0, s_wcnt, s_wlo, s_whi, tid, slot, np, ulo, uhi);
         if (is) {
-            const int i = before + graph_rank(ballot, lane);
-            s_pl[i] = tid;
-            s_tr[i] = trans[(size_t)c * cm + s_a[tid]];
+            s_pl[slot] = tid;
+            s_tr[slot] = trans[(size_t)c * cm + s_a[tid]];
         }
         // column m's sources besides 0: what its cells reach of that hull (slo > shi: none)
         int slo = ulo > lo - kw ? ulo : lo - kw, shi = uhi < hi - 1 ? uhi : hi - 1;

@@ -1,5 +1,5 @@
 // smm_align_lse.h -- the log-semiring span loop of the transcript-likelihood kernels (smm_align_logz.hip: exact transcripts;
-// smm_align_opt_logz.hip: optional entries): one column of lse_k( src(p - k) + len[k] ) over smm_align_tile.h's tiles.
+// smm_align_opt_logz.hip: optional entries; smm_align_graph_logz.hip: the paths of a graph): one column of lse_k( src(p - k) + len[k] ) over smm_align_tile.h's tiles.
 // Include after smm_align_tile.h.
 #pragma once
 
@@ -10,8 +10,10 @@ template <class Src, class Out>
 __device__ __forceinline__ void alogz_column(int lo, int hi, int slo, int shi, int d_all, double *s_h, const double *s_len,
                                              int tid, Src src, Out out)
 {
-    align_tiles(lo, hi, slo, shi, d_all, s_h, tid, src, [&](int n0, int d_first, int d_end, const double *hp) {
+    align_tiles(lo, hi, slo, shi, d_all, s_h, tid, src, [&](int n0, int d_from, int d_end, const double *hp) {
         double acc[SMM_ALIGN_R], sum[SMM_ALIGN_R];
+        // (d_from >= d_end: no source is in reach of this tile -- a graph's column can have one -- and its cells are -inf)
+        const int d_first = d_from < d_end ? d_from : d_end;
         // sweep 1: the largest term of each cell
         align_sweep_max(d_first, d_end, hp, s_len, acc);
         // sweep 2: sum exp(term - max); a cell without a finite term takes the reference 0 and sums zeros

@@ -377,7 +377,7 @@ __global__ void __launch_bounds__(SMM_AOL_OCC_THREADS) smm_align_opt_logz_occ_ke
     __shared__ double s_carry[SMM_MAX_TRANSCRIPT];
     __shared__ double s_wave[2][SMM_AOL_OCC_THREADS / 64];
     __shared__ int s_a[SMM_MAX_TRANSCRIPT];
-    __shared__ int s_dir[SMM_MAX_TRANSCRIPT];                  // pred(m) = {m-1} and succ(m-1) = {m}: S[.][m] is E[.][m-1]
+    __shared__ int s_dir[SMM_MAX_TRANSCRIPT];                  // pred(m) = {m-1} and succ(m-1) = {m}: S[.][m] is E[.][m-1] (no flags: never)
 
     const int tid = threadIdx.x;
     const int vid = a.order[blockIdx.x];
@@ -399,7 +399,7 @@ __global__ void __launch_bounds__(SMM_AOL_OCC_THREADS) smm_align_opt_logz_occ_ke
     const double lzb = a.part[a.poff[vid] + (size_t)rows * cm + (size_t)cm * cm + cm];   // the backward kernel's
 
     align_load_ids(a, v, s_a, tid, SMM_AOL_OCC_THREADS, [&](int m, bool) {   // (a finite logZ_o had valid ids)
-        s_dir[m] = m > 0 && a.optional[t0 + m] == 0 && (m == 1 || a.optional[t0 + m - 1] == 0);
+        s_dir[m] = a.optional && m > 0 && a.optional[t0 + m] == 0 && (m == 1 || a.optional[t0 + m - 1] == 0);
         s_carry[m] = 0.0;
     });
     __syncthreads();
@@ -516,6 +516,12 @@ void smm_launch_align_opt_logz_fwd(const SmmAlignLogzArgs &a, hipStream_t stream
 void smm_launch_align_opt_logz_bwd(const SmmAlignLogzArgs &a, hipStream_t stream)
 {
     hipLaunchKernelGGL(smm_align_opt_logz_bwd_kernel, dim3((unsigned)a.b), dim3(SMM_ALIGN_THREADS), 0, stream, a);
+    smm_launch_align_opt_logz_tail(a, stream);
+}
+
+// g_elp, the videos' parts of g_len, the sums over the videos: from the columns, ranges and parts a backward kernel left
+void smm_launch_align_opt_logz_tail(const SmmAlignLogzArgs &a, hipStream_t stream)
+{
     hipLaunchKernelGGL(smm_align_opt_logz_occ_kernel, dim3((unsigned)a.b), dim3(SMM_AOL_OCC_THREADS), 0, stream, a);
     hipLaunchKernelGGL(smm_align_opt_logz_glen_kernel, dim3((unsigned)a.b), dim3(SMM_ALIGN_THREADS), 0, stream, a);
     const unsigned cells = (unsigned)(a.k_rows * a.c_max + a.c_max * a.c_max + a.c_max);

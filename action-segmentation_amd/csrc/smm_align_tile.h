@@ -1,6 +1,6 @@
 // smm_align_tile.h -- what the transcript kernels share (smm_align.hip: the best alignment; smm_align_opt.hip: the same with
-// optional entries; smm_align_graph.hip: the same over the paths of a transcript graph, which keeps its structure to itself;
-// smm_align_logz.hip, smm_align_opt_logz.hip: the sums over all alignments): a video's header, its transcript
+// optional entries; smm_align_graph.hip: the same over the paths of a transcript graph, whose structure is in smm_align_graph.h;
+// smm_align_logz.hip, smm_align_opt_logz.hip, smm_align_graph_logz.hip: the sums over all alignments): a video's header, its transcript
 // in LDS, the tests on the bits and on the tables, the prefix-sum phase, the cells of a column that lie on a complete alignment,
 // the tile walk of a column and the sweep of a thread's cells over the distances, the hulls of the per-class running values,
 // the alignment's output phase, and the block scan and row store of the g_elp kernels.  What is log-semiring only is in

@@ -2039,6 +2039,10 @@ static const AlignFamily ALIGN_OPT_LOGZ = {
     [](const smm_shape *s, int64_t m, int64_t t) { return (size_t)(3 * m + (4 * m + s->c_max) * (t + 1)); },
     [](const smm_shape *s, int64_t t) { return glen_part(s, t) + (size_t)((int64_t)s->c_max * s->c_max + s->c_max + 1); }};
 
+// ... over the paths of a transcript graph: the same block without the running sums (a column reads its neighbours' columns)
+static const AlignFamily ALIGN_GRAPH_LOGZ = {
+    [](const smm_shape *, int64_t m, int64_t t) { return (size_t)(3 * m + 4 * m * (t + 1)); }, ALIGN_OPT_LOGZ.part};
+
 struct AlignLayout {
     size_t o_toff, o_hoff, o_poff, o_order, meta_end, o_cols, o_part, total;
 };
@@ -2240,7 +2244,7 @@ extern "C" int smm_align_graph_f64(const smm_shape *shape, const int64_t *length
 }
 
 // ------------------------------------------------------------------------------------------------ transcript likelihood
-// What the four likelihood entry points (forward and backward, exact and with optional entries) share up to their launch:
+// What the six likelihood entry points (forward and backward: exact, with optional entries, over a graph) share up to their launch:
 // the refusals, the staging, the kernel arguments but for `optional` and what the backward call adds
 static int align_logz_prepare(const AlignFamily &f, const smm_shape *shape, const int64_t *lengths_host,
                               const int64_t *frame_offset_host, const int32_t *group_host, const int32_t *kp_host,
@@ -2365,6 +2369,56 @@ extern "C" int smm_align_opt_logz_bwd_f64(const smm_shape *shape, const int64_t 
     if (rc != SMM_OK) return rc;
     a.optional = optional; a.p_used = p_used;
     smm_launch_align_opt_logz_bwd(a, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ ... over a transcript graph
+extern "C" size_t smm_align_graph_logz_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host,
+                                                       const int64_t *node_offset_host)
+{
+    return align_workspace_bytes(ALIGN_GRAPH_LOGZ, shape, lengths_host, node_offset_host);
+}
+
+extern "C" int smm_align_graph_logz_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                        const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                        const double *elp, const double *trans, const double *init, const double *len_scores,
+                                        const double *endpen, const int32_t *node_class, const uint32_t *pred_mask,
+                                        const uint8_t *node_flags, const int64_t *node_offset_host, double *logz_g,
+                                        void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!pred_mask || !node_flags) return SMM_ERR_ARG;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    SmmAlignLogzArgs a;
+    const int rc = align_logz_prepare(ALIGN_GRAPH_LOGZ, shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host,
+                                      elp, trans, init, len_scores, endpen, node_class, node_offset_host, logz_g, workspace,
+                                      workspace_bytes, hs, &a);
+    if (rc != SMM_OK) return rc;
+    a.pred_mask = pred_mask; a.node_flags = node_flags;
+    smm_launch_align_graph_logz_fwd(a, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
+extern "C" int smm_align_graph_logz_bwd_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                            const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                            const double *elp, const double *trans, const double *init, const double *len_scores,
+                                            const double *endpen, const int32_t *node_class, const uint32_t *pred_mask,
+                                            const uint8_t *node_flags, const int64_t *node_offset_host, const double *logz_g,
+                                            const double *grad_logz, double *g_elp, double *g_trans, double *g_init,
+                                            double *g_len, double *p_used, double *p_end, void *workspace, size_t workspace_bytes,
+                                            void *stream)
+{
+    if (!pred_mask || !node_flags || !g_elp || !g_trans || !g_init || !g_len) return SMM_ERR_ARG;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    SmmAlignLogzArgs a;
+    int rc = align_logz_prepare(ALIGN_GRAPH_LOGZ, shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp,
+                                trans, init, len_scores, endpen, node_class, node_offset_host, logz_g, workspace,
+                                workspace_bytes, hs, &a);
+    if (rc == SMM_OK) rc = align_logz_bwd_outputs(shape, grad_logz, g_elp, g_trans, g_init, g_len, hs, &a);
+    if (rc != SMM_OK) return rc;
+    a.pred_mask = pred_mask; a.node_flags = node_flags; a.p_used = p_used; a.p_end = p_end;
+    smm_launch_align_graph_logz_bwd(a, hs);
     SMM_HIP(hipGetLastError());
     return SMM_OK;
 }

@@ -264,7 +264,10 @@ struct SmmAlignLogzArgs {
     const double *len;         // [g][k_rows][c_max]
     const double *endpen;      // [b][c_max] or null
     const int32_t *transcript; // [toff[b]] local state ids (caller's; checked against n_states on load)
-    const uint8_t *optional;   // [toff[b]] non-zero: the entry may be left out            (smm_align_opt_logz only, as `p_used`)
+    const uint8_t *optional;   // [toff[b]] non-zero: the entry may be left out   (smm_align_opt_logz only; null: no entry is optional
+                               // and none takes its start posteriors from the entry before it)
+    const uint32_t *pred_mask; // [8 * toff[b]] bit j of node m's 8 words: j may directly precede m   (smm_align_graph_logz only)
+    const uint8_t *node_flags; // [toff[b]] bit 0: may be the first segment, bit 1: the last          (smm_align_graph_logz only)
     const int64_t *toff;       // [b + 1]
     const int64_t *hoff;       // [b] doubles
     const int64_t *poff;       // [b] doubles
@@ -274,7 +277,8 @@ struct SmmAlignLogzArgs {
     double *logz;              // [b]: the forward launch writes it, the backward launches read it
     const double *grad;        // [b] or null (= 1)                      (backward only, as the five below)
     double *g_elp, *g_trans, *g_init, *g_len;   // smm_logz_bwd_f64's layouts; g_elp zero at launch
-    double *p_used;            // [toff[b]] or null
+    double *p_used;            // [toff[b]] or null                      (smm_align_opt_logz, smm_align_graph_logz)
+    double *p_end;             // [toff[b]] or null                      (smm_align_graph_logz only)
     int32_t *err;              // sticky error word
     int32_t c_max, k_rows, b, n_groups;
 };
@@ -282,3 +286,10 @@ void smm_launch_align_logz_fwd(const SmmAlignLogzArgs &a, hipStream_t stream);
 void smm_launch_align_logz_bwd(const SmmAlignLogzArgs &a, hipStream_t stream);
 void smm_launch_align_opt_logz_fwd(const SmmAlignLogzArgs &a, hipStream_t stream);
 void smm_launch_align_opt_logz_bwd(const SmmAlignLogzArgs &a, hipStream_t stream);
+// the g_elp, g_len and reduce kernels of smm_align_opt_logz.hip alone: what follows a backward kernel that left that unit's
+// columns, ranges and parts in the workspace (smm_align_graph_logz.hip does, with a null `optional`)
+void smm_launch_align_opt_logz_tail(const SmmAlignLogzArgs &a, hipStream_t stream);
+// ... over the paths of a transcript graph (smm_align_graph_logz.hip): the block of video i at cols + hoff[i]: the columns'
+// ranges (3 M doubles), then h | gam | q | bh, each [M][T+1]; its parts as smm_align_opt_logz's
+void smm_launch_align_graph_logz_fwd(const SmmAlignLogzArgs &a, hipStream_t stream);
+void smm_launch_align_graph_logz_bwd(const SmmAlignLogzArgs &a, hipStream_t stream);

@@ -678,7 +678,7 @@ def _transcript_offsets(batch, transcript_offset, what):
 
 
 def _transcript_workspace_bytes(batch, transcript_offset, what, of):
-    """The four ``*_workspace_bytes`` below: libsmmdp's ``smm_<what>`` on the checked offsets; 0 is its refusal."""
+    """The ``*_workspace_bytes`` of the transcript entry points below: libsmmdp's ``smm_<what>`` on the checked offsets; 0 is its refusal."""
     off = _transcript_offsets(batch, transcript_offset, what)
     n = getattr(_lib.load(), 'smm_' + what)(ctypes.byref(batch.shape), ctypes.c_void_p(batch.lengths.ctypes.data),
                                             ctypes.c_void_p(off.ctypes.data))
@@ -813,6 +813,7 @@ class TranscriptGraph:
         if not end.any():
             raise ValueError("TranscriptGraph: no end node")
         self.ids, self.pred, self.start, self.end = ids, p, start, end
+        self._trie = False                                  # from_candidates: no two paths spell the same labels
         self.end_candidate = (np.full(M, -1, np.int64) if end_candidate is None
                               else np.asarray(end_candidate, dtype=np.int64).reshape(-1))
         if self.end_candidate.size != M:
@@ -877,7 +878,9 @@ class TranscriptGraph:
         inner = np.flatnonzero(par >= 0)
         pred[inner, par[inner]] = True
         endc = np.array(endc, np.int64)
-        return cls(ids, pred, par < 0, endc >= 0, end_candidate=endc)
+        g = cls(ids, pred, par < 0, endc >= 0, end_candidate=endc)
+        g._trie = True
+        return g
 
     @staticmethod
     def trie_nodes(candidates):
@@ -902,6 +905,32 @@ class TranscriptGraph:
     def node_flags(self):
         """-> uint8 [M]: bit 0 = start, bit 1 = end."""
         return (self.start.astype(np.uint8) | (self.end.astype(np.uint8) << 1)).astype(np.uint8)
+
+    def is_ambiguous(self):
+        """Host only, exact: True when two different start -> end paths spell the same class sequence --
+        ``align_graph_logz`` then counts the segmentations with that class sequence once per path.  Over the pairs (i, j) of
+        equal class, in topological order, `same[i, j]` says that a path from a start node ending in i and one ending in j
+        spell the same labels, `diff[i, j]` that two such paths differ (always when i != j); each row is one boolean
+        pred[i] @ R @ pred[j].T, O(M^3) bit operations at worst.  Ambiguous iff diff holds for a pair of end nodes (i = j
+        included).  A graph from ``from_candidates`` is unambiguous by construction."""
+        if self._trie:
+            return False
+        M = len(self)
+        pred = self.pred.astype(np.int64)
+        eq = self.ids[:, None] == self.ids[None, :]
+        same = np.zeros((M, M), np.int64)
+        diff = np.zeros((M, M), np.int64)
+        for t in range(M):
+            lower = pred[:t + 1]
+            row = eq[t, :t + 1] & ((self.start[t] & self.start[:t + 1]) | (lower @ (pred[t] @ same) > 0))
+            same[t, :t + 1] = row
+            same[:t + 1, t] = row
+            drow = row.copy()
+            drow[t] = row[t] and bool(pred[t] @ diff @ pred[t] > 0)
+            diff[t, :t + 1] = drow
+            diff[:t + 1, t] = drow
+        ends = np.flatnonzero(self.end)
+        return bool(diff[np.ix_(ends, ends)].any())
 
     def candidate_of(self, used):
         """The candidate an alignment chose: ``end_candidate`` of the last used node (``used``: the call's per-node flags of
@@ -1085,6 +1114,84 @@ def align_opt_logz_bwd(batch, elp, trans, init, len_scores, transcripts, optiona
         _dev(used, f64, 'p_used'), *_ws_args(ws), _stream()))
     if want_entry_prob:
         g['entry_prob'] = list(torch.split(used, np.diff(off).tolist()))
+    g['_keep'] = st
+    return g
+
+
+def align_graph_logz_workspace_bytes(batch, node_offset):
+    """Bytes of workspace smm_align_graph_logz_f64 / smm_align_graph_logz_bwd_f64 need for this batch and these node offsets
+    (int64 [b + 1]; host only)."""
+    return _transcript_workspace_bytes(batch, node_offset, 'align_graph_logz_workspace_bytes', 'transcript-graph likelihood')
+
+
+def _align_graph_logz_inputs(batch, elp, trans, init, len_scores, graphs, endpen, staged, what):
+    """The arguments the forward and the backward call share, from the tables on: (ctypes values, node offsets, (classes,
+    masks, flags) on the device).  Every check on the host arrays comes before a device is touched."""
+    f64 = torch.float64
+    if len(graphs) != batch.b:
+        raise ValueError("%s: %d graphs for %d videos" % (what, len(graphs), batch.b))
+    if batch.no_eos:
+        raise ValueError("%s: add_eos=False is not supported" % what)
+    off = np.zeros(batch.b + 1, np.int64)
+    np.cumsum([len(g) for g in graphs], out=off[1:])
+    if staged is not None:
+        ids_dev, masks_dev, flags_dev = staged
+        if ids_dev.shape[0] != off[-1]:
+            raise ValueError("%s: staged classes, masks and flags of other graphs" % what)
+    else:
+        ids = np.ascontiguousarray(np.concatenate([g.ids for g in graphs]).astype(np.int32))
+        masks = np.ascontiguousarray(np.concatenate([g.packed_masks() for g in graphs]).reshape(-1))
+        flags = np.ascontiguousarray(np.concatenate([g.node_flags() for g in graphs]))
+        ids_dev = torch.from_numpy(ids).to(elp.device)
+        masks_dev = torch.from_numpy(masks.view(np.int32)).to(elp.device)   # (the bits of the uint32 words)
+        flags_dev = torch.from_numpy(flags).to(elp.device)
+    args = (_dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
+            _dev(endpen, f64, 'endpen'), _dev(ids_dev, torch.int32, 'node_class'), _dev(masks_dev, torch.int32, 'pred_mask'),
+            _dev(flags_dev, torch.uint8, 'node_flags'), ctypes.c_void_p(off.ctypes.data))
+    return args, off, (ids_dev, masks_dev, flags_dev)
+
+
+def align_graph_logz(batch, elp, trans, init, len_scores, graphs, endpen=None, ws=None, staged=None):
+    """Transcript-graph likelihood (smm_align_graph_logz_f64): per video log Z_g, the log of the sum over every ALIGNMENT of
+    the video to its ``TranscriptGraph`` (LOCAL state ids) -- a start -> end path and the boundaries of its nodes' segments.
+    For a candidate set (``TranscriptGraph.from_candidates``) that is the likelihood of "one of these transcripts"; where two
+    paths spell the same class sequence (``TranscriptGraph.is_ambiguous``) its segmentations count once per path.
+    -> dict(logz fp64 [b] (-inf: no alignment; NaN and the error word: a NaN reached the DP), ws (keep it for
+    ``align_graph_logz_bwd``), _staged (classes, masks and flags on the device), _err, _keep).  ``ws``: at least
+    ``align_graph_logz_workspace_bytes``.  ``staged``: the ``_staged`` entry of an earlier call for the same graphs: the call
+    then copies nothing from the host itself and can be captured into a graph."""
+    lib = _lib.load()
+    args, off, st = _align_graph_logz_inputs(batch, elp, trans, init, len_scores, graphs, endpen, staged, 'align_graph_logz')
+    ws = _own_workspace(ws, align_graph_logz_workspace_bytes(batch, off), elp.device)
+    out = torch.empty(batch.b, dtype=torch.float64, device=elp.device)
+    _lib.check(lib.smm_align_graph_logz_f64(*batch.head(), *args, _dev(out, torch.float64, 'logz_g'), *_ws_args(ws), _stream()))
+    return dict(logz=out, ws=ws, _staged=st, _err=_err_copy(batch, ws), _keep=(ws,))
+
+
+def align_graph_logz_bwd(batch, elp, trans, init, len_scores, graphs, logz_g, grad_logz=None, endpen=None, ws=None, staged=None,
+                         want_node_prob=False, want_end_prob=False):
+    """Gradient of sum_i grad_logz[i] * log Z_g(i) (smm_align_graph_logz_bwd_f64).  Must follow ``align_graph_logz`` for the
+    same batch, tables and graphs with the same workspace ``ws`` on the same stream; ``logz_g`` = its output.
+    -> dict(elp [total_frames, c_max], trans, init, len) fp64, plus with ``want_node_prob`` node_prob and with
+    ``want_end_prob`` end_prob: lists of per-video fp64 views of one device tensor each, the posterior probability that the
+    path crosses the node / ends in it (end_prob sums to 1 over a video's nodes).  Videos whose log Z_g is -inf or NaN
+    contribute zeros."""
+    lib = _lib.load()
+    f64 = torch.float64
+    args, off, st = _align_graph_logz_inputs(batch, elp, trans, init, len_scores, graphs, endpen, staged, 'align_graph_logz_bwd')
+    if ws is None or ws.numel() < align_graph_logz_workspace_bytes(batch, off):
+        raise ValueError("align_graph_logz_bwd: pass the workspace the align_graph_logz call wrote")
+    g = _grad_outputs(elp, trans, init, len_scores)
+    used = torch.empty(int(off[-1]), dtype=f64, device=elp.device) if want_node_prob else None
+    ended = torch.empty(int(off[-1]), dtype=f64, device=elp.device) if want_end_prob else None
+    _lib.check(lib.smm_align_graph_logz_bwd_f64(
+        *batch.head(), *args, _dev(logz_g, f64, 'logz_g'), _dev(grad_logz, f64, 'grad_logz'), _dev(g['elp'], f64, 'g_elp'),
+        _dev(g['trans'], f64, 'g_trans'), _dev(g['init'], f64, 'g_init'), _dev(g['len'], f64, 'g_len'),
+        _dev(used, f64, 'p_used'), _dev(ended, f64, 'p_end'), *_ws_args(ws), _stream()))
+    if want_node_prob:
+        g['node_prob'] = list(torch.split(used, np.diff(off).tolist()))
+    if want_end_prob:
+        g['end_prob'] = list(torch.split(ended, np.diff(off).tolist()))
     g['_keep'] = st
     return g
 

@@ -456,6 +456,107 @@ class SemiMarkovModel(object):
                 {name: int(c) for name, c in zip(pc.video_names, chosen)})
 
     @staticmethod
+    def _candidate_chunks(cands, name, what):
+        """The DISTINCT candidates of one video, each under the index of its first appearance, split as ``align_candidates``
+        splits them: consecutive tries of at most ``ops.MAX_TRANSCRIPT`` nodes, packed greedily in candidate order.
+        De-duplicating first keeps a class sequence from being summed once per chunk it would appear in.
+        -> [[(index, class sequence)]], one list per trie."""
+        from . import ops
+        if not cands:
+            raise ValueError("%s: no candidates for video %r" % (what, name))
+        chunks, cur, seen, known = [], [], set(), set()
+        for ci, cand in enumerate(cands):
+            seq = tuple(int(c) for c in np.asarray(cand.cpu() if torch.is_tensor(cand) else cand, dtype=np.int64).reshape(-1))
+            if len(seq) == 0 or len(seq) > ops.MAX_TRANSCRIPT:
+                raise ValueError("%s: candidate %d of video %r has %d entries (1 to %d)" % (what, ci, name, len(seq), ops.MAX_TRANSCRIPT))
+            if seq in known:
+                continue
+            known.add(seq)
+            prefixes = {seq[:n] for n in range(1, len(seq) + 1)}
+            if cur and len(seen | prefixes) > ops.MAX_TRANSCRIPT:
+                chunks.append(cur)
+                cur, seen = [], set()
+            cur.append((ci, seq))
+            seen |= prefixes
+        chunks.append(cur)
+        return chunks
+
+    def _candidate_rounds(self, data, candidates_by_video, shard, what):
+        """-> (pc, rounds): the prepared corpus and, per launch, one (trie, owner) pair per video -- owner[node]: the index of
+        the candidate that ends in the node, else -1 -- or None for a video all of whose tries went out in earlier launches
+        (it then repeats its last trie, and the launch's values for it are not used)."""
+        from . import ops
+        self.model.eval()
+        chunks = {name: self._candidate_chunks(cands, name, what) for name, cands in candidates_by_video.items()}
+        pc = self.prepare(data, shard=shard)
+        if pc.n_videos == 0:
+            return pc, []
+        missing = [name for name in pc.video_names if name not in chunks]
+        if missing:
+            raise ValueError("%s: no candidates for video %r" % (what, missing[0]))
+        rounds = []
+        for r in range(max(len(chunks[name]) for name in pc.video_names)):
+            row = []
+            for name in pc.video_names:
+                mine = chunks[name]
+                part = mine[min(r, len(mine) - 1)]
+                trie = ops.TranscriptGraph.from_candidates([seq for _, seq in part])
+                owner = np.where(trie.end_candidate >= 0, np.array([ci for ci, _ in part], np.int64)[trie.end_candidate], -1)
+                row.append((trie, owner, r < len(mine)))
+            rounds.append(row)
+        return pc, rounds
+
+    def candidate_log_likelihood(self, data, candidates_by_video, conditional=False, shard=None):
+        """The likelihood of "the video follows one of these transcripts": ``candidates_by_video[name]`` is a list of class
+        sequences in global class ids.  Returns ``{video: float}``: the log of the sum, over the DISTINCT candidates, of the
+        sum over every segmentation with that class sequence (``conditional``: minus log Z, the log-probability that the
+        video's class sequence is one of the candidates); -inf where no candidate can be laid over the video.  The candidates
+        go to the GPU as their prefix trie (``SemiMarkovModule.transcript_graph_scores_packed``): shared prefixes are summed
+        once.  A set whose trie would exceed ``ops.MAX_TRANSCRIPT`` nodes is split as ``align_candidates`` splits it, after
+        de-duplication, and the tries' values are combined by logsumexp."""
+        pc, rounds = self._candidate_rounds(data, candidates_by_video, shard, 'candidate_log_likelihood')
+        if pc.n_videos == 0:
+            return {}
+        total = torch.full((pc.n_videos,), float('-inf'), dtype=torch.float64)
+        for row in rounds:
+            z = self.model.transcript_graph_scores_packed(pc, [t for t, _, _ in row], conditional=conditional)
+            live = torch.tensor([fresh for _, _, fresh in row])
+            total = torch.logaddexp(total, torch.where(live, z, torch.full_like(z, float('-inf'))))
+        return {name: float(v) for name, v in zip(pc.video_names, total.tolist())}
+
+    def candidate_posteriors(self, data, candidates_by_video, shard=None):
+        """``{video: fp64 [n_candidates]}``: the posterior probability of each candidate transcript given the frames and "the
+        video follows one of them" -- log Z_a of the candidate minus the candidates' logsumexp, exponentiated; it adds up to 1.
+        Identical candidates share one class sequence and so one mass: it goes to the one with the lowest index, the others
+        get 0.  All zeros where no candidate can be laid over the video.  One forward and one backward launch per trie
+        (``SemiMarkovModule.transcript_node_posteriors_packed``: the end posteriors of the trie's nodes); a set split into
+        several tries weighs each trie by its share of the total."""
+        pc, rounds = self._candidate_rounds(data, candidates_by_video, shard, 'candidate_posteriors')
+        if pc.n_videos == 0:
+            return {}
+        out = [np.zeros(len(candidates_by_video[name])) for name in pc.video_names]
+        zs = []
+        for row in rounds:
+            graphs = [t for t, _, _ in row]
+            z = self.model.transcript_graph_scores_packed(pc, graphs).numpy()
+            _, p_end = self.model.transcript_node_posteriors_packed(pc, graphs)
+            zs.append(np.where([fresh for _, _, fresh in row], z, -np.inf))
+            for i, (_, owner, fresh) in enumerate(row):
+                if fresh and np.isfinite(z[i]):
+                    ends = owner >= 0
+                    out[i][owner[ends]] = p_end[i][ends]            # (within the trie; weighed below)
+        zs = np.array(zs)                                           # [launches, videos]
+        top = zs.max(axis=0)
+        with np.errstate(invalid='ignore'):
+            share = np.where(np.isfinite(top), np.exp(zs - np.where(np.isfinite(top), top, 0.0)), 0.0)
+        share = share / np.maximum(share.sum(axis=0), 1e-300)
+        for r, row in enumerate(rounds):
+            for i, (_, owner, fresh) in enumerate(row):
+                if fresh:
+                    out[i][owner[owner >= 0]] *= share[r, i]
+        return dict(zip(pc.video_names, out))
+
+    @staticmethod
     def _one_kind_of_flags(optional_by_video, optional_classes, what):
         if optional_by_video is not None and optional_classes is not None:
             raise ValueError("%s: give optional_by_video or optional_classes, not both" % what)

@@ -226,6 +226,47 @@ class _TranscriptOptLogPartition(torch.autograd.Function):
         return None, None, None, None, None, None, g_w, g_cst, g_iv, g['trans'], g['init'], g['len']
 
 
+class _TranscriptGraphLogPartition(torch.autograd.Function):
+    """log Z_g of every video of one launch -- the sum over every alignment to every start -> end path of the video's
+    transcript graph -- beside ``_TranscriptOptLogPartition``.  Forward: smm_emission_f64 + smm_align_graph_logz_f64 on a private
+    workspace that survives until backward; backward: smm_align_graph_logz_bwd_f64 + smm_emission_bwd_f64.  ``local``: one
+    ``ops.TranscriptGraph`` in local state ids per video."""
+
+    @staticmethod
+    def forward(ctx, batch, x, cons, endpen, local, w, cst, inv_var, trans, init, len_scores):
+        r = _emit(batch, x, cons, endpen, (w, cst, trans, init, len_scores, None), inv_var)
+        out = ops.align_graph_logz(batch, r['elp'], trans, init, len_scores, local, endpen=endpen)
+        ctx.batch, ctx.endpen, ctx.ws, ctx.local, ctx.staged = batch, endpen, out['ws'], local, out['_staged']
+        ctx.save_for_backward(x, r['elp'], trans, init, len_scores, out['logz'])
+        return out['logz']
+
+    @staticmethod
+    def backward(ctx, gz):
+        x, elp, trans, init, len_scores, logz = ctx.saved_tensors
+        g = ops.align_graph_logz_bwd(ctx.batch, elp, trans, init, len_scores, ctx.local, logz,
+                                     grad_logz=gz.to(torch.float64).contiguous(), endpen=ctx.endpen, ws=ctx.ws, staged=ctx.staged)
+        g_w, g_cst, g_iv = ops.emission_bwd(ctx.batch, x, g['elp'], ws=ctx.ws)
+        return None, None, None, None, None, g_w, g_cst, g_iv, g['trans'], g['init'], g['len']
+
+
+def _checked_graphs(graphs, n_videos, ambiguous, names, what):
+    """The graphs of a launch, checked on the host before a device is touched: one ``ops.TranscriptGraph`` per video;
+    ``ambiguous='raise'``: ValueError naming the first video two start -> end paths of whose graph spell the same class
+    sequence (``TranscriptGraph.is_ambiguous``), ``'allow'``: the sum over paths and boundaries as defined."""
+    if ambiguous not in ('raise', 'allow'):
+        raise ValueError("%s: ambiguous must be 'raise' or 'allow'" % what)
+    if len(graphs) != n_videos:
+        raise ValueError("%s: %d graphs for %d videos" % (what, len(graphs), n_videos))
+    for i, g in enumerate(graphs):
+        if not isinstance(g, ops.TranscriptGraph):
+            raise ValueError("%s: an ops.TranscriptGraph expected for video %r" % (what, i if names is None else names[i]))
+        if ambiguous == 'raise' and g.is_ambiguous():
+            raise ValueError("%s: two start -> end paths of the graph of video %r spell the same class sequence, so its "
+                             "segmentations would be counted once per path; pass ambiguous='allow' for that sum over "
+                             "alignments" % (what, i if names is None else names[i]))
+    return list(graphs)
+
+
 def _checked_optional(transcripts, optional, ambiguous, names, what):
     """The flags of a launch as boolean arrays, checked on the host before a device is touched (``transcripts`` in global or
     local ids: the map between them is one-to-one within a video): one sequence per video, as long as its transcript; ``ambiguous='raise'``: ValueError naming the first video two subsets of whose optional entries give the
@@ -1320,6 +1361,87 @@ class SemiMarkovModule(nn.Module):
         _check_transcript_logz(out['logz'], None, 'transcript_entry_posteriors_packed', allow_none=True)
         return [p.cpu().numpy() for p in grads['entry_prob']]
 
+    # ------------------------------------------------------------------ transcript-graph likelihood (smm_align_graph_logz_f64)
+    def transcript_graph_log_partition(self, features, lengths, valid_classes_per_instance, graphs, add_eos=True,
+                                       additional_allowed_ends_per_instance=None, constraints=None, ambiguous='raise'):
+        """log Z_g per video of a zero-padded single-task batch (argument conventions of ``align_graph``): the log of the sum
+        over every segmentation whose class sequence is a start -> end path of ``graphs[i]`` (an ``ops.TranscriptGraph`` in
+        GLOBAL class ids) -- for a candidate set (``TranscriptGraph.from_candidates``) the joint log-likelihood of the frames and
+        "one of these transcripts"; minus ``log_partition`` the conditional one.  fp64 b on the device, differentiable w.r.t.
+        the module's parameters (smm_emission_f64 + smm_align_graph_logz_f64 forward, smm_align_graph_logz_bwd_f64 +
+        smm_emission_bwd_f64 backward).  ``ambiguous``: 'raise' (ValueError naming the first video two paths of whose graph
+        spell the same class sequence) or 'allow' (such a sequence's segmentations count once per path).  ValueError for
+        add_eos=False, a wrong number of graphs, and for a video none of whose paths can be laid over it (log Z_g = -inf; a
+        class that is not valid for the video does that); SmmError when a NaN reached the DP."""
+        if not add_eos:
+            raise ValueError("transcript_graph_log_partition: add_eos=False is not supported")
+        graphs = _checked_graphs(graphs, features.size(0), ambiguous, None, 'transcript_graph_log_partition')
+        valid_classes = self._check_valid_classes(valid_classes_per_instance)
+        ids = list(range(self.n_classes)) if valid_classes is None else [int(v) for v in valid_classes]
+        local = self._local_graphs(graphs, np.array([ids + [self.n_classes]], np.int64), [len(ids)], np.zeros(len(graphs), np.int64))
+        self._require_device(features, 'transcript_graph_log_partition')
+        st = self._one_group_tables(valid_classes, features.device)
+        batch, x, cons, endpen, _, _ = self._stage_padded(features, lengths, valid_classes, additional_allowed_ends_per_instance,
+                                                          constraints, check_no_eos=False, tables=st)
+        z = _TranscriptGraphLogPartition.apply(batch, x, cons, endpen, local, st['w'], st['cst'], st['inv_var'], st['trans'],
+                                               st['init'], st['len'])
+        _check_transcript_logz(z, None, 'transcript_graph_log_partition')
+        return z
+
+    def transcript_graph_log_partition_packed(self, pc, graphs, ambiguous='raise'):
+        """``transcript_graph_log_partition`` for a whole PackedCorpus in one launch of each kernel: ``graphs`` holds one
+        ``ops.TranscriptGraph`` in GLOBAL class ids per video, in the order of ``pc.video_names``.  fp64 [n_videos],
+        differentiable."""
+        graphs = _checked_graphs(graphs, len(pc.video_names), ambiguous, list(pc.video_names), 'transcript_graph_log_partition_packed')
+        self._require_device(pc.x, 'transcript_graph_log_partition_packed')
+        if pc.batch is not None and pc.batch.no_eos:
+            raise ValueError("transcript_graph_log_partition_packed: add_eos=False is not supported")
+        self.prepare_packed(pc, differentiable=True)
+        t, batch = pc.tables, pc.batch
+        group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
+        local = self._local_graphs(graphs, t['class_map'].cpu().numpy(), batch.n_states, group)
+        z = _TranscriptGraphLogPartition.apply(batch, pc.x, pc.cons, pc.endpen, local, t['w'], t['cst'], t['inv_var'], t['trans'],
+                                               t['init'], t['len'])
+        _check_transcript_logz(z, list(pc.video_names), 'transcript_graph_log_partition_packed')
+        return z
+
+    @torch.no_grad()
+    def transcript_graph_scores_packed(self, pc, graphs, conditional=False, ambiguous='raise'):
+        """Without autograd, on the cached decode tables: log Z_g of every video of a PackedCorpus (``conditional``: minus its
+        log Z) as a CPU fp64 tensor; -inf for a video none of whose paths can be laid over it.  One emission launch, then the
+        DP launches.  SmmError when a NaN reached the DP.  ``ambiguous``: as in ``transcript_graph_log_partition``."""
+        if pc.batch is not None and pc.batch.no_eos:
+            raise ValueError("transcript_graph_scores_packed: add_eos=False is not supported")
+        graphs = _checked_graphs(graphs, len(pc.video_names), ambiguous, list(pc.video_names), 'transcript_graph_scores_packed')
+        batch, x, cons, endpen, g, inv_var = self._packed_stage(pc, 'transcript_graph_scores_packed')
+        group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
+        local = self._local_graphs(graphs, g[5].cpu().numpy(), batch.n_states, group)
+        r = _emit(batch, x, cons, endpen, g, inv_var)
+        z = ops.align_graph_logz(batch, r['elp'], r['trans'], r['init'], r['len'], local, endpen=endpen)['logz']
+        if conditional:
+            z = z - ops.logz(batch, r['elp'], r['trans'], r['init'], r['len'], endpen=endpen)
+        return _check_transcript_logz(z, None, 'transcript_graph_scores_packed', allow_none=True)
+
+    @torch.no_grad()
+    def transcript_node_posteriors_packed(self, pc, graphs):
+        """Per video of a PackedCorpus the posterior probability, given the frames and "the class sequence is a path of the
+        graph", that the path crosses each node and that it ends in it (p_used and p_end of smm_align_graph_logz_bwd_f64):
+        (p_used, p_end), two lists of fp64 CPU arrays in the order of ``pc.video_names``; zeros for a video without an
+        alignment, p_end adds up to 1 otherwise.  Paths that spell the same class sequence share its mass as they share its
+        segmentations.  One emission launch, then the forward and the backward launches.  SmmError when a NaN reached the DP."""
+        if pc.batch is not None and pc.batch.no_eos:
+            raise ValueError("transcript_node_posteriors_packed: add_eos=False is not supported")
+        graphs = _checked_graphs(graphs, len(pc.video_names), 'allow', list(pc.video_names), 'transcript_node_posteriors_packed')
+        batch, x, cons, endpen, g, inv_var = self._packed_stage(pc, 'transcript_node_posteriors_packed')
+        group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
+        local = self._local_graphs(graphs, g[5].cpu().numpy(), batch.n_states, group)
+        r = _emit(batch, x, cons, endpen, g, inv_var)
+        out = ops.align_graph_logz(batch, r['elp'], r['trans'], r['init'], r['len'], local, endpen=endpen)
+        grads = ops.align_graph_logz_bwd(batch, r['elp'], r['trans'], r['init'], r['len'], local, out['logz'], endpen=endpen,
+                                         ws=out['ws'], staged=out['_staged'], want_node_prob=True, want_end_prob=True)
+        _check_transcript_logz(out['logz'], None, 'transcript_node_posteriors_packed', allow_none=True)
+        return [p.cpu().numpy() for p in grads['node_prob']], [p.cpu().numpy() for p in grads['end_prob']]
+
     # ------------------------------------------------------------------ packed multi-task decode
     def stacked_tables(self, pc, differentiable=False):
         """fp64 factor tables of every group of a PackedCorpus stacked to [groups, ...] and zero-padded to c_max columns.
@@ -1622,7 +1744,8 @@ class SemiMarkovModule(nn.Module):
         return torch.mv(mean_of, z)
 
     def log_likelihood(self, features, lengths, valid_classes_per_instance, spans=None, add_eos=True, use_mean_z=False,
-                       additional_allowed_ends_per_instance=None, constraints=None, transcripts=None, transcript_optional=None):
+                       additional_allowed_ends_per_instance=None, constraints=None, transcripts=None, transcript_optional=None,
+                       transcript_graphs=None):
         """(mean log-likelihood, mean log_det) like the reference (:597-658).
 
         spans given: joint score p(x, y) (differentiable), or with --sm_train_discriminatively the conditional
@@ -1631,9 +1754,14 @@ class SemiMarkovModule(nn.Module):
         transcripts given (and no spans): only the order of each video's actions is known -- the mean of log Z_a
         (``transcript_log_partition``), or with --sm_train_discriminatively of log Z_a - log Z.  ``transcript_optional``: one
         boolean sequence per transcript, the flagged entries may be missing (log Z_o; ValueError for an ambiguous transcript).
+        transcript_graphs given (and neither spans nor transcripts): one ``ops.TranscriptGraph`` per video, e.g. the trie of its
+        candidate transcripts -- the mean of log Z_g (``transcript_graph_log_partition``; ValueError for an ambiguous graph),
+        or with --sm_train_discriminatively of log Z_g - log Z.
         """
         if spans is not None and transcripts is not None:
             raise ValueError("log_likelihood: give spans (full supervision) or transcripts (the order only), not both")
+        if transcript_graphs is not None and (spans is not None or transcripts is not None):
+            raise ValueError("log_likelihood: give transcript_graphs alone, without spans or transcripts")
         if transcript_optional is not None and transcripts is None:
             raise ValueError("log_likelihood: transcript_optional goes with transcripts")
         no_eos = not add_eos
@@ -1644,6 +1772,14 @@ class SemiMarkovModule(nn.Module):
             ll = self.transcript_log_partition(features, lengths, valid_classes_per_instance, transcripts, add_eos=add_eos,
                                                additional_allowed_ends_per_instance=additional_allowed_ends_per_instance,
                                                constraints=constraints, optional=transcript_optional)
+            if getattr(self.args, 'sm_train_discriminatively', False):
+                ll = ll - self.log_partition(features, lengths, valid_classes, additional_allowed_ends_per_instance,
+                                             constraints)
+        elif transcript_graphs is not None:
+            ll = self.transcript_graph_log_partition(features, lengths, valid_classes_per_instance, transcript_graphs,
+                                                     add_eos=add_eos,
+                                                     additional_allowed_ends_per_instance=additional_allowed_ends_per_instance,
+                                                     constraints=constraints)
             if getattr(self.args, 'sm_train_discriminatively', False):
                 ll = ll - self.log_partition(features, lengths, valid_classes, additional_allowed_ends_per_instance,
                                              constraints)

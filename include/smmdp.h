@@ -35,6 +35,8 @@
  *   smm_align_logz_bwd_f64     and its gradient (the objective and the E-step of transcript supervision; the reference has none)
  *   smm_align_opt_logz_f64 / <- ... with optional transcript entries: the sum over every alignment, any subset of them left
  *   smm_align_opt_logz_bwd_f64   out, its gradient and each entry's posterior of being used (the reference has none)
+ *   smm_align_graph_logz_f64 / <- ... over a transcript graph: the sum over every start -> end path's alignments ("one of these
+ *   smm_align_graph_logz_bwd_f64   N transcripts" as a trie), its gradient and the node / end posteriors (the reference has none)
  *
  * The reference has no FFI: its boundary is the Python call SemiMarkovCRF(scores, lengths) on a dense
  * b x N x K x C x C tensor.  These entry points take the FACTORS of that tensor instead,
@@ -750,6 +752,73 @@ int smm_align_opt_logz_bwd_f64(const smm_shape *shape, const int64_t *lengths_ho
                                double *g_elp, double *g_trans, double *g_init, double *g_len,
                                double *p_used /* dev double, laid out like transcript, nullable */, void *workspace,
                                size_t workspace_bytes, void *stream);
+
+/*
+ * Transcript-graph likelihood (csrc/smm_align_graph_logz.hip): the log-semiring counterpart of smm_align_graph_f64, with its
+ * gradient and the node / end posteriors.  Per video log Z_g = log of the sum of exp score over every ALIGNMENT of the video to
+ * the graph: a start -> end path, and the boundaries of its nodes' segments.  With a candidate set as its prefix trie this is
+ * the "one of these N transcripts" objective, and p_end the posterior over the candidates.  Nodes, pred, start, end, the mask /
+ * flag / offset encodings and kw = kp - 1 are exactly smm_align_graph_f64's; lse, cum and closing_j as in
+ * smm_align_opt_logz_f64; succ(j) = { m : j in pred(m) }.
+ *   forward   h[0][m]   = init[a_m] if start(m), else -inf
+ *             h[n][m]   = lse_{j in pred(m)} ( gam[n][j] + trans[a_m][a_j] ) - cum[n][a_m]            0 < n < T
+ *             gam[n][m] = cum[n][a_m] + lse_{k=1..min(kw,n)} ( h[n-k][m] + len[k][a_m] )              n = 1..T
+ *             logZ_g    = lse_{j : end(j)} ( gam[T][j] + closing_j )
+ *   backward  bg[T][j]  = closing_j if end(j), else -inf
+ *             bh[s][m]  = lse_{k=1..min(kw,T-s)} ( len[k][a_m] + cum[s+k][a_m] + bg[s+k][m] )         s = 0..T-1
+ *             bg[n][j]  = lse_{m in succ(j)} ( trans[a_m][a_j] - cum[n][a_m] + bh[n][m] )             0 < n < T
+ *             (identity: lse_{m : start(m)} ( h[0][m] + bh[0][m] ) = logZ_g)
+ *   marginals S, E, occ as smm_align_opt_logz_f64;  p_used[m] = sum_n E[n][m]      node m lies on the path
+ *             p_end[j]  = exp(gam[T][j] + closing_j - logZ_g) for end(j), else 0   the path ends in node j
+ *   gradients of sum_i u_i logZ_g(i)   (u = grad_logz, NULL = ones): g_elp, g_len as smm_align_opt_logz_f64;
+ *             g_trans[c][c'] = sum_i u_i sum_{edges j->m : a_m=c, a_j=c'} sum_{0<n<T}
+ *                                      exp(gam[n][j] + trans[c][c'] - cum[n][c] + bh[n][m] - logZ_g)
+ *             g_init[c]      = sum_i u_i sum_{m : start(m), a_m=c} S[0][m]
+ * What is summed is paths times boundaries, not class sequences: two start -> end paths that spell the same class sequence
+ * count its segmentations twice (the Python layer ships the predicate: TranscriptGraph.is_ambiguous).  A prefix trie never
+ * has two such paths: for a trie logZ_g = lse over the distinct candidates of smm_align_logz_f64's logZ_a.
+ * The start posteriors S[0][m] are normalised by the backward pass's own total (the identity's left side), so g_init of a video
+ * adds up to u_i.  Nothing else is decided by the structure: every other posterior is a sum of exponentials, and a chain's
+ * g_trans is 1 per transition only to the family's accuracy.
+ * Numerics of smm_align_logz_f64 for the span sums; a sum over pred(m) or succ(j) takes its own maximum as the reference and
+ * exponentiates in fp64; a single predecessor or successor comes out as (gam + trans) - cum, smm_align_logz_f64's
+ * association, exactly.  Every sum is taken in a fixed order without atomics: two calls on the same inputs give the same bits.
+ *   - Degenerate videos follow smm_align_graph_f64's rule: no start -> end path, Lmin > T, kw < 1, Lmax kw < T, an id outside
+ *     [0, n_states) or a mask bit j >= m give logZ_g = -inf, exactly zero gradient contributions and p_used / p_end 0; the
+ *     error word stays clear and no table is read.
+ *   - A video that passes this rule but has no alignment of finite score gets the same.
+ *   - The error word is set, logZ_g is NaN, the contributions, p_used and p_end are zero under smm_align_graph_f64's
+ *     conditions: every node and every edge, on a start -> end path or not.
+ * smm_align_graph_logz_bwd_f64 must follow smm_align_graph_logz_f64 for the same batch, tables and graphs on the same
+ * workspace and stream: it reads the cum, h and gam columns and the columns' ranges the forward call left there.  g_elp,
+ * g_trans, g_init, g_len have smm_logz_bwd_f64's layouts and are overwritten entirely; p_used and p_end (nullable) are laid out
+ * like node_class and written for every node.  Staging the backward call clears the error word, and the backward call sets it
+ * again for every video whose logz_g is NaN.  Enqueued on `stream` only; never synchronises; a video is never split.
+ * The workspace is smm_align_graph_logz_workspace_bytes: smm_workspace_bytes (cum lives in its history area), the offsets and
+ * the launch order, then per video 8 * (3 M + 4 M (T + 1)) bytes -- the columns' recorded ranges and the h, gam, q and bh
+ * columns -- then per video 8 * (min(k_rows, T + 1) c_max + c_max^2 + c_max + 1) bytes: its parts of g_len, g_trans and g_init
+ * and the backward pass's own logZ_g; each area starts on a multiple of 256 bytes.
+ * Refusals as smm_align_graph_f64: SMM_ERR_ARG for a NULL required pointer, non-monotone offsets or a video without nodes;
+ * SMM_ERR_UNSUPPORTED for SMM_SHAPE_NO_EOS, more than SMM_MAX_TRANSCRIPT nodes in a video, c_max or k_rows beyond the compiled
+ * kernels; SMM_ERR_WORKSPACE below smm_align_graph_logz_workspace_bytes -- all before anything is staged.
+ */
+/* host only; 0 on whatever the calls refuse for the shape, the lengths or the offsets */
+size_t smm_align_graph_logz_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host, const int64_t *node_offset_host);
+int smm_align_graph_logz_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                             const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                             const double *elp, const double *trans, const double *init, const double *len_scores,
+                             const double *endpen, const int32_t *node_class, const uint32_t *pred_mask,
+                             const uint8_t *node_flags, const int64_t *node_offset_host, double *logz_g /* dev [b] */,
+                             void *workspace, size_t workspace_bytes, void *stream);
+int smm_align_graph_logz_bwd_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                 const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                 const double *elp, const double *trans, const double *init, const double *len_scores,
+                                 const double *endpen, const int32_t *node_class, const uint32_t *pred_mask,
+                                 const uint8_t *node_flags, const int64_t *node_offset_host, const double *logz_g,
+                                 const double *grad_logz /* nullable */, double *g_elp, double *g_trans, double *g_init,
+                                 double *g_len, double *p_used /* dev double, laid out like node_class, nullable */,
+                                 double *p_end /* the same layout, nullable */, void *workspace, size_t workspace_bytes,
+                                 void *stream);
 
 /*
  * Factor tables of every parameter group from the model parameters (training steps), and their chain rule.
