@@ -2423,6 +2423,35 @@ extern "C" int smm_align_graph_logz_bwd_f64(const smm_shape *shape, const int64_
     return SMM_OK;
 }
 
+// alignments drawn from the graph posterior (smm_align_graph_sample.hip): the forward call's staging and arguments again (the
+// same layout, so the same columns), then the sampler's own outputs
+extern "C" int smm_align_graph_sample_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                          const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                          const double *elp, const double *trans, const double *init, const double *len_scores,
+                                          const double *endpen, const int64_t *class_map, const int32_t *node_class,
+                                          const uint32_t *pred_mask, const uint8_t *node_flags, const int64_t *node_offset_host,
+                                          const double *logz_g, int32_t n_samples, uint64_t seed, int64_t *spans_out,
+                                          int64_t *labels_out, double *logp_out, int32_t *n_segs_out, int32_t *used_out,
+                                          void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!pred_mask || !node_flags || n_samples <= 0) return SMM_ERR_ARG;
+    if (!spans_out && !labels_out && !logp_out && !n_segs_out && !used_out) return SMM_ERR_ARG;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    SmmAlignSampleArgs a{};
+    const int rc = align_logz_prepare(ALIGN_GRAPH_LOGZ, shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host,
+                                      elp, trans, init, len_scores, endpen, node_class, node_offset_host, logz_g, workspace,
+                                      workspace_bytes, hs, &a.g);
+    if (rc != SMM_OK) return rc;
+    a.g.pred_mask = pred_mask; a.g.node_flags = node_flags;
+    a.class_map = class_map;
+    a.spans = spans_out; a.labels = labels_out; a.logp = logp_out; a.n_segs = n_segs_out; a.used = used_out;
+    a.total_frames = shape->total_frames; a.n_nodes = node_offset_host[shape->b];
+    a.seed = seed; a.t_max = shape->t_max; a.n_samples = n_samples;
+    smm_launch_align_graph_sample(a, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ dense boundary
 struct DenseLayout {
     size_t o_len, o_alpha, o_beta, o_bp_from, o_bp_k, o_rmsg, total;

@@ -293,3 +293,19 @@ void smm_launch_align_opt_logz_tail(const SmmAlignLogzArgs &a, hipStream_t strea
 // ranges (3 M doubles), then h | gam | q | bh, each [M][T+1]; its parts as smm_align_opt_logz's
 void smm_launch_align_graph_logz_fwd(const SmmAlignLogzArgs &a, hipStream_t stream);
 void smm_launch_align_graph_logz_bwd(const SmmAlignLogzArgs &a, hipStream_t stream);
+
+// alignments drawn from the transcript-graph posterior (smm_align_graph_sample.hip): after smm_launch_align_graph_logz_fwd on
+// the same workspace -- it reads cum, the h and gam columns and the columns' ranges, and writes the error word only
+struct SmmAlignSampleArgs {
+    SmmAlignLogzArgs g;        // the forward launch's arguments (logz: read; the backward call's fields: unused)
+    const int64_t *class_map;  // [g][c_max+1] or null
+    int64_t *spans;            // [n_samples][b][t_max+1] or null
+    int64_t *labels;           // [n_samples][total_frames] or null
+    double *logp;              // [n_samples][b] or null
+    int32_t *n_segs;           // [n_samples][b] or null
+    int32_t *used;             // [n_samples][n_nodes] or null
+    int64_t total_frames, n_nodes;
+    uint64_t seed;
+    int32_t t_max, n_samples;
+};
+void smm_launch_align_graph_sample(const SmmAlignSampleArgs &a, hipStream_t stream);

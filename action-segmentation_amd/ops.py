@@ -1196,6 +1196,42 @@ def align_graph_logz_bwd(batch, elp, trans, init, len_scores, graphs, logz_g, gr
     return g
 
 
+def align_graph_sample(batch, elp, trans, init, len_scores, graphs, logz_g, n_samples, seed=0, endpen=None, class_map=None,
+                       ws=None, staged=None, want_spans=True, want_labels=True, want_used=True):
+    """Alignments drawn from the transcript-graph posterior (smm_align_graph_sample_f64): per video ``n_samples`` independent
+    draws of a start -> end path of its ``TranscriptGraph`` (LOCAL state ids) and the boundaries of its nodes' segments, from
+    the distribution whose normaliser ``align_graph_logz`` returns.  Must follow ``align_graph_logz`` for the same batch,
+    tables and graphs with the same workspace ``ws`` on the same stream (``ws`` and ``staged``: its ``ws`` and ``_staged``
+    entries); ``logz_g`` = its output.  ``align_graph_logz_bwd`` may run in between: the samples do not change.
+    -> dict(spans int64 [n_samples, b, t_max+1] or None, labels int64 [n_samples, total_frames] (-1 on frames no video covers)
+    or None, logp fp64 [n_samples, b]: the exact log-probability of the drawn alignment -- on an ambiguous graph of the path
+    and its boundaries, not of the class sequence --, n_segs int32 [n_samples, b], used: a list of per-video int32
+    [n_samples, M_i] views of one device tensor, 1 for the nodes of the sampled path, or None, _err, _keep).  A video without
+    an alignment (log Z_g = -inf) gets spans and labels -1, n_segs 0, used 0 and logp NaN.  Sample j depends on
+    (seed, video, j) only."""
+    lib = _lib.load()
+    n_samples = int(n_samples)
+    if n_samples <= 0:
+        raise ValueError("align_graph_sample: n_samples must be positive, got %d" % n_samples)
+    if ws is None:
+        raise ValueError("align_graph_sample: pass the workspace the align_graph_logz call wrote")
+    f64 = torch.float64
+    args, off, st = _align_graph_logz_inputs(batch, elp, trans, init, len_scores, graphs, endpen, staged, 'align_graph_sample')
+    if ws.numel() < align_graph_logz_workspace_bytes(batch, off):
+        raise ValueError("align_graph_sample: pass the workspace the align_graph_logz call wrote")
+    dev = elp.device
+    spans, labels, logp, n_segs = _device_outputs(batch, dev, want_spans, want_labels, (n_samples,))
+    used = torch.empty((n_samples, int(off[-1])), dtype=torch.int32, device=dev) if want_used else None
+    _lib.check(lib.smm_align_graph_sample_f64(
+        *batch.head(), *args[:5], _dev(class_map, torch.int64, 'class_map'), *args[5:], _dev(logz_g, f64, 'logz_g'),
+        ctypes.c_int32(n_samples), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _dev(spans, torch.int64, 'spans'),
+        _dev(labels, torch.int64, 'labels'), _dev(logp, f64, 'logp'), _dev(n_segs, torch.int32, 'n_segs'),
+        _dev(used, torch.int32, 'used'), *_ws_args(ws), _stream()))
+    return dict(spans=spans, labels=labels, logp=logp, n_segs=n_segs,
+                used=None if used is None else list(torch.split(used, np.diff(off).tolist(), dim=1)),
+                _err=_err_copy(batch, ws), _staged=st, _keep=(ws,))
+
+
 def transcript_is_ambiguous(ids, optional):
     """Host only: True when two different subsets of the optional entries of this transcript give the same non-empty class
     sequence -- ``align_opt_logz`` then counts the segmentations with that class sequence once per subset.  Exact: over the

@@ -556,6 +556,71 @@ class SemiMarkovModel(object):
                     out[i][owner[owner >= 0]] *= share[r, i]
         return dict(zip(pc.video_names, out))
 
+    def sample_alignments(self, data, transcripts_by_video, n_samples, seed=0, shard=None, *, optional_by_video=None,
+                          optional_classes=None):
+        """Alignments of every video of ``data`` drawn from the posterior given its transcript (``align``'s conventions for
+        ``transcripts_by_video``, ``optional_by_video`` and ``optional_classes``): where the boundaries lie and, with optional
+        entries, which of them are kept.  Returns ``{video: int64 [n_samples, T]}`` frame labels -- pseudo-labels for
+        ``fit_supervised`` (stochastic EM from transcripts) --, rows of -1 where the transcript cannot be laid over the video.
+        Sample j depends on (seed, video, j) only.  One emission launch, the forward launch and the sampler on the packed
+        corpus (``SemiMarkovModule.sample_alignments_packed``)."""
+        from . import ops
+        self._one_kind_of_flags(optional_by_video, optional_classes, 'sample_alignments')
+        if int(n_samples) < 1:
+            raise ValueError("sample_alignments: n_samples must be positive, got %d" % int(n_samples))
+        self.model.eval()
+        pc = self.prepare(data, shard=shard)
+        if pc.n_videos == 0:
+            return {}
+        missing = [name for name in pc.video_names if name not in transcripts_by_video]
+        if missing:
+            raise ValueError("sample_alignments: no transcript for video %r" % (missing[0],))
+        transcripts = [transcripts_by_video[name] for name in pc.video_names]
+        optional = self._optional_flags(pc, transcripts, optional_by_video, optional_classes, 'sample_alignments')
+        if optional is None:
+            graphs = [ops.TranscriptGraph.chain(t) for t in transcripts]
+        else:
+            graphs = [ops.TranscriptGraph.from_optional(t, f) for t, f in zip(transcripts, optional)]
+        labels, _, _ = self.model.sample_alignments_packed(pc, graphs, n_samples, seed=seed)
+        lab = labels.cpu().numpy()
+        assert lab.size == 0 or int(lab.max()) < self.model.n_classes, "alignments should not contain EOS"
+        return {name: lab[:, off:off + t] for name, off, t in zip(pc.video_names, pc.frame_offset, pc.lengths)}
+
+    def sample_candidates(self, data, candidates_by_video, n_samples, seed=0, shard=None):
+        """Joint draws of which candidate transcript a video follows and where its boundaries lie, from the posterior given
+        the frames and "the video follows one of them" (``candidates_by_video`` as in ``align_candidates``).  Returns
+        ``({video: int64 [n_samples, T] frame labels}, {video: int64 [n_samples] candidate index})``; identical candidates
+        map to the lowest index, as in ``candidate_posteriors``; labels and index -1 where no candidate can be laid over the
+        video.  The candidates go to the GPU as one prefix trie per video: ValueError for a set whose trie needs more than
+        ``ops.MAX_TRANSCRIPT`` nodes (a draw across several tries is not offered)."""
+        from . import ops
+        if int(n_samples) < 1:
+            raise ValueError("sample_candidates: n_samples must be positive, got %d" % int(n_samples))
+        for name, cands in candidates_by_video.items():
+            if not cands:
+                raise ValueError("sample_candidates: no candidates for video %r" % (name,))
+            nodes = ops.TranscriptGraph.trie_nodes(cands)
+            if nodes > ops.MAX_TRANSCRIPT:
+                raise ValueError("sample_candidates: the trie of the candidates of video %r has %d nodes (at most %d)"
+                                 % (name, nodes, ops.MAX_TRANSCRIPT))
+        self.model.eval()
+        pc = self.prepare(data, shard=shard)
+        if pc.n_videos == 0:
+            return {}, {}
+        missing = [name for name in pc.video_names if name not in candidates_by_video]
+        if missing:
+            raise ValueError("sample_candidates: no candidates for video %r" % (missing[0],))
+        graphs = [ops.TranscriptGraph.from_candidates(candidates_by_video[name]) for name in pc.video_names]
+        labels, _, used = self.model.sample_alignments_packed(pc, graphs, n_samples, seed=seed)
+        lab = labels.cpu().numpy()
+        assert lab.size == 0 or int(lab.max()) < self.model.n_classes, "alignments should not contain EOS"
+        chosen = {}
+        for name, g, u in zip(pc.video_names, graphs, used):
+            u = u.cpu().numpy() != 0                               # [n_samples, M]; the end node is the last used one
+            last = u.shape[1] - 1 - np.argmax(u[:, ::-1], axis=1)
+            chosen[name] = np.where(u.any(axis=1), g.end_candidate[last], -1).astype(np.int64)
+        return ({name: lab[:, off:off + t] for name, off, t in zip(pc.video_names, pc.frame_offset, pc.lengths)}, chosen)
+
     @staticmethod
     def _one_kind_of_flags(optional_by_video, optional_classes, what):
         if optional_by_video is not None and optional_classes is not None:

@@ -155,6 +155,17 @@ def _align(r, local, want_spans, optional=None, graphs=False):
     return _paths(r['batch'], out, want_spans), out['best']
 
 
+def _sample_alignments(r, local, n_samples, seed, want_spans):
+    """The forward launch over the graphs ``local`` (local state ids) on a private workspace, then the sampler on it:
+    (spans or labels, logp, used).  A video without an alignment is no error: rows of -1 and logp NaN."""
+    b = r['batch']
+    z = ops.align_graph_logz(b, r['elp'], r['trans'], r['init'], r['len'], local, endpen=r['endpen'])
+    out = ops.align_graph_sample(b, r['elp'], r['trans'], r['init'], r['len'], local, z['logz'], n_samples, seed=seed,
+                                 endpen=r['endpen'], class_map=r['class_map'], ws=z['ws'], staged=z['_staged'],
+                                 want_spans=want_spans, want_labels=not want_spans)
+    return _paths(b, out, want_spans), out['logp'], out['used']
+
+
 class _LogPartition(torch.autograd.Function):
     """log Z of every video of one launch as a differentiable function of the fp64 factor tables (emission factors w,
     cst; transition, initial and length tables; stacked per parameter group).  Forward: smm_emission_f64 +
@@ -1441,6 +1452,51 @@ class SemiMarkovModule(nn.Module):
                                          ws=out['ws'], staged=out['_staged'], want_node_prob=True, want_end_prob=True)
         _check_transcript_logz(out['logz'], None, 'transcript_node_posteriors_packed', allow_none=True)
         return [p.cpu().numpy() for p in grads['node_prob']], [p.cpu().numpy() for p in grads['end_prob']]
+
+    # ------------------------------------------------------------------ samples of the graph posterior (smm_align_graph_sample_f64)
+    @torch.no_grad()
+    def sample_alignments(self, features, lengths, valid_classes_per_instance, graphs, n_samples=1, seed=0, add_eos=True,
+                          additional_allowed_ends_per_instance=None, constraints=None):
+        """Alignments drawn from the posterior of transcript supervision, p(alignment | x, "the class sequence is a
+        start -> end path of ``graphs[i]``"), for a zero-padded single-task batch (argument conventions of ``align_graph``;
+        graphs in GLOBAL class ids): one emission launch, the forward launch (smm_align_graph_logz_f64) and the sampler
+        (smm_align_graph_sample_f64).  Sample j depends on (seed, video, j) only.
+
+        Returns (spans, log_prob, used): spans CPU int64 n_samples x b x (Tmax+1) in ``viterbi``'s pred_spans format, log_prob
+        fp64 n_samples x b on the device -- the exact log-probability of each drawn alignment (path and boundaries) --, used a
+        list of per-video int32 device tensors n_samples x M_i, 1 for the nodes of the sampled path.  A video none of whose
+        paths can be laid over it gives rows of -1, log_prob NaN and no used node.  ValueError for a wrong number of graphs,
+        n_samples < 1 or add_eos=False; SmmError when a NaN reached the DP.  No autograd."""
+        if not add_eos:
+            raise ValueError("sample_alignments: add_eos=False is not supported")
+        if int(n_samples) < 1:
+            raise ValueError("sample_alignments: n_samples must be positive, got %d" % int(n_samples))
+        graphs = _checked_graphs(graphs, len(lengths), 'allow', None, 'sample_alignments')
+        self._require_device(features, 'sample_alignments')
+        batch, x, cons, endpen, tab, g1 = self._stage_padded(
+            features, lengths, self._check_valid_classes(valid_classes_per_instance), additional_allowed_ends_per_instance,
+            constraints, check_no_eos=False)
+        local = self._local_graphs(graphs, g1[5].cpu().numpy(), batch.n_states, np.zeros(batch.b, np.int64))
+        return _sample_alignments(_emit(batch, x, cons, endpen, g1, tab['inv_var']), local, n_samples, seed, want_spans=True)
+
+    @torch.no_grad()
+    def sample_alignments_packed(self, pc, graphs, n_samples, seed=0):
+        """``sample_alignments`` for a whole PackedCorpus: one emission launch, the forward launch and the sampler.  ``graphs``:
+        one ``ops.TranscriptGraph`` in GLOBAL class ids per video, in the order of ``pc.video_names``.  Returns (labels,
+        log_prob, used): device int64 n_samples x total_frames (global class ids on the packed frame axis, -1 on frames no
+        video covers and on videos without an alignment), fp64 n_samples x n_videos and the per-video flags of the sampled
+        paths' nodes."""
+        if getattr(pc, 'batch', None) is not None and pc.batch.no_eos:
+            raise ValueError("sample_alignments_packed: add_eos=False is not supported")
+        if int(n_samples) < 1:
+            raise ValueError("sample_alignments_packed: n_samples must be positive, got %d" % int(n_samples))
+        graphs = _checked_graphs(graphs, len(pc.video_names), 'allow', list(pc.video_names), 'sample_alignments_packed')
+        batch, x, cons, endpen, g, inv_var = self._packed_stage(pc, 'sample_alignments_packed')
+        if batch.no_eos:                                           # (a corpus this call prepared)
+            raise ValueError("sample_alignments_packed: add_eos=False is not supported")
+        group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
+        local = self._local_graphs(graphs, g[5].cpu().numpy(), batch.n_states, group)
+        return _sample_alignments(_emit(batch, x, cons, endpen, g, inv_var), local, n_samples, seed, want_spans=False)
 
     # ------------------------------------------------------------------ packed multi-task decode
     def stacked_tables(self, pc, differentiable=False):

@@ -37,6 +37,8 @@
  *   smm_align_opt_logz_bwd_f64   out, its gradient and each entry's posterior of being used (the reference has none)
  *   smm_align_graph_logz_f64 / <- ... over a transcript graph: the sum over every start -> end path's alignments ("one of these
  *   smm_align_graph_logz_bwd_f64   N transcripts" as a trie), its gradient and the node / end posteriors (the reference has none)
+ *   smm_align_graph_sample_f64 <- ... and alignments drawn from that posterior: a path of the graph and its boundaries (pseudo-labels
+ *                              for stochastic EM from transcripts, boundary uncertainty; the reference has none)
  *
  * The reference has no FFI: its boundary is the Python call SemiMarkovCRF(scores, lengths) on a dense
  * b x N x K x C x C tensor.  These entry points take the FACTORS of that tensor instead,
@@ -127,7 +129,9 @@ int smm_device_count(void);
 
 /* Bytes of device workspace any entry point below needs for this shape (lengths: host array [b]).
  * Returns 0 on invalid arguments.  The workspace is scratch: its contents are undefined after a call,
- * except between smm_logz_f64 and smm_logz_bwd_f64 / smm_sample_f64 / smm_entropy_f64 / smm_kl_f64. */
+ * except between smm_logz_f64 and smm_logz_bwd_f64 / smm_sample_f64 / smm_entropy_f64 / smm_kl_f64, and between a transcript
+ * likelihood call and the calls its comment names (smm_align_graph_logz_f64: smm_align_graph_logz_bwd_f64 and
+ * smm_align_graph_sample_f64, in either order). */
 size_t smm_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host);
 
 /* Byte offset, inside the workspace, of the int32 error word the kernels set.  1: a NaN / inf-inf reached the DP of
@@ -819,6 +823,51 @@ int smm_align_graph_logz_bwd_f64(const smm_shape *shape, const int64_t *lengths_
                                  double *g_len, double *p_used /* dev double, laid out like node_class, nullable */,
                                  double *p_end /* the same layout, nullable */, void *workspace, size_t workspace_bytes,
                                  void *stream);
+
+/*
+ * Alignments drawn from the transcript-graph posterior (csrc/smm_align_graph_sample.hip): n_samples independent draws per video
+ * from p(alignment | x, "the class sequence is a start -> end path of the graph"), the distribution whose normaliser
+ * smm_align_graph_logz_f64 returns.  An ALIGNMENT is a start -> end path and the boundaries of its nodes' segments: on an
+ * ambiguous graph two paths that spell the same class sequence are two alignments, each with its own probability, exactly as
+ * they are two terms of log Z_g.  A chain samples the boundaries of a plain transcript, TranscriptGraph.from_optional which
+ * optional entries are kept as well, a prefix trie which candidate.
+ * Call order: the call must follow smm_align_graph_logz_f64 for the same batch, tables and graphs on the same workspace and
+ * stream; logz_g is that call's output.  It reads cum, the h and gam columns and the columns' ranges, and writes NOTHING into
+ * the workspace but the error word; there is no size query of its own (smm_align_graph_logz_workspace_bytes).
+ * smm_align_graph_logz_bwd_f64 may run before or after it, or between two sampler calls: the backward call writes only the q
+ * and bh columns and the per-video gradient parts, none of which the sampler reads, so the samples do not change by a bit.
+ * The walk, one per (video, sample), from n = T, its weights taken from the forward histories only:
+ *   end node     j ~ exp(gam[T][j] + closing_j) over the nodes with end(j)
+ *   span         the segment of node j that ends at n starts at n - k,  k ~ exp(h[n-k][j] + len[k][a_j]),  k = 1..min(kw, n)
+ *   predecessor  at s = n - k > 0,  i ~ exp(gam[s][i] + trans[a_j][a_i]) over i in pred(j);  the walk stops at s = 0
+ * A candidate outside the ranges the forward call recorded for its column is never loaded and has no mass.
+ * Random numbers: Philox4x32-10 keyed by `seed`, counter = (decision number, sample, video, 1) -- smm_sample_f64's last word is
+ * 0, so the two samplers never share a stream under one seed; every decision takes one counter value, also one with a single
+ * candidate.  Sample j depends on (seed, video, j) only: not on n_samples, the grid or the order the waves run in.
+ * Outputs (each nullable, not all): spans_out and labels_out in smm_sample_f64's encodings (class map applied, the EOS id at
+ * position T; labels_out frames no video covers are left alone); n_segs_out the number of nodes on the path; used_out 1 for the
+ * nodes on the path, laid out like node_class per sample; logp_out the exact log-probability of the drawn alignment: its score
+ * summed in fp64 from init, the elp of every segment, len, trans and the closing term, minus logz_g.  The histories carry the
+ * forward kernel's rounding; they decide the draws, never this value.
+ *   - A video whose logz_g is -inf has no alignment: spans and labels -1, n_segs 0, used 0, logp NaN; the error word stays clear.
+ *   - A NaN logz_g, or a decision without a candidate of finite weight, sets the error word and gives the same outputs.
+ * Enqueued on `stream` only; never synchronises; no atomics but the error word.
+ * Refusals: SMM_ERR_ARG for a NULL required pointer (logz_g included), n_samples <= 0, every output NULL, non-monotone offsets or
+ * a video without nodes; SMM_ERR_UNSUPPORTED for SMM_SHAPE_NO_EOS, more than SMM_MAX_TRANSCRIPT nodes in a video, c_max or k_rows
+ * beyond the compiled kernels; SMM_ERR_WORKSPACE below smm_align_graph_logz_workspace_bytes -- all before anything is staged.
+ */
+int smm_align_graph_sample_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                               const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                               const double *elp, const double *trans, const double *init, const double *len_scores,
+                               const double *endpen, const int64_t *class_map /* nullable */, const int32_t *node_class,
+                               const uint32_t *pred_mask, const uint8_t *node_flags, const int64_t *node_offset_host,
+                               const double *logz_g, int32_t n_samples, uint64_t seed,
+                               int64_t *spans_out  /* dev [n_samples][b][t_max+1], nullable */,
+                               int64_t *labels_out /* dev [n_samples][total_frames], nullable */,
+                               double *logp_out    /* dev [n_samples][b], nullable */,
+                               int32_t *n_segs_out /* dev [n_samples][b], nullable */,
+                               int32_t *used_out   /* dev [n_samples][node_offset_host[b]], nullable */,
+                               void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Factor tables of every parameter group from the model parameters (training steps), and their chain rule.
