@@ -710,71 +710,6 @@ def _optional_flags(off, optional):
     return np.ascontiguousarray(np.concatenate(flags).astype(np.uint8))
 
 
-def _align_call(batch, elp, trans, init, len_scores, transcripts, flags, endpen, class_map, ws, want_spans, want_labels,
-                want_used, staged=None):
-    """smm_align_f64 (``flags`` None) or smm_align_opt_f64 (``flags``: one boolean sequence per video).  ``staged``: the ids and
-    flags on the device, from an earlier call."""
-    lib = _lib.load()
-    dev = elp.device
-    f64 = torch.float64
-    ids, off = _transcript_arrays(batch, transcripts)
-    flags = None if flags is None else _optional_flags(off, flags)
-    need = align_workspace_bytes(batch, off) if flags is None else align_opt_workspace_bytes(batch, off)
-    spans, labels, best, n_segs = _device_outputs(batch, dev, want_spans, want_labels)
-    ws = _own_workspace(ws, need, dev)
-    ids_dev = torch.from_numpy(ids).to(dev) if staged is None else staged[0]
-    tables = (_dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
-              _dev(endpen, f64, 'endpen'), _dev(class_map, torch.int64, 'class_map'), _dev(ids_dev, torch.int32, 'transcript'))
-    outs = (_dev(spans, torch.int64, 'spans'), _dev(labels, torch.int64, 'labels'), _dev(best, f64, 'best'),
-            _dev(n_segs, torch.int32, 'n_segs'))
-    if flags is None:
-        _lib.check(lib.smm_align_f64(*batch.head(), *tables, ctypes.c_void_p(off.ctypes.data), *outs, *_ws_args(ws), _stream()))
-        return dict(spans=spans, labels=labels, best=best, n_segs=n_segs, _err=_err_copy(batch, ws), _keep=(ids_dev, ws))
-    if staged is not None:
-        flags_dev = staged[1]
-        if staged[0].shape[0] != ids.shape[0] or flags_dev.shape[0] != flags.shape[0]:
-            raise ValueError("align_optional: staged ids and flags of another transcript")
-    else:
-        flags_dev = torch.from_numpy(flags).to(dev)
-    used = torch.empty(ids.shape[0], dtype=torch.int32, device=dev) if want_used else None
-    _lib.check(lib.smm_align_opt_f64(*batch.head(), *tables, _dev(flags_dev, torch.uint8, 'optional'),
-                                     ctypes.c_void_p(off.ctypes.data), *outs, _dev(used, torch.int32, 'used'), *_ws_args(ws),
-                                     _stream()))
-    return dict(spans=spans, labels=labels, best=best, n_segs=n_segs,
-                used=None if used is None else list(torch.split(used, np.diff(off).tolist())),
-                _err=_err_copy(batch, ws), _staged=(ids_dev, flags_dev), _keep=(ws,))
-
-
-def align(batch, elp, trans, init, len_scores, transcripts, endpen=None, class_map=None, ws=None, want_spans=True,
-          want_labels=True):
-    """Forced alignment (smm_align_f64): per video the best segmentation whose class sequence is its transcript -- a sequence
-    of LOCAL state ids, one per segment, consecutive repeats allowed -- so only the boundaries are free.  Bit for bit
-    ``viterbi`` on the lattice whose states are the transcript positions; with the transcript of the Viterbi path, the Viterbi
-    decode.  Returns dict(spans int64 [b, t_max+1] (span encoding, class map applied) or None, labels int64 [total_frames]
-    (global ids, -1 on frames no video covers) or None, best fp64 [b], n_segs int32 [b] (the transcript's length)).  A video
-    whose transcript cannot be laid over its frames (more entries than frames, too few for the span limit, an id that is no
-    state of the video) gets best -inf, n_segs 0, spans and labels -1.  ``ws``: a uint8 workspace of at least
-    ``align_workspace_bytes`` (default: a private one for this call).  Optional entries: ``align_optional``."""
-    return _align_call(batch, elp, trans, init, len_scores, transcripts, None, endpen, class_map, ws, want_spans, want_labels,
-                       False)
-
-
-def align_optional(batch, elp, trans, init, len_scores, transcripts, optional, endpen=None, class_map=None, ws=None,
-                   want_spans=True, want_labels=True, want_used=False, staged=None):
-    """``align`` with optional transcript entries (smm_align_opt_f64, also when no flag is set): ``optional`` is one boolean
-    sequence per video, as long as its transcript; the flagged entries may be left out, and the result is the best over every
-    subset of them.  ValueError when their count or a length differs from the transcripts'.  Returns ``align``'s dict, n_segs
-    counting the entries that got a segment, plus ``used``: None, or with ``want_used`` a list of per-video int32 views of one
-    device tensor, 1 for an entry that has a segment, else 0.  More MANDATORY entries than frames is what leaves no alignment.
-    ``ws``: at least ``align_opt_workspace_bytes``.  ``staged``: the ``_staged`` entry of an earlier call's result for the same
-    transcripts and flags -- the ids and flags on the device: the call then copies nothing from the host itself and can be
-    captured into a graph (keep that earlier result alive as long as the graph)."""
-    if optional is None:
-        raise ValueError("align_optional: one sequence of flags per video expected (no flags: align)")
-    return _align_call(batch, elp, trans, init, len_scores, transcripts, optional, endpen, class_map, ws, want_spans, want_labels,
-                       want_used, staged)
-
-
 class TranscriptGraph:
     """What smm_align_graph_f64 aligns a video to: a DAG whose nodes carry a class id, numbered in topological order.
     ``ids`` int64 [M]; ``pred`` bool [M, M], strictly lower triangular: pred[m, j] -- node j may directly precede node m;
@@ -944,6 +879,152 @@ def align_graph_workspace_bytes(batch, node_offset):
     return _transcript_workspace_bytes(batch, node_offset, 'align_graph_workspace_bytes', 'graph alignment')
 
 
+ALIGN_LOGZ_TILE = _lib.ALIGN_LOGZ_TILE
+
+
+def align_logz_workspace_bytes(batch, transcript_offset):
+    """Bytes of workspace smm_align_logz_f64 / smm_align_logz_bwd_f64 need for this batch and these transcript offsets (int64
+    [b + 1]; host only)."""
+    return _transcript_workspace_bytes(batch, transcript_offset, 'align_logz_workspace_bytes', 'transcript likelihood')
+
+
+def align_opt_logz_workspace_bytes(batch, transcript_offset):
+    """Bytes of workspace smm_align_opt_logz_f64 / smm_align_opt_logz_bwd_f64 need for this batch and these transcript offsets
+    (int64 [b + 1]; host only)."""
+    return _transcript_workspace_bytes(batch, transcript_offset, 'align_opt_logz_workspace_bytes', 'transcript likelihood')
+
+
+def align_graph_logz_workspace_bytes(batch, node_offset):
+    """Bytes of workspace smm_align_graph_logz_f64 / smm_align_graph_logz_bwd_f64 need for this batch and these node offsets
+    (int64 [b + 1]; host only)."""
+    return _transcript_workspace_bytes(batch, node_offset, 'align_graph_logz_workspace_bytes', 'transcript-graph likelihood')
+
+
+# (kind of supervision, what is computed) -> (the forward launch's symbol in the library, its workspace size, its value's name)
+_TRANSCRIPT_LAUNCH = {
+    ('chain', 'alignment'): ('smm_align_f64', align_workspace_bytes, 'best'),
+    ('optional', 'alignment'): ('smm_align_opt_f64', align_opt_workspace_bytes, 'best'),
+    ('graph', 'alignment'): ('smm_align_graph_f64', align_graph_workspace_bytes, 'best'),
+    ('chain', 'likelihood'): ('smm_align_logz_f64', align_logz_workspace_bytes, 'logz_a'),
+    ('optional', 'likelihood'): ('smm_align_opt_logz_f64', align_opt_logz_workspace_bytes, 'logz_o'),
+    ('graph', 'likelihood'): ('smm_align_graph_logz_f64', align_graph_logz_workspace_bytes, 'logz_g'),
+}
+
+
+class _Supervision:
+    """What one launch of the transcript family is supervised by, staged.  ``kind``: 'chain' (a transcript per video),
+    'optional' (a transcript and one flag per entry) or 'graph' (a ``TranscriptGraph`` per video); ``off``: int64 [b + 1] on
+    the host, the videos' entry / node offsets; ``dev``: the device tensors -- (ids,), (ids, flags) or (classes, masks, flags),
+    what a launcher returns as ``_staged``; ``need``: the bytes of workspace the launch takes."""
+    FIELDS = {'chain': (('transcript', torch.int32),),
+              'optional': (('transcript', torch.int32), ('optional', torch.uint8)),
+              'graph': (('node_class', torch.int32), ('pred_mask', torch.int32), ('node_flags', torch.uint8))}
+
+    def __init__(self, kind, off, dev, need):
+        self.kind, self.off, self.dev, self.need = kind, off, dev, need
+        self.n = int(off[-1])
+
+    def args(self):
+        """The library call's pointer arguments: the device arrays, then the offsets."""
+        return tuple(_dev(t, dtype, name) for t, (name, dtype) in zip(self.dev, self.FIELDS[self.kind])) + (
+            ctypes.c_void_p(self.off.ctypes.data),)
+
+    def per_video(self, t, dim=0):
+        """One view per video of a device tensor that has one column per entry / node."""
+        return list(torch.split(t, np.diff(self.off).tolist(), dim=dim))
+
+
+def _supervision(kind, computed, what, batch, dev, given, optional=None, staged=None):
+    """The supervision of the launch ``what``: ``given`` -- per-video sequences of local ids (with ``optional``: one boolean
+    sequence per video) or one ``TranscriptGraph`` per video -- checked on the host, sized, and then taken from ``staged``
+    (an earlier call's ``_staged``) or copied to ``dev``.  Every check on the host arrays, the workspace size among them,
+    comes before a device is touched.  A 'chain' likelihood also takes the (ids on the device, offsets on the host) pair an
+    earlier call returned as ``transcript``."""
+    pair = (computed == 'likelihood' and kind == 'chain' and isinstance(given, tuple) and len(given) == 2
+            and torch.is_tensor(given[0]))
+    if kind == 'graph':
+        if len(given) != batch.b:
+            raise ValueError("%s: %d graphs for %d videos" % (what, len(given), batch.b))
+        if batch.no_eos:
+            raise ValueError("%s: add_eos=False is not supported" % what)
+        off = np.zeros(batch.b + 1, np.int64)
+        np.cumsum([len(g) for g in given], out=off[1:])
+    elif pair:
+        staged, off = (given[0],), given[1]
+    else:
+        if kind == 'optional' and optional is None:
+            raise ValueError("%s: one sequence of flags per video expected (no flags: %s)"
+                             % (what, 'align' if computed == 'alignment' else 'align_logz'))
+        ids, off = _transcript_arrays(batch, given)
+        host = (ids, _optional_flags(off, optional)) if kind == 'optional' else (ids,)
+    need = _TRANSCRIPT_LAUNCH[kind, computed][1](batch, off)
+    if staged is None:
+        if kind == 'graph':
+            host = (np.concatenate([g.ids for g in given]).astype(np.int32),
+                    np.concatenate([g.packed_masks() for g in given]).reshape(-1).view(np.int32),   # (the bits of the uint32 words)
+                    np.concatenate([g.node_flags() for g in given]))
+        staged = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in host)
+    elif kind == 'graph' and staged[0].shape[0] != off[-1]:
+        raise ValueError("%s: staged classes, masks and flags of other graphs" % what)
+    elif kind == 'optional' and (staged[0].shape[0] != off[-1] or staged[1].shape[0] != off[-1]):
+        raise ValueError("%s: staged ids and flags of another transcript" % what)
+    return _Supervision(kind, off, tuple(staged), need)
+
+
+def _tables(elp, trans, init, len_scores, endpen):
+    f64 = torch.float64
+    return (_dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
+            _dev(endpen, f64, 'endpen'))
+
+
+def _align_launch(kind, what, batch, elp, trans, init, len_scores, given, optional, endpen, class_map, ws, want_spans, want_labels,
+                  want_used, staged):
+    """smm_align_f64, smm_align_opt_f64 or smm_align_graph_f64 by ``kind``; the plain transcript's call has no ``used``."""
+    lib = _lib.load()
+    dev = elp.device
+    sup = _supervision(kind, 'alignment', what, batch, dev, given, optional, staged)
+    spans, labels, best, n_segs = _device_outputs(batch, dev, want_spans, want_labels)
+    ws = _own_workspace(ws, sup.need, dev)
+    used = torch.empty(sup.n, dtype=torch.int32, device=dev) if want_used else None
+    _lib.check(getattr(lib, _TRANSCRIPT_LAUNCH[kind, 'alignment'][0])(
+        *batch.head(), *_tables(elp, trans, init, len_scores, endpen), _dev(class_map, torch.int64, 'class_map'), *sup.args(),
+        _dev(spans, torch.int64, 'spans'), _dev(labels, torch.int64, 'labels'), _dev(best, torch.float64, 'best'),
+        _dev(n_segs, torch.int32, 'n_segs'), *(() if kind == 'chain' else (_dev(used, torch.int32, 'used'),)), *_ws_args(ws),
+        _stream()))
+    out = dict(spans=spans, labels=labels, best=best, n_segs=n_segs, _err=_err_copy(batch, ws))
+    if kind == 'chain':
+        return dict(out, _keep=sup.dev + (ws,))
+    return dict(out, used=None if used is None else sup.per_video(used), _staged=sup.dev, _keep=(ws,))
+
+
+def align(batch, elp, trans, init, len_scores, transcripts, endpen=None, class_map=None, ws=None, want_spans=True,
+          want_labels=True):
+    """Forced alignment (smm_align_f64): per video the best segmentation whose class sequence is its transcript -- a sequence
+    of LOCAL state ids, one per segment, consecutive repeats allowed -- so only the boundaries are free.  Bit for bit
+    ``viterbi`` on the lattice whose states are the transcript positions; with the transcript of the Viterbi path, the Viterbi
+    decode.  Returns dict(spans int64 [b, t_max+1] (span encoding, class map applied) or None, labels int64 [total_frames]
+    (global ids, -1 on frames no video covers) or None, best fp64 [b], n_segs int32 [b] (the transcript's length)).  A video
+    whose transcript cannot be laid over its frames (more entries than frames, too few for the span limit, an id that is no
+    state of the video) gets best -inf, n_segs 0, spans and labels -1.  ``ws``: a uint8 workspace of at least
+    ``align_workspace_bytes`` (default: a private one for this call).  Optional entries: ``align_optional``."""
+    return _align_launch('chain', 'align', batch, elp, trans, init, len_scores, transcripts, None, endpen, class_map, ws, want_spans,
+                         want_labels, False, None)
+
+
+def align_optional(batch, elp, trans, init, len_scores, transcripts, optional, endpen=None, class_map=None, ws=None,
+                   want_spans=True, want_labels=True, want_used=False, staged=None):
+    """``align`` with optional transcript entries (smm_align_opt_f64, also when no flag is set): ``optional`` is one boolean
+    sequence per video, as long as its transcript; the flagged entries may be left out, and the result is the best over every
+    subset of them.  ValueError when their count or a length differs from the transcripts'.  Returns ``align``'s dict, n_segs
+    counting the entries that got a segment, plus ``used``: None, or with ``want_used`` a list of per-video int32 views of one
+    device tensor, 1 for an entry that has a segment, else 0.  More MANDATORY entries than frames is what leaves no alignment.
+    ``ws``: at least ``align_opt_workspace_bytes``.  ``staged``: the ``_staged`` entry of an earlier call's result for the same
+    transcripts and flags -- the ids and flags on the device: the call then copies nothing from the host itself and can be
+    captured into a graph (keep that earlier result alive as long as the graph)."""
+    return _align_launch('optional', 'align_optional', batch, elp, trans, init, len_scores, transcripts, optional, endpen, class_map,
+                         ws, want_spans, want_labels, want_used, staged)
+
+
 def align_graph(batch, elp, trans, init, len_scores, graphs, endpen=None, class_map=None, ws=None, want_spans=True,
                 want_labels=True, want_used=False, staged=None):
     """Forced alignment to a transcript graph (smm_align_graph_f64): per video the best segmentation whose class sequence is
@@ -954,63 +1035,21 @@ def align_graph(batch, elp, trans, init, len_scores, graphs, endpen=None, class_
     over its frames gets best -inf, n_segs 0, spans and labels -1.  ValueError when the number of graphs differs from the
     videos'.  ``ws``: at least ``align_graph_workspace_bytes``.  ``staged``: the ``_staged`` entry of an earlier call's result
     for the same graphs -- classes, masks and flags on the device -- as in ``align_optional``."""
+    return _align_launch('graph', 'align_graph', batch, elp, trans, init, len_scores, graphs, None, endpen, class_map, ws,
+                         want_spans, want_labels, want_used, staged)
+
+
+def _logz_launch(kind, what, batch, elp, trans, init, len_scores, given, optional, endpen, ws, staged):
+    """smm_align_logz_f64, smm_align_opt_logz_f64 or smm_align_graph_logz_f64 by ``kind`` -> (dict(logz, ws, _staged, _err),
+    the supervision)."""
     lib = _lib.load()
-    dev = elp.device
-    f64 = torch.float64
-    if len(graphs) != batch.b:
-        raise ValueError("align_graph: %d graphs for %d videos" % (len(graphs), batch.b))
-    if batch.no_eos:
-        raise ValueError("align_graph: add_eos=False is not supported")
-    off = np.zeros(batch.b + 1, np.int64)
-    np.cumsum([len(g) for g in graphs], out=off[1:])
-    need = align_graph_workspace_bytes(batch, off)
-    spans, labels, best, n_segs = _device_outputs(batch, dev, want_spans, want_labels)
-    ws = _own_workspace(ws, need, dev)
-    if staged is not None:
-        ids_dev, masks_dev, flags_dev = staged
-        if ids_dev.shape[0] != off[-1]:
-            raise ValueError("align_graph: staged classes, masks and flags of other graphs")
-    else:
-        ids = np.ascontiguousarray(np.concatenate([g.ids for g in graphs]).astype(np.int32))
-        masks = np.ascontiguousarray(np.concatenate([g.packed_masks() for g in graphs]).reshape(-1))
-        ids_dev = torch.from_numpy(ids).to(dev)
-        masks_dev = torch.from_numpy(masks.view(np.int32)).to(dev)   # (the bits of the uint32 words)
-        flags_dev = torch.from_numpy(np.ascontiguousarray(np.concatenate([g.node_flags() for g in graphs]))).to(dev)
-    used = torch.empty(int(off[-1]), dtype=torch.int32, device=dev) if want_used else None
-    _lib.check(lib.smm_align_graph_f64(
-        *batch.head(), _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'),
-        _dev(len_scores, f64, 'len_scores'), _dev(endpen, f64, 'endpen'), _dev(class_map, torch.int64, 'class_map'),
-        _dev(ids_dev, torch.int32, 'node_class'), _dev(masks_dev, torch.int32, 'pred_mask'),
-        _dev(flags_dev, torch.uint8, 'node_flags'), ctypes.c_void_p(off.ctypes.data), _dev(spans, torch.int64, 'spans'),
-        _dev(labels, torch.int64, 'labels'), _dev(best, f64, 'best'), _dev(n_segs, torch.int32, 'n_segs'),
-        _dev(used, torch.int32, 'used'), *_ws_args(ws), _stream()))
-    return dict(spans=spans, labels=labels, best=best, n_segs=n_segs,
-                used=None if used is None else list(torch.split(used, np.diff(off).tolist())),
-                _err=_err_copy(batch, ws), _staged=(ids_dev, masks_dev, flags_dev), _keep=(ws,))
-
-
-ALIGN_LOGZ_TILE = _lib.ALIGN_LOGZ_TILE
-
-
-def align_logz_workspace_bytes(batch, transcript_offset):
-    """Bytes of workspace smm_align_logz_f64 / smm_align_logz_bwd_f64 need for this batch and these transcript offsets (int64
-    [b + 1]; host only)."""
-    return _transcript_workspace_bytes(batch, transcript_offset, 'align_logz_workspace_bytes', 'transcript likelihood')
-
-
-def _align_logz_inputs(batch, elp, trans, init, len_scores, transcripts, endpen):
-    """The arguments the forward and the backward call share, from the tables on: (ctypes values, what they keep alive).
-    ``transcripts``: per-video sequences of local ids, or the (ids on the device, offsets on the host) pair an earlier call
-    returned as ``transcript``."""
-    f64 = torch.float64
-    if isinstance(transcripts, tuple) and len(transcripts) == 2 and torch.is_tensor(transcripts[0]):
-        ids_dev, off = transcripts
-    else:
-        ids, off = _transcript_arrays(batch, transcripts)
-        ids_dev = torch.from_numpy(ids).to(elp.device)
-    args = (_dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
-            _dev(endpen, f64, 'endpen'), _dev(ids_dev, torch.int32, 'transcript'), ctypes.c_void_p(off.ctypes.data))
-    return args, (ids_dev, off)
+    symbol, _, name = _TRANSCRIPT_LAUNCH[kind, 'likelihood']
+    sup = _supervision(kind, 'likelihood', what, batch, elp.device, given, optional, staged)
+    args = _tables(elp, trans, init, len_scores, endpen) + sup.args()
+    ws = _own_workspace(ws, sup.need, elp.device)
+    out = torch.empty(batch.b, dtype=torch.float64, device=elp.device)
+    _lib.check(getattr(lib, symbol)(*batch.head(), *args, _dev(out, torch.float64, name), *_ws_args(ws), _stream()))
+    return dict(logz=out, ws=ws, _staged=sup.dev, _err=_err_copy(batch, ws)), sup
 
 
 def align_logz(batch, elp, trans, init, len_scores, transcripts, endpen=None, ws=None):
@@ -1024,55 +1063,8 @@ def align_logz(batch, elp, trans, init, len_scores, transcripts, endpen=None, ws
 def align_logz_ex(batch, elp, trans, init, len_scores, transcripts, endpen=None, ws=None):
     """``align_logz`` with what a backward call needs: dict(logz, ws, transcript (ids on the device, offsets on the host),
     _err (the launch's error words, copied))."""
-    lib = _lib.load()
-    dev = elp.device
-    args, tr = _align_logz_inputs(batch, elp, trans, init, len_scores, transcripts, endpen)
-    ws = _own_workspace(ws, align_logz_workspace_bytes(batch, tr[1]), dev)
-    out = torch.empty(batch.b, dtype=torch.float64, device=dev)
-    _lib.check(lib.smm_align_logz_f64(*batch.head(), *args, _dev(out, torch.float64, 'logz_a'), *_ws_args(ws), _stream()))
-    return dict(logz=out, ws=ws, transcript=tr, _err=_err_copy(batch, ws))
-
-
-def align_logz_bwd(batch, elp, trans, init, len_scores, transcripts, logz_a, grad_logz=None, endpen=None, ws=None):
-    """Gradient of sum_i grad_logz[i] * log Z_a(i) (smm_align_logz_bwd_f64).  Must follow ``align_logz`` for the same batch,
-    tables and transcripts with the same workspace ``ws`` on the same stream; ``logz_a`` = its output.
-    -> dict(elp [total_frames, c_max], trans, init, len) fp64; videos whose log Z_a is -inf or NaN contribute zeros."""
-    lib = _lib.load()
-    f64 = torch.float64
-    args, tr = _align_logz_inputs(batch, elp, trans, init, len_scores, transcripts, endpen)
-    if ws is None or ws.numel() < align_logz_workspace_bytes(batch, tr[1]):
-        raise ValueError("align_logz_bwd: pass the workspace the align_logz call wrote")
-    g = _grad_outputs(elp, trans, init, len_scores)
-    _lib.check(lib.smm_align_logz_bwd_f64(
-        *batch.head(), *args, _dev(logz_a, f64, 'logz_a'), _dev(grad_logz, f64, 'grad_logz'), _dev(g['elp'], f64, 'g_elp'),
-        _dev(g['trans'], f64, 'g_trans'), _dev(g['init'], f64, 'g_init'), _dev(g['len'], f64, 'g_len'), *_ws_args(ws), _stream()))
-    return g
-
-
-def align_opt_logz_workspace_bytes(batch, transcript_offset):
-    """Bytes of workspace smm_align_opt_logz_f64 / smm_align_opt_logz_bwd_f64 need for this batch and these transcript offsets
-    (int64 [b + 1]; host only)."""
-    return _transcript_workspace_bytes(batch, transcript_offset, 'align_opt_logz_workspace_bytes', 'transcript likelihood')
-
-
-def _align_opt_logz_inputs(batch, elp, trans, init, len_scores, transcripts, optional, endpen, staged, what):
-    """The arguments the forward and the backward call share, from the tables on: (ctypes values, offsets, (ids, flags) on the
-    device).  Every check on the host arrays comes before a device is touched."""
-    if optional is None:
-        raise ValueError("%s: one sequence of flags per video expected (no flags: align_logz)" % what)
-    f64 = torch.float64
-    ids, off = _transcript_arrays(batch, transcripts)
-    flags = _optional_flags(off, optional)
-    if staged is not None:
-        ids_dev, flags_dev = staged
-        if ids_dev.shape[0] != ids.shape[0] or flags_dev.shape[0] != flags.shape[0]:
-            raise ValueError("%s: staged ids and flags of another transcript" % what)
-    else:
-        ids_dev, flags_dev = torch.from_numpy(ids).to(elp.device), torch.from_numpy(flags).to(elp.device)
-    args = (_dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
-            _dev(endpen, f64, 'endpen'), _dev(ids_dev, torch.int32, 'transcript'), _dev(flags_dev, torch.uint8, 'optional'),
-            ctypes.c_void_p(off.ctypes.data))
-    return args, off, (ids_dev, flags_dev)
+    out, sup = _logz_launch('chain', 'align_logz', batch, elp, trans, init, len_scores, transcripts, None, endpen, ws, None)
+    return dict(logz=out['logz'], ws=out['ws'], transcript=(sup.dev[0], sup.off), _err=out['_err'])
 
 
 def align_opt_logz(batch, elp, trans, init, len_scores, transcripts, optional, endpen=None, ws=None, staged=None):
@@ -1084,71 +1076,7 @@ def align_opt_logz(batch, elp, trans, init, len_scores, transcripts, optional, e
     reached the DP), ws (keep it for ``align_opt_logz_bwd``), _staged (ids and flags on the device), _err).  ``ws``: at least
     ``align_opt_logz_workspace_bytes``.  ``staged``: the ``_staged`` entry of an earlier call for the same transcripts and
     flags: the call then copies nothing from the host itself and can be captured into a graph."""
-    lib = _lib.load()
-    args, off, st = _align_opt_logz_inputs(batch, elp, trans, init, len_scores, transcripts, optional, endpen, staged,
-                                           'align_opt_logz')
-    ws = _own_workspace(ws, align_opt_logz_workspace_bytes(batch, off), elp.device)
-    out = torch.empty(batch.b, dtype=torch.float64, device=elp.device)
-    _lib.check(lib.smm_align_opt_logz_f64(*batch.head(), *args, _dev(out, torch.float64, 'logz_o'), *_ws_args(ws), _stream()))
-    return dict(logz=out, ws=ws, _staged=st, _err=_err_copy(batch, ws))
-
-
-def align_opt_logz_bwd(batch, elp, trans, init, len_scores, transcripts, optional, logz_o, grad_logz=None, endpen=None, ws=None,
-                       staged=None, want_entry_prob=False):
-    """Gradient of sum_i grad_logz[i] * log Z_o(i) (smm_align_opt_logz_bwd_f64).  Must follow ``align_opt_logz`` for the same
-    batch, tables, transcripts and flags with the same workspace ``ws`` on the same stream; ``logz_o`` = its output.
-    -> dict(elp [total_frames, c_max], trans, init, len) fp64, plus with ``want_entry_prob`` entry_prob: a list of per-video
-    fp64 views of one device tensor, the posterior probability that the entry has a segment (1 for a mandatory entry).  Videos
-    whose log Z_o is -inf or NaN contribute zeros."""
-    lib = _lib.load()
-    f64 = torch.float64
-    args, off, st = _align_opt_logz_inputs(batch, elp, trans, init, len_scores, transcripts, optional, endpen, staged,
-                                           'align_opt_logz_bwd')
-    if ws is None or ws.numel() < align_opt_logz_workspace_bytes(batch, off):
-        raise ValueError("align_opt_logz_bwd: pass the workspace the align_opt_logz call wrote")
-    g = _grad_outputs(elp, trans, init, len_scores)
-    used = torch.empty(int(off[-1]), dtype=f64, device=elp.device) if want_entry_prob else None
-    _lib.check(lib.smm_align_opt_logz_bwd_f64(
-        *batch.head(), *args, _dev(logz_o, f64, 'logz_o'), _dev(grad_logz, f64, 'grad_logz'), _dev(g['elp'], f64, 'g_elp'),
-        _dev(g['trans'], f64, 'g_trans'), _dev(g['init'], f64, 'g_init'), _dev(g['len'], f64, 'g_len'),
-        _dev(used, f64, 'p_used'), *_ws_args(ws), _stream()))
-    if want_entry_prob:
-        g['entry_prob'] = list(torch.split(used, np.diff(off).tolist()))
-    g['_keep'] = st
-    return g
-
-
-def align_graph_logz_workspace_bytes(batch, node_offset):
-    """Bytes of workspace smm_align_graph_logz_f64 / smm_align_graph_logz_bwd_f64 need for this batch and these node offsets
-    (int64 [b + 1]; host only)."""
-    return _transcript_workspace_bytes(batch, node_offset, 'align_graph_logz_workspace_bytes', 'transcript-graph likelihood')
-
-
-def _align_graph_logz_inputs(batch, elp, trans, init, len_scores, graphs, endpen, staged, what):
-    """The arguments the forward and the backward call share, from the tables on: (ctypes values, node offsets, (classes,
-    masks, flags) on the device).  Every check on the host arrays comes before a device is touched."""
-    f64 = torch.float64
-    if len(graphs) != batch.b:
-        raise ValueError("%s: %d graphs for %d videos" % (what, len(graphs), batch.b))
-    if batch.no_eos:
-        raise ValueError("%s: add_eos=False is not supported" % what)
-    off = np.zeros(batch.b + 1, np.int64)
-    np.cumsum([len(g) for g in graphs], out=off[1:])
-    if staged is not None:
-        ids_dev, masks_dev, flags_dev = staged
-        if ids_dev.shape[0] != off[-1]:
-            raise ValueError("%s: staged classes, masks and flags of other graphs" % what)
-    else:
-        ids = np.ascontiguousarray(np.concatenate([g.ids for g in graphs]).astype(np.int32))
-        masks = np.ascontiguousarray(np.concatenate([g.packed_masks() for g in graphs]).reshape(-1))
-        flags = np.ascontiguousarray(np.concatenate([g.node_flags() for g in graphs]))
-        ids_dev = torch.from_numpy(ids).to(elp.device)
-        masks_dev = torch.from_numpy(masks.view(np.int32)).to(elp.device)   # (the bits of the uint32 words)
-        flags_dev = torch.from_numpy(flags).to(elp.device)
-    args = (_dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
-            _dev(endpen, f64, 'endpen'), _dev(ids_dev, torch.int32, 'node_class'), _dev(masks_dev, torch.int32, 'pred_mask'),
-            _dev(flags_dev, torch.uint8, 'node_flags'), ctypes.c_void_p(off.ctypes.data))
-    return args, off, (ids_dev, masks_dev, flags_dev)
+    return _logz_launch('optional', 'align_opt_logz', batch, elp, trans, init, len_scores, transcripts, optional, endpen, ws, staged)[0]
 
 
 def align_graph_logz(batch, elp, trans, init, len_scores, graphs, endpen=None, ws=None, staged=None):
@@ -1160,12 +1088,51 @@ def align_graph_logz(batch, elp, trans, init, len_scores, graphs, endpen=None, w
     ``align_graph_logz_bwd``), _staged (classes, masks and flags on the device), _err, _keep).  ``ws``: at least
     ``align_graph_logz_workspace_bytes``.  ``staged``: the ``_staged`` entry of an earlier call for the same graphs: the call
     then copies nothing from the host itself and can be captured into a graph."""
+    out = _logz_launch('graph', 'align_graph_logz', batch, elp, trans, init, len_scores, graphs, None, endpen, ws, staged)[0]
+    return dict(out, _keep=(out['ws'],))
+
+
+def _logz_bwd_launch(kind, what, batch, elp, trans, init, len_scores, given, optional, logz_val, grad_logz, endpen, ws, staged,
+                     **posteriors):
+    """smm_align_logz_bwd_f64, smm_align_opt_logz_bwd_f64 or smm_align_graph_logz_bwd_f64 by ``kind``.  ``posteriors``: the
+    kind's optional outputs in the library's order (p_used, p_end), each under the key of the result it goes to and with
+    whether it is wanted."""
     lib = _lib.load()
-    args, off, st = _align_graph_logz_inputs(batch, elp, trans, init, len_scores, graphs, endpen, staged, 'align_graph_logz')
-    ws = _own_workspace(ws, align_graph_logz_workspace_bytes(batch, off), elp.device)
-    out = torch.empty(batch.b, dtype=torch.float64, device=elp.device)
-    _lib.check(lib.smm_align_graph_logz_f64(*batch.head(), *args, _dev(out, torch.float64, 'logz_g'), *_ws_args(ws), _stream()))
-    return dict(logz=out, ws=ws, _staged=st, _err=_err_copy(batch, ws), _keep=(ws,))
+    f64 = torch.float64
+    symbol, _, name = _TRANSCRIPT_LAUNCH[kind, 'likelihood']
+    sup = _supervision(kind, 'likelihood', what, batch, elp.device, given, optional, staged)
+    args = _tables(elp, trans, init, len_scores, endpen) + sup.args()
+    if ws is None or ws.numel() < sup.need:
+        raise ValueError("%s: pass the workspace the %s call wrote" % (what, what[:-len('_bwd')]))
+    g = _grad_outputs(elp, trans, init, len_scores)
+    post = {key: torch.empty(sup.n, dtype=f64, device=elp.device) if want else None for key, want in posteriors.items()}
+    _lib.check(getattr(lib, symbol.replace('_f64', '_bwd_f64'))(
+        *batch.head(), *args, _dev(logz_val, f64, name), _dev(grad_logz, f64, 'grad_logz'), _dev(g['elp'], f64, 'g_elp'),
+        _dev(g['trans'], f64, 'g_trans'), _dev(g['init'], f64, 'g_init'), _dev(g['len'], f64, 'g_len'),
+        *[_dev(t, f64, p) for t, p in zip(post.values(), ('p_used', 'p_end'))], *_ws_args(ws), _stream()))
+    g.update((key, sup.per_video(t)) for key, t in post.items() if t is not None)
+    if kind != 'chain':
+        g['_keep'] = sup.dev
+    return g
+
+
+def align_logz_bwd(batch, elp, trans, init, len_scores, transcripts, logz_a, grad_logz=None, endpen=None, ws=None):
+    """Gradient of sum_i grad_logz[i] * log Z_a(i) (smm_align_logz_bwd_f64).  Must follow ``align_logz`` for the same batch,
+    tables and transcripts with the same workspace ``ws`` on the same stream; ``logz_a`` = its output.
+    -> dict(elp [total_frames, c_max], trans, init, len) fp64; videos whose log Z_a is -inf or NaN contribute zeros."""
+    return _logz_bwd_launch('chain', 'align_logz_bwd', batch, elp, trans, init, len_scores, transcripts, None, logz_a, grad_logz,
+                            endpen, ws, None)
+
+
+def align_opt_logz_bwd(batch, elp, trans, init, len_scores, transcripts, optional, logz_o, grad_logz=None, endpen=None, ws=None,
+                       staged=None, want_entry_prob=False):
+    """Gradient of sum_i grad_logz[i] * log Z_o(i) (smm_align_opt_logz_bwd_f64).  Must follow ``align_opt_logz`` for the same
+    batch, tables, transcripts and flags with the same workspace ``ws`` on the same stream; ``logz_o`` = its output.
+    -> dict(elp [total_frames, c_max], trans, init, len) fp64, plus with ``want_entry_prob`` entry_prob: a list of per-video
+    fp64 views of one device tensor, the posterior probability that the entry has a segment (1 for a mandatory entry).  Videos
+    whose log Z_o is -inf or NaN contribute zeros."""
+    return _logz_bwd_launch('optional', 'align_opt_logz_bwd', batch, elp, trans, init, len_scores, transcripts, optional, logz_o,
+                            grad_logz, endpen, ws, staged, entry_prob=want_entry_prob)
 
 
 def align_graph_logz_bwd(batch, elp, trans, init, len_scores, graphs, logz_g, grad_logz=None, endpen=None, ws=None, staged=None,
@@ -1176,24 +1143,8 @@ def align_graph_logz_bwd(batch, elp, trans, init, len_scores, graphs, logz_g, gr
     ``want_end_prob`` end_prob: lists of per-video fp64 views of one device tensor each, the posterior probability that the
     path crosses the node / ends in it (end_prob sums to 1 over a video's nodes).  Videos whose log Z_g is -inf or NaN
     contribute zeros."""
-    lib = _lib.load()
-    f64 = torch.float64
-    args, off, st = _align_graph_logz_inputs(batch, elp, trans, init, len_scores, graphs, endpen, staged, 'align_graph_logz_bwd')
-    if ws is None or ws.numel() < align_graph_logz_workspace_bytes(batch, off):
-        raise ValueError("align_graph_logz_bwd: pass the workspace the align_graph_logz call wrote")
-    g = _grad_outputs(elp, trans, init, len_scores)
-    used = torch.empty(int(off[-1]), dtype=f64, device=elp.device) if want_node_prob else None
-    ended = torch.empty(int(off[-1]), dtype=f64, device=elp.device) if want_end_prob else None
-    _lib.check(lib.smm_align_graph_logz_bwd_f64(
-        *batch.head(), *args, _dev(logz_g, f64, 'logz_g'), _dev(grad_logz, f64, 'grad_logz'), _dev(g['elp'], f64, 'g_elp'),
-        _dev(g['trans'], f64, 'g_trans'), _dev(g['init'], f64, 'g_init'), _dev(g['len'], f64, 'g_len'),
-        _dev(used, f64, 'p_used'), _dev(ended, f64, 'p_end'), *_ws_args(ws), _stream()))
-    if want_node_prob:
-        g['node_prob'] = list(torch.split(used, np.diff(off).tolist()))
-    if want_end_prob:
-        g['end_prob'] = list(torch.split(ended, np.diff(off).tolist()))
-    g['_keep'] = st
-    return g
+    return _logz_bwd_launch('graph', 'align_graph_logz_bwd', batch, elp, trans, init, len_scores, graphs, None, logz_g, grad_logz,
+                            endpen, ws, staged, node_prob=want_node_prob, end_prob=want_end_prob)
 
 
 def align_graph_sample(batch, elp, trans, init, len_scores, graphs, logz_g, n_samples, seed=0, endpen=None, class_map=None,
@@ -1216,20 +1167,20 @@ def align_graph_sample(batch, elp, trans, init, len_scores, graphs, logz_g, n_sa
     if ws is None:
         raise ValueError("align_graph_sample: pass the workspace the align_graph_logz call wrote")
     f64 = torch.float64
-    args, off, st = _align_graph_logz_inputs(batch, elp, trans, init, len_scores, graphs, endpen, staged, 'align_graph_sample')
-    if ws.numel() < align_graph_logz_workspace_bytes(batch, off):
-        raise ValueError("align_graph_sample: pass the workspace the align_graph_logz call wrote")
     dev = elp.device
+    sup = _supervision('graph', 'likelihood', 'align_graph_sample', batch, dev, graphs, None, staged)
+    tables = _tables(elp, trans, init, len_scores, endpen)
+    if ws.numel() < sup.need:
+        raise ValueError("align_graph_sample: pass the workspace the align_graph_logz call wrote")
     spans, labels, logp, n_segs = _device_outputs(batch, dev, want_spans, want_labels, (n_samples,))
-    used = torch.empty((n_samples, int(off[-1])), dtype=torch.int32, device=dev) if want_used else None
+    used = torch.empty((n_samples, sup.n), dtype=torch.int32, device=dev) if want_used else None
     _lib.check(lib.smm_align_graph_sample_f64(
-        *batch.head(), *args[:5], _dev(class_map, torch.int64, 'class_map'), *args[5:], _dev(logz_g, f64, 'logz_g'),
+        *batch.head(), *tables, _dev(class_map, torch.int64, 'class_map'), *sup.args(), _dev(logz_g, f64, 'logz_g'),
         ctypes.c_int32(n_samples), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _dev(spans, torch.int64, 'spans'),
         _dev(labels, torch.int64, 'labels'), _dev(logp, f64, 'logp'), _dev(n_segs, torch.int32, 'n_segs'),
         _dev(used, torch.int32, 'used'), *_ws_args(ws), _stream()))
-    return dict(spans=spans, labels=labels, logp=logp, n_segs=n_segs,
-                used=None if used is None else list(torch.split(used, np.diff(off).tolist(), dim=1)),
-                _err=_err_copy(batch, ws), _staged=st, _keep=(ws,))
+    return dict(spans=spans, labels=labels, logp=logp, n_segs=n_segs, used=None if used is None else sup.per_video(used, dim=1),
+                _err=_err_copy(batch, ws), _staged=sup.dev, _keep=(ws,))
 
 
 def transcript_is_ambiguous(ids, optional):

@@ -340,6 +340,22 @@ class SemiMarkovModel(object):
         state.pop('_step_columns', None)
         return state
 
+    @staticmethod
+    def _per_video(pc, by_video, missing):
+        """The values of ``by_video`` for the videos of ``pc``, in the order of ``pc.video_names``; ValueError ``missing`` (a
+        text with one place for the name) for the first video without one."""
+        absent = [name for name in pc.video_names if name not in by_video]
+        if absent:
+            raise ValueError(missing % (absent[0],))
+        return [by_video[name] for name in pc.video_names]
+
+    def _labels_by_video(self, pc, labels, what='alignments'):
+        """Frame labels on the packed frame axis, [total_frames] or [n_samples, total_frames], to the host -> {video: its
+        frames' int64 [T] or [n_samples, T]}."""
+        lab = labels.cpu().numpy()
+        assert lab.size == 0 or int(lab.max()) < self.model.n_classes, "%s should not contain EOS" % what
+        return {name: lab[..., off:off + t] for name, off, t in zip(pc.video_names, pc.frame_offset, pc.lengths)}
+
     def _predict_mbr(self, test_data, fused, shard):
         """``predict(decoder='mbr')``: the minimum-Bayes-risk segmentation under frame loss of every video."""
         if fused:
@@ -347,10 +363,7 @@ class SemiMarkovModel(object):
             if pc.n_videos == 0:
                 return {}                                   # this rank's shard is empty
             self.last_predict_path = 'fused MBR: posteriors + smm_mbr_f64 on the packed corpus'
-            labels, _ = self.model.mbr_decode_packed(pc)
-            lab = labels.cpu().numpy()
-            assert lab.size == 0 or int(lab.max()) < self.model.n_classes, "predictions should not contain EOS"
-            return {name: lab[off:off + t] for name, off, t in zip(pc.video_names, pc.frame_offset, pc.lengths)}
+            return self._labels_by_video(pc, self.model.mbr_decode_packed(pc)[0], 'predictions')
         self.last_predict_path = 'per batch, padded: mbr_decode() spans'
         cons_fn = self._test_constraints(test_data)
         loader = make_data_loader(self.args, test_data, shuffle=False, batch_by_task=True, batch_size=self.args.batch_size,
@@ -385,15 +398,9 @@ class SemiMarkovModel(object):
         pc = self.prepare(data, shard=shard)
         if pc.n_videos == 0:
             return {}
-        missing = [name for name in pc.video_names if name not in transcripts_by_video]
-        if missing:
-            raise ValueError("align: no transcript for video %r" % (missing[0],))
-        transcripts = [transcripts_by_video[name] for name in pc.video_names]
+        transcripts = self._per_video(pc, transcripts_by_video, "align: no transcript for video %r")
         optional = self._optional_flags(pc, transcripts, optional_by_video, optional_classes, 'align')
-        labels, _ = self.model.align_packed(pc, transcripts, optional=optional)
-        lab = labels.cpu().numpy()
-        assert lab.size == 0 or int(lab.max()) < self.model.n_classes, "alignments should not contain EOS"
-        return {name: lab[off:off + t] for name, off, t in zip(pc.video_names, pc.frame_offset, pc.lengths)}
+        return self._labels_by_video(pc, self.model.align_packed(pc, transcripts, optional=optional)[0])
 
     def align_candidates(self, data, candidates_by_video, shard=None):
         """"The video follows one of these transcripts": ``candidates_by_video[name]`` is a list of class sequences in global
@@ -401,44 +408,21 @@ class SemiMarkovModel(object):
         over every candidate, and which one it follows; labels -1 and index -1 where no candidate can be laid over the video.
         The candidates of a video go to the GPU as their prefix trie (``ops.TranscriptGraph.from_candidates``,
         ``SemiMarkovModule.align_graph_packed``): one launch scores all of them, shared prefixes once.  A list whose trie would
-        exceed ``ops.MAX_TRANSCRIPT`` nodes is split into consecutive tries, packed greedily in candidate order, each aligned
-        by its own launch on the same prepared corpus; a strictly better score replaces the earlier one on the device, so a
-        tie keeps the earlier chunk.  ValueError for a video without candidates or a single candidate longer than
+        exceed ``ops.MAX_TRANSCRIPT`` nodes is split into consecutive tries (``_candidate_chunks``: its distinct candidates,
+        packed greedily in candidate order), each aligned by its own launch on the same prepared corpus; a strictly better
+        score replaces the earlier one on the device, so a tie keeps the earlier trie, and identical candidates answer to the
+        lowest index.  ValueError for a video without candidates, an empty candidate or one longer than
         ``ops.MAX_TRANSCRIPT``.  Under an exact tie between different candidates the chosen index is deterministic but
         otherwise unspecified."""
-        from . import ops
-        self.model.eval()
-        pc = self.prepare(data, shard=shard)
+        pc, rounds = self._candidate_rounds(data, candidates_by_video, shard, 'align_candidates')
         if pc.n_videos == 0:
             return {}, {}
-        chunks = []                                         # per video: [(first candidate index, its candidates)]
-        for name in pc.video_names:
-            cands = candidates_by_video.get(name)
-            if not cands:
-                raise ValueError("align_candidates: no candidates for video %r" % (name,))
-            mine, first, cur, seen = [], 0, [], set()
-            for ci, cand in enumerate(cands):
-                seq = tuple(int(c) for c in np.asarray(cand.cpu() if torch.is_tensor(cand) else cand, dtype=np.int64).reshape(-1))
-                if len(seq) > ops.MAX_TRANSCRIPT:
-                    raise ValueError("align_candidates: candidate %d of video %r has %d entries (at most %d)"
-                                     % (ci, name, len(seq), ops.MAX_TRANSCRIPT))
-                new = {seq[:n] for n in range(1, len(seq) + 1)} - seen
-                if cur and len(seen) + len(new) > ops.MAX_TRANSCRIPT:
-                    mine.append((first, cur))
-                    first, cur, seen, new = ci, [], set(), {seq[:n] for n in range(1, len(seq) + 1)}
-                cur.append(seq)
-                seen |= new
-            mine.append((first, cur))
-            chunks.append(mine)
         labels = scores = None
-        chosen = np.full(pc.n_videos, -1, np.int64)
-        for r in range(max(len(c) for c in chunks)):
-            # a video with fewer chunks repeats its last one: the same score never replaces
-            part = [c[min(r, len(c) - 1)] for c in chunks]
-            graphs = [ops.TranscriptGraph.from_candidates(cands) for _, cands in part]
-            lab, sc, used = self.model.align_graph_packed(pc, graphs)
-            within = np.array([g.candidate_of(u.cpu().numpy()) for g, u in zip(graphs, used)], np.int64)
-            idx = np.where(within >= 0, within + np.array([first for first, _ in part], np.int64), -1)
+        for row in rounds:
+            # (a video all of whose tries went out earlier repeats its last one: the same score never replaces)
+            lab, sc, used = self.model.align_graph_packed(pc, [trie for trie, _, _ in row])
+            ends = [np.flatnonzero(u.cpu().numpy()) for u in used]          # the path's nodes; the last one is its end
+            idx = np.array([owner[e[-1]] if e.size else -1 for (_, owner, _), e in zip(row, ends)], np.int64)
             if labels is None:
                 labels, scores, chosen = lab, sc, idx
                 # the packed frame axis: which video a covered frame belongs to
@@ -446,20 +430,17 @@ class SemiMarkovModel(object):
                 video = torch.repeat_interleave(torch.arange(pc.n_videos, device=lab.device),
                                                 torch.as_tensor(np.asarray(pc.lengths, np.int64), device=lab.device))
                 continue
-            better = sc > scores                            # (strictly: a tie keeps the earlier chunk)
+            better = sc > scores                            # (strictly: a tie keeps the earlier trie)
             labels[where] = torch.where(better[video], lab[where], labels[where])
             scores = torch.where(better, sc, scores)
             chosen = np.where(better.cpu().numpy(), idx, chosen)
-        lab = labels.cpu().numpy()
-        assert lab.size == 0 or int(lab.max()) < self.model.n_classes, "alignments should not contain EOS"
-        return ({name: lab[off:off + t] for name, off, t in zip(pc.video_names, pc.frame_offset, pc.lengths)},
-                {name: int(c) for name, c in zip(pc.video_names, chosen)})
+        return self._labels_by_video(pc, labels), {name: int(c) for name, c in zip(pc.video_names, chosen)}
 
     @staticmethod
     def _candidate_chunks(cands, name, what):
-        """The DISTINCT candidates of one video, each under the index of its first appearance, split as ``align_candidates``
-        splits them: consecutive tries of at most ``ops.MAX_TRANSCRIPT`` nodes, packed greedily in candidate order.
-        De-duplicating first keeps a class sequence from being summed once per chunk it would appear in.
+        """The DISTINCT candidates of one video, each under the index of its first appearance, split into consecutive tries of
+        at most ``ops.MAX_TRANSCRIPT`` nodes, packed greedily in candidate order.  De-duplicating first keeps a class sequence
+        from being summed once per chunk it would appear in.
         -> [[(index, class sequence)]], one list per trie."""
         from . import ops
         if not cands:
@@ -482,23 +463,20 @@ class SemiMarkovModel(object):
         return chunks
 
     def _candidate_rounds(self, data, candidates_by_video, shard, what):
-        """-> (pc, rounds): the prepared corpus and, per launch, one (trie, owner) pair per video -- owner[node]: the index of
-        the candidate that ends in the node, else -1 -- or None for a video all of whose tries went out in earlier launches
-        (it then repeats its last trie, and the launch's values for it are not used)."""
+        """-> (pc, rounds): the prepared corpus and, per launch, one (trie, owner, fresh) triple per video -- owner[node]: the
+        index of the candidate that ends in the node, else -1; fresh: False for a video all of whose tries went out in earlier
+        launches (it then repeats its last trie: a sum leaves the launch's values for it out, a maximum is not moved by them)."""
         from . import ops
         self.model.eval()
         chunks = {name: self._candidate_chunks(cands, name, what) for name, cands in candidates_by_video.items()}
         pc = self.prepare(data, shard=shard)
         if pc.n_videos == 0:
             return pc, []
-        missing = [name for name in pc.video_names if name not in chunks]
-        if missing:
-            raise ValueError("%s: no candidates for video %r" % (what, missing[0]))
+        chunks = self._per_video(pc, chunks, what + ": no candidates for video %r")
         rounds = []
-        for r in range(max(len(chunks[name]) for name in pc.video_names)):
+        for r in range(max(len(mine) for mine in chunks)):
             row = []
-            for name in pc.video_names:
-                mine = chunks[name]
+            for mine in chunks:
                 part = mine[min(r, len(mine) - 1)]
                 trie = ops.TranscriptGraph.from_candidates([seq for _, seq in part])
                 owner = np.where(trie.end_candidate >= 0, np.array([ci for ci, _ in part], np.int64)[trie.end_candidate], -1)
@@ -572,19 +550,13 @@ class SemiMarkovModel(object):
         pc = self.prepare(data, shard=shard)
         if pc.n_videos == 0:
             return {}
-        missing = [name for name in pc.video_names if name not in transcripts_by_video]
-        if missing:
-            raise ValueError("sample_alignments: no transcript for video %r" % (missing[0],))
-        transcripts = [transcripts_by_video[name] for name in pc.video_names]
+        transcripts = self._per_video(pc, transcripts_by_video, "sample_alignments: no transcript for video %r")
         optional = self._optional_flags(pc, transcripts, optional_by_video, optional_classes, 'sample_alignments')
         if optional is None:
             graphs = [ops.TranscriptGraph.chain(t) for t in transcripts]
         else:
             graphs = [ops.TranscriptGraph.from_optional(t, f) for t, f in zip(transcripts, optional)]
-        labels, _, _ = self.model.sample_alignments_packed(pc, graphs, n_samples, seed=seed)
-        lab = labels.cpu().numpy()
-        assert lab.size == 0 or int(lab.max()) < self.model.n_classes, "alignments should not contain EOS"
-        return {name: lab[:, off:off + t] for name, off, t in zip(pc.video_names, pc.frame_offset, pc.lengths)}
+        return self._labels_by_video(pc, self.model.sample_alignments_packed(pc, graphs, n_samples, seed=seed)[0])
 
     def sample_candidates(self, data, candidates_by_video, n_samples, seed=0, shard=None):
         """Joint draws of which candidate transcript a video follows and where its boundaries lie, from the posterior given
@@ -607,19 +579,15 @@ class SemiMarkovModel(object):
         pc = self.prepare(data, shard=shard)
         if pc.n_videos == 0:
             return {}, {}
-        missing = [name for name in pc.video_names if name not in candidates_by_video]
-        if missing:
-            raise ValueError("sample_candidates: no candidates for video %r" % (missing[0],))
-        graphs = [ops.TranscriptGraph.from_candidates(candidates_by_video[name]) for name in pc.video_names]
+        graphs = [ops.TranscriptGraph.from_candidates(cands)
+                  for cands in self._per_video(pc, candidates_by_video, "sample_candidates: no candidates for video %r")]
         labels, _, used = self.model.sample_alignments_packed(pc, graphs, n_samples, seed=seed)
-        lab = labels.cpu().numpy()
-        assert lab.size == 0 or int(lab.max()) < self.model.n_classes, "alignments should not contain EOS"
         chosen = {}
         for name, g, u in zip(pc.video_names, graphs, used):
             u = u.cpu().numpy() != 0                               # [n_samples, M]; the end node is the last used one
             last = u.shape[1] - 1 - np.argmax(u[:, ::-1], axis=1)
             chosen[name] = np.where(u.any(axis=1), g.end_candidate[last], -1).astype(np.int64)
-        return ({name: lab[:, off:off + t] for name, off, t in zip(pc.video_names, pc.frame_offset, pc.lengths)}, chosen)
+        return self._labels_by_video(pc, labels), chosen
 
     @staticmethod
     def _one_kind_of_flags(optional_by_video, optional_classes, what):
@@ -657,10 +625,7 @@ class SemiMarkovModel(object):
             return [np.isin(np.asarray(t.cpu() if torch.is_tensor(t) else t, dtype=np.int64).reshape(-1), classes)
                     for t in transcripts]
         if optional_by_video is not None:
-            missing = [name for name in pc.video_names if name not in optional_by_video]
-            if missing:
-                raise ValueError("%s: no optional flags for video %r" % (what, missing[0]))
-            return [optional_by_video[name] for name in pc.video_names]
+            return SemiMarkovModel._per_video(pc, optional_by_video, what + ": no optional flags for video %r")
         return None
 
     def transcript_log_likelihood(self, data, transcripts_by_video, conditional=False, shard=None, *, optional_by_video=None,
@@ -680,10 +645,7 @@ class SemiMarkovModel(object):
         pc = self.prepare(data, shard=shard)
         if pc.n_videos == 0:
             return {}
-        missing = [name for name in pc.video_names if name not in transcripts_by_video]
-        if missing:
-            raise ValueError("transcript_log_likelihood: no transcript for video %r" % (missing[0],))
-        transcripts = [transcripts_by_video[name] for name in pc.video_names]
+        transcripts = self._per_video(pc, transcripts_by_video, "transcript_log_likelihood: no transcript for video %r")
         optional = self._optional_flags(pc, transcripts, optional_by_video, optional_classes, 'transcript_log_likelihood')
         z = self.model.transcript_scores_packed(pc, transcripts, conditional=conditional, optional=optional, ambiguous=ambiguous)
         return {name: float(v) for name, v in zip(pc.video_names, z.tolist())}
@@ -701,10 +663,7 @@ class SemiMarkovModel(object):
         pc = self.prepare(data, shard=shard)
         if pc.n_videos == 0:
             return {}
-        missing = [name for name in pc.video_names if name not in transcripts_by_video]
-        if missing:
-            raise ValueError("transcript_entry_posteriors: no transcript for video %r" % (missing[0],))
-        transcripts = [transcripts_by_video[name] for name in pc.video_names]
+        transcripts = self._per_video(pc, transcripts_by_video, "transcript_entry_posteriors: no transcript for video %r")
         optional = self._optional_flags(pc, transcripts, optional_by_video, optional_classes, 'transcript_entry_posteriors')
         post = self.model.transcript_entry_posteriors_packed(pc, transcripts, optional, ambiguous=ambiguous)
         return dict(zip(pc.video_names, post))

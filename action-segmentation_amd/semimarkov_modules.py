@@ -141,29 +141,57 @@ def _kbest(r, k, want_spans):
     return _paths(r['batch'], out, want_spans), out['score']
 
 
-def _align(r, local, want_spans, optional=None, graphs=False):
-    """``local``: transcripts in local state ids; with ``graphs`` one ``ops.TranscriptGraph`` per video, and the per-video
-    ``used`` flags of the nodes as a third result."""
-    kw = dict(endpen=r['endpen'], class_map=r['class_map'], want_spans=want_spans, want_labels=not want_spans)
-    if graphs:
-        out = ops.align_graph(r['batch'], r['elp'], r['trans'], r['init'], r['len'], local, want_used=True, **kw)
-        return _paths(r['batch'], out, want_spans), out['best'], out['used']
-    if optional is None:
-        out = ops.align(r['batch'], r['elp'], r['trans'], r['init'], r['len'], local, **kw)
-    else:
-        out = ops.align_optional(r['batch'], r['elp'], r['trans'], r['init'], r['len'], local, optional, **kw)
-    return _paths(r['batch'], out, want_spans), out['best']
+# The ``ops`` launchers of the transcript family by the kind of supervision: alignment, likelihood as the backward needs it,
+# that backward, likelihood as a value.  A supervision is (kind, what the launchers take behind the tables): ('chain',
+# (transcripts,)), ('optional', (transcripts, flags)) or ('graph', (graphs,)), all in LOCAL state ids.
+_ALIGN, _LOGZ, _LOGZ_BWD, _SCORE = range(4)
+_TRANSCRIPT_OPS = {'chain': ('align', 'align_logz_ex', 'align_logz_bwd', 'align_logz'),
+                   'optional': ('align_optional', 'align_opt_logz', 'align_opt_logz_bwd', 'align_opt_logz'),
+                   'graph': ('align_graph', 'align_graph_logz', 'align_graph_logz_bwd', 'align_graph_logz')}
 
 
-def _sample_alignments(r, local, n_samples, seed, want_spans):
-    """The forward launch over the graphs ``local`` (local state ids) on a private workspace, then the sampler on it:
-    (spans or labels, logp, used).  A video without an alignment is no error: rows of -1 and logp NaN."""
+def _supervised(which, r, sup, *more, **kw):
+    """The launcher ``which`` of the supervision's kind on the record of ``_emit``."""
+    kind, given = sup
+    return getattr(ops, _TRANSCRIPT_OPS[kind][which])(r['batch'], r['elp'], r['trans'], r['init'], r['len'], *given, *more,
+                                                      endpen=r['endpen'], **kw)
+
+
+def _align(r, sup, want_spans):
+    """-> (spans or labels, scores); for graphs the per-video ``used`` flags of the nodes as a third result."""
+    graphs = sup[0] == 'graph'
+    out = _supervised(_ALIGN, r, sup, class_map=r['class_map'], want_spans=want_spans, want_labels=not want_spans,
+                      **(dict(want_used=True) if graphs else {}))
+    paths = _paths(r['batch'], out, want_spans)
+    return (paths, out['best'], out['used']) if graphs else (paths, out['best'])
+
+
+def _sample_alignments(r, sup, n_samples, seed, want_spans):
+    """The forward launch over the graphs of ``sup`` on a private workspace, then the sampler on it: (spans or labels, logp,
+    used).  A video without an alignment is no error: rows of -1 and logp NaN."""
     b = r['batch']
-    z = ops.align_graph_logz(b, r['elp'], r['trans'], r['init'], r['len'], local, endpen=r['endpen'])
-    out = ops.align_graph_sample(b, r['elp'], r['trans'], r['init'], r['len'], local, z['logz'], n_samples, seed=seed,
+    z = _supervised(_LOGZ, r, sup)
+    out = ops.align_graph_sample(b, r['elp'], r['trans'], r['init'], r['len'], sup[1][0], z['logz'], n_samples, seed=seed,
                                  endpen=r['endpen'], class_map=r['class_map'], ws=z['ws'], staged=z['_staged'],
                                  want_spans=want_spans, want_labels=not want_spans)
     return _paths(b, out, want_spans), out['logp'], out['used']
+
+
+def _transcript_scores(r, sup, conditional, what):
+    """Without autograd: the likelihood of the supervision per video (``conditional``: minus log Z) as a CPU fp64 tensor."""
+    z = _supervised(_SCORE, r, sup)
+    z = z if torch.is_tensor(z) else z['logz']
+    if conditional:
+        z = z - ops.logz(r['batch'], r['elp'], r['trans'], r['init'], r['len'], endpen=r['endpen'])
+    return _check_transcript_logz(z, None, what, allow_none=True)
+
+
+def _transcript_posteriors(r, sup, what, **want):
+    """The forward and the backward launch of an 'optional' or 'graph' supervision for the posteriors ``want`` names."""
+    out = _supervised(_LOGZ, r, sup)
+    grads = _supervised(_LOGZ_BWD, r, sup, out['logz'], ws=out['ws'], staged=out['_staged'], **want)
+    _check_transcript_logz(out['logz'], None, what, allow_none=True)
+    return grads
 
 
 class _LogPartition(torch.autograd.Function):
@@ -191,99 +219,75 @@ class _LogPartition(torch.autograd.Function):
         return None, None, None, None, g_w, g_cst, g_iv, g['trans'], g['init'], g['len']
 
 
-class _TranscriptLogPartition(torch.autograd.Function):
-    """log Z_a of every video of one launch -- the sum over the segmentations whose class sequence is the video's transcript --
-    as a differentiable function of the fp64 factor tables, beside ``_LogPartition``.  Forward: smm_emission_f64 +
-    smm_align_logz_f64 on a private workspace that survives until backward; backward: smm_align_logz_bwd_f64 (the posterior
-    of the alignments) + smm_emission_bwd_f64.  ``local``: the transcripts in local state ids."""
+class _AlignmentLogPartition(torch.autograd.Function):
+    """The likelihood of every video's supervision in one launch, as a differentiable function of the fp64 factor tables,
+    beside ``_LogPartition``: log Z_a -- the sum over the segmentations whose class sequence is the video's transcript --, log
+    Z_o -- over every alignment with any subset of the optional entries left out -- or log Z_g -- over every alignment to
+    every start -> end path of the video's graph --, by the kind of ``sup`` (``_TRANSCRIPT_OPS``).  Forward: smm_emission_f64 +
+    the kind's forward launch on a private workspace that survives until backward; backward: the kind's backward launch (the
+    posterior of the alignments) + smm_emission_bwd_f64."""
 
     @staticmethod
-    def forward(ctx, batch, x, cons, endpen, local, w, cst, inv_var, trans, init, len_scores):
+    def forward(ctx, batch, x, cons, endpen, sup, w, cst, inv_var, trans, init, len_scores):
         r = _emit(batch, x, cons, endpen, (w, cst, trans, init, len_scores, None), inv_var)
-        out = ops.align_logz_ex(batch, r['elp'], trans, init, len_scores, local, endpen=endpen)
-        ctx.batch, ctx.endpen, ctx.ws, ctx.transcript = batch, endpen, out['ws'], out['transcript']
+        out = _supervised(_LOGZ, r, sup)
+        if sup[0] == 'chain':       # the backward launch takes a plain transcript as the forward's (ids on the device, offsets)
+            ctx.sup, ctx.staged = ('chain', (out['transcript'],)), {}
+        else:                       # ... and the other kinds as they came, beside what the forward launch staged of them
+            ctx.sup, ctx.staged = sup, dict(staged=out['_staged'])
+        ctx.batch, ctx.endpen, ctx.ws = batch, endpen, out['ws']
         ctx.save_for_backward(x, r['elp'], trans, init, len_scores, out['logz'])
         return out['logz']
 
     @staticmethod
     def backward(ctx, gz):
         x, elp, trans, init, len_scores, logz = ctx.saved_tensors
-        g = ops.align_logz_bwd(ctx.batch, elp, trans, init, len_scores, ctx.transcript, logz,
-                               grad_logz=gz.to(torch.float64).contiguous(), endpen=ctx.endpen, ws=ctx.ws)
+        r = dict(batch=ctx.batch, elp=elp, trans=trans, init=init, len=len_scores, endpen=ctx.endpen)
+        g = _supervised(_LOGZ_BWD, r, ctx.sup, logz, grad_logz=gz.to(torch.float64).contiguous(), ws=ctx.ws, **ctx.staged)
         g_w, g_cst, g_iv = ops.emission_bwd(ctx.batch, x, g['elp'], ws=ctx.ws)
         return None, None, None, None, None, g_w, g_cst, g_iv, g['trans'], g['init'], g['len']
 
 
-class _TranscriptOptLogPartition(torch.autograd.Function):
-    """log Z_o of every video of one launch -- the sum over every alignment to the video's transcript with any subset of its
-    optional entries left out -- beside ``_TranscriptLogPartition``.  Forward: smm_emission_f64 + smm_align_opt_logz_f64 on a
-    private workspace that survives until backward; backward: smm_align_opt_logz_bwd_f64 + smm_emission_bwd_f64.  ``local``:
-    the transcripts in local state ids, ``optional``: one boolean sequence per video."""
-
-    @staticmethod
-    def forward(ctx, batch, x, cons, endpen, local, optional, w, cst, inv_var, trans, init, len_scores):
-        r = _emit(batch, x, cons, endpen, (w, cst, trans, init, len_scores, None), inv_var)
-        out = ops.align_opt_logz(batch, r['elp'], trans, init, len_scores, local, optional, endpen=endpen)
-        ctx.batch, ctx.endpen, ctx.ws, ctx.local, ctx.optional, ctx.staged = batch, endpen, out['ws'], local, optional, out['_staged']
-        ctx.save_for_backward(x, r['elp'], trans, init, len_scores, out['logz'])
-        return out['logz']
-
-    @staticmethod
-    def backward(ctx, gz):
-        x, elp, trans, init, len_scores, logz = ctx.saved_tensors
-        g = ops.align_opt_logz_bwd(ctx.batch, elp, trans, init, len_scores, ctx.local, ctx.optional, logz,
-                                   grad_logz=gz.to(torch.float64).contiguous(), endpen=ctx.endpen, ws=ctx.ws, staged=ctx.staged)
-        g_w, g_cst, g_iv = ops.emission_bwd(ctx.batch, x, g['elp'], ws=ctx.ws)
-        return None, None, None, None, None, None, g_w, g_cst, g_iv, g['trans'], g['init'], g['len']
+def _alignment_log_partition(staged, sup):
+    """``_AlignmentLogPartition`` on what ``_packed_stage`` returns (differentiable tables)."""
+    batch, x, cons, endpen, g, inv_var = staged
+    return _AlignmentLogPartition.apply(batch, x, cons, endpen, sup, g[0], g[1], inv_var, g[2], g[3], g[4])
 
 
-class _TranscriptGraphLogPartition(torch.autograd.Function):
-    """log Z_g of every video of one launch -- the sum over every alignment to every start -> end path of the video's
-    transcript graph -- beside ``_TranscriptOptLogPartition``.  Forward: smm_emission_f64 + smm_align_graph_logz_f64 on a private
-    workspace that survives until backward; backward: smm_align_graph_logz_bwd_f64 + smm_emission_bwd_f64.  ``local``: one
-    ``ops.TranscriptGraph`` in local state ids per video."""
+def _check_ambiguous(ambiguous, what):
+    if ambiguous not in ('raise', 'allow'):
+        raise ValueError("%s: ambiguous must be 'raise' or 'allow'" % what)
+    return ambiguous == 'raise'
 
-    @staticmethod
-    def forward(ctx, batch, x, cons, endpen, local, w, cst, inv_var, trans, init, len_scores):
-        r = _emit(batch, x, cons, endpen, (w, cst, trans, init, len_scores, None), inv_var)
-        out = ops.align_graph_logz(batch, r['elp'], trans, init, len_scores, local, endpen=endpen)
-        ctx.batch, ctx.endpen, ctx.ws, ctx.local, ctx.staged = batch, endpen, out['ws'], local, out['_staged']
-        ctx.save_for_backward(x, r['elp'], trans, init, len_scores, out['logz'])
-        return out['logz']
 
-    @staticmethod
-    def backward(ctx, gz):
-        x, elp, trans, init, len_scores, logz = ctx.saved_tensors
-        g = ops.align_graph_logz_bwd(ctx.batch, elp, trans, init, len_scores, ctx.local, logz,
-                                     grad_logz=gz.to(torch.float64).contiguous(), endpen=ctx.endpen, ws=ctx.ws, staged=ctx.staged)
-        g_w, g_cst, g_iv = ops.emission_bwd(ctx.batch, x, g['elp'], ws=ctx.ws)
-        return None, None, None, None, None, g_w, g_cst, g_iv, g['trans'], g['init'], g['len']
+def _video(names, i):
+    """How a refusal names video ``i``: by its name in a corpus, by its index in a padded batch."""
+    return i if names is None else names[i]
 
 
 def _checked_graphs(graphs, n_videos, ambiguous, names, what):
     """The graphs of a launch, checked on the host before a device is touched: one ``ops.TranscriptGraph`` per video;
     ``ambiguous='raise'``: ValueError naming the first video two start -> end paths of whose graph spell the same class
     sequence (``TranscriptGraph.is_ambiguous``), ``'allow'``: the sum over paths and boundaries as defined."""
-    if ambiguous not in ('raise', 'allow'):
-        raise ValueError("%s: ambiguous must be 'raise' or 'allow'" % what)
+    refuse = _check_ambiguous(ambiguous, what)
     if len(graphs) != n_videos:
         raise ValueError("%s: %d graphs for %d videos" % (what, len(graphs), n_videos))
     for i, g in enumerate(graphs):
         if not isinstance(g, ops.TranscriptGraph):
-            raise ValueError("%s: an ops.TranscriptGraph expected for video %r" % (what, i if names is None else names[i]))
-        if ambiguous == 'raise' and g.is_ambiguous():
+            raise ValueError("%s: an ops.TranscriptGraph expected for video %r" % (what, _video(names, i)))
+        if refuse and g.is_ambiguous():
             raise ValueError("%s: two start -> end paths of the graph of video %r spell the same class sequence, so its "
                              "segmentations would be counted once per path; pass ambiguous='allow' for that sum over "
-                             "alignments" % (what, i if names is None else names[i]))
+                             "alignments" % (what, _video(names, i)))
     return list(graphs)
 
 
 def _checked_optional(transcripts, optional, ambiguous, names, what):
     """The flags of a launch as boolean arrays, checked on the host before a device is touched (``transcripts`` in global or
-    local ids: the map between them is one-to-one within a video): one sequence per video, as long as its transcript; ``ambiguous='raise'``: ValueError naming the first video two subsets of whose optional entries give the
-    same class sequence (``ops.transcript_is_ambiguous``), ``'allow'``: the sum over alignments as defined."""
-    if ambiguous not in ('raise', 'allow'):
-        raise ValueError("%s: ambiguous must be 'raise' or 'allow'" % what)
+    local ids: the map between them is one-to-one within a video): one sequence per video, as long as its transcript;
+    ``ambiguous='raise'``: ValueError naming the first video two subsets of whose optional entries give the same class
+    sequence (``ops.transcript_is_ambiguous``), ``'allow'``: the sum over alignments as defined."""
+    refuse = _check_ambiguous(ambiguous, what)
     if len(optional) != len(transcripts):
         raise ValueError("%s: %d sequences of optional flags for %d videos" % (what, len(optional), len(transcripts)))
     flags = [np.asarray(f.detach().cpu() if torch.is_tensor(f) else f).reshape(-1) != 0 for f in optional]
@@ -291,11 +295,11 @@ def _checked_optional(transcripts, optional, ambiguous, names, what):
     for i, (a, f) in enumerate(zip(ids, flags)):
         if f.size != len(a):
             raise ValueError("%s: %d optional flags for the %d transcript entries of video %r"
-                             % (what, f.size, len(a), i if names is None else names[i]))
-        if ambiguous == 'raise' and ops.transcript_is_ambiguous(a, f):
+                             % (what, f.size, len(a), _video(names, i)))
+        if refuse and ops.transcript_is_ambiguous(a, f):
             raise ValueError("%s: two subsets of the optional entries of video %r give the same class sequence, so its "
                              "segmentations would be counted once per subset; pass ambiguous='allow' for that sum over "
-                             "alignments" % (what, i if names is None else names[i]))
+                             "alignments" % (what, _video(names, i)))
     return flags
 
 
@@ -308,8 +312,7 @@ def _check_transcript_logz(z, names, what, allow_none=False):
     if bad and not allow_none:
         i = bad[0]
         raise ValueError("%s: no segmentation of video %r has its transcript (more entries than frames, too few for the span "
-                         "limit, or forbidden by the tables): log Z_a = -inf cannot be trained on"
-                         % (what, i if names is None else names[i]))
+                         "limit, or forbidden by the tables): log Z_a = -inf cannot be trained on" % (what, _video(names, i)))
     return zh
 
 
@@ -990,11 +993,11 @@ class SemiMarkovModule(nn.Module):
         tabs = self._differentiable_tables(self._check_valid_classes(valid_classes_per_instance), features.device)
         return _PosteriorValue.apply('entropy', launch, *tabs)
 
-    def _packed_stage(self, pc, what):
+    def _packed_stage(self, pc, what, differentiable=False):
         """``_stage_padded`` for a PackedCorpus, prepared for this module here: (batch, x, cons, endpen, tables stacked per
-        group, inv_var) -- the arguments of ``_emit`` / ``_emit_logz``."""
+        group, inv_var) -- the arguments of ``_emit`` / ``_emit_logz``.  ``differentiable``: tables with autograd history."""
         self._require_device(pc.x, what)
-        self.prepare_packed(pc)
+        self.prepare_packed(pc, differentiable)
         t = pc.tables
         return pc.batch, pc.x, pc.cons, pc.endpen, tuple(t[k] for k in TABLE_NAMES) + (t['class_map'],), t['inv_var']
 
@@ -1163,25 +1166,96 @@ class SemiMarkovModule(nn.Module):
         no video covers) and fp64 n_videos in the order of ``pc.video_names``."""
         return _mbr(self._packed_posterior_launch(pc, 'mbr_decode_packed', with_backward=True), want_spans=False)
 
-    # ------------------------------------------------------------------ forced alignment (smm_align_f64)
+    # ------------------------------------------------------------------ the transcript family: its supervision, staged
+    @staticmethod
+    def _local_ids(class_map_host, n_states, group):
+        """Per video the look-up GLOBAL class id -> local state id: the position of the id among the video's valid classes."""
+        lookup = [{int(c): j for j, c in reversed(list(enumerate(class_map_host[g, :n_states[g]])))} for g in range(len(n_states))]
+        return [lookup[int(g)] for g in group]
+
     @staticmethod
     def _local_transcripts(transcripts, class_map_host, n_states, group):
         """Transcripts in GLOBAL class ids -> local state ids: the position of each id among its video's valid classes."""
         if len(transcripts) != len(group):
             raise ValueError("align: %d transcripts for %d videos" % (len(transcripts), len(group)))
-        lookup = [{int(c): j for j, c in reversed(list(enumerate(class_map_host[g, :n_states[g]])))} for g in range(len(n_states))]
         out = []
-        for i, t in enumerate(transcripts):
+        for i, (t, lk) in enumerate(zip(transcripts, SemiMarkovModule._local_ids(class_map_host, n_states, group))):
             ids = np.asarray(t.detach().cpu() if torch.is_tensor(t) else t, dtype=np.int64).reshape(-1)
             if ids.size == 0:
                 raise ValueError("align: the transcript of video %d is empty" % i)
-            lk = lookup[int(group[i])]
             bad = [int(c) for c in ids if int(c) not in lk]
             if bad:
                 raise ValueError("align: class %d in the transcript of video %d is not a valid class of that video" % (bad[0], i))
             out.append(np.array([lk[int(c)] for c in ids], np.int64))
         return out
 
+    @staticmethod
+    def _local_graphs(graphs, class_map_host, n_states, group):
+        """Graphs in GLOBAL class ids -> local state ids, as ``_local_transcripts`` maps transcripts; a class that is no valid
+        class of the video becomes -1, which leaves that video without an alignment."""
+        if len(graphs) != len(group):
+            raise ValueError("align_graph: %d graphs for %d videos" % (len(graphs), len(group)))
+        return [gr.with_ids([lk.get(int(c), -1) for c in gr.ids])
+                for gr, lk in zip(graphs, SemiMarkovModule._local_ids(class_map_host, n_states, group))]
+
+    @staticmethod
+    def _checked_supervision(given, optional, graphs, n_videos, ambiguous, names, what):
+        """What supervises a launch -- transcripts (with ``optional``: one boolean sequence each) or ``graphs`` --, checked on
+        the host -> (given, optional).  ``ambiguous``: 'raise' / 'allow' from the likelihoods and the sampler
+        (``_checked_graphs`` / ``_checked_optional``); None from the alignments, which hand flags and graphs to the launcher as
+        they came."""
+        if ambiguous is not None and graphs:
+            given = _checked_graphs(given, n_videos, ambiguous, names, what)
+        elif ambiguous is not None and optional is not None:
+            optional = _checked_optional(given, optional, ambiguous, names, what)
+        return given, optional
+
+    def _local_supervision(self, given, optional, graphs, class_map_host, n_states, group):
+        """The same in LOCAL state ids, as the launch helpers take it (``_TRANSCRIPT_OPS``)."""
+        if graphs:
+            return 'graph', (self._local_graphs(given, class_map_host, n_states, group),)
+        local = self._local_transcripts(given, class_map_host, n_states, group)
+        return ('chain', (local,)) if optional is None else ('optional', (local, optional))
+
+    def _supervised_padded(self, what, features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
+                           constraints, given, optional=None, graphs=False, ambiguous=None, differentiable=False):
+        """Stage a transcript-family launch on a zero-padded single-task batch -> (the record of ``_emit``, supervision); with
+        ``differentiable`` the first is (batch, x, cons, endpen, tables with autograd history, inv_var) for
+        ``_alignment_log_partition``, which emits itself.  Every check on the host comes before a device is touched.  (Staged
+        without no_time_split and, add_eos=False being refused, without the length check.)"""
+        if not add_eos:
+            raise ValueError("%s: add_eos=False is not supported" % what)
+        b = features.size(0)
+        given, optional = self._checked_supervision(given, optional, graphs, b, ambiguous, None, what)
+        valid_classes = self._check_valid_classes(valid_classes_per_instance)
+        ids = list(range(self.n_classes)) if valid_classes is None else [int(v) for v in valid_classes]
+        sup = self._local_supervision(given, optional, graphs, np.array([ids + [self.n_classes]], np.int64), [len(ids)],
+                                      np.zeros(b, np.int64))
+        self._require_device(features, what)
+        st = self._one_group_tables(valid_classes, features.device) if differentiable else None
+        batch, x, cons, endpen, tab, g1 = self._stage_padded(features, lengths, valid_classes, additional_allowed_ends_per_instance,
+                                                             constraints, check_no_eos=False, tables=st)
+        if differentiable:
+            return (batch, x, cons, endpen, tuple(st[k] for k in TABLE_NAMES) + (None,), st['inv_var']), sup
+        return _emit(batch, x, cons, endpen, g1, tab['inv_var']), sup
+
+    def _supervised_packed(self, pc, what, given, optional=None, graphs=False, ambiguous=None, differentiable=False):
+        """``_supervised_padded`` for a PackedCorpus, prepared for this module here; the supervision in the order of
+        ``pc.video_names``, which its refusals name the videos by."""
+        no_eos = "%s: add_eos=False is not supported" % what
+        if getattr(pc, 'batch', None) is not None and pc.batch.no_eos:
+            raise ValueError(no_eos)
+        names = list(pc.video_names)
+        given, optional = self._checked_supervision(given, optional, graphs, len(names), ambiguous, names, what)
+        staged = self._packed_stage(pc, what, differentiable)
+        batch = staged[0]
+        if batch.no_eos:                                           # (a corpus this call prepared)
+            raise ValueError(no_eos)
+        group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
+        sup = self._local_supervision(given, optional, graphs, staged[4][5].cpu().numpy(), batch.n_states, group)
+        return (staged if differentiable else _emit(*staged)), sup
+
+    # ------------------------------------------------------------------ forced alignment (smm_align_f64)
     @torch.no_grad()
     def align(self, features, lengths, valid_classes_per_instance, transcripts, add_eos=True,
               additional_allowed_ends_per_instance=None, constraints=None, optional=None):
@@ -1197,15 +1271,9 @@ class SemiMarkovModule(nn.Module):
         ``optional``: one boolean sequence per video, as long as its transcript; the flagged entries may be left out and the
         result is the best over every subset of them (smm_align_opt_f64; ``ops.align_optional``).  ValueError when their count or a
         length differs from the transcripts'."""
-        if not add_eos:
-            raise ValueError("align: add_eos=False is not supported")
-        self._require_device(features, 'align')
-        # (this entry point stages without no_time_split and, having refused add_eos=False above, without the length check)
-        batch, x, cons, endpen, tab, g1 = self._stage_padded(
-            features, lengths, self._check_valid_classes(valid_classes_per_instance), additional_allowed_ends_per_instance,
-            constraints, check_no_eos=False)
-        local = self._local_transcripts(transcripts, g1[5].cpu().numpy(), batch.n_states, np.zeros(batch.b, np.int64))
-        return _align(_emit(batch, x, cons, endpen, g1, tab['inv_var']), local, want_spans=True, optional=optional)
+        r, sup = self._supervised_padded('align', features, lengths, valid_classes_per_instance, add_eos,
+                                         additional_allowed_ends_per_instance, constraints, transcripts, optional)
+        return _align(r, sup, want_spans=True)
 
     @torch.no_grad()
     def align_packed(self, pc, transcripts, optional=None):
@@ -1213,24 +1281,9 @@ class SemiMarkovModule(nn.Module):
         GLOBAL class ids per video, in the order of ``pc.video_names``.  Returns (labels, scores): device int64 total_frames
         (global class ids on the packed frame axis, -1 on frames no video covers and on videos without an alignment) and fp64
         n_videos.  ``optional``: as in ``align``."""
-        self._require_device(pc.x, 'align_packed')
-        if pc.batch.no_eos:
-            raise ValueError("align_packed: add_eos=False is not supported")
-        batch, x, cons, endpen, g, inv_var = self._packed_stage(pc, 'align_packed')
-        group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
-        local = self._local_transcripts(transcripts, g[5].cpu().numpy(), batch.n_states, group)
-        return _align(_emit(batch, x, cons, endpen, g, inv_var), local, want_spans=False, optional=optional)
+        return _align(*self._supervised_packed(pc, 'align_packed', transcripts, optional), want_spans=False)
 
     # ------------------------------------------------------------------ alignment to a transcript graph (smm_align_graph_f64)
-    @staticmethod
-    def _local_graphs(graphs, class_map_host, n_states, group):
-        """Graphs in GLOBAL class ids -> local state ids, as ``_local_transcripts`` maps transcripts; a class that is no valid
-        class of the video becomes -1, which leaves that video without an alignment."""
-        if len(graphs) != len(group):
-            raise ValueError("align_graph: %d graphs for %d videos" % (len(graphs), len(group)))
-        lookup = [{int(c): j for j, c in reversed(list(enumerate(class_map_host[g, :n_states[g]])))} for g in range(len(n_states))]
-        return [gr.with_ids([lookup[int(group[i])].get(int(c), -1) for c in gr.ids]) for i, gr in enumerate(graphs)]
-
     @torch.no_grad()
     def align_graph(self, features, lengths, valid_classes_per_instance, graphs, add_eos=True,
                     additional_allowed_ends_per_instance=None, constraints=None):
@@ -1243,16 +1296,11 @@ class SemiMarkovModule(nn.Module):
         the path (``graph.candidate_of(used[i])`` names the candidate of a trie).  A video none of whose paths can be laid over
         it, or whose graph names a class that is not valid for it, gives a row of -1, score -inf and no used node.  ValueError
         for a wrong number of graphs or add_eos=False; SmmError when a NaN reached the DP.  No autograd."""
-        if not add_eos:
-            raise ValueError("align_graph: add_eos=False is not supported")
         if len(graphs) != len(lengths):
             raise ValueError("align_graph: %d graphs for %d videos" % (len(graphs), len(lengths)))
-        self._require_device(features, 'align_graph')
-        batch, x, cons, endpen, tab, g1 = self._stage_padded(
-            features, lengths, self._check_valid_classes(valid_classes_per_instance), additional_allowed_ends_per_instance,
-            constraints, check_no_eos=False)
-        local = self._local_graphs(graphs, g1[5].cpu().numpy(), batch.n_states, np.zeros(batch.b, np.int64))
-        return _align(_emit(batch, x, cons, endpen, g1, tab['inv_var']), local, want_spans=True, graphs=True)
+        r, sup = self._supervised_padded('align_graph', features, lengths, valid_classes_per_instance, add_eos,
+                                         additional_allowed_ends_per_instance, constraints, graphs, graphs=True)
+        return _align(r, sup, want_spans=True)
 
     @torch.no_grad()
     def align_graph_packed(self, pc, graphs):
@@ -1260,13 +1308,7 @@ class SemiMarkovModule(nn.Module):
         ``ops.TranscriptGraph`` in GLOBAL class ids per video, in the order of ``pc.video_names``.  Returns (labels, scores,
         used): device int64 total_frames (-1 on frames no video covers and on videos without an alignment), fp64 n_videos and
         the per-video flags of the nodes on the path."""
-        self._require_device(pc.x, 'align_graph_packed')
-        if pc.batch.no_eos:
-            raise ValueError("align_graph_packed: add_eos=False is not supported")
-        batch, x, cons, endpen, g, inv_var = self._packed_stage(pc, 'align_graph_packed')
-        group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
-        local = self._local_graphs(graphs, g[5].cpu().numpy(), batch.n_states, group)
-        return _align(_emit(batch, x, cons, endpen, g, inv_var), local, want_spans=False, graphs=True)
+        return _align(*self._supervised_packed(pc, 'align_graph_packed', graphs, graphs=True), want_spans=False)
 
     # ------------------------------------------------------------------ transcript likelihood (smm_align_logz_f64)
     def transcript_log_partition(self, features, lengths, valid_classes_per_instance, transcripts, add_eos=True,
@@ -1284,26 +1326,11 @@ class SemiMarkovModule(nn.Module):
         (smm_align_opt_logz_f64 / _bwd_f64) -- the likelihood of the set of class sequences when no two subsets give the same
         one.  ``ambiguous``: 'raise' (ValueError naming the first video with two such subsets) or 'allow' (the sum over
         alignments as defined, a segmentation counted once per subset that yields its class sequence)."""
-        if not add_eos:
-            raise ValueError("transcript_log_partition: add_eos=False is not supported")
         if len(transcripts) != features.size(0):
             raise ValueError("transcript_log_partition: %d transcripts for %d videos" % (len(transcripts), features.size(0)))
-        valid_classes = self._check_valid_classes(valid_classes_per_instance)
-        ids = list(range(self.n_classes)) if valid_classes is None else [int(v) for v in valid_classes]
-        local = self._local_transcripts(transcripts, np.array([ids + [self.n_classes]], np.int64), [len(ids)],
-                                        np.zeros(len(transcripts), np.int64))
-        if optional is not None:
-            optional = _checked_optional(local, optional, ambiguous, None, 'transcript_log_partition')
-        self._require_device(features, 'transcript_log_partition')
-        st = self._one_group_tables(valid_classes, features.device)
-        batch, x, cons, endpen, _, _ = self._stage_padded(features, lengths, valid_classes, additional_allowed_ends_per_instance,
-                                                          constraints, check_no_eos=False, tables=st)
-        if optional is None:
-            z = _TranscriptLogPartition.apply(batch, x, cons, endpen, local, st['w'], st['cst'], st['inv_var'], st['trans'],
-                                              st['init'], st['len'])
-        else:
-            z = _TranscriptOptLogPartition.apply(batch, x, cons, endpen, local, optional, st['w'], st['cst'], st['inv_var'],
-                                                 st['trans'], st['init'], st['len'])
+        z = _alignment_log_partition(*self._supervised_padded(
+            'transcript_log_partition', features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
+            constraints, transcripts, optional, ambiguous=ambiguous, differentiable=True))
         _check_transcript_logz(z, None, 'transcript_log_partition')
         return z
 
@@ -1311,21 +1338,8 @@ class SemiMarkovModule(nn.Module):
         """``transcript_log_partition`` for a whole PackedCorpus in one launch of each kernel: ``transcripts`` holds one sequence
         of GLOBAL class ids per video, in the order of ``pc.video_names``.  fp64 [n_videos], differentiable.  ``optional``,
         ``ambiguous``: as in ``transcript_log_partition``."""
-        if optional is not None:
-            optional = _checked_optional(transcripts, optional, ambiguous, list(pc.video_names), 'transcript_log_partition_packed')
-        self._require_device(pc.x, 'transcript_log_partition_packed')
-        if pc.batch is not None and pc.batch.no_eos:
-            raise ValueError("transcript_log_partition_packed: add_eos=False is not supported")
-        self.prepare_packed(pc, differentiable=True)
-        t, batch = pc.tables, pc.batch
-        group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
-        local = self._local_transcripts(transcripts, t['class_map'].cpu().numpy(), batch.n_states, group)
-        if optional is None:
-            z = _TranscriptLogPartition.apply(batch, pc.x, pc.cons, pc.endpen, local, t['w'], t['cst'], t['inv_var'], t['trans'],
-                                              t['init'], t['len'])
-        else:
-            z = _TranscriptOptLogPartition.apply(batch, pc.x, pc.cons, pc.endpen, local, optional, t['w'], t['cst'], t['inv_var'],
-                                                 t['trans'], t['init'], t['len'])
+        z = _alignment_log_partition(*self._supervised_packed(pc, 'transcript_log_partition_packed', transcripts, optional,
+                                                              ambiguous=ambiguous, differentiable=True))
         _check_transcript_logz(z, list(pc.video_names), 'transcript_log_partition_packed')
         return z
 
@@ -1335,21 +1349,8 @@ class SemiMarkovModule(nn.Module):
         log Z) as a CPU fp64 tensor; -inf for a video no segmentation of which has its transcript.  One emission launch, then
         the DP launches.  SmmError when a NaN reached the DP.  ``optional``, ``ambiguous``: as in ``transcript_log_partition``
         (log Z_o in place of log Z_a)."""
-        if pc.batch is not None and pc.batch.no_eos:
-            raise ValueError("transcript_scores_packed: add_eos=False is not supported")
-        if optional is not None:
-            optional = _checked_optional(transcripts, optional, ambiguous, list(pc.video_names), 'transcript_scores_packed')
-        batch, x, cons, endpen, g, inv_var = self._packed_stage(pc, 'transcript_scores_packed')
-        group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
-        local = self._local_transcripts(transcripts, g[5].cpu().numpy(), batch.n_states, group)
-        r = _emit(batch, x, cons, endpen, g, inv_var)
-        if optional is None:
-            z = ops.align_logz(batch, r['elp'], r['trans'], r['init'], r['len'], local, endpen=endpen)
-        else:
-            z = ops.align_opt_logz(batch, r['elp'], r['trans'], r['init'], r['len'], local, optional, endpen=endpen)['logz']
-        if conditional:
-            z = z - ops.logz(batch, r['elp'], r['trans'], r['init'], r['len'], endpen=endpen)
-        return _check_transcript_logz(z, None, 'transcript_scores_packed', allow_none=True)
+        r, sup = self._supervised_packed(pc, 'transcript_scores_packed', transcripts, optional, ambiguous=ambiguous)
+        return _transcript_scores(r, sup, conditional, 'transcript_scores_packed')
 
     @torch.no_grad()
     def transcript_entry_posteriors_packed(self, pc, transcripts, optional, ambiguous='raise'):
@@ -1357,19 +1358,10 @@ class SemiMarkovModule(nn.Module):
         frames and the transcript with its ``optional`` flags (p_used of smm_align_opt_logz_bwd_f64: 1 for a mandatory entry):
         a list of fp64 CPU arrays in the order of ``pc.video_names``; zeros for a video without an alignment.  One emission
         launch, then the forward and the backward launches.  SmmError when a NaN reached the DP."""
-        if pc.batch is not None and pc.batch.no_eos:
-            raise ValueError("transcript_entry_posteriors_packed: add_eos=False is not supported")
         if optional is None:
             raise ValueError("transcript_entry_posteriors_packed: one sequence of optional flags per video expected")
-        optional = _checked_optional(transcripts, optional, ambiguous, list(pc.video_names), 'transcript_entry_posteriors_packed')
-        batch, x, cons, endpen, g, inv_var = self._packed_stage(pc, 'transcript_entry_posteriors_packed')
-        group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
-        local = self._local_transcripts(transcripts, g[5].cpu().numpy(), batch.n_states, group)
-        r = _emit(batch, x, cons, endpen, g, inv_var)
-        out = ops.align_opt_logz(batch, r['elp'], r['trans'], r['init'], r['len'], local, optional, endpen=endpen)
-        grads = ops.align_opt_logz_bwd(batch, r['elp'], r['trans'], r['init'], r['len'], local, optional, out['logz'],
-                                       endpen=endpen, ws=out['ws'], staged=out['_staged'], want_entry_prob=True)
-        _check_transcript_logz(out['logz'], None, 'transcript_entry_posteriors_packed', allow_none=True)
+        r, sup = self._supervised_packed(pc, 'transcript_entry_posteriors_packed', transcripts, optional, ambiguous=ambiguous)
+        grads = _transcript_posteriors(r, sup, 'transcript_entry_posteriors_packed', want_entry_prob=True)
         return [p.cpu().numpy() for p in grads['entry_prob']]
 
     # ------------------------------------------------------------------ transcript-graph likelihood (smm_align_graph_logz_f64)
@@ -1384,18 +1376,9 @@ class SemiMarkovModule(nn.Module):
         spell the same class sequence) or 'allow' (such a sequence's segmentations count once per path).  ValueError for
         add_eos=False, a wrong number of graphs, and for a video none of whose paths can be laid over it (log Z_g = -inf; a
         class that is not valid for the video does that); SmmError when a NaN reached the DP."""
-        if not add_eos:
-            raise ValueError("transcript_graph_log_partition: add_eos=False is not supported")
-        graphs = _checked_graphs(graphs, features.size(0), ambiguous, None, 'transcript_graph_log_partition')
-        valid_classes = self._check_valid_classes(valid_classes_per_instance)
-        ids = list(range(self.n_classes)) if valid_classes is None else [int(v) for v in valid_classes]
-        local = self._local_graphs(graphs, np.array([ids + [self.n_classes]], np.int64), [len(ids)], np.zeros(len(graphs), np.int64))
-        self._require_device(features, 'transcript_graph_log_partition')
-        st = self._one_group_tables(valid_classes, features.device)
-        batch, x, cons, endpen, _, _ = self._stage_padded(features, lengths, valid_classes, additional_allowed_ends_per_instance,
-                                                          constraints, check_no_eos=False, tables=st)
-        z = _TranscriptGraphLogPartition.apply(batch, x, cons, endpen, local, st['w'], st['cst'], st['inv_var'], st['trans'],
-                                               st['init'], st['len'])
+        z = _alignment_log_partition(*self._supervised_padded(
+            'transcript_graph_log_partition', features, lengths, valid_classes_per_instance, add_eos,
+            additional_allowed_ends_per_instance, constraints, graphs, graphs=True, ambiguous=ambiguous, differentiable=True))
         _check_transcript_logz(z, None, 'transcript_graph_log_partition')
         return z
 
@@ -1403,16 +1386,8 @@ class SemiMarkovModule(nn.Module):
         """``transcript_graph_log_partition`` for a whole PackedCorpus in one launch of each kernel: ``graphs`` holds one
         ``ops.TranscriptGraph`` in GLOBAL class ids per video, in the order of ``pc.video_names``.  fp64 [n_videos],
         differentiable."""
-        graphs = _checked_graphs(graphs, len(pc.video_names), ambiguous, list(pc.video_names), 'transcript_graph_log_partition_packed')
-        self._require_device(pc.x, 'transcript_graph_log_partition_packed')
-        if pc.batch is not None and pc.batch.no_eos:
-            raise ValueError("transcript_graph_log_partition_packed: add_eos=False is not supported")
-        self.prepare_packed(pc, differentiable=True)
-        t, batch = pc.tables, pc.batch
-        group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
-        local = self._local_graphs(graphs, t['class_map'].cpu().numpy(), batch.n_states, group)
-        z = _TranscriptGraphLogPartition.apply(batch, pc.x, pc.cons, pc.endpen, local, t['w'], t['cst'], t['inv_var'], t['trans'],
-                                               t['init'], t['len'])
+        z = _alignment_log_partition(*self._supervised_packed(pc, 'transcript_graph_log_partition_packed', graphs, graphs=True,
+                                                              ambiguous=ambiguous, differentiable=True))
         _check_transcript_logz(z, list(pc.video_names), 'transcript_graph_log_partition_packed')
         return z
 
@@ -1421,17 +1396,8 @@ class SemiMarkovModule(nn.Module):
         """Without autograd, on the cached decode tables: log Z_g of every video of a PackedCorpus (``conditional``: minus its
         log Z) as a CPU fp64 tensor; -inf for a video none of whose paths can be laid over it.  One emission launch, then the
         DP launches.  SmmError when a NaN reached the DP.  ``ambiguous``: as in ``transcript_graph_log_partition``."""
-        if pc.batch is not None and pc.batch.no_eos:
-            raise ValueError("transcript_graph_scores_packed: add_eos=False is not supported")
-        graphs = _checked_graphs(graphs, len(pc.video_names), ambiguous, list(pc.video_names), 'transcript_graph_scores_packed')
-        batch, x, cons, endpen, g, inv_var = self._packed_stage(pc, 'transcript_graph_scores_packed')
-        group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
-        local = self._local_graphs(graphs, g[5].cpu().numpy(), batch.n_states, group)
-        r = _emit(batch, x, cons, endpen, g, inv_var)
-        z = ops.align_graph_logz(batch, r['elp'], r['trans'], r['init'], r['len'], local, endpen=endpen)['logz']
-        if conditional:
-            z = z - ops.logz(batch, r['elp'], r['trans'], r['init'], r['len'], endpen=endpen)
-        return _check_transcript_logz(z, None, 'transcript_graph_scores_packed', allow_none=True)
+        r, sup = self._supervised_packed(pc, 'transcript_graph_scores_packed', graphs, graphs=True, ambiguous=ambiguous)
+        return _transcript_scores(r, sup, conditional, 'transcript_graph_scores_packed')
 
     @torch.no_grad()
     def transcript_node_posteriors_packed(self, pc, graphs):
@@ -1440,17 +1406,8 @@ class SemiMarkovModule(nn.Module):
         (p_used, p_end), two lists of fp64 CPU arrays in the order of ``pc.video_names``; zeros for a video without an
         alignment, p_end adds up to 1 otherwise.  Paths that spell the same class sequence share its mass as they share its
         segmentations.  One emission launch, then the forward and the backward launches.  SmmError when a NaN reached the DP."""
-        if pc.batch is not None and pc.batch.no_eos:
-            raise ValueError("transcript_node_posteriors_packed: add_eos=False is not supported")
-        graphs = _checked_graphs(graphs, len(pc.video_names), 'allow', list(pc.video_names), 'transcript_node_posteriors_packed')
-        batch, x, cons, endpen, g, inv_var = self._packed_stage(pc, 'transcript_node_posteriors_packed')
-        group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
-        local = self._local_graphs(graphs, g[5].cpu().numpy(), batch.n_states, group)
-        r = _emit(batch, x, cons, endpen, g, inv_var)
-        out = ops.align_graph_logz(batch, r['elp'], r['trans'], r['init'], r['len'], local, endpen=endpen)
-        grads = ops.align_graph_logz_bwd(batch, r['elp'], r['trans'], r['init'], r['len'], local, out['logz'], endpen=endpen,
-                                         ws=out['ws'], staged=out['_staged'], want_node_prob=True, want_end_prob=True)
-        _check_transcript_logz(out['logz'], None, 'transcript_node_posteriors_packed', allow_none=True)
+        r, sup = self._supervised_packed(pc, 'transcript_node_posteriors_packed', graphs, graphs=True, ambiguous='allow')
+        grads = _transcript_posteriors(r, sup, 'transcript_node_posteriors_packed', want_node_prob=True, want_end_prob=True)
         return [p.cpu().numpy() for p in grads['node_prob']], [p.cpu().numpy() for p in grads['end_prob']]
 
     # ------------------------------------------------------------------ samples of the graph posterior (smm_align_graph_sample_f64)
@@ -1467,17 +1424,11 @@ class SemiMarkovModule(nn.Module):
         list of per-video int32 device tensors n_samples x M_i, 1 for the nodes of the sampled path.  A video none of whose
         paths can be laid over it gives rows of -1, log_prob NaN and no used node.  ValueError for a wrong number of graphs,
         n_samples < 1 or add_eos=False; SmmError when a NaN reached the DP.  No autograd."""
-        if not add_eos:
-            raise ValueError("sample_alignments: add_eos=False is not supported")
         if int(n_samples) < 1:
             raise ValueError("sample_alignments: n_samples must be positive, got %d" % int(n_samples))
-        graphs = _checked_graphs(graphs, len(lengths), 'allow', None, 'sample_alignments')
-        self._require_device(features, 'sample_alignments')
-        batch, x, cons, endpen, tab, g1 = self._stage_padded(
-            features, lengths, self._check_valid_classes(valid_classes_per_instance), additional_allowed_ends_per_instance,
-            constraints, check_no_eos=False)
-        local = self._local_graphs(graphs, g1[5].cpu().numpy(), batch.n_states, np.zeros(batch.b, np.int64))
-        return _sample_alignments(_emit(batch, x, cons, endpen, g1, tab['inv_var']), local, n_samples, seed, want_spans=True)
+        r, sup = self._supervised_padded('sample_alignments', features, lengths, valid_classes_per_instance, add_eos,
+                                         additional_allowed_ends_per_instance, constraints, graphs, graphs=True, ambiguous='allow')
+        return _sample_alignments(r, sup, n_samples, seed, want_spans=True)
 
     @torch.no_grad()
     def sample_alignments_packed(self, pc, graphs, n_samples, seed=0):
@@ -1486,17 +1437,10 @@ class SemiMarkovModule(nn.Module):
         log_prob, used): device int64 n_samples x total_frames (global class ids on the packed frame axis, -1 on frames no
         video covers and on videos without an alignment), fp64 n_samples x n_videos and the per-video flags of the sampled
         paths' nodes."""
-        if getattr(pc, 'batch', None) is not None and pc.batch.no_eos:
-            raise ValueError("sample_alignments_packed: add_eos=False is not supported")
         if int(n_samples) < 1:
             raise ValueError("sample_alignments_packed: n_samples must be positive, got %d" % int(n_samples))
-        graphs = _checked_graphs(graphs, len(pc.video_names), 'allow', list(pc.video_names), 'sample_alignments_packed')
-        batch, x, cons, endpen, g, inv_var = self._packed_stage(pc, 'sample_alignments_packed')
-        if batch.no_eos:                                           # (a corpus this call prepared)
-            raise ValueError("sample_alignments_packed: add_eos=False is not supported")
-        group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
-        local = self._local_graphs(graphs, g[5].cpu().numpy(), batch.n_states, group)
-        return _sample_alignments(_emit(batch, x, cons, endpen, g, inv_var), local, n_samples, seed, want_spans=False)
+        r, sup = self._supervised_packed(pc, 'sample_alignments_packed', graphs, graphs=True, ambiguous='allow')
+        return _sample_alignments(r, sup, n_samples, seed, want_spans=False)
 
     # ------------------------------------------------------------------ packed multi-task decode
     def stacked_tables(self, pc, differentiable=False):

@@ -8,13 +8,18 @@ No GPU: ``semimarkov_modules.ops`` is replaced by a recording stand-in whose lau
 each filled with a serial number, so the arguments of a later call show which earlier output they consumed.  Everything else
 of ``ops`` stays real (``Batch``, ``TablesMeta``, ``_lib``, ``workspace``; ``Batch.workspace_bytes`` is a host call into the
 library).  The committed table was made from the module in front of the refactor that gave the padded staging, the one-group
-stack and each posterior operation one statement; tests/test_module_trace_host.py holds every later module to it.
+stack and each posterior operation one statement; the rows of the transcript family (alignment with optional entries and to a
+graph, the three transcript likelihoods with their backward passes, the graph sampler) were made from ``ops.py``,
+``semimarkov_modules.py`` and ``semimarkov.py`` exactly as they stood in front of the refactor that gave that family one
+statement of its supervision, its autograd function and its staging.  tests/test_module_trace_host.py holds every later module
+to it.
 
 What a call keeps: the launcher's name; every argument under its parameter name, after binding to the real launcher's
 signature (a default left out and the same value spelled out are one call); a ``Batch`` as its fields and ``shape.flags``;
 a tensor as dtype, shape, strides, device type and a digest of its bytes (floating values rounded to 8 decimals first: the
-last bit of an exp or a log differs between CPUs); a uint8 tensor -- a workspace -- as its index by first appearance within
-the entry point.  The entry point's return value (and the parameters' gradients after a backward) are kept the same way.
+last bit of an exp or a log differs between CPUs); a uint8 tensor -- a workspace, or the staged flags of a transcript -- as its
+index by first appearance within the entry point; an ``ops.TranscriptGraph`` as its classes, edges, start and end flags and
+candidate indices.  The entry point's return value (and the parameters' gradients after a backward) are kept the same way.
 The table stores the launcher names of each case and an 8-digit digest per call.
 """
 import hashlib
@@ -35,7 +40,9 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 LAUNCHERS = ('emission', 'emission_bwd', 'decode', 'viterbi', 'logz', 'logz_bwd', 'sample', 'entropy', 'entropy_bwd', 'kl',
-             'kl_bwd', 'kbest', 'mbr', 'align', 'check_decoded', '_err_copy', 'pinned_labels')
+             'kl_bwd', 'kbest', 'mbr', 'align', 'check_decoded', '_err_copy', 'pinned_labels', 'align_optional', 'align_graph',
+             'align_logz', 'align_logz_ex', 'align_logz_bwd', 'align_opt_logz', 'align_opt_logz_bwd', 'align_graph_logz',
+             'align_graph_logz_bwd', 'align_graph_sample')
 BATCH_FIELDS = ('b', 'd', 'n_groups', 'c_max', 'k_rows', 't_max', 'total_frames', 'lengths', 'frame_offset', 'group', 'kp',
                 'n_states')
 
@@ -87,6 +94,8 @@ class Recorder:
             return {'dict': {str(k): self.rec(e) for k, e in v.items()}}
         if isinstance(v, torch.device):
             return str(v)
+        if isinstance(v, real.TranscriptGraph):
+            return {'TranscriptGraph': {k: getattr(v, k).tolist() for k in ('ids', 'pred', 'start', 'end', 'end_candidate')}}
         if type(v).__name__ == 'PackedCorpus':
             return {'PackedCorpus': {k: self.rec(getattr(v, k, None)) for k in
                                      ('tables', 'n_states', 'c_max', 'k_rows', 'kp', 'endpen', 'cons', 'batch')}}
@@ -100,7 +109,7 @@ class Recorder:
 
     def _new(self, shape, dtype=torch.float64):
         self._serial += 1
-        return torch.full(tuple(int(s) for s in shape), self._serial, dtype=dtype)
+        return torch.full(tuple(int(s) for s in shape), self._serial % 251 if dtype == torch.uint8 else self._serial, dtype=dtype)
 
     def _err(self):
         return self._new((8,), torch.int32)
@@ -188,6 +197,97 @@ class Recorder:
         spans, labels, best, n_segs = self._paths(a['batch'], a['want_spans'], a['want_labels'])
         return dict(spans=spans, labels=labels, best=best, n_segs=n_segs, _err=self._err(), _keep=())
 
+    # ---------------------------------------------------------------- the transcript family
+    def _entries(self, supervision):
+        """Transcript entries / graph nodes per video; ``supervision`` may be the (ids, offsets) pair of ``align_logz_ex``."""
+        if isinstance(supervision, tuple) and len(supervision) == 2 and torch.is_tensor(supervision[0]):
+            return np.diff(supervision[1]).tolist()
+        return [len(s) if isinstance(s, self._real.TranscriptGraph) else int(np.asarray(s).size) for s in supervision]
+
+    def _staged(self, kind, n, given=None):
+        """What a launcher keeps of its supervision on the device: chain (ids,), optional (ids, flags), graph (ids, masks,
+        flags); ``given``: the caller's ``staged``, handed on as it came."""
+        if given is not None:
+            return given
+        i32, u8 = torch.int32, torch.uint8
+        return {'chain': lambda: (self._new((n,), i32),), 'optional': lambda: (self._new((n,), i32), self._new((n,), u8)),
+                'graph': lambda: (self._new((n,), i32), self._new((n * 8,), i32), self._new((n,), u8))}[kind]()
+
+    def _own_ws(self, given):
+        return given if given is not None else torch.zeros(16, dtype=torch.uint8)
+
+    def _per_video(self, t, sizes, dim=0):
+        return list(torch.split(t, [int(n) for n in sizes], dim=dim))
+
+    def _align_like(self, name, kind, args, kwargs):
+        a = self._note(name, args, kwargs)
+        sizes = self._entries(a['graphs'] if kind == 'graph' else a['transcripts'])
+        spans, labels, best, n_segs = self._paths(a['batch'], a['want_spans'], a['want_labels'])
+        used = self._per_video(self._new((sum(sizes),), torch.int32), sizes) if a['want_used'] else None
+        return dict(spans=spans, labels=labels, best=best, n_segs=n_segs, used=used, _err=self._err(),
+                    _staged=self._staged(kind, sum(sizes), a['staged']), _keep=(self._own_ws(a['ws']),))
+
+    def align_optional(self, *args, **kwargs):
+        return self._align_like('align_optional', 'optional', args, kwargs)
+
+    def align_graph(self, *args, **kwargs):
+        return self._align_like('align_graph', 'graph', args, kwargs)
+
+    def align_logz(self, *args, **kwargs):
+        return self._new((self._note('align_logz', args, kwargs)['batch'].b,))
+
+    def align_logz_ex(self, *args, **kwargs):
+        a = self._note('align_logz_ex', args, kwargs)
+        sizes = self._entries(a['transcripts'])
+        off = np.zeros(len(sizes) + 1, np.int64)
+        np.cumsum(sizes, out=off[1:])
+        return dict(logz=self._new((a['batch'].b,)), ws=self._own_ws(a['ws']),
+                    transcript=(self._staged('chain', sum(sizes))[0], off), _err=self._err())
+
+    def _logz_like(self, name, kind, args, kwargs):
+        a = self._note(name, args, kwargs)
+        n = sum(self._entries(a['graphs'] if kind == 'graph' else a['transcripts']))
+        ws = self._own_ws(a['ws'])
+        out = dict(logz=self._new((a['batch'].b,)), ws=ws, _staged=self._staged(kind, n, a['staged']), _err=self._err())
+        if kind == 'graph':
+            out['_keep'] = (ws,)
+        return out
+
+    def align_opt_logz(self, *args, **kwargs):
+        return self._logz_like('align_opt_logz', 'optional', args, kwargs)
+
+    def align_graph_logz(self, *args, **kwargs):
+        return self._logz_like('align_graph_logz', 'graph', args, kwargs)
+
+    def align_logz_bwd(self, *args, **kwargs):
+        a = self._note('align_logz_bwd', args, kwargs)
+        return self._like(a['elp'], a['trans'], a['init'], a['len_scores'])
+
+    def _logz_bwd_like(self, name, kind, wanted, args, kwargs):
+        a = self._note(name, args, kwargs)
+        sizes = self._entries(a['graphs'] if kind == 'graph' else a['transcripts'])
+        g = self._like(a['elp'], a['trans'], a['init'], a['len_scores'])
+        for want, key in wanted:
+            if a[want]:
+                g[key] = self._per_video(self._new((sum(sizes),)), sizes)
+        g['_keep'] = self._staged(kind, sum(sizes), a['staged'])
+        return g
+
+    def align_opt_logz_bwd(self, *args, **kwargs):
+        return self._logz_bwd_like('align_opt_logz_bwd', 'optional', (('want_entry_prob', 'entry_prob'),), args, kwargs)
+
+    def align_graph_logz_bwd(self, *args, **kwargs):
+        return self._logz_bwd_like('align_graph_logz_bwd', 'graph', (('want_node_prob', 'node_prob'), ('want_end_prob', 'end_prob')),
+                                   args, kwargs)
+
+    def align_graph_sample(self, *args, **kwargs):
+        a = self._note('align_graph_sample', args, kwargs)
+        n, sizes = int(a['n_samples']), self._entries(a['graphs'])
+        spans, labels, logp, n_segs = self._paths(a['batch'], a['want_spans'], a['want_labels'], (n,))
+        used = self._per_video(self._new((n, sum(sizes)), torch.int32), sizes, dim=1) if a['want_used'] else None
+        return dict(spans=spans, labels=labels, logp=logp, n_segs=n_segs, used=used, _err=self._err(),
+                    _staged=self._staged('graph', sum(sizes), a['staged']), _keep=(self._own_ws(a['ws']),))
+
     def check_decoded(self, *args, **kwargs):
         self._note('check_decoded', args, kwargs)
 
@@ -266,10 +366,20 @@ def padded_inputs(vc, cons, addl):
     spans[0, 0], spans[0, 3], spans[0, 5] = ids_list[0], ids_list[1], ids_list[-1]
     spans[1, 0], spans[1, 2] = ids_list[1], ids_list[-1]
     spans[2, 0], spans[2, 1] = ids_list[0], ids_list[-1]
+    a, b, d = ids_list[0], ids_list[1], ids_list[-1]
     return types.SimpleNamespace(
         x=x, lengths=torch.tensor(LENGTHS), vcpi=[ids] * B if vc else None, cons=cons1 if cons else None,
         cons2=cons2 if cons else None, addl=[{1}, set(), {0}] if addl else None, spans=spans,
-        transcripts=[[ids_list[0], ids_list[1], ids_list[-1]], [ids_list[1], ids_list[-1]], [ids_list[0], ids_list[-1]]])
+        transcripts=[[a, b, d], [b, d], [a, d]], optional=[[0, 1, 0], torch.tensor([1, 0]), [False, False]],
+        graphs=lambda ops: _graphs(ops, a, b, d, 2))
+
+
+def _graphs(ops, a, b, d, other):
+    """A candidate trie, a transcript with an optional entry and a chain, none ambiguous.  ``other``: a class of one candidate
+    of the trie -- with ``SUBSET`` as the valid classes, or past the classes of a packed video's task, it is no valid class of
+    the video (local id -1)."""
+    G = ops.TranscriptGraph
+    return [G.from_candidates([[a, b, d], [a, d], [a, b, d], [other, d]]), G.from_optional([b, a, d], [0, 1, 0]), G.chain([a, d])]
 
 
 def _backward(value, *modules):
@@ -305,6 +415,20 @@ def padded_entry_points():
     ep['viterbi_kbest'] = (all_opts, lambda m, o, i, eos: m.viterbi_kbest(i.x, i.lengths, i.vcpi, 3, eos, i.addl, i.cons))
     ep['mbr_decode'] = (all_opts, lambda m, o, i, eos: m.mbr_decode(*std(i, eos)))
     ep['align'] = (('vc', 'cons', 'addl'), lambda m, o, i, eos: m.align(i.x, i.lengths, i.vcpi, i.transcripts, True, i.addl, i.cons))
+    from action_segmentation_amd import ops
+    sup = ('vc', 'cons', 'addl')                 # (the transcript family refuses add_eos=False)
+    tail = lambda i: (True, i.addl, i.cons)
+    ep['align.optional'] = (sup, lambda m, o, i, eos: m.align(i.x, i.lengths, i.vcpi, i.transcripts, *tail(i), optional=i.optional))
+    ep['align_graph'] = (sup, lambda m, o, i, eos: m.align_graph(i.x, i.lengths, i.vcpi, i.graphs(ops), *tail(i)))
+    for tag, opt in (('', lambda i: None), ('.optional', lambda i: i.optional)):
+        tlp = lambda m, o, i, eos, opt=opt: m.transcript_log_partition(i.x, i.lengths, i.vcpi, i.transcripts, *tail(i),
+                                                                       optional=opt(i))
+        ep['transcript_log_partition' + tag] = (sup, tlp)
+        ep['transcript_log_partition%s.grad' % tag] = (sup, lambda m, o, i, eos, tlp=tlp: _backward(tlp(m, o, i, eos), m))
+    tglp = lambda m, o, i, eos: m.transcript_graph_log_partition(i.x, i.lengths, i.vcpi, i.graphs(ops), *tail(i))
+    ep['transcript_graph_log_partition'] = (sup, tglp)
+    ep['transcript_graph_log_partition.grad'] = (sup, lambda m, o, i, eos: _backward(tglp(m, o, i, eos), m))
+    ep['sample_alignments'] = (sup, lambda m, o, i, eos: m.sample_alignments(i.x, i.lengths, i.vcpi, i.graphs(ops), 2, 5, *tail(i)))
     ep['log_partition'] = (all_opts, lambda m, o, i, eos: m.log_partition(i.x, i.lengths, checked(m, i), i.addl, i.cons,
                                                                          no_eos=not eos))
     ep['log_partition.grad'] = (all_opts, lambda m, o, i, eos: _backward(
@@ -373,7 +497,60 @@ def _kl_packed_keeps_pc(m, o, pc, name):
     return {'value': v, 'pc_kept': all(a is b for a, b in zip(before, (pc.batch, pc.tables, pc.endpen)))}
 
 
+def _optional(m, pc):
+    return [[0, 1, 0]] * len(pc.group)
+
+
+def _packed_graphs(m, pc):
+    """``_graphs`` over the corpus, turn by turn; the class no video of the task has is one past its valid classes, or past
+    every class of the model."""
+    from action_segmentation_amd import ops
+    out = []
+    for v, (g, t) in enumerate(zip(pc.group, _transcripts(m, pc))):
+        vc = pc.groups[g]['valid_classes']
+        valid = set(range(m.n_classes)) if vc is None else {int(c) for c in vc}
+        other = min(c for c in range(m.n_classes + 2) if c not in valid and c != m.n_classes)
+        out.append(_graphs(ops, t[0], t[1], t[1], other)[v % 3])
+    return out
+
+
+def _transcript_packed_entry_points():
+    """The packed entry points of the transcript family, on a prepared corpus as ``align_packed`` above (all but one read
+    ``pc.batch`` before they prepare the corpus)."""
+    ep = {}
+    pre = lambda m, pc: m.prepare_packed(pc)
+    ep['align_packed.optional'] = lambda m, o, pc: m.align_packed(pre(m, pc), _transcripts(m, pc), optional=_optional(m, pc))
+    ep['align_graph_packed'] = lambda m, o, pc: m.align_graph_packed(pre(m, pc), _packed_graphs(m, pc))
+    for tag, opt in (('', lambda m, pc: None), ('.optional', _optional)):
+        tlp = lambda m, o, pc, opt=opt: m.transcript_log_partition_packed(pre(m, pc), _transcripts(m, pc), optional=opt(m, pc))
+        ep['transcript_log_partition_packed' + tag] = tlp
+        ep['transcript_log_partition_packed%s.grad' % tag] = lambda m, o, pc, tlp=tlp: _backward(tlp(m, o, pc), m)
+        for ctag, cond in (('', False), ('.conditional', True)):
+            ep['transcript_scores_packed%s%s' % (tag, ctag)] = lambda m, o, pc, opt=opt, cond=cond: m.transcript_scores_packed(
+                pre(m, pc), _transcripts(m, pc), conditional=cond, optional=opt(m, pc))
+    ep['transcript_entry_posteriors_packed'] = lambda m, o, pc: m.transcript_entry_posteriors_packed(
+        pre(m, pc), _transcripts(m, pc), _optional(m, pc))
+    tglp = lambda m, o, pc: m.transcript_graph_log_partition_packed(pre(m, pc), _packed_graphs(m, pc))
+    ep['transcript_graph_log_partition_packed'] = tglp
+    ep['transcript_graph_log_partition_packed.grad'] = lambda m, o, pc: _backward(tglp(m, o, pc), m)
+    for ctag, cond in (('', False), ('.conditional', True)):
+        ep['transcript_graph_scores_packed' + ctag] = lambda m, o, pc, cond=cond: m.transcript_graph_scores_packed(
+            pre(m, pc), _packed_graphs(m, pc), conditional=cond)
+    ep['transcript_node_posteriors_packed'] = lambda m, o, pc: m.transcript_node_posteriors_packed(pre(m, pc), _packed_graphs(m, pc))
+    ep['sample_alignments_packed'] = lambda m, o, pc: m.sample_alignments_packed(pre(m, pc), _packed_graphs(m, pc), 2, 5)
+    return ep
+
+
 def packed_entry_points():
+    ep = {}
+    for name, fn in _core_packed_entry_points().items():
+        ep[name] = fn
+        if name == 'align_packed':                      # (the rest of its family follows it)
+            ep.update(_transcript_packed_entry_points())
+    return ep
+
+
+def _core_packed_entry_points():
     return {
         'prepare_packed': lambda m, o, pc: m.prepare_packed(pc),
         'decode_packed.spans': lambda m, o, pc: m.decode_packed(pc, want_spans=True),

@@ -161,3 +161,35 @@ def test_label_lease_pool_follows_the_last_reference(monkeypatch):
     assert padded.numel() == 80 and int(padded.min()) == -1 and int(padded.max()) == -1
     bigger = ops.lease_host_labels(B(1000), dev)                  # a free buffer that is too small is replaced, not added
     assert bigger.numel() == 1000 and len(ops._label_leases[0]) <= ops.LABEL_LEASES
+
+
+def _model_trace_generator():
+    import importlib.util
+    import os
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_golden_model_trace.py")
+    spec = importlib.util.spec_from_file_location("make_golden_model_trace", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_transcript_methods_call_the_module_as_the_golden_trace():
+    """tests/golden/model_transcript_trace.json: what every transcript-supervised method of the model hands to its module's
+    packed entry points -- which videos' transcripts, flags and candidate tries, in which order -- and what it makes of their
+    answers, on recording fakes whose values are hashes of their arguments.  ``align_candidates`` is held to its result and
+    the number of its launches over candidate lists with duplicates, with a duplicate behind a split, and with more tries for
+    one video than for another.  A case that differs: ``python tests/golden/make_golden_model_trace.py --show CASE``."""
+    import json
+    gen = _model_trace_generator()
+    with open(gen.OUT) as f:
+        table = json.load(f)
+    cases = gen.cases()
+    assert [r["case"] for r in table] == [cid for cid, _, _ in cases]
+    methods = {cid.split("|")[0] for cid, _, _ in cases}
+    assert methods == {"align", "align_candidates", "candidate_log_likelihood", "candidate_posteriors", "sample_alignments",
+                       "sample_candidates", "transcript_log_likelihood", "transcript_entry_posteriors"}
+    for want, (cid, fn, whole) in zip(table, cases):
+        got = dict(gen.trace(fn, whole)[0], case=cid)
+        assert got == want, cid
+    split = {r["case"]: r for r in table}["align_candidates|split"]
+    assert len(split["entries"]) >= 3 and split["result"][1] == {"v_a": 1, "v_b": 0, "v_c": 0}   # (each one a duplicated candidate)
