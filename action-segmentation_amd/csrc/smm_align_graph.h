@@ -1,6 +1,8 @@
 // smm_align_graph.h -- what the transcript-graph kernels share (smm_align_graph.hip: the best alignment over the paths of a
-// graph; smm_align_graph_logz.hip: the sum over them): the structure in LDS, the path lengths, the cells of a column that lie
-// on a complete alignment, the test of the tables the structure reads, and the compaction of a ballot into a list.
+// graph; smm_align_graph_logz.hip: the sum over them; smm_align_graph_entropy.hip: the entropy of their posterior): the
+// structure in LDS, the path lengths, the cells of a column that lie
+// on a complete alignment, the test of the tables the structure reads, the compaction of a ballot into a list, and the block
+// sum of the posterior kernels (smm_align_graph_logz.hip, smm_align_graph_entropy.hip).
 // Include after smm_align_tile.h.
 #pragma once
 
@@ -163,4 +165,17 @@ __device__ __forceinline__ void graph_compact(bool is, int lo, int hi, int *s_wc
         uhi = s_whi[w] > uhi ? s_whi[w] : uhi;
     }
     slot = before + graph_rank(ballot, lane);
+}
+
+// the sum of x over the workgroup, in every thread: a butterfly per wave, the waves in order
+__device__ __forceinline__ double graph_block_sum(double x, double *s_red, int tid)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_xor(x, off);
+    __syncthreads();                                           // the readers of the sum before this one
+    if ((tid & 63) == 0) s_red[tid >> 6] = x;
+    __syncthreads();
+    double s = 0.0;
+    for (int w = 0; w < SMM_ALIGN_THREADS / 64; ++w) s = s + s_red[w];
+    return s;
 }

@@ -44,19 +44,6 @@
 #define SMM_GRAPH_U 4                                            // positions per thread and round when h is formed
 #define SMM_AGL_RNG 5                                            // ints per column (smm_align_opt_logz.hip: SMM_AOL_RNG)
 
-// the sum of x over the workgroup, in every thread: a butterfly per wave, the waves in order
-__device__ __forceinline__ double agl_block_sum(double x, double *s_red, int tid)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_xor(x, off);
-    __syncthreads();                                           // the readers of the sum before this one
-    if ((tid & 63) == 0) s_red[tid >> 6] = x;
-    __syncthreads();
-    double s = 0.0;
-    for (int w = 0; w < SMM_ALIGN_THREADS / 64; ++w) s = s + s_red[w];
-    return s;
-}
-
 __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_logz_fwd_kernel(SmmAlignLogzArgs a)
 {
     __shared__ double s_h[SMM_ALIGN_HS];
@@ -345,7 +332,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_logz_bwd_ke
                     if (n >= s_slo[t] && n <= s_shi[t]) x = x + exp((g + ((s_tr[i] - cu) + bhcol[(size_t)t * T1 + n])) - lz);
                 }
             }
-            const double tot = agl_block_sum(x, s_red, tid);
+            const double tot = graph_block_sum(x, s_red, tid);
             if (tid == 0) tpart[(size_t)cc * cm + c] += tot;
             i0 = i1;
         }
@@ -355,7 +342,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_logz_bwd_ke
         if (p_used || p_end) {
             double x = 0.0;
             for (int n = elo + tid; n <= ehi; n += SMM_ALIGN_THREADS) x = x + exp((gm[n] + (qm[n] - cumc[n])) - lz);
-            const double pu = agl_block_sum(x, s_red, tid);
+            const double pu = graph_block_sum(x, s_red, tid);
             if (tid == 0) {
                 if (p_used) p_used[m] = pu;
                 if (p_end) p_end[m] = (endm && ehi == T) ? exp((gm[T] + (qm[T] - cumc[T])) - lz) : 0.0;
@@ -395,8 +382,13 @@ void smm_launch_align_graph_logz_fwd(const SmmAlignLogzArgs &a, hipStream_t stre
     hipLaunchKernelGGL(smm_align_graph_logz_fwd_kernel, dim3((unsigned)a.b), dim3(SMM_ALIGN_THREADS), 0, stream, a);
 }
 
-void smm_launch_align_graph_logz_bwd(const SmmAlignLogzArgs &a, hipStream_t stream)
+void smm_launch_align_graph_logz_bwd_columns(const SmmAlignLogzArgs &a, hipStream_t stream)
 {
     hipLaunchKernelGGL(smm_align_graph_logz_bwd_kernel, dim3((unsigned)a.b), dim3(SMM_ALIGN_THREADS), 0, stream, a);
+}
+
+void smm_launch_align_graph_logz_bwd(const SmmAlignLogzArgs &a, hipStream_t stream)
+{
+    smm_launch_align_graph_logz_bwd_columns(a, stream);
     smm_launch_align_opt_logz_tail(a, stream);                 // g_elp, the videos' parts of g_len, the sums over the videos
 }

@@ -2452,6 +2452,30 @@ extern "C" int smm_align_graph_sample_f64(const smm_shape *shape, const int64_t 
     return SMM_OK;
 }
 
+// the entropy of the graph posterior (smm_align_graph_entropy.hip): the backward call's staging and arguments without its
+// outputs, its first kernel for the q and bh columns -- not the g_elp / g_len / reduce tail --, then the entropy kernel
+extern "C" int smm_align_graph_entropy_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                           const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                           const double *elp, const double *trans, const double *init, const double *len_scores,
+                                           const double *endpen, const int32_t *node_class, const uint32_t *pred_mask,
+                                           const uint8_t *node_flags, const int64_t *node_offset_host, const double *logz_g,
+                                           double *h_out, double *h_parts, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!pred_mask || !node_flags || !h_out) return SMM_ERR_ARG;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    SmmAlignEntropyArgs a{};
+    const int rc = align_logz_prepare(ALIGN_GRAPH_LOGZ, shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host,
+                                      elp, trans, init, len_scores, endpen, node_class, node_offset_host, logz_g, workspace,
+                                      workspace_bytes, hs, &a.g);
+    if (rc != SMM_OK) return rc;
+    a.g.pred_mask = pred_mask; a.g.node_flags = node_flags;
+    a.h_out = h_out; a.h_parts = h_parts;
+    smm_launch_align_graph_logz_bwd_columns(a.g, hs);
+    smm_launch_align_graph_entropy(a, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ dense boundary
 struct DenseLayout {
     size_t o_len, o_alpha, o_beta, o_bp_from, o_bp_k, o_rmsg, total;

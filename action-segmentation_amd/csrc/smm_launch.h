@@ -293,6 +293,18 @@ void smm_launch_align_opt_logz_tail(const SmmAlignLogzArgs &a, hipStream_t strea
 // ranges (3 M doubles), then h | gam | q | bh, each [M][T+1]; its parts as smm_align_opt_logz's
 void smm_launch_align_graph_logz_fwd(const SmmAlignLogzArgs &a, hipStream_t stream);
 void smm_launch_align_graph_logz_bwd(const SmmAlignLogzArgs &a, hipStream_t stream);
+// ... its first kernel alone: the q and bh columns, the videos' parts of g_trans and g_init and, where asked for, p_used / p_end
+void smm_launch_align_graph_logz_bwd_columns(const SmmAlignLogzArgs &a, hipStream_t stream);
+
+// the entropy of the transcript-graph posterior (smm_align_graph_entropy.hip): after smm_launch_align_graph_logz_fwd and
+// smm_launch_align_graph_logz_bwd_columns on the same workspace -- it reads cum, the h, gam, q and bh columns and the columns'
+// ranges, and writes the error word only
+struct SmmAlignEntropyArgs {
+    SmmAlignLogzArgs g;        // the forward launch's arguments (logz: read; the backward call's fields: unused)
+    double *h_out;             // [b]
+    double *h_parts;           // [b][3]: end node, span, predecessor; or null
+};
+void smm_launch_align_graph_entropy(const SmmAlignEntropyArgs &a, hipStream_t stream);
 
 // alignments drawn from the transcript-graph posterior (smm_align_graph_sample.hip): after smm_launch_align_graph_logz_fwd on
 // the same workspace -- it reads cum, the h and gam columns and the columns' ranges, and writes the error word only

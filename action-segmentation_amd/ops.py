@@ -1183,6 +1183,32 @@ def align_graph_sample(batch, elp, trans, init, len_scores, graphs, logz_g, n_sa
                 _err=_err_copy(batch, ws), _staged=sup.dev, _keep=(ws,))
 
 
+def align_graph_entropy(batch, elp, trans, init, len_scores, graphs, logz_g, endpen=None, ws=None, staged=None, want_parts=False):
+    """The exact entropy of the transcript-graph posterior (smm_align_graph_entropy_f64): per video H = -sum p log p in nats
+    over the ALIGNMENTS of the video to its ``TranscriptGraph`` -- the distribution ``align_graph_sample`` draws from, whose
+    normaliser ``align_graph_logz`` returns.  Must follow ``align_graph_logz`` for the same batch, tables and graphs with the
+    same workspace ``ws`` on the same stream (``ws`` and ``staged``: its ``ws`` and ``_staged`` entries); ``logz_g`` = its
+    output.  ``align_graph_logz_bwd`` and ``align_graph_sample`` may run before or after it: neither's results change.
+    -> dict(entropy fp64 [b], parts fp64 [b, 3] (with ``want_parts``: the entropy of the end node -- for a trie of the
+    posterior over the candidates --, of the segments' starts, and of the predecessors; they add up to ``entropy``) or None,
+    _err, _staged, _keep).  A video without an alignment (log Z_g = -inf) gets NaN.  The values are not differentiable."""
+    lib = _lib.load()
+    if ws is None:
+        raise ValueError("align_graph_entropy: pass the workspace the align_graph_logz call wrote")
+    f64 = torch.float64
+    dev = elp.device
+    sup = _supervision('graph', 'likelihood', 'align_graph_entropy', batch, dev, graphs, None, staged)
+    if ws.numel() < sup.need:
+        raise ValueError("align_graph_entropy: pass the workspace the align_graph_logz call wrote")
+    tables = _tables(elp, trans, init, len_scores, endpen)
+    entropy = torch.empty(batch.b, dtype=f64, device=dev)
+    parts = torch.empty((batch.b, 3), dtype=f64, device=dev) if want_parts else None
+    _lib.check(lib.smm_align_graph_entropy_f64(
+        *batch.head(), *tables, *sup.args(), _dev(logz_g, f64, 'logz_g'), _dev(entropy, f64, 'entropy'), _dev(parts, f64, 'parts'),
+        *_ws_args(ws), _stream()))
+    return dict(entropy=entropy, parts=parts, _err=_err_copy(batch, ws), _staged=sup.dev, _keep=(ws,))
+
+
 def transcript_is_ambiguous(ids, optional):
     """Host only: True when two different subsets of the optional entries of this transcript give the same non-empty class
     sequence -- ``align_opt_logz`` then counts the segmentations with that class sequence once per subset.  Exact: over the

@@ -568,13 +568,7 @@ class SemiMarkovModel(object):
         from . import ops
         if int(n_samples) < 1:
             raise ValueError("sample_candidates: n_samples must be positive, got %d" % int(n_samples))
-        for name, cands in candidates_by_video.items():
-            if not cands:
-                raise ValueError("sample_candidates: no candidates for video %r" % (name,))
-            nodes = ops.TranscriptGraph.trie_nodes(cands)
-            if nodes > ops.MAX_TRANSCRIPT:
-                raise ValueError("sample_candidates: the trie of the candidates of video %r has %d nodes (at most %d)"
-                                 % (name, nodes, ops.MAX_TRANSCRIPT))
+        self._one_trie_each(candidates_by_video, 'sample_candidates')
         self.model.eval()
         pc = self.prepare(data, shard=shard)
         if pc.n_videos == 0:
@@ -588,6 +582,58 @@ class SemiMarkovModel(object):
             last = u.shape[1] - 1 - np.argmax(u[:, ::-1], axis=1)
             chosen[name] = np.where(u.any(axis=1), g.end_candidate[last], -1).astype(np.int64)
         return self._labels_by_video(pc, labels), chosen
+
+    def alignment_entropy(self, data, transcripts_by_video, shard=None, *, optional_by_video=None, optional_classes=None):
+        """``{video: float}``: the exact entropy, in nats, of the posterior ``sample_alignments`` draws from -- how sure the
+        model is of where the boundaries of the video's transcript lie and, with optional entries, of which are kept
+        (``align``'s conventions for ``transcripts_by_video``, ``optional_by_video`` and ``optional_classes``).  0 when one
+        alignment has all the mass; NaN where the transcript cannot be laid over the video.  Ranks weakly labelled videos for
+        annotation and selects pseudo-labels for ``fit_supervised``.  One emission launch, the forward launch and the entropy
+        launch on the packed corpus (``SemiMarkovModule.alignment_entropy_packed``)."""
+        from . import ops
+        self._one_kind_of_flags(optional_by_video, optional_classes, 'alignment_entropy')
+        self.model.eval()
+        pc = self.prepare(data, shard=shard)
+        if pc.n_videos == 0:
+            return {}
+        transcripts = self._per_video(pc, transcripts_by_video, "alignment_entropy: no transcript for video %r")
+        optional = self._optional_flags(pc, transcripts, optional_by_video, optional_classes, 'alignment_entropy')
+        if optional is None:
+            graphs = [ops.TranscriptGraph.chain(t) for t in transcripts]
+        else:
+            graphs = [ops.TranscriptGraph.from_optional(t, f) for t, f in zip(transcripts, optional)]
+        return dict(zip(pc.video_names, self.model.alignment_entropy_packed(pc, graphs).tolist()))
+
+    def candidate_entropy(self, data, candidates_by_video, shard=None):
+        """``{video: dict(total=, candidates=, boundaries=)}`` in nats, given the frames and "the video follows one of these
+        transcripts" (``candidates_by_video`` as in ``align_candidates``): the entropy of the joint posterior over candidate and
+        boundaries, of ``candidate_posteriors`` -- is the candidate set decided? --, and their difference, the expected entropy
+        of the boundaries given the candidate.  NaN where no candidate can be laid over the video.  The candidates go to the
+        GPU as one prefix trie per video: ValueError for an empty set or one whose trie needs more than ``ops.MAX_TRANSCRIPT``
+        nodes, as in ``sample_candidates``."""
+        from . import ops
+        self._one_trie_each(candidates_by_video, 'candidate_entropy')
+        self.model.eval()
+        pc = self.prepare(data, shard=shard)
+        if pc.n_videos == 0:
+            return {}
+        graphs = [ops.TranscriptGraph.from_candidates(cands)
+                  for cands in self._per_video(pc, candidates_by_video, "candidate_entropy: no candidates for video %r")]
+        h, parts = self.model.alignment_entropy_packed(pc, graphs, want_parts=True)
+        return {name: dict(total=t, candidates=e, boundaries=t - e)
+                for name, t, e in zip(pc.video_names, h.tolist(), parts[:, 0].tolist())}
+
+    @staticmethod
+    def _one_trie_each(candidates_by_video, what):
+        """ValueError for a video without candidates or whose candidates' trie needs more than ``ops.MAX_TRANSCRIPT`` nodes."""
+        from . import ops
+        for name, cands in candidates_by_video.items():
+            if not cands:
+                raise ValueError("%s: no candidates for video %r" % (what, name))
+            nodes = ops.TranscriptGraph.trie_nodes(cands)
+            if nodes > ops.MAX_TRANSCRIPT:
+                raise ValueError("%s: the trie of the candidates of video %r has %d nodes (at most %d)"
+                                 % (what, name, nodes, ops.MAX_TRANSCRIPT))
 
     @staticmethod
     def _one_kind_of_flags(optional_by_video, optional_classes, what):

@@ -177,6 +177,17 @@ def _sample_alignments(r, sup, n_samples, seed, want_spans):
     return _paths(b, out, want_spans), out['logp'], out['used']
 
 
+def _alignment_entropy(r, sup, want_parts):
+    """The forward launch over the graphs of ``sup`` on a private workspace, then the entropy launch on it: (H, parts or None).
+    A video without an alignment is no error: NaN."""
+    b = r['batch']
+    z = _supervised(_LOGZ, r, sup)
+    out = ops.align_graph_entropy(b, r['elp'], r['trans'], r['init'], r['len'], sup[1][0], z['logz'], endpen=r['endpen'],
+                                  ws=z['ws'], staged=z['_staged'], want_parts=want_parts)
+    ops.check_decoded(b, out)
+    return out['entropy'], out['parts']
+
+
 def _transcript_scores(r, sup, conditional, what):
     """Without autograd: the likelihood of the supervision per video (``conditional``: minus log Z) as a CPU fp64 tensor."""
     z = _supervised(_SCORE, r, sup)
@@ -1441,6 +1452,34 @@ class SemiMarkovModule(nn.Module):
             raise ValueError("sample_alignments_packed: n_samples must be positive, got %d" % int(n_samples))
         r, sup = self._supervised_packed(pc, 'sample_alignments_packed', graphs, graphs=True, ambiguous='allow')
         return _sample_alignments(r, sup, n_samples, seed, want_spans=False)
+
+    # ------------------------------------------------------------------ entropy of the graph posterior (smm_align_graph_entropy_f64)
+    @torch.no_grad()
+    def alignment_entropy(self, features, lengths, valid_classes_per_instance, graphs, add_eos=True,
+                          additional_allowed_ends_per_instance=None, constraints=None, want_parts=False):
+        """The exact entropy, in nats, of the posterior ``sample_alignments`` draws from, p(alignment | x, "the class sequence
+        is a start -> end path of ``graphs[i]``"), for a zero-padded single-task batch (argument conventions of
+        ``align_graph``; graphs in GLOBAL class ids): one emission launch, the forward launch (smm_align_graph_logz_f64) and the
+        entropy launch (smm_align_graph_entropy_f64).  An alignment is a path and its boundaries: on an ambiguous graph two
+        paths that spell one class sequence are two alignments.
+
+        Returns fp64 b on the device, or with ``want_parts`` the pair (entropy, parts): parts fp64 b x 3, the entropy of the
+        end node (for a trie: of the posterior over the candidates), of the segments' starts and of the predecessors, which
+        add up to the entropy.  A video none of whose paths can be laid over it gives NaN.  ValueError for a wrong number of
+        graphs or add_eos=False; SmmError when a NaN reached the DP.  The result is NOT differentiable: no autograd."""
+        r, sup = self._supervised_padded('alignment_entropy', features, lengths, valid_classes_per_instance, add_eos,
+                                         additional_allowed_ends_per_instance, constraints, graphs, graphs=True, ambiguous='allow')
+        h, parts = _alignment_entropy(r, sup, want_parts)
+        return (h, parts) if want_parts else h
+
+    @torch.no_grad()
+    def alignment_entropy_packed(self, pc, graphs, want_parts=False):
+        """``alignment_entropy`` for a whole PackedCorpus: one emission launch, the forward launch and the entropy launch.
+        ``graphs``: one ``ops.TranscriptGraph`` in GLOBAL class ids per video, in the order of ``pc.video_names``.  Returns fp64
+        n_videos on the device, or with ``want_parts`` (entropy, parts fp64 n_videos x 3).  Not differentiable."""
+        r, sup = self._supervised_packed(pc, 'alignment_entropy_packed', graphs, graphs=True, ambiguous='allow')
+        h, parts = _alignment_entropy(r, sup, want_parts)
+        return (h, parts) if want_parts else h
 
     # ------------------------------------------------------------------ packed multi-task decode
     def stacked_tables(self, pc, differentiable=False):

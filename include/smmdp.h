@@ -39,6 +39,8 @@
  *   smm_align_graph_logz_bwd_f64   N transcripts" as a trie), its gradient and the node / end posteriors (the reference has none)
  *   smm_align_graph_sample_f64 <- ... and alignments drawn from that posterior: a path of the graph and its boundaries (pseudo-labels
  *                              for stochastic EM from transcripts, boundary uncertainty; the reference has none)
+ *   smm_align_graph_entropy_f64 <- ... and the exact entropy of that posterior: how sure the model is of the alignment, of the
+ *                              candidate and of the boundaries (the reference has none)
  *
  * The reference has no FFI: its boundary is the Python call SemiMarkovCRF(scores, lengths) on a dense
  * b x N x K x C x C tensor.  These entry points take the FACTORS of that tensor instead,
@@ -130,8 +132,8 @@ int smm_device_count(void);
 /* Bytes of device workspace any entry point below needs for this shape (lengths: host array [b]).
  * Returns 0 on invalid arguments.  The workspace is scratch: its contents are undefined after a call,
  * except between smm_logz_f64 and smm_logz_bwd_f64 / smm_sample_f64 / smm_entropy_f64 / smm_kl_f64, and between a transcript
- * likelihood call and the calls its comment names (smm_align_graph_logz_f64: smm_align_graph_logz_bwd_f64 and
- * smm_align_graph_sample_f64, in either order). */
+ * likelihood call and the calls its comment names (smm_align_graph_logz_f64: smm_align_graph_logz_bwd_f64,
+ * smm_align_graph_sample_f64 and smm_align_graph_entropy_f64, in any order). */
 size_t smm_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host);
 
 /* Byte offset, inside the workspace, of the int32 error word the kernels set.  1: a NaN / inf-inf reached the DP of
@@ -868,6 +870,49 @@ int smm_align_graph_sample_f64(const smm_shape *shape, const int64_t *lengths_ho
                                int32_t *n_segs_out /* dev [n_samples][b], nullable */,
                                int32_t *used_out   /* dev [n_samples][node_offset_host[b]], nullable */,
                                void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * The exact entropy of the transcript-graph posterior (csrc/smm_align_graph_entropy.hip): per video
+ * H = -sum_y p(y) log p(y) in nats over the ALIGNMENTS y of smm_align_graph_sample_f64's distribution -- "how sure is the model
+ * of this alignment?".  On an ambiguous graph two paths that spell one class sequence are two alignments, exactly as in log Z_g
+ * and in the sampler.  What smm_entropy_f64 is to smm_logz_f64.
+ * The chain rule of entropy over the sampler's decisions, in smm_align_graph_logz_f64's notation (h, gam, q[n][j] =
+ * cum[n][a_j] + bg[n][j], bh, closing_j, kw, and the ranges [lo_j, hi_j] of gam / q and [slo_j, shi_j] of h / bh the forward
+ * call records per column).  For a list of weights w, of which only the finite, in-range ones count:
+ *   Hloc(w) = log Z - A / Z,   Z = sum exp(w - max w),   A = sum exp(w - max w) (w - max w)        a single candidate: exactly 0
+ *   E[n][j] = exp(gam[n][j] + (q[n][j] - cum[n][a_j]) - logZ_g)                a segment of node j ends at n
+ *   S[s][j] = exp(h[s][j] + bh[s][j] - logZ_g)                                 a segment of node j starts at s
+ *   H_end   = Hloc( gam[T][j] + closing_j : end(j) )
+ *   H_span  = sum_j sum_{n in [lo_j, hi_j]}   E[n][j] Hloc( h[n-k][j] + len[k][a_j] : k = 1..min(kw, n) )
+ *   H_pred  = sum_j sum_{s in [slo_j, shi_j]} S[s][j] Hloc( gam[s][i] + trans[a_j][a_i] : i in pred(j) )
+ *   h_out   = (H_end + H_span) + H_pred;   h_parts (nullable) = H_end, H_span, H_pred per video; every term >= 0
+ * H_end is the entropy of p_end: for a prefix trie the entropy of the posterior over the candidates, and h_out - H_end the
+ * expected boundary entropy given the candidate.  A chain has H_end = H_pred = 0.0 exactly, and H = 0.0 when T = M.
+ * Call order: the call must follow smm_align_graph_logz_f64 for the same batch, tables and graphs on the same workspace and
+ * stream; logz_g is that call's output.  It launches smm_align_graph_logz_bwd_f64's first kernel itself for the q and bh
+ * columns (without p_used / p_end, and without the g_elp / g_len / reduce kernels behind it: nothing of a gradient is
+ * computed that the entropy does not read), then one kernel of its own, one workgroup per video.  It may run before, after or
+ * between smm_align_graph_logz_bwd_f64 and smm_align_graph_sample_f64 calls: it writes what the backward call's first kernel
+ * writes, which is a function of the forward call's columns alone, so a later backward call's outputs and the sampler's draws
+ * do not change by a bit.  Staging is the backward call's and clears the error word; there is no size query of its own
+ * (smm_align_graph_logz_workspace_bytes).
+ * Numerics: the span sums as smm_align_logz_f64's second sweep (fp32 exponentials of fp64 differences, fp64 sums) with a second
+ * accumulator; the sums over end nodes and predecessors exponentiate in fp64; E, S and every total in fp64.  Every sum is taken
+ * in a fixed order, without atomics: two calls on the same inputs give the same bits.
+ *   - A video whose logz_g is -inf has no alignment: h_out and its parts are NaN; the error word stays clear.
+ *   - A NaN logz_g gives the same and sets the error word.  Videos beside such a video are not affected.
+ * Enqueued on `stream` only; never synchronises; a video is never split.
+ * Refusals: SMM_ERR_ARG for a NULL required pointer (logz_g and h_out included), non-monotone offsets or a video without nodes;
+ * SMM_ERR_UNSUPPORTED for SMM_SHAPE_NO_EOS, more than SMM_MAX_TRANSCRIPT nodes in a video, c_max or k_rows beyond the compiled
+ * kernels; SMM_ERR_WORKSPACE below smm_align_graph_logz_workspace_bytes -- all before anything is staged.
+ */
+int smm_align_graph_entropy_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                const double *elp, const double *trans, const double *init, const double *len_scores,
+                                const double *endpen /* nullable */, const int32_t *node_class, const uint32_t *pred_mask,
+                                const uint8_t *node_flags, const int64_t *node_offset_host, const double *logz_g /* dev [b] */,
+                                double *h_out /* dev [b] */, double *h_parts /* dev [b][3]: end, span, pred; nullable */,
+                                void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Factor tables of every parameter group from the model parameters (training steps), and their chain rule.
