@@ -142,6 +142,99 @@ def test_edit_distance_long_sequences():
         assert got['a']['total_levenshtein'][0] == wex['levenshtein'][0]
 
 
+def pack_task(gt, pred, width):
+    """One task's videos on the packed frame axis: (pred cuda [F], gt cuda [F, width] -1 padded, lengths, offsets)."""
+    lengths = [len(p) for p in pred]
+    offsets = [int(x) for x in np.concatenate([[0], np.cumsum(lengths)[:-1]])]
+    gm = np.full((sum(lengths), width), -1, dtype=np.int64)
+    r = 0
+    for frames in gt:
+        for f in frames:
+            gm[r, :len(f)] = f
+            r += 1
+    pr = np.concatenate([np.asarray(p, dtype=np.int64) for p in pred])
+    return torch.from_numpy(pr).cuda(), torch.from_numpy(gm).cuda(), lengths, offsets
+
+
+def permuted(rng, ids, pred):
+    """Predictions in a permuted id space of the same task (what the Hungarian assignment has to undo)."""
+    perm = dict(zip(ids, rng.permutation(ids).tolist()))
+    return [[perm[x] for x in v] for v in pred]
+
+
+@pytest.mark.parametrize('optimal', [False, True])
+@pytest.mark.parametrize('width', [1, 2])
+def test_confusion_kernel_over_several_chunks(optimal, width):
+    """smm_eval_confusion_kernel takes 4096 frames per workgroup: videos of exactly one chunk, one frame more, two chunks
+    and a frame, and a short one in one launch -> grid.y = 3, blockIdx.y >= 1 adds into the table, and 6 of the 12
+    (video, y) workgroups return at once."""
+    from action_segmentation_amd.evaluation import LabelSpace, evaluate_labels
+    rng = np.random.default_rng(40 + width + 10 * optimal)
+    ids = list(range(7))
+    bkg = ids[0::2]
+    gt, pred = [], []
+    for t in (4096, 4097, 8193, 100):
+        g, p = random_task(rng, ids, n_videos=1, t_lo=t, t_hi=t, width=width, mean_len=25, flip=0.3)
+        gt += g
+        pred += p
+    if optimal:
+        pred = permuted(rng, ids, pred)
+    pred_d, gt_d, lengths, offsets = pack_task(gt, pred, width)
+    got = evaluate_labels(pred_d, gt_d, lengths, offsets, ['a'] * 4, LabelSpace({'a': ids}, bkg), optimal, seed=9)
+    want, _ = eval_ref.task_counters(gt, pred, bkg, ids, optimal, seed=9)
+    assert_stats(got['a'], want)
+
+
+def runs_with_exact_count(rng, t, n_runs, n_ids):
+    """t frames in exactly n_runs runs of near-equal length; neighbouring runs carry different labels."""
+    assert 1 <= n_runs <= t
+    bounds = [r * t // n_runs for r in range(n_runs + 1)]
+    out, lab = [], int(rng.integers(0, n_ids))
+    for r in range(n_runs):
+        out += [lab] * (bounds[r + 1] - bounds[r])
+        lab = (lab + int(rng.integers(1, n_ids))) % n_ids
+    return out
+
+
+@pytest.mark.parametrize('n,m', [(1, 130), (130, 1), (63, 64), (64, 63), (65, 128), (129, 64), (128, 128)])
+def test_edit_distance_segment_counts_at_the_wave_boundaries(n, m):
+    """The Levenshtein wave (64 lanes over the m + 1 cells of a row, n rows): more predicted than ground-truth segments
+    and the other way round, m + 1 at and next to a multiple of 64 (m = 63, 64, 128), one row, one column."""
+    from action_segmentation_amd.evaluation import CN, LabelSpace, evaluate_labels
+    rng = np.random.default_rng(1000 * n + m)
+    ids = list(range(6))
+    t = 2 * max(n, m) + 1
+    gt, pred = runs_with_exact_count(rng, t, n, 6), runs_with_exact_count(rng, t, m, 6)
+    pred_d, gt_d, lengths, offsets = pack_task([[[x] for x in gt]], [pred], 1)
+    got, ex = evaluate_labels(pred_d, gt_d, lengths, offsets, ['a'], LabelSpace({'a': ids}, [0]), False, return_extras=True)
+    want, wex = eval_ref.task_counters([[[x] for x in gt]], [pred], [0], ids, False)
+    per_video = ex['a']['per_video']
+    assert per_video.shape[0] == 1
+    assert int(per_video[0, CN['segs_gt']]) == n
+    assert int(per_video[0, CN['segs_pred']]) == m
+    assert int(per_video[0, CN['levenshtein']]) == int(wex['levenshtein'][0])
+    assert int(wex['max_segments'][0]) == max(n, m)
+    assert_stats(got['a'], want)
+
+
+@pytest.mark.parametrize('optimal', [False, True])
+def test_task_with_the_most_labels_the_kernels_take(optimal):
+    """63 labels (SMM_EVAL_MAX_LABELS): the 64 x 64 LDS histogram and the 128-entry per-label tables at their limit."""
+    from action_segmentation_amd import _lib
+    from action_segmentation_amd.evaluation import LabelSpace, evaluate_labels
+    rng = np.random.default_rng(63 + optimal)
+    ids = list(range(63))
+    assert len(ids) == _lib.EVAL_MAX_LABELS
+    bkg = ids[0::2]
+    gt, pred = random_task(rng, ids, n_videos=3, t_lo=200, t_hi=400, width=1, mean_len=3, flip=0.3)
+    if optimal:
+        pred = permuted(rng, ids, pred)
+    pred_d, gt_d, lengths, offsets = pack_task(gt, pred, 1)
+    got = evaluate_labels(pred_d, gt_d, lengths, offsets, ['a'] * 3, LabelSpace({'a': ids}, bkg), optimal, seed=9)
+    want, _ = eval_ref.task_counters(gt, pred, bkg, ids, optimal, seed=9)
+    assert_stats(got['a'], want)
+
+
 def test_labels_outside_the_task_are_reported():
     from action_segmentation_amd.evaluation import LabelSpace, evaluate_labels
     space = LabelSpace({'a': [0, 1, 2], 'b': [3, 4]}, [0, 3])

@@ -40,15 +40,9 @@ def test_log_hsmm_known_answer_like_the_reference_test():
     assert torch.allclose(sequence[torch.arange(0, b), lengths - 1], torch.full((1,), C).long())
 
 
-@pytest.mark.parametrize('seed', range(4))
-def test_dense_kernel_matches_oracle(seed):
+def check_dense_kernel(edge, lengths, integer):
     from action_segmentation_amd.struct import SemiMarkovCRF
-    g = torch.Generator().manual_seed(seed)
-    b, n, k, c = 3, 30 + seed, 6 + seed, 5
-    integer = seed % 2 == 0                                         # exact ties every other seed
-    edge = (torch.randint(-4, 1, (b, n - 1, k, c, c), generator=g).float() if integer
-            else torch.randn(b, n - 1, k, c, c, generator=g))
-    lengths = torch.tensor([n, n - 3, n - 1])
+    _, _, k, c, _ = edge.shape
     dist = SemiMarkovCRF(edge.cuda(), lengths=lengths)
     v, segs = O.viterbi_backpointers(edge.double(), lengths)
     parts = dist.argmax
@@ -65,17 +59,43 @@ def test_dense_kernel_matches_oracle(seed):
     np.testing.assert_allclose(dist.log_prob(gold.cuda()).cpu().numpy(), (v - z).numpy(), rtol=1e-4, atol=1e-4)
 
 
+def random_edge(g, shape, integer):
+    """Dense potentials; ``integer``: a lattice of small integers, where ties order the back-pointers."""
+    return torch.randint(-4, 1, shape, generator=g).float() if integer else torch.randn(*shape, generator=g)
+
+
 @pytest.mark.parametrize('seed', range(4))
-def test_dense_partition_gradient_and_log_marginals(seed):
+def test_dense_kernel_matches_oracle(seed):
+    g = torch.Generator().manual_seed(seed)
+    b, n, k, c = 3, 30 + seed, 6 + seed, 5
+    integer = seed % 2 == 0                                         # exact ties every other seed
+    edge = random_edge(g, (b, n - 1, k, c, c), integer)
+    check_dense_kernel(edge, torch.tensor([n, n - 3, n - 1]), integer)
+
+
+# Shapes beyond one trip of the kernels' strided loops (csrc/smm_dense.hip launches min(1024, K C rounded up to 64) threads):
+#   (2, 80, 70, 16)  1120 (k, to) pairs on 1024 threads: 96 threads make a second trip of the alpha loop; the backward kernel
+#                    has 64 slices of 16 `from`; K - 1 = 69 is above n for the first 69 positions and below it after them
+#                    (and above the whole second instance but for its last 11 positions)
+#   (2, 12, 3, 130)  C above two waves: 390 pairs on 448 threads, beta on 130 of them; 3 backward slices, 58 idle threads
+WIDE = [((2, 80, 70, 16), [80, 41]), ((2, 12, 3, 130), [12, 7])]
+WIDE_IDS = ['k70_c16', 'k3_c130']
+
+
+@pytest.mark.parametrize('seed', range(2))
+@pytest.mark.parametrize('shape,lengths', WIDE, ids=WIDE_IDS)
+def test_dense_kernel_matches_oracle_beyond_one_trip(shape, lengths, seed):
+    b, n, k, c = shape
+    integer = seed % 2 == 0
+    edge = random_edge(torch.Generator().manual_seed(10 + seed), (b, n - 1, k, c, c), integer)
+    check_dense_kernel(edge, torch.tensor(lengths), integer)
+
+
+def check_dense_gradient(edge, lengths, w):
     """Autograd through the dense boundary (reference: loss.backward() through torch_struct's LogSemiring DP,
     semimarkov.py:286 / semimarkov_modules.py:652-657) against autograd through the oracle DP, fp64."""
     from action_segmentation_amd.struct import SemiMarkovCRF, SemiMarkov, LogSemiring
-    g = torch.Generator().manual_seed(100 + seed)
-    b, n, k, c = 3, 24 + 5 * seed, 4 + 3 * seed, 3 + 2 * seed
-    edge = torch.randn(b, n - 1, k, c, c, generator=g)
-    if seed == 3:
-        edge[:, :, :, 1, :] = BIG_NEG                               # a forbidden label
-    lengths = torch.tensor([n, n - 4, 2])
+    b, _, k, c, _ = edge.shape
     z, want = O.marginals(edge.double(), lengths, O.LogSemiring)
     got = SemiMarkov(LogSemiring).marginals(edge.cuda(), lengths=lengths)
     assert got.shape == edge.shape and got.dtype == edge.dtype
@@ -83,7 +103,6 @@ def test_dense_partition_gradient_and_log_marginals(seed):
     # every position but the last is covered by exactly one span: expected span mass per instance = 1 at n = 0
     np.testing.assert_allclose(got[:, 0].flatten(1).sum(1).cpu().numpy(), np.ones(b), rtol=1e-5)
     # weighted upstream gradient + chain rule through a parameter
-    w = torch.tensor([0.5, -2.0, 3.0])
     scale = torch.tensor(0.7, requires_grad=True)
     e_dev = edge.cuda().requires_grad_(True)
     dist = SemiMarkovCRF(e_dev * scale.cuda(), lengths=lengths)
@@ -101,6 +120,54 @@ def test_dense_partition_gradient_and_log_marginals(seed):
     e2 = edge.cuda().requires_grad_(True)
     SemiMarkovCRF(e2, lengths=lengths).log_prob(gold.cuda()).sum().backward()
     np.testing.assert_allclose(e2.grad.cpu().numpy(), (gold.double() - want).numpy(), rtol=5e-5, atol=1e-6)
+
+
+@pytest.mark.parametrize('seed', range(4))
+def test_dense_partition_gradient_and_log_marginals(seed):
+    g = torch.Generator().manual_seed(100 + seed)
+    b, n, k, c = 3, 24 + 5 * seed, 4 + 3 * seed, 3 + 2 * seed
+    edge = torch.randn(b, n - 1, k, c, c, generator=g)
+    if seed == 3:
+        edge[:, :, :, 1, :] = BIG_NEG                               # a forbidden label
+    check_dense_gradient(edge, torch.tensor([n, n - 4, 2]), torch.tensor([0.5, -2.0, 3.0]))
+
+
+@pytest.mark.parametrize('seed', range(2))
+@pytest.mark.parametrize('shape,lengths', WIDE, ids=WIDE_IDS)
+def test_dense_partition_gradient_beyond_one_trip(shape, lengths, seed):
+    b, n, k, c = shape
+    edge = random_edge(torch.Generator().manual_seed(110 + seed), (b, n - 1, k, c, c), seed % 2 == 0)
+    check_dense_gradient(edge, torch.tensor(lengths), torch.tensor([0.5, -2.0]))
+
+
+def test_dense_instance_of_length_one():
+    """lengths = [n, 1]: no edge belongs to the second instance.  Its value is `plus` over beta[0] = one (log C under the Log
+    semiring, 0 under Max), its span row holds position 0 only, and it has no posterior mass."""
+    from action_segmentation_amd.struct import SemiMarkovCRF, SemiMarkov, LogSemiring, _dense_dp
+    b, n, k, c = 2, 6, 4, 3
+    edge = torch.randn(b, n - 1, k, c, c, generator=torch.Generator().manual_seed(5))
+    lengths = torch.tensor([n, 1])
+    dist = SemiMarkovCRF(edge.cuda(), lengths=lengths)
+    v, segs = O.viterbi_backpointers(edge.double(), lengths)
+    z, want = O.marginals(edge.double(), lengths, O.LogSemiring)
+    assert segs[1] == [] and float(v[1]) == 0.0 and abs(float(z[1]) - np.log(c)) < 1e-15
+    assert float(want[1].abs().sum()) == 0.0
+    np.testing.assert_allclose(dist.max.cpu().numpy(), v.numpy(), rtol=1e-6)
+    np.testing.assert_allclose(dist.partition.cpu().numpy(), z.numpy(), rtol=1e-6)
+    assert float(dist.max[1]) == 0.0
+    _, spans = _dense_dp(edge.cuda(), lengths, False, True)
+    spans = spans.cpu()
+    np.testing.assert_array_equal(spans[0].numpy(), O.spans_from_segments(segs, n)[0].numpy())
+    assert int(spans[1, 0]) == 0                                    # torch.max order: the smallest final label
+    assert spans[1, 1:].tolist() == [-1] * (n - 1)
+    parts = dist.argmax
+    assert float(parts[1].abs().sum()) == 0.0
+    got = SemiMarkov(LogSemiring).marginals(edge.cuda(), lengths=lengths)
+    np.testing.assert_allclose(got.cpu().numpy(), want.numpy(), rtol=2e-5, atol=1e-7)
+    assert float(got[1].abs().sum()) == 0.0
+    e = edge.cuda().requires_grad_(True)
+    SemiMarkovCRF(e, lengths=lengths).partition.sum().backward()
+    assert float(e.grad[1].abs().sum()) == 0.0
 
 
 def test_dense_marginals_reference_shape():
