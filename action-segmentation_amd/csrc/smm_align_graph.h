@@ -1,5 +1,6 @@
 // smm_align_graph.h -- what the transcript-graph kernels share (smm_align_graph.hip: the best alignment over the paths of a
-// graph; smm_align_graph_logz.hip: the sum over them; smm_align_graph_entropy.hip: the entropy of their posterior): the
+// graph; smm_align_graph_logz.hip: the sum over them; smm_align_graph_entropy.hip: the entropy of their posterior;
+// smm_align_graph_kl.hip: the KL between two such posteriors): the
 // structure in LDS, the path lengths, the cells of a column that lie
 // on a complete alignment, the test of the tables the structure reads, the compaction of a ballot into a list, and the block
 // sum of the posterior kernels (smm_align_graph_logz.hip, smm_align_graph_entropy.hip).
@@ -47,6 +48,33 @@ __device__ __forceinline__ void graph_load(const Args &a, const AlignVideo &v, i
         }
         if (!ok) s_flag[0] = 1;
     }
+}
+
+// ... without the masks in LDS (smm_align_graph_kl.hip, whose two sides' tiles leave no 8 KB for them): the same tests, classes
+// and flags -> LDS; a column then reads its own mask row from global memory (graph_edge_row).
+template <class Args>
+__device__ __forceinline__ void graph_load_nodes(const Args &a, const AlignVideo &v, int *s_a, int *s_fl, int *s_flag, int tid)
+{
+    if (tid < v.M) {
+        const int id = a.transcript[v.t0 + tid];
+        bool ok = id >= 0 && id < v.C;
+        s_a[tid] = ok ? id : 0;
+        s_fl[tid] = a.node_flags[v.t0 + tid] & 3;
+        const uint32_t *mask = a.pred_mask + (size_t)(v.t0 + tid) * SMM_GRAPH_WORDS;
+#pragma unroll
+        for (int w = 0; w < SMM_GRAPH_WORDS; ++w) {
+            const int below = tid - 32 * w;
+            const uint32_t allowed = below <= 0 ? 0u : below >= 32 ? 0xffffffffu : (1u << below) - 1u;
+            ok &= (mask[w] & ~allowed) == 0;
+        }
+        if (!ok) s_flag[0] = 1;
+    }
+}
+
+// node j < SMM_MAX_TRANSCRIPT may directly precede the node whose mask row this is (8 words in global memory)
+__device__ __forceinline__ bool graph_edge_row(const uint32_t *row, int j)
+{
+    return (row[j >> 5] >> (j & 31)) & 1u;
 }
 
 // Path lengths (wave 0 calls it, tid < 64; serially in topological order; the fences order a lane's writes before the other

@@ -260,6 +260,31 @@ __device__ __forceinline__ void align_tiles(int lo, int hi, int slo, int shi, in
     }
 }
 
+// ... of two columns with the same ranges at once (smm_align_graph_kl.hip: the two sides of a comparison): the same tiles, the
+// same barriers, srcp -> s_hp and srcq -> s_hq; cells(n0, d_first, d_end, hp, hq).
+template <class SrcP, class SrcQ, class Cells>
+__device__ __forceinline__ void align_tiles2(int lo, int hi, int slo, int shi, int d_all, double *s_hp, double *s_hq, int tid,
+                                             SrcP srcp, SrcQ srcq, Cells cells)
+{
+    for (int tb = lo; tb <= hi; tb += SMM_ALIGN_P) {
+        const int x = tb - shi, y = tb + SMM_ALIGN_P - SMM_ALIGN_R - slo + 1;
+        const int y_up = (y + SMM_ALIGN_R - 1) / SMM_ALIGN_R * SMM_ALIGN_R;
+        const int d_end = y_up < d_all ? y_up : d_all;
+        const int d_first = x <= 0 ? -SMM_ALIGN_R : x / SMM_ALIGN_R * SMM_ALIGN_R;
+        const int i_first = SMM_ALIGN_OFF - (d_end - 1), i_last = SMM_ALIGN_OFF + SMM_ALIGN_P - SMM_ALIGN_R - d_first;
+        __syncthreads();                                       // the previous tile's readers; what the caller wrote for the sources
+        for (int i = i_first + tid; i <= i_last; i += SMM_ALIGN_THREADS) {
+            const int s = tb - SMM_ALIGN_OFF + i;
+            const bool in = s >= slo && s <= shi;
+            s_hp[i] = in ? srcp(s) : SMM_NEG_INF;
+            s_hq[i] = in ? srcq(s) : SMM_NEG_INF;
+        }
+        __syncthreads();
+        const int n0 = tb + tid * SMM_ALIGN_R;
+        if (n0 <= hi) cells(n0, d_first, d_end, s_hp + SMM_ALIGN_OFF + tid * SMM_ALIGN_R, s_hq + SMM_ALIGN_OFF + tid * SMM_ALIGN_R);
+    }
+}
+
 // The sweep of a thread's R cells over the distances: f(r, h[n0 - d] + len[d + r]) for every d in [d_first, d_end) and cell r.
 // One LDS read of h serves the R cells; the length scores slide through R registers, one broadcast read per step
 // (lw[(d + r) % R] = len[d + r]; d_first is a multiple of R).
@@ -277,6 +302,30 @@ __device__ __forceinline__ void align_sweep(int d_first, int d_end, const double
             lw[(j + SMM_ALIGN_R - 1) % SMM_ALIGN_R] = s_len[d + 2 * SMM_ALIGN_R - 1];
 #pragma unroll
             for (int r = 0; r < SMM_ALIGN_R; ++r) f(r, hv + lw[(j + r) % SMM_ALIGN_R]);
+        }
+    }
+}
+
+// ... of two columns at once (align_tiles2): f(r, hp[n0 - d] + lenp[d + r], hq[n0 - d] + lenq[d + r])
+template <class F>
+__device__ __forceinline__ void align_sweep2(int d_first, int d_end, const double *hp, const double *hq, const double *s_lenp,
+                                             const double *s_lenq, F f)
+{
+    double lp[SMM_ALIGN_R], lq[SMM_ALIGN_R];
+#pragma unroll
+    for (int q = 0; q < SMM_ALIGN_R - 1; ++q) {
+        lp[q] = s_lenp[d_first + q + SMM_ALIGN_R];
+        lq[q] = s_lenq[d_first + q + SMM_ALIGN_R];
+    }
+    for (int d0 = d_first; d0 < d_end; d0 += SMM_ALIGN_R) {
+#pragma unroll
+        for (int j = 0; j < SMM_ALIGN_R; ++j) {
+            const int d = d0 + j;
+            const double vp = hp[-d], vq = hq[-d];
+            lp[(j + SMM_ALIGN_R - 1) % SMM_ALIGN_R] = s_lenp[d + 2 * SMM_ALIGN_R - 1];
+            lq[(j + SMM_ALIGN_R - 1) % SMM_ALIGN_R] = s_lenq[d + 2 * SMM_ALIGN_R - 1];
+#pragma unroll
+            for (int r = 0; r < SMM_ALIGN_R; ++r) f(r, vp + lp[(j + r) % SMM_ALIGN_R], vq + lq[(j + r) % SMM_ALIGN_R]);
         }
     }
 }

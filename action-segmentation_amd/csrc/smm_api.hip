@@ -2476,6 +2476,41 @@ extern "C" int smm_align_graph_entropy_f64(const smm_shape *shape, const int64_t
     return SMM_OK;
 }
 
+// KL and cross-entropy of two graph posteriors (smm_align_graph_kl.hip): the entropy call's staging, arguments and first kernel
+// on p's workspace; q's workspace is only read -- its columns lie where the same layout puts p's, nothing is staged there
+extern "C" int smm_align_graph_kl_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                      const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                      const double *elp_p, const double *trans_p, const double *init_p, const double *len_scores_p,
+                                      const double *endpen_p, const double *logz_g_p, void *workspace_p, size_t workspace_p_bytes,
+                                      const double *trans_q, const double *len_scores_q, const double *endpen_q,
+                                      const double *logz_g_q, const void *workspace_q, size_t workspace_q_bytes,
+                                      const int32_t *node_class, const uint32_t *pred_mask, const uint8_t *node_flags,
+                                      const int64_t *node_offset_host, double *kl_out, double *xent_out, double *kl_parts,
+                                      void *stream)
+{
+    if (!pred_mask || !node_flags || !kl_out || !trans_q || !len_scores_q || !logz_g_q || !workspace_q) return SMM_ERR_ARG;
+    if (!shape_ok(shape) || !lengths_host || !frame_offset_host || !n_states_host || !node_offset_host) return SMM_ERR_ARG;
+    if (!elp_p || !trans_p || !init_p || !len_scores_p || !node_class || !logz_g_p || !workspace_p) return SMM_ERR_ARG;
+    AlignLayout lo;
+    int rc = align_layout(ALIGN_GRAPH_LOGZ, shape, lengths_host, node_offset_host, &lo);
+    if (rc != SMM_OK) return rc;
+    if (workspace_p_bytes < lo.total || workspace_q_bytes < lo.total) return SMM_ERR_WORKSPACE;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    SmmAlignKlArgs a{};
+    rc = align_logz_prepare(ALIGN_GRAPH_LOGZ, shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp_p,
+                            trans_p, init_p, len_scores_p, endpen_p, node_class, node_offset_host, logz_g_p, workspace_p,
+                            workspace_p_bytes, hs, &a.g);
+    if (rc != SMM_OK) return rc;
+    a.g.pred_mask = pred_mask; a.g.node_flags = node_flags;
+    a.trans_q = trans_q; a.len_q = len_scores_q; a.endpen_q = endpen_q; a.logz_q = logz_g_q;
+    a.cols_q = reinterpret_cast<const double *>(static_cast<const char *>(workspace_q) + lo.o_cols);
+    a.kl_out = kl_out; a.xent_out = xent_out; a.kl_parts = kl_parts;
+    smm_launch_align_graph_logz_bwd_columns(a.g, hs);
+    smm_launch_align_graph_kl(a, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ dense boundary
 struct DenseLayout {
     size_t o_len, o_alpha, o_beta, o_bp_from, o_bp_k, o_rmsg, total;

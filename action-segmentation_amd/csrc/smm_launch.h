@@ -306,6 +306,23 @@ struct SmmAlignEntropyArgs {
 };
 void smm_launch_align_graph_entropy(const SmmAlignEntropyArgs &a, hipStream_t stream);
 
+// KL(p || q) and the cross-entropy H(p, q) of two transcript-graph posteriors over the same videos and graphs
+// (smm_align_graph_kl.hip): after smm_launch_align_graph_logz_fwd per side and smm_launch_align_graph_logz_bwd_columns on p's
+// workspace -- of p's it reads what the entropy kernel reads, of q's the h and gam columns and the columns' ranges only, and it
+// writes p's error word only
+struct SmmAlignKlArgs {
+    SmmAlignLogzArgs g;        // p's forward launch's arguments (logz: read; the backward call's fields: unused)
+    const double *trans_q;     // [g][c_max][c_max]
+    const double *len_q;       // [g][k_rows][c_max]
+    const double *endpen_q;    // [b][c_max] or null
+    const double *logz_q;      // [b]
+    const double *cols_q;      // q's workspace at the offset of `cols` in p's: the same layout, so hoff serves both
+    double *kl_out;            // [b]
+    double *xent_out;          // [b] or null
+    double *kl_parts;          // [b][3]: end node, span, predecessor; or null
+};
+void smm_launch_align_graph_kl(const SmmAlignKlArgs &a, hipStream_t stream);
+
 // alignments drawn from the transcript-graph posterior (smm_align_graph_sample.hip): after smm_launch_align_graph_logz_fwd on
 // the same workspace -- it reads cum, the h and gam columns and the columns' ranges, and writes the error word only
 struct SmmAlignSampleArgs {

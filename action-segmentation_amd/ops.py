@@ -1209,6 +1209,41 @@ def align_graph_entropy(batch, elp, trans, init, len_scores, graphs, logz_g, end
     return dict(entropy=entropy, parts=parts, _err=_err_copy(batch, ws), _staged=sup.dev, _keep=(ws,))
 
 
+def align_graph_kl(batch, p, q, graphs, staged=None, want_cross_entropy=False, want_parts=False):
+    """The exact KL divergence KL(p || q) between two transcript-graph posteriors over the ALIGNMENTS of the same videos to the
+    same ``TranscriptGraph``s (smm_align_graph_kl_f64), in nats, and with ``want_cross_entropy`` H(p, q) = -sum p log q.
+    ``p`` = (elp, trans, init, len_scores, endpen or None, logz_g, ws) and ``q`` = (trans, len_scores, endpen or None, logz_g, ws):
+    each side's tables and the ``logz`` and ``ws`` entries of its own ``align_graph_logz`` call for this batch and these graphs,
+    both on the current stream.  q's workspace is only read (its elp and init entered through it); p's is used as
+    ``align_graph_entropy`` uses it, so p's backward, sampler and entropy results do not change.  ``staged``: either call's
+    ``_staged`` entry.  -> dict(kl fp64 [b], cross_entropy fp64 [b] or None, parts fp64 [b, 3] (with ``want_parts``: the KL of
+    the end node -- for a trie the KL between the posteriors over the candidates --, of the segments' starts, and of the
+    predecessors; they add up to ``kl``) or None, _err, _staged, _keep).  Bit-identical sides give exactly 0.  A video p cannot
+    align (log Z_g = -inf) gets NaN; one p can align and q cannot gets +inf, as does one where p puts mass on an alignment q
+    excludes.  The values are not differentiable."""
+    lib = _lib.load()
+    elp, trans, init, len_scores, endpen, logz_p, ws_p = p
+    trans_q, len_q, endpen_q, logz_q, ws_q = q
+    if ws_p is None or ws_q is None:
+        raise ValueError("align_graph_kl: pass the workspace the align_graph_logz call wrote")
+    f64 = torch.float64
+    dev = elp.device
+    sup = _supervision('graph', 'likelihood', 'align_graph_kl', batch, dev, graphs, None, staged)
+    if ws_p.numel() < sup.need or ws_q.numel() < sup.need:
+        raise ValueError("align_graph_kl: pass the workspace the align_graph_logz call wrote")
+    tables = _tables(elp, trans, init, len_scores, endpen)
+    node_class, pred_mask, node_flags, node_off = sup.args()
+    kl = torch.empty(batch.b, dtype=f64, device=dev)
+    xent = torch.empty(batch.b, dtype=f64, device=dev) if want_cross_entropy else None
+    parts = torch.empty((batch.b, 3), dtype=f64, device=dev) if want_parts else None
+    _lib.check(lib.smm_align_graph_kl_f64(
+        *batch.head(), *tables, _dev(logz_p, f64, 'logz_g'), *_ws_args(ws_p),
+        _dev(trans_q, f64, 'trans'), _dev(len_q, f64, 'len_scores'), _dev(endpen_q, f64, 'endpen'), _dev(logz_q, f64, 'logz_g'),
+        *_ws_args(ws_q), node_class, pred_mask, node_flags, node_off, _dev(kl, f64, 'kl'), _dev(xent, f64, 'cross_entropy'),
+        _dev(parts, f64, 'parts'), _stream()))
+    return dict(kl=kl, cross_entropy=xent, parts=parts, _err=_err_copy(batch, ws_p), _staged=sup.dev, _keep=(ws_p, ws_q))
+
+
 def transcript_is_ambiguous(ids, optional):
     """Host only: True when two different subsets of the optional entries of this transcript give the same non-empty class
     sequence -- ``align_opt_logz`` then counts the segmentations with that class sequence once per subset.  Exact: over the

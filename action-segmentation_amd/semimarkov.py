@@ -624,6 +624,54 @@ class SemiMarkovModel(object):
                 for name, t, e in zip(pc.video_names, h.tolist(), parts[:, 0].tolist())}
 
     @staticmethod
+    def _other_module(other, what):
+        if not isinstance(other, SemiMarkovModel):
+            raise TypeError("%s: other must be a SemiMarkovModel" % what)
+        other.model.eval()
+        return other.model
+
+    def alignment_kl(self, other, data, transcripts_by_video, shard=None, *, optional_by_video=None, optional_classes=None):
+        """``{video: float}``: the exact KL(p || q), in nats, between this model's posterior over the alignments of each video
+        to its transcript and ``other``'s (a SemiMarkovModel on the same lattice; ``alignment_entropy``'s conventions for the
+        transcripts and the optional entries): teacher against student, one EM epoch against the next -- it goes to 0 as
+        training converges and is exactly 0 against the model itself.  NaN where the transcript cannot be laid over the video,
+        +inf where ``other`` excludes an alignment this model does not.  Two emission launches, two forward launches and the KL
+        launch on the packed corpus (``SemiMarkovModule.alignment_kl_packed``)."""
+        from . import ops
+        self._one_kind_of_flags(optional_by_video, optional_classes, 'alignment_kl')
+        q = self._other_module(other, 'alignment_kl')
+        self.model.eval()
+        pc = self.prepare(data, shard=shard)
+        if pc.n_videos == 0:
+            return {}
+        transcripts = self._per_video(pc, transcripts_by_video, "alignment_kl: no transcript for video %r")
+        optional = self._optional_flags(pc, transcripts, optional_by_video, optional_classes, 'alignment_kl')
+        if optional is None:
+            graphs = [ops.TranscriptGraph.chain(t) for t in transcripts]
+        else:
+            graphs = [ops.TranscriptGraph.from_optional(t, f) for t, f in zip(transcripts, optional)]
+        return dict(zip(pc.video_names, self.model.alignment_kl_packed(q, pc, graphs).tolist()))
+
+    def candidate_kl(self, other, data, candidates_by_video, shard=None):
+        """``{video: dict(total=, candidates=, boundaries=)}`` in nats, given the frames and "the video follows one of these
+        transcripts" (``candidates_by_video`` as in ``candidate_entropy``): the KL between this model's and ``other``'s joint
+        posteriors over candidate and boundaries, the KL between their ``candidate_posteriors`` -- do the two models pick the
+        same transcript? --, and their difference, the expected KL of the boundaries given the candidate.  NaN where no
+        candidate can be laid over the video.  One prefix trie per video: ValueError as ``candidate_entropy``."""
+        from . import ops
+        self._one_trie_each(candidates_by_video, 'candidate_kl')
+        q = self._other_module(other, 'candidate_kl')
+        self.model.eval()
+        pc = self.prepare(data, shard=shard)
+        if pc.n_videos == 0:
+            return {}
+        graphs = [ops.TranscriptGraph.from_candidates(cands)
+                  for cands in self._per_video(pc, candidates_by_video, "candidate_kl: no candidates for video %r")]
+        kl, parts = self.model.alignment_kl_packed(q, pc, graphs, want_parts=True)
+        return {name: dict(total=t, candidates=e, boundaries=t - e)
+                for name, t, e in zip(pc.video_names, kl.tolist(), parts[:, 0].tolist())}
+
+    @staticmethod
     def _one_trie_each(candidates_by_video, what):
         """ValueError for a video without candidates or whose candidates' trie needs more than ``ops.MAX_TRANSCRIPT`` nodes."""
         from . import ops

@@ -188,6 +188,21 @@ def _alignment_entropy(r, sup, want_parts):
     return out['entropy'], out['parts']
 
 
+def _alignment_kl(r, q, sup, what, want_cross_entropy, want_parts):
+    """One forward launch per side over the graphs of ``sup``, each on a private workspace, then the KL launch on both
+    (smm_align_graph_kl_f64): (KL(p || q) or H(p, q), parts or None).  A video p cannot align is no error: NaN."""
+    b = r['batch']
+    SemiMarkovModule._check_same_batch(b, q['batch'], what)
+    zq = _supervised(_LOGZ, q, sup)
+    zp = _supervised(_LOGZ, r, sup, staged=zq['_staged'])
+    out = ops.align_graph_kl(b, (r['elp'], r['trans'], r['init'], r['len'], r['endpen'], zp['logz'], zp['ws']),
+                             (q['trans'], q['len'], q['endpen'], zq['logz'], zq['ws']), sup[1][0], staged=zp['_staged'],
+                             want_cross_entropy=want_cross_entropy, want_parts=want_parts)
+    ops.check_decoded(b, out)
+    ops.check_decoded(b, zq)                                   # (the KL launch leaves q's error word as q's forward launch set it)
+    return (out['cross_entropy'] if want_cross_entropy else out['kl']), out['parts']
+
+
 def _transcript_scores(r, sup, conditional, what):
     """Without autograd: the likelihood of the supervision per video (``conditional``: minus log Z) as a CPU fp64 tensor."""
     z = _supervised(_SCORE, r, sup)
@@ -1480,6 +1495,72 @@ class SemiMarkovModule(nn.Module):
         r, sup = self._supervised_packed(pc, 'alignment_entropy_packed', graphs, graphs=True, ambiguous='allow')
         h, parts = _alignment_entropy(r, sup, want_parts)
         return (h, parts) if want_parts else h
+
+    # ------------------------------------------------------------------ KL of two graph posteriors (smm_align_graph_kl_f64)
+    def _alignment_kl_padded(self, other, what, features, lengths, valid_classes_per_instance, graphs, add_eos,
+                             additional_allowed_ends_per_instance, constraints, other_constraints, want_cross_entropy, want_parts):
+        self._check_same_lattice(other, what)
+        q, _ = other._supervised_padded(what, features, lengths, valid_classes_per_instance, add_eos,
+                                        additional_allowed_ends_per_instance, other_constraints, graphs, graphs=True,
+                                        ambiguous='allow')
+        r, sup = self._supervised_padded(what, features, lengths, valid_classes_per_instance, add_eos,
+                                         additional_allowed_ends_per_instance, constraints, graphs, graphs=True, ambiguous='allow')
+        return _alignment_kl(r, q, sup, what, want_cross_entropy, want_parts)
+
+    def _alignment_kl_packed(self, other, pc, graphs, what, want_cross_entropy, want_parts):
+        self._check_same_lattice(other, what)
+        saved = dict(pc.__dict__)                                  # (q first, `pc` left prepared for `self`: as _kl_packed)
+        try:
+            q, _ = other._supervised_packed(pc, what, graphs, graphs=True, ambiguous='allow')
+        finally:
+            pc.__dict__.clear()
+            pc.__dict__.update(saved)
+        r, sup = self._supervised_packed(pc, what, graphs, graphs=True, ambiguous='allow')
+        return _alignment_kl(r, q, sup, what, want_cross_entropy, want_parts)
+
+    @torch.no_grad()
+    def alignment_kl(self, other, features, lengths, valid_classes_per_instance, graphs, add_eos=True,
+                     additional_allowed_ends_per_instance=None, constraints=None, other_constraints=None, want_parts=False):
+        """The exact KL(p || q), in nats, between two posteriors over the alignments of each video to ``graphs[i]`` (argument
+        conventions of ``alignment_entropy``; graphs in GLOBAL class ids): p is this module's under ``constraints``, q is
+        ``other``'s under ``other_constraints`` (``other`` may be ``self``); each side builds its tables, emissions and end
+        penalties from its own parameters.  Two emission launches, two forward launches (smm_align_graph_logz_f64), one KL
+        launch (smm_align_graph_kl_f64); the value keeps its relative accuracy as q -> p and is exactly 0 for the same inputs.
+
+        Returns fp64 b on the device, or with ``want_parts`` the pair (kl, parts): parts fp64 b x 3, the KL of the end node
+        (for a trie: between the two posteriors over the candidates), of the segments' starts and of the predecessors, which
+        add up to the KL.  NaN for a video p cannot align, +inf where q excludes an alignment p does not.  TypeError when
+        ``other`` is no SemiMarkovModule, ValueError when the lattices differ, for a wrong number of graphs or add_eos=False;
+        SmmError when a NaN reached the DP.  No autograd."""
+        kl, parts = self._alignment_kl_padded(other, 'alignment_kl', features, lengths, valid_classes_per_instance, graphs, add_eos,
+                                              additional_allowed_ends_per_instance, constraints, other_constraints, False,
+                                              want_parts)
+        return (kl, parts) if want_parts else kl
+
+    @torch.no_grad()
+    def alignment_cross_entropy(self, other, features, lengths, valid_classes_per_instance, graphs, add_eos=True,
+                                additional_allowed_ends_per_instance=None, constraints=None, other_constraints=None,
+                                want_parts=False):
+        """The exact cross-entropy H(p, q) = -sum p log q = H(p) + KL(p || q) of the same two posteriors, in nats: arguments,
+        launches and refusals as ``alignment_kl`` (the parts are the KL's); with ``other`` = ``self`` and the same constraints
+        it is ``alignment_entropy``'s value to that kernel's fp32 rounding."""
+        xe, parts = self._alignment_kl_padded(other, 'alignment_cross_entropy', features, lengths, valid_classes_per_instance,
+                                              graphs, add_eos, additional_allowed_ends_per_instance, constraints,
+                                              other_constraints, True, want_parts)
+        return (xe, parts) if want_parts else xe
+
+    @torch.no_grad()
+    def alignment_kl_packed(self, other, pc, graphs, want_parts=False):
+        """``alignment_kl`` for a whole PackedCorpus: fp64 n_videos on the device in the order of ``pc.video_names``, or with
+        ``want_parts`` (kl, parts fp64 n_videos x 3).  q's tables and end penalties are built on ``pc``'s layout; ``pc`` is left
+        prepared for ``self``."""
+        kl, parts = self._alignment_kl_packed(other, pc, graphs, 'alignment_kl_packed', False, want_parts)
+        return (kl, parts) if want_parts else kl
+
+    @torch.no_grad()
+    def alignment_cross_entropy_packed(self, other, pc, graphs):
+        """``alignment_cross_entropy`` for a whole PackedCorpus: fp64 n_videos on the device."""
+        return self._alignment_kl_packed(other, pc, graphs, 'alignment_cross_entropy_packed', True, False)[0]
 
     # ------------------------------------------------------------------ packed multi-task decode
     def stacked_tables(self, pc, differentiable=False):

@@ -41,6 +41,8 @@
  *                              for stochastic EM from transcripts, boundary uncertainty; the reference has none)
  *   smm_align_graph_entropy_f64 <- ... and the exact entropy of that posterior: how sure the model is of the alignment, of the
  *                              candidate and of the boundaries (the reference has none)
+ *   smm_align_graph_kl_f64    <- ... and the exact KL divergence and cross-entropy between two such posteriors over the same
+ *                              videos and graphs: teacher against student, one EM epoch against the next (the reference has none)
  *
  * The reference has no FFI: its boundary is the Python call SemiMarkovCRF(scores, lengths) on a dense
  * b x N x K x C x C tensor.  These entry points take the FACTORS of that tensor instead,
@@ -133,7 +135,7 @@ int smm_device_count(void);
  * Returns 0 on invalid arguments.  The workspace is scratch: its contents are undefined after a call,
  * except between smm_logz_f64 and smm_logz_bwd_f64 / smm_sample_f64 / smm_entropy_f64 / smm_kl_f64, and between a transcript
  * likelihood call and the calls its comment names (smm_align_graph_logz_f64: smm_align_graph_logz_bwd_f64,
- * smm_align_graph_sample_f64 and smm_align_graph_entropy_f64, in any order). */
+ * smm_align_graph_sample_f64, smm_align_graph_entropy_f64 and smm_align_graph_kl_f64, in any order). */
 size_t smm_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host);
 
 /* Byte offset, inside the workspace, of the int32 error word the kernels set.  1: a NaN / inf-inf reached the DP of
@@ -913,6 +915,61 @@ int smm_align_graph_entropy_f64(const smm_shape *shape, const int64_t *lengths_h
                                 const uint8_t *node_flags, const int64_t *node_offset_host, const double *logz_g /* dev [b] */,
                                 double *h_out /* dev [b] */, double *h_parts /* dev [b][3]: end, span, pred; nullable */,
                                 void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * The exact KL divergence and cross-entropy between two transcript-graph posteriors (csrc/smm_align_graph_kl.hip): per video
+ * KL(p || q) = sum_y p(y) log( p(y) / q(y) ) and H(p, q) = -sum_y p(y) log q(y) in nats over the ALIGNMENTS y of the video to
+ * its graph -- teacher against student, one EM epoch against the next, a model with narration constraints against one without.
+ * What smm_kl_f64 is to smm_entropy_f64.  Both sides share the videos, lengths, class sets, span limit and graphs; each has its
+ * own elp, tables and closing scores and the workspace of its own smm_align_graph_logz_f64 call.
+ * The chain rule of relative entropy over the sampler's decisions, in smm_align_graph_entropy_f64's notation.  For a decision
+ * with the candidates' weights w_p (p's columns and tables) and w_q (q's), m_. the largest finite weight of a side, and over
+ * the candidates with e_p = exp(w_p - m_p) > 0:
+ *   S_p = sum e_p,  S_q = sum exp(w_q - m_q) (every candidate: q's normaliser),  Y = sum e_p (w_q - w_p),  A_p = sum e_p (w_p - m_p)
+ *   KLloc  = (m_q - m_p) + log S_q - log S_p - Y / S_p   clamped at 0;      Hloc_p = log S_p - A_p / S_p
+ *   KL_end  = KLloc( gam[T][j] + closing_j : end(j) )
+ *   KL_span = sum_j sum_{n in [lo_j, hi_j]}   E[n][j] KLloc( h[n-k][j] + len[k][a_j] : k = 1..min(kw, n) )
+ *   KL_pred = sum_j sum_{s in [slo_j, shi_j]} S[s][j] KLloc( gam[s][i] + trans[a_j][a_i] : i in pred(j) )
+ *   kl_out   = (KL_end + KL_span) + KL_pred;    kl_parts (nullable) = KL_end, KL_span, KL_pred per video; every term >= 0
+ *   xent_out (nullable) = the same three sums of weight * (Hloc_p + KLloc)
+ * E and S are p's posteriors exactly as the entropy kernel forms them.  A candidate with e_p > 0 whose w_q is -inf makes KLloc
+ * +inf: an answer, not an error.  A candidate of p-weight 0 contributes nothing (never 0 * inf).  Both sides run the same
+ * operations: bit-identical sides give exactly 0.0 in every part.  For a prefix trie KL_end is the KL between the two
+ * posteriors over the candidates and kl_out - KL_end the expected KL of the boundaries given the candidate; a chain has
+ * KL_end = KL_pred = 0.0 exactly.  q needs no backward pass; its elp and init are never read (they enter through its h and gam
+ * columns only).
+ * Call order: one smm_align_graph_logz_f64 per side on the same stream first, each on its own workspace; logz_g_p / logz_g_q
+ * are their outputs.  The call stages p's workspace as the entropy call does (clearing its error word), launches
+ * smm_align_graph_logz_bwd_f64's first kernel on it for p's q and bh columns, then one kernel of its own, one workgroup per
+ * video.  q's workspace is ONLY READ: nothing is staged there and its error word is not touched.  Before any of q's columns
+ * is read, the five ints each forward call recorded per column are compared: they are a function of graph, T and span limit
+ * only, so a mismatch means that workspace_q belongs to other graphs -- that video gets NaN and the error word.  As the
+ * entropy call, it may run before, after or between p's backward, sampler and entropy calls without changing a bit of theirs.
+ * There is no size query of its own (smm_align_graph_logz_workspace_bytes, for either side).
+ * Numerics: EVERY exponential is fp64, on both sides, the span sums included: fp32 exponentials leave about 1e-7 in
+ * log S_q - log S_p, which is the whole value between two near-identical posteriors.  There is no fp32 path for Hloc_p, so
+ * H(p, p) equals smm_align_graph_entropy_f64's value only to that kernel's own fp32 rounding (1e-5 relative).  Every sum is
+ * taken in a fixed order, without atomics: two calls on the same inputs give the same bits.
+ *   logz_g_p = -inf                      KL, cross-entropy and parts NaN; the error word stays clear
+ *   logz_g_p or logz_g_q NaN             NaN; the error word (of p's workspace) is set
+ *   logz_g_q = -inf, logz_g_p finite     +inf (q's columns are not read); the error word stays clear
+ * Videos beside such a video are not affected.
+ * Enqueued on `stream` only; never synchronises; a video is never split.
+ * Refusals: SMM_ERR_ARG for a NULL required pointer (both logz_g, workspace_q and kl_out included), b = 0, non-monotone offsets
+ * or a video without nodes; SMM_ERR_UNSUPPORTED for SMM_SHAPE_NO_EOS, more than SMM_MAX_TRANSCRIPT nodes in a video, c_max or
+ * k_rows beyond the compiled kernels; SMM_ERR_WORKSPACE when either side is below smm_align_graph_logz_workspace_bytes -- all
+ * before anything is staged.
+ */
+int smm_align_graph_kl_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                           const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                           const double *elp_p, const double *trans_p, const double *init_p, const double *len_scores_p,
+                           const double *endpen_p /* nullable */, const double *logz_g_p /* dev [b] */,
+                           void *workspace_p, size_t workspace_p_bytes,
+                           const double *trans_q, const double *len_scores_q, const double *endpen_q /* nullable */,
+                           const double *logz_g_q /* dev [b] */, const void *workspace_q, size_t workspace_q_bytes,
+                           const int32_t *node_class, const uint32_t *pred_mask, const uint8_t *node_flags,
+                           const int64_t *node_offset_host, double *kl_out /* dev [b] */, double *xent_out /* dev [b], nullable */,
+                           double *kl_parts /* dev [b][3]: end, span, pred; nullable */, void *stream);
 
 /*
  * Factor tables of every parameter group from the model parameters (training steps), and their chain rule.
