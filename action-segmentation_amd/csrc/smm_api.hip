@@ -2511,6 +2511,124 @@ extern "C" int smm_align_graph_kl_f64(const smm_shape *shape, const int64_t *len
     return SMM_OK;
 }
 
+// gradients of the entropy, cross-entropy and KL of graph posteriors (smm_align_graph_entropy_bwd.hip).  The caller's scratch:
+// per video five [M][T+1] blocks, one part per video, q's log Z as the call uses it and V+ per video.  The kernels find a
+// video's five blocks from the workspace's column offsets (ALIGN_GRAPH_LOGZ above: 3 M + 4 M (T + 1) doubles per video), so
+// a change of that family's cell formula is a change of smm_align_graph_entropy_bwd.hip's agb_video
+static bool agbwd_layout(const smm_shape *s, const int64_t *lengths, const int64_t *noff, size_t *pv_base, size_t *total_doubles)
+{
+    AlignLayout lo;
+    if (align_layout(ALIGN_GRAPH_LOGZ, s, lengths, noff, &lo) != SMM_OK) return false;
+    size_t cells = 0;
+    for (int i = 0; i < s->b; ++i) cells += (size_t)(noff[i + 1] - noff[i]) * (size_t)(lengths[i] + 1);
+    *pv_base = 5 * cells;
+    *total_doubles = 5 * cells + (size_t)s->b * (smm_align_graph_entropy_bwd_part_doubles(s->c_max, s->k_rows) + 2);
+    return true;
+}
+
+extern "C" size_t smm_align_graph_entropy_bwd_scratch_bytes(const smm_shape *shape, const int64_t *lengths_host,
+                                                            const int64_t *node_offset_host)
+{
+    size_t pv = 0, tot = 0;
+    if (!agbwd_layout(shape, lengths_host, node_offset_host, &pv, &tot)) return 0;
+    return sizeof(double) * tot;
+}
+
+// both entry points (workspace_q null: the entropy, q is p): the refusals, p's staging, each side's q and bh columns, the launch
+static int agbwd_run(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                     const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host, const double *elp_p,
+                     const double *trans_p, const double *init_p, const double *len_p, const double *endpen_p,
+                     const double *logz_p, void *ws_p, size_t ws_p_bytes, const double *trans_q, const double *len_q,
+                     const double *endpen_q, const double *logz_q, void *ws_q, size_t ws_q_bytes, const int32_t *node_class,
+                     const uint32_t *pred_mask, const uint8_t *node_flags, const int64_t *node_offset_host, int kl,
+                     const double *grad_out, double *g_elp, double *g_trans, double *g_init, double *g_len, double *value_out,
+                     void *scratch, size_t scratch_bytes, hipStream_t hs)
+{
+    if (!pred_mask || !node_flags || !g_elp || !g_trans || !g_init || !g_len || !scratch) return SMM_ERR_ARG;
+    if (!shape_ok(shape) || !lengths_host || !frame_offset_host || !n_states_host || !node_offset_host) return SMM_ERR_ARG;
+    if (!elp_p || !trans_p || !init_p || !len_p || !node_class || !logz_p || !ws_p) return SMM_ERR_ARG;
+    AlignLayout lo;
+    int rc = align_layout(ALIGN_GRAPH_LOGZ, shape, lengths_host, node_offset_host, &lo);
+    if (rc != SMM_OK) return rc;
+    if (ws_q && ws_q == ws_p) return SMM_ERR_ARG;              // (one posterior against itself is the entropy call's)
+    if (ws_p_bytes < lo.total || (ws_q && ws_q_bytes < lo.total)) return SMM_ERR_WORKSPACE;
+    size_t pv_base = 0, tot = 0;
+    agbwd_layout(shape, lengths_host, node_offset_host, &pv_base, &tot);
+    if (scratch_bytes < sizeof(double) * tot) return SMM_ERR_WORKSPACE;
+    SmmAlignEntBwdArgs a{};
+    rc = align_logz_prepare(ALIGN_GRAPH_LOGZ, shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp_p,
+                            trans_p, init_p, len_p, endpen_p, node_class, node_offset_host, logz_p, ws_p, ws_p_bytes, hs, &a.g);
+    if (rc == SMM_OK) rc = align_logz_bwd_outputs(shape, grad_out, g_elp, g_trans, g_init, g_len, hs, &a.g);
+    if (rc != SMM_OK) return rc;
+    a.g.pred_mask = pred_mask; a.g.node_flags = node_flags;
+    smm_launch_align_graph_logz_bwd_columns(a.g, hs);
+    a.scratch = static_cast<double *>(scratch);
+    if (ws_q) {
+        // First the recorded ranges of the two sides, video by video: a video whose ranges differ gets a NaN in place of q's
+        // log Z, which the q-side launch below skips (and answers with the error word) as every later kernel does -- nothing of
+        // q's workspace is read or written through ranges that were not compared.  Then q's q and bh columns and parts,
+        // exactly as q's own backward call would write them first: p's staged metadata (the two sides share it), q's tables,
+        // histories, columns and parts
+        Staged sq;
+        plan_point(make_plan(shape, lengths_host), ws_q, &sq);
+        char *bq = static_cast<char *>(ws_q);
+        double *lzq = a.scratch + pv_base + (size_t)shape->b * smm_align_graph_entropy_bwd_part_doubles(shape->c_max, shape->k_rows);
+        a.cols_q = reinterpret_cast<double *>(bq + lo.o_cols);
+        smm_launch_align_graph_entropy_bwd_check(a, logz_q, lzq, hs);
+        SmmAlignLogzArgs q = a.g;
+        q.trans = trans_q; q.len = len_q; q.endpen = endpen_q; q.logz = lzq;
+        q.hist = sq.hist; q.cols = reinterpret_cast<double *>(bq + lo.o_cols); q.part = reinterpret_cast<double *>(bq + lo.o_part);
+        q.grad = nullptr; q.g_elp = q.g_trans = q.g_init = q.g_len = nullptr;
+        smm_launch_align_graph_logz_bwd_columns(q, hs);
+        a.trans_q = trans_q; a.len_q = len_q; a.endpen_q = endpen_q; a.logz_q = lzq;
+        a.hist_q = sq.hist;
+    } else {
+        a.trans_q = trans_p; a.len_q = len_p; a.endpen_q = endpen_p; a.logz_q = logz_p;
+        a.hist_q = a.g.hist; a.cols_q = a.g.cols;
+    }
+    a.value = value_out;
+    a.pv_base = (int64_t)pv_base;
+    a.kl = kl;
+    smm_launch_align_graph_entropy_bwd(a, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
+extern "C" int smm_align_graph_entropy_bwd_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                               const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                               const double *elp, const double *trans, const double *init, const double *len_scores,
+                                               const double *endpen, const int32_t *node_class, const uint32_t *pred_mask,
+                                               const uint8_t *node_flags, const int64_t *node_offset_host, const double *logz_g,
+                                               const double *grad_out, double *g_elp, double *g_trans, double *g_init,
+                                               double *g_len, double *value_out, void *scratch, size_t scratch_bytes,
+                                               void *workspace, size_t workspace_bytes, void *stream)
+{
+    return agbwd_run(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp, trans, init, len_scores,
+                     endpen, logz_g, workspace, workspace_bytes, nullptr, nullptr, nullptr, nullptr, nullptr, 0, node_class,
+                     pred_mask, node_flags, node_offset_host, 0, grad_out, g_elp, g_trans, g_init, g_len, value_out, scratch,
+                     scratch_bytes, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int smm_align_graph_kl_bwd_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                          const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                          const double *elp_p, const double *trans_p, const double *init_p,
+                                          const double *len_scores_p, const double *endpen_p, const double *logz_g_p,
+                                          void *workspace_p, size_t workspace_p_bytes, const double *trans_q,
+                                          const double *len_scores_q, const double *endpen_q, const double *logz_g_q,
+                                          void *workspace_q, size_t workspace_q_bytes, const int32_t *node_class,
+                                          const uint32_t *pred_mask, const uint8_t *node_flags, const int64_t *node_offset_host,
+                                          int32_t mode, const double *grad_out, double *g_elp, double *g_trans, double *g_init,
+                                          double *g_len, double *value_out, void *scratch, size_t scratch_bytes, void *stream)
+{
+    if (mode != SMM_KL_BWD_CROSS_ENTROPY && mode != SMM_KL_BWD_KL) return SMM_ERR_ARG;
+    if (!trans_q || !len_scores_q || !logz_g_q || !workspace_q) return SMM_ERR_ARG;
+    return agbwd_run(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp_p, trans_p, init_p,
+                     len_scores_p, endpen_p, logz_g_p, workspace_p, workspace_p_bytes, trans_q, len_scores_q, endpen_q, logz_g_q,
+                     workspace_q, workspace_q_bytes, node_class, pred_mask, node_flags, node_offset_host,
+                     mode == SMM_KL_BWD_KL ? 1 : 0, grad_out, g_elp, g_trans, g_init, g_len, value_out, scratch, scratch_bytes,
+                     static_cast<hipStream_t>(stream));
+}
+
 // ------------------------------------------------------------------------------------------------ dense boundary
 struct DenseLayout {
     size_t o_len, o_alpha, o_beta, o_bp_from, o_bp_k, o_rmsg, total;

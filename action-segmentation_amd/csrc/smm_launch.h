@@ -323,6 +323,30 @@ struct SmmAlignKlArgs {
 };
 void smm_launch_align_graph_kl(const SmmAlignKlArgs &a, hipStream_t stream);
 
+// gradients of the entropy, cross-entropy and KL of transcript-graph posteriors with respect to p's tables
+// (smm_align_graph_entropy_bwd.hip): after smm_launch_align_graph_logz_fwd and smm_launch_align_graph_logz_bwd_columns per side
+// (for the entropy q's pointers are p's) -- of both sides it reads cum, the four column blocks and the columns' ranges; it
+// writes the caller's scratch, the gradients and p's error word
+struct SmmAlignEntBwdArgs {
+    SmmAlignLogzArgs g;        // p's backward launch's arguments (grad: the upstream weights; g_elp zero at launch)
+    const double *trans_q;     // [g][c_max][c_max]
+    const double *len_q;       // [g][k_rows][c_max]
+    const double *endpen_q;    // [b][c_max] or null
+    const double *logz_q;      // [b]
+    const double *hist_q;      // q's history area: the same plan, so the videos' hist_off serve both
+    const double *cols_q;      // q's workspace at the offset of `cols` in p's
+    double *value;             // [b] or null: V-
+    double *scratch;           // caller's: per video five [M][T+1] blocks, then the videos' parts at pv_base, then q's log Z as the
+                               // call uses it [b], then V+ [b]
+    int64_t pv_base;           // doubles in front of the parts
+    int32_t kl;                // 0: cross-entropy (entropy), 1: KL
+};
+size_t smm_align_graph_entropy_bwd_part_doubles(int c_max, int k_rows);   // the parts of one video
+void smm_launch_align_graph_entropy_bwd(const SmmAlignEntBwdArgs &a, hipStream_t stream);
+// ... before q's workspace is touched: out[i] = logz_q[i] where the two sides' recorded ranges agree, NaN where they differ
+// (g.cols, g.hoff, g.toff, g.logz and cols_q are read)
+void smm_launch_align_graph_entropy_bwd_check(const SmmAlignEntBwdArgs &a, const double *logz_q, double *out, hipStream_t stream);
+
 // alignments drawn from the transcript-graph posterior (smm_align_graph_sample.hip): after smm_launch_align_graph_logz_fwd on
 // the same workspace -- it reads cum, the h and gam columns and the columns' ranges, and writes the error word only
 struct SmmAlignSampleArgs {

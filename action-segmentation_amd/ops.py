@@ -1191,7 +1191,7 @@ def align_graph_entropy(batch, elp, trans, init, len_scores, graphs, logz_g, end
     output.  ``align_graph_logz_bwd`` and ``align_graph_sample`` may run before or after it: neither's results change.
     -> dict(entropy fp64 [b], parts fp64 [b, 3] (with ``want_parts``: the entropy of the end node -- for a trie of the
     posterior over the candidates --, of the segments' starts, and of the predecessors; they add up to ``entropy``) or None,
-    _err, _staged, _keep).  A video without an alignment (log Z_g = -inf) gets NaN.  The values are not differentiable."""
+    _err, _staged, _keep).  A video without an alignment (log Z_g = -inf) gets NaN.  Gradient: ``align_graph_entropy_bwd``."""
     lib = _lib.load()
     if ws is None:
         raise ValueError("align_graph_entropy: pass the workspace the align_graph_logz call wrote")
@@ -1220,7 +1220,7 @@ def align_graph_kl(batch, p, q, graphs, staged=None, want_cross_entropy=False, w
     the end node -- for a trie the KL between the posteriors over the candidates --, of the segments' starts, and of the
     predecessors; they add up to ``kl``) or None, _err, _staged, _keep).  Bit-identical sides give exactly 0.  A video p cannot
     align (log Z_g = -inf) gets NaN; one p can align and q cannot gets +inf, as does one where p puts mass on an alignment q
-    excludes.  The values are not differentiable."""
+    excludes.  Gradient: ``align_graph_kl_bwd``."""
     lib = _lib.load()
     elp, trans, init, len_scores, endpen, logz_p, ws_p = p
     trans_q, len_q, endpen_q, logz_q, ws_q = q
@@ -1242,6 +1242,85 @@ def align_graph_kl(batch, p, q, graphs, staged=None, want_cross_entropy=False, w
         *_ws_args(ws_q), node_class, pred_mask, node_flags, node_off, _dev(kl, f64, 'kl'), _dev(xent, f64, 'cross_entropy'),
         _dev(parts, f64, 'parts'), _stream()))
     return dict(kl=kl, cross_entropy=xent, parts=parts, _err=_err_copy(batch, ws_p), _staged=sup.dev, _keep=(ws_p, ws_q))
+
+
+def align_graph_entropy_bwd_scratch_bytes(batch, node_offset):
+    """Bytes of scratch smm_align_graph_entropy_bwd_f64 / smm_align_graph_kl_bwd_f64 need for this batch and these node
+    offsets (int64 [b + 1]; host only); raises ValueError for what the calls refuse."""
+    off = np.ascontiguousarray(node_offset, dtype=np.int64)
+    n = _lib.load().smm_align_graph_entropy_bwd_scratch_bytes(ctypes.byref(batch.shape), ctypes.c_void_p(batch.lengths.ctypes.data),
+                                                              ctypes.c_void_p(off.ctypes.data))
+    if n == 0:
+        raise ValueError("align_graph_entropy_bwd: the library refuses this batch and these node offsets")
+    return int(n)
+
+
+def _graph_value_bwd(what, batch, p, q, graphs, grad_out, staged, mode, scratch=None):
+    """smm_align_graph_entropy_bwd_f64 (``q`` None) or smm_align_graph_kl_bwd_f64 with ``mode``.  Every check on the host
+    arrays comes before a device is touched.  ``scratch``: a uint8 tensor of at least
+    ``align_graph_entropy_bwd_scratch_bytes`` (its contents do not matter); default: a private one."""
+    lib = _lib.load()
+    elp, trans, init, len_scores, endpen, logz_p, ws_p = p
+    if ws_p is None or (q is not None and q[4] is None):
+        raise ValueError("%s: pass the workspace the align_graph_logz call wrote" % what)
+    f64 = torch.float64
+    dev = elp.device
+    sup = _supervision('graph', 'likelihood', what, batch, dev, graphs, None, staged)
+    if ws_p.numel() < sup.need or (q is not None and q[4].numel() < sup.need):
+        raise ValueError("%s: pass the workspace the align_graph_logz call wrote" % what)
+    if q is not None and q[4].data_ptr() == ws_p.data_ptr():
+        raise ValueError("%s: the two sides need a workspace each (one posterior against itself: align_graph_entropy_bwd)" % what)
+    need = align_graph_entropy_bwd_scratch_bytes(batch, sup.off)
+    tables = _tables(elp, trans, init, len_scores, endpen)
+    node_class, pred_mask, node_flags, node_off = sup.args()
+    g = _grad_outputs(elp, trans, init, len_scores)
+    value = torch.empty(batch.b, dtype=f64, device=dev)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif scratch.dtype != torch.uint8 or scratch.numel() < need:
+        raise ValueError("%s: scratch must be a uint8 tensor of at least %d bytes" % (what, need))
+    outs = (_dev(grad_out, f64, 'grad_out'), _dev(g['elp'], f64, 'g_elp'), _dev(g['trans'], f64, 'g_trans'),
+            _dev(g['init'], f64, 'g_init'), _dev(g['len'], f64, 'g_len'), _dev(value, f64, 'value'), *_ws_args(scratch))
+    if q is None:
+        _lib.check(lib.smm_align_graph_entropy_bwd_f64(
+            *batch.head(), *tables, node_class, pred_mask, node_flags, node_off, _dev(logz_p, f64, 'logz_g'), *outs,
+            *_ws_args(ws_p), _stream()))
+        keep = (ws_p, scratch)
+    else:
+        trans_q, len_q, endpen_q, logz_q, ws_q = q
+        _lib.check(lib.smm_align_graph_kl_bwd_f64(
+            *batch.head(), *tables, _dev(logz_p, f64, 'logz_g'), *_ws_args(ws_p),
+            _dev(trans_q, f64, 'trans'), _dev(len_q, f64, 'len_scores'), _dev(endpen_q, f64, 'endpen'), _dev(logz_q, f64, 'logz_g'),
+            *_ws_args(ws_q), node_class, pred_mask, node_flags, node_off, ctypes.c_int32(mode), *outs, _stream()))
+        keep = (ws_p, ws_q, scratch)
+    g.update(value=value, value_plus=scratch[:need].view(f64)[-batch.b:], _err=_err_copy(batch, ws_p), _staged=sup.dev, _keep=keep)
+    return g
+
+
+def align_graph_entropy_bwd(batch, elp, trans, init, len_scores, graphs, logz_g, grad_out=None, endpen=None, ws=None, staged=None,
+                            scratch=None):
+    """Gradient of sum_i grad_out[i] * H_i, the entropy ``align_graph_entropy`` returns, with respect to the tables
+    (smm_align_graph_entropy_bwd_f64).  Must follow ``align_graph_logz`` for the same batch, tables and graphs with the same
+    workspace ``ws`` on the same stream; ``logz_g`` = its output.  The backward, sampler, entropy and KL results on that
+    workspace do not change.  -> dict(elp [total_frames, c_max], trans, init, len fp64, value fp64 [b]: H by the message pass
+    over the sampler's decisions (value_plus: by the time-forward walk's), _err, _staged, _keep).  A video without an
+    alignment contributes zeros and gets the value NaN.  ``scratch``: the caller's, of ``align_graph_entropy_bwd_scratch_bytes``
+    (uint8; it need not be initialised); default: a private one."""
+    return _graph_value_bwd('align_graph_entropy_bwd', batch, (elp, trans, init, len_scores, endpen, logz_g, ws), None, graphs,
+                            grad_out, staged, 0, scratch)
+
+
+def align_graph_kl_bwd(batch, p, q, graphs, grad_out=None, staged=None, cross_entropy=False, scratch=None):
+    """Gradient of sum_i grad_out[i] * KL_i(p || q), or with ``cross_entropy`` of H_i(p, q), with respect to p's tables
+    (smm_align_graph_kl_bwd_f64).  ``p`` and ``q`` as ``align_graph_kl`` takes them.  q's workspace receives what q's own
+    ``align_graph_logz_bwd`` would write first, so neither side's later results change.  The gradient with respect to q's
+    tables is mu_q - mu_p from two ``align_graph_logz_bwd`` calls.  -> dict(elp, trans, init, len, value, value_plus, _err,
+    _staged, _keep) as ``align_graph_entropy_bwd``.  Bit-identical sides give exactly 0 everywhere in the KL mode; a video
+    whose value is +inf gets NaN rows and makes its group's tables NaN; a q workspace written for other graphs (the columns'
+    recorded ranges differ) gives that video NaN, zeros and the error word, and is not written.  The two sides need a workspace
+    each.  ``scratch``: as ``align_graph_entropy_bwd``'s."""
+    return _graph_value_bwd('align_graph_kl_bwd', batch, p, q, graphs, grad_out, staged,
+                            _lib.KL_BWD_CROSS_ENTROPY if cross_entropy else _lib.KL_BWD_KL, scratch)
 
 
 def transcript_is_ambiguous(ids, optional):

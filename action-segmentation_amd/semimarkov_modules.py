@@ -178,19 +178,20 @@ def _sample_alignments(r, sup, n_samples, seed, want_spans):
 
 
 def _alignment_entropy(r, sup, want_parts):
-    """The forward launch over the graphs of ``sup`` on a private workspace, then the entropy launch on it: (H, parts or None).
-    A video without an alignment is no error: NaN."""
+    """The forward launch over the graphs of ``sup`` on a private workspace, then the entropy launch on it: (H, parts or None,
+    (the forward launch,)).  A video without an alignment is no error: NaN."""
     b = r['batch']
     z = _supervised(_LOGZ, r, sup)
     out = ops.align_graph_entropy(b, r['elp'], r['trans'], r['init'], r['len'], sup[1][0], z['logz'], endpen=r['endpen'],
                                   ws=z['ws'], staged=z['_staged'], want_parts=want_parts)
     ops.check_decoded(b, out)
-    return out['entropy'], out['parts']
+    return out['entropy'], out['parts'], (z,)
 
 
 def _alignment_kl(r, q, sup, what, want_cross_entropy, want_parts):
     """One forward launch per side over the graphs of ``sup``, each on a private workspace, then the KL launch on both
-    (smm_align_graph_kl_f64): (KL(p || q) or H(p, q), parts or None).  A video p cannot align is no error: NaN."""
+    (smm_align_graph_kl_f64): (KL(p || q) or H(p, q), parts or None, (p's forward launch, q's)).  A video p cannot align is no
+    error: NaN."""
     b = r['batch']
     SemiMarkovModule._check_same_batch(b, q['batch'], what)
     zq = _supervised(_LOGZ, q, sup)
@@ -200,7 +201,7 @@ def _alignment_kl(r, q, sup, what, want_cross_entropy, want_parts):
                              want_cross_entropy=want_cross_entropy, want_parts=want_parts)
     ops.check_decoded(b, out)
     ops.check_decoded(b, zq)                                   # (the KL launch leaves q's error word as q's forward launch set it)
-    return (out['cross_entropy'] if want_cross_entropy else out['kl']), out['parts']
+    return (out['cross_entropy'] if want_cross_entropy else out['kl']), out['parts'], (zp, zq)
 
 
 def _transcript_scores(r, sup, conditional, what):
@@ -375,6 +376,63 @@ class _PosteriorValue(torch.autograd.Function):
         mp = ops.logz_bwd(b, grad_logz=up, with_backward=True, **_after_logz(r))
         gq = {k: mq[k] - mp[k] for k in ('elp', 'trans', 'init', 'len')}
         return (None, None) + _table_grads(b, r['x'], g, r['ws']) + _table_grads(b, q['x'], gq, q['ws'])
+
+
+class _AlignmentValue(torch.autograd.Function):
+    """``_PosteriorValue`` for the transcript-graph posteriors: the entropy, cross-entropy or KL of every video's posterior over
+    its ALIGNMENTS as a differentiable function of the fp64 factor tables of p, and of q for the two-sided values.  ``launch()``
+    computes the value exactly as the non-differentiable method does and returns (value, [p's record, q's], the supervision,
+    (p's forward launch, q's)); the forward launches keep their workspaces until the backward runs.  Backward:
+    smm_align_graph_entropy_bwd_f64 / smm_align_graph_kl_bwd_f64 for p's tables, mu_q - mu_p (two smm_align_graph_logz_bwd_f64)
+    for q's, then the emission chain rule of each side."""
+
+    @staticmethod
+    def forward(ctx, kind, launch, *tables):
+        value, ctx.recs, ctx.sup, ctx.fwd = launch()
+        ctx.kind = kind
+        return value
+
+    @staticmethod
+    def backward(ctx, gv):
+        up = gv.to(torch.float64).contiguous()
+        r, zp, graphs = ctx.recs[0], ctx.fwd[0], ctx.sup[1][0]
+        b = r['batch']
+        side = (r['elp'], r['trans'], r['init'], r['len'], r['endpen'], zp['logz'], zp['ws'])
+        if ctx.kind == 'entropy':
+            g = ops.align_graph_entropy_bwd(b, *side[:4], graphs, zp['logz'], grad_out=up, endpen=r['endpen'], ws=zp['ws'],
+                                            staged=zp['_staged'])
+            return (None, None) + _table_grads(b, r['x'], g, zp['ws'])
+        q, zq = ctx.recs[1], ctx.fwd[1]
+        g = ops.align_graph_kl_bwd(b, side, (q['trans'], q['len'], q['endpen'], zq['logz'], zq['ws']), graphs, grad_out=up,
+                                   staged=zp['_staged'], cross_entropy=ctx.kind == 'cross_entropy')
+        mq = _supervised(_LOGZ_BWD, q, ctx.sup, zq['logz'], grad_logz=up, ws=zq['ws'], staged=zq['_staged'])
+        mp = _supervised(_LOGZ_BWD, r, ctx.sup, zp['logz'], grad_logz=up, ws=zp['ws'], staged=zp['_staged'])
+        gq = {k: mq[k] - mp[k] for k in ('elp', 'trans', 'init', 'len')}
+        return (None, None) + _table_grads(b, r['x'], g, zp['ws']) + _table_grads(b, q['x'], gq, zq['ws'])
+
+
+def _alignment_value(kind, what, names, sides, tables, want_parts):
+    """The differentiable route of the ``alignment_*`` methods.  ``sides``: what ``_supervised_padded`` / ``_supervised_packed``
+    return (the record of ``_emit``, the supervision), p's first, then q's for the two-sided values; ``tables``: each side's
+    (w, cst, trans, init, len) with autograd history, which the gradients go to.  The value comes from the launches of the
+    non-differentiable route, bit for bit; the parts carry no gradient.  A video without an alignment is refused here, by its
+    name: a NaN cannot be trained on."""
+    sup = sides[0][1]
+    parts = []
+
+    def launch():
+        recs = [r for r, _ in sides]
+        if kind == 'entropy':
+            value, pt, fwd = _alignment_entropy(recs[0], sup, want_parts)
+        else:
+            value, pt, fwd = _alignment_kl(recs[0], recs[1], sup, what, kind == 'cross_entropy', want_parts)
+        for z in fwd:
+            _check_transcript_logz(z['logz'], names, what)
+        parts.append(pt)
+        return value, recs, sup, fwd
+
+    value = _AlignmentValue.apply(kind, launch, *tables)
+    return (value, parts[0]) if want_parts else value
 
 
 class _FactorTables(torch.autograd.Function):
@@ -1469,9 +1527,8 @@ class SemiMarkovModule(nn.Module):
         return _sample_alignments(r, sup, n_samples, seed, want_spans=False)
 
     # ------------------------------------------------------------------ entropy of the graph posterior (smm_align_graph_entropy_f64)
-    @torch.no_grad()
     def alignment_entropy(self, features, lengths, valid_classes_per_instance, graphs, add_eos=True,
-                          additional_allowed_ends_per_instance=None, constraints=None, want_parts=False):
+                          additional_allowed_ends_per_instance=None, constraints=None, want_parts=False, *, differentiable=False):
         """The exact entropy, in nats, of the posterior ``sample_alignments`` draws from, p(alignment | x, "the class sequence
         is a start -> end path of ``graphs[i]``"), for a zero-padded single-task batch (argument conventions of
         ``align_graph``; graphs in GLOBAL class ids): one emission launch, the forward launch (smm_align_graph_logz_f64) and the
@@ -1481,46 +1538,70 @@ class SemiMarkovModule(nn.Module):
         Returns fp64 b on the device, or with ``want_parts`` the pair (entropy, parts): parts fp64 b x 3, the entropy of the
         end node (for a trie: of the posterior over the candidates), of the segments' starts and of the predecessors, which
         add up to the entropy.  A video none of whose paths can be laid over it gives NaN.  ValueError for a wrong number of
-        graphs or add_eos=False; SmmError when a NaN reached the DP.  The result is NOT differentiable: no autograd."""
-        r, sup = self._supervised_padded('alignment_entropy', features, lengths, valid_classes_per_instance, add_eos,
-                                         additional_allowed_ends_per_instance, constraints, graphs, graphs=True, ambiguous='allow')
-        h, parts = _alignment_entropy(r, sup, want_parts)
-        return (h, parts) if want_parts else h
+        graphs or add_eos=False; SmmError when a NaN reached the DP.
+        ``differentiable``: the same value (bit for bit, from the same launches), differentiable with respect to the module's
+        parameters: the backward runs smm_align_graph_entropy_bwd_f64 and the chain rule through the emission scorer and the
+        factor tables; the parts carry no gradient.  A video without an alignment is then a ValueError that names it
+        (``transcript_graph_log_partition``'s): a NaN cannot be trained on."""
+        with torch.no_grad():
+            side = self._supervised_padded('alignment_entropy', features, lengths, valid_classes_per_instance, add_eos,
+                                           additional_allowed_ends_per_instance, constraints, graphs, graphs=True, ambiguous='allow')
+            if not differentiable:
+                h, parts, _ = _alignment_entropy(*side, want_parts)
+                return (h, parts) if want_parts else h
+        tabs = self._differentiable_tables(self._check_valid_classes(valid_classes_per_instance), features.device)
+        return _alignment_value('entropy', 'alignment_entropy', None, [side], tabs, want_parts)
 
-    @torch.no_grad()
-    def alignment_entropy_packed(self, pc, graphs, want_parts=False):
+    def alignment_entropy_packed(self, pc, graphs, want_parts=False, *, differentiable=False):
         """``alignment_entropy`` for a whole PackedCorpus: one emission launch, the forward launch and the entropy launch.
         ``graphs``: one ``ops.TranscriptGraph`` in GLOBAL class ids per video, in the order of ``pc.video_names``.  Returns fp64
-        n_videos on the device, or with ``want_parts`` (entropy, parts fp64 n_videos x 3).  Not differentiable."""
-        r, sup = self._supervised_packed(pc, 'alignment_entropy_packed', graphs, graphs=True, ambiguous='allow')
-        h, parts = _alignment_entropy(r, sup, want_parts)
-        return (h, parts) if want_parts else h
+        n_videos on the device, or with ``want_parts`` (entropy, parts fp64 n_videos x 3).  ``differentiable``: as
+        ``alignment_entropy``'s; the tables are ``stacked_tables(pc, differentiable=True)``."""
+        with torch.no_grad():
+            side = self._supervised_packed(pc, 'alignment_entropy_packed', graphs, graphs=True, ambiguous='allow')
+            if not differentiable:
+                h, parts, _ = _alignment_entropy(*side, want_parts)
+                return (h, parts) if want_parts else h
+        st = self.stacked_tables(pc, differentiable=True)[0]
+        return _alignment_value('entropy', 'alignment_entropy_packed', list(pc.video_names), [side], tuple(st[k] for k in TABLE_NAMES),
+                                want_parts)
 
     # ------------------------------------------------------------------ KL of two graph posteriors (smm_align_graph_kl_f64)
     def _alignment_kl_padded(self, other, what, features, lengths, valid_classes_per_instance, graphs, add_eos,
-                             additional_allowed_ends_per_instance, constraints, other_constraints, want_cross_entropy, want_parts):
+                             additional_allowed_ends_per_instance, constraints, other_constraints, want_cross_entropy, want_parts,
+                             differentiable=False):
         self._check_same_lattice(other, what)
-        q, _ = other._supervised_padded(what, features, lengths, valid_classes_per_instance, add_eos,
-                                        additional_allowed_ends_per_instance, other_constraints, graphs, graphs=True,
-                                        ambiguous='allow')
-        r, sup = self._supervised_padded(what, features, lengths, valid_classes_per_instance, add_eos,
-                                         additional_allowed_ends_per_instance, constraints, graphs, graphs=True, ambiguous='allow')
-        return _alignment_kl(r, q, sup, what, want_cross_entropy, want_parts)
+        stage = lambda m, c: m._supervised_padded(what, features, lengths, valid_classes_per_instance, add_eos,
+                                                  additional_allowed_ends_per_instance, c, graphs, graphs=True, ambiguous='allow')
+        with torch.no_grad():
+            q = stage(other, other_constraints)
+            p = stage(self, constraints)
+            if not differentiable:
+                value, parts, _ = _alignment_kl(p[0], q[0], p[1], what, want_cross_entropy, want_parts)
+                return (value, parts) if want_parts else value
+        valid = self._check_valid_classes(valid_classes_per_instance)
+        tabs = self._differentiable_tables(valid, features.device) + other._differentiable_tables(valid, features.device)
+        return _alignment_value('cross_entropy' if want_cross_entropy else 'kl', what, None, [p, q], tabs, want_parts)
 
-    def _alignment_kl_packed(self, other, pc, graphs, what, want_cross_entropy, want_parts):
+    def _alignment_kl_packed(self, other, pc, graphs, what, want_cross_entropy, want_parts, differentiable=False):
         self._check_same_lattice(other, what)
-        saved = dict(pc.__dict__)                                  # (q first, `pc` left prepared for `self`: as _kl_packed)
-        try:
-            q, _ = other._supervised_packed(pc, what, graphs, graphs=True, ambiguous='allow')
-        finally:
-            pc.__dict__.clear()
-            pc.__dict__.update(saved)
-        r, sup = self._supervised_packed(pc, what, graphs, graphs=True, ambiguous='allow')
-        return _alignment_kl(r, q, sup, what, want_cross_entropy, want_parts)
+        with torch.no_grad():
+            saved = dict(pc.__dict__)                              # (q first, `pc` left prepared for `self`: as _kl_packed)
+            try:
+                q = other._supervised_packed(pc, what, graphs, graphs=True, ambiguous='allow')
+            finally:
+                pc.__dict__.clear()
+                pc.__dict__.update(saved)
+            p = self._supervised_packed(pc, what, graphs, graphs=True, ambiguous='allow')
+            if not differentiable:
+                value, parts, _ = _alignment_kl(p[0], q[0], p[1], what, want_cross_entropy, want_parts)
+                return (value, parts) if want_parts else value
+        tabs = tuple(m.stacked_tables(pc, differentiable=True)[0][k] for m in (self, other) for k in TABLE_NAMES)
+        return _alignment_value('cross_entropy' if want_cross_entropy else 'kl', what, list(pc.video_names), [p, q], tabs, want_parts)
 
-    @torch.no_grad()
     def alignment_kl(self, other, features, lengths, valid_classes_per_instance, graphs, add_eos=True,
-                     additional_allowed_ends_per_instance=None, constraints=None, other_constraints=None, want_parts=False):
+                     additional_allowed_ends_per_instance=None, constraints=None, other_constraints=None, want_parts=False, *,
+                     differentiable=False):
         """The exact KL(p || q), in nats, between two posteriors over the alignments of each video to ``graphs[i]`` (argument
         conventions of ``alignment_entropy``; graphs in GLOBAL class ids): p is this module's under ``constraints``, q is
         ``other``'s under ``other_constraints`` (``other`` may be ``self``); each side builds its tables, emissions and end
@@ -1531,36 +1612,34 @@ class SemiMarkovModule(nn.Module):
         (for a trie: between the two posteriors over the candidates), of the segments' starts and of the predecessors, which
         add up to the KL.  NaN for a video p cannot align, +inf where q excludes an alignment p does not.  TypeError when
         ``other`` is no SemiMarkovModule, ValueError when the lattices differ, for a wrong number of graphs or add_eos=False;
-        SmmError when a NaN reached the DP.  No autograd."""
-        kl, parts = self._alignment_kl_padded(other, 'alignment_kl', features, lengths, valid_classes_per_instance, graphs, add_eos,
-                                              additional_allowed_ends_per_instance, constraints, other_constraints, False,
-                                              want_parts)
-        return (kl, parts) if want_parts else kl
+        SmmError when a NaN reached the DP.
+        ``differentiable``: the same value (bit for bit), differentiable with respect to both modules' parameters: the backward
+        runs smm_align_graph_kl_bwd_f64 for p's tables, mu_q - mu_p (two smm_align_graph_logz_bwd_f64) for q's, and each side's
+        chain rule through the emission scorer and the factor tables.  A video either side cannot align is then a ValueError."""
+        return self._alignment_kl_padded(other, 'alignment_kl', features, lengths, valid_classes_per_instance, graphs, add_eos,
+                                         additional_allowed_ends_per_instance, constraints, other_constraints, False, want_parts,
+                                         differentiable)
 
-    @torch.no_grad()
     def alignment_cross_entropy(self, other, features, lengths, valid_classes_per_instance, graphs, add_eos=True,
                                 additional_allowed_ends_per_instance=None, constraints=None, other_constraints=None,
-                                want_parts=False):
+                                want_parts=False, *, differentiable=False):
         """The exact cross-entropy H(p, q) = -sum p log q = H(p) + KL(p || q) of the same two posteriors, in nats: arguments,
         launches and refusals as ``alignment_kl`` (the parts are the KL's); with ``other`` = ``self`` and the same constraints
-        it is ``alignment_entropy``'s value to that kernel's fp32 rounding."""
-        xe, parts = self._alignment_kl_padded(other, 'alignment_cross_entropy', features, lengths, valid_classes_per_instance,
-                                              graphs, add_eos, additional_allowed_ends_per_instance, constraints,
-                                              other_constraints, True, want_parts)
-        return (xe, parts) if want_parts else xe
+        it is ``alignment_entropy``'s value to that kernel's fp32 rounding.  ``differentiable``: as ``alignment_kl``'s."""
+        return self._alignment_kl_padded(other, 'alignment_cross_entropy', features, lengths, valid_classes_per_instance, graphs,
+                                         add_eos, additional_allowed_ends_per_instance, constraints, other_constraints, True,
+                                         want_parts, differentiable)
 
-    @torch.no_grad()
-    def alignment_kl_packed(self, other, pc, graphs, want_parts=False):
+    def alignment_kl_packed(self, other, pc, graphs, want_parts=False, *, differentiable=False):
         """``alignment_kl`` for a whole PackedCorpus: fp64 n_videos on the device in the order of ``pc.video_names``, or with
         ``want_parts`` (kl, parts fp64 n_videos x 3).  q's tables and end penalties are built on ``pc``'s layout; ``pc`` is left
-        prepared for ``self``."""
-        kl, parts = self._alignment_kl_packed(other, pc, graphs, 'alignment_kl_packed', False, want_parts)
-        return (kl, parts) if want_parts else kl
+        prepared for ``self``.  ``differentiable``: as ``alignment_kl``'s."""
+        return self._alignment_kl_packed(other, pc, graphs, 'alignment_kl_packed', False, want_parts, differentiable)
 
-    @torch.no_grad()
-    def alignment_cross_entropy_packed(self, other, pc, graphs):
-        """``alignment_cross_entropy`` for a whole PackedCorpus: fp64 n_videos on the device."""
-        return self._alignment_kl_packed(other, pc, graphs, 'alignment_cross_entropy_packed', True, False)[0]
+    def alignment_cross_entropy_packed(self, other, pc, graphs, *, differentiable=False):
+        """``alignment_cross_entropy`` for a whole PackedCorpus: fp64 n_videos on the device.  ``differentiable``: as
+        ``alignment_kl``'s."""
+        return self._alignment_kl_packed(other, pc, graphs, 'alignment_cross_entropy_packed', True, False, differentiable)
 
     # ------------------------------------------------------------------ packed multi-task decode
     def stacked_tables(self, pc, differentiable=False):

@@ -43,6 +43,8 @@
  *                              candidate and of the boundaries (the reference has none)
  *   smm_align_graph_kl_f64    <- ... and the exact KL divergence and cross-entropy between two such posteriors over the same
  *                              videos and graphs: teacher against student, one EM epoch against the next (the reference has none)
+ *   smm_align_graph_entropy_bwd_f64 / <- ... and the gradients of those three values with respect to p's tables: entropy
+ *   smm_align_graph_kl_bwd_f64   regularisation, distillation of an alignment posterior (the reference has none)
  *
  * The reference has no FFI: its boundary is the Python call SemiMarkovCRF(scores, lengths) on a dense
  * b x N x K x C x C tensor.  These entry points take the FACTORS of that tensor instead,
@@ -970,6 +972,84 @@ int smm_align_graph_kl_f64(const smm_shape *shape, const int64_t *lengths_host, 
                            const int32_t *node_class, const uint32_t *pred_mask, const uint8_t *node_flags,
                            const int64_t *node_offset_host, double *kl_out /* dev [b] */, double *xent_out /* dev [b], nullable */,
                            double *kl_parts /* dev [b][3]: end, span, pred; nullable */, void *stream);
+
+/*
+ * The gradients of smm_align_graph_entropy_f64's and smm_align_graph_kl_f64's values with respect to p's tables
+ * (csrc/smm_align_graph_entropy_bwd.hip): V = H(p) (smm_align_graph_entropy_bwd_f64) or H(p, q) / KL(p || q)
+ * (smm_align_graph_kl_bwd_f64, `mode` = SMM_KL_BWD_CROSS_ENTROPY / SMM_KL_BWD_KL).  What smm_entropy_bwd_f64 and smm_kl_bwd_f64 are
+ * to smm_entropy_f64 and smm_kl_f64.  Entropy regularisation of weakly supervised training, distillation of a teacher's
+ * alignment posterior, cross-entropy against a constrained posterior.
+ * In smm_align_graph_logz_f64's notation, an occurrence o is a span (node j, start s, end n = s + k), an edge (i -> j at
+ * boundary s) or a start (node m at 0), with the log-weight under a side
+ *   span   h[s][j] + len[k][a_j] + cum[n][a_j] + bg[n][j]
+ *   edge   gam[s][i] + trans[a_j][a_i] - cum[s][a_j] + bh[s][j]
+ *   start  init[a_m] + bh[0][m]
+ * p(o) = exp(w_p(o) - logZ_p);  l(o) = -(w_q(o) - logZ_q) (the entropy: q = p), for the KL (w_p(o) - logZ_p) - (w_q(o) - logZ_q);
+ *   dV / d theta = sum over the occurrences that read the entry of  p(o) ( l(o) + eta-(S_o) + eta+(E_o) - V )
+ * S_o / E_o: the decision node in front of / behind o (span: start node (s, j) / end node (n, j); edge: end node (s, i) / start
+ * node (s, j); start: none / start node (0, m)).  eta- is the chain rule of the value calls run as a message pass over the
+ * sampler's decisions, eta+ the same over the decisions of the time-forward walk, read from the backward columns; with
+ * L(c) = -log q_loc(c) of a candidate, for the KL log p_loc(c) - log q_loc(c):
+ *   eta-S(0, j) = 0;  eta-S(s, j) = sum_{i in pred(j)} p(i | start (s, j)) [ L(i) + eta-E(s, i) ]
+ *   eta-E(n, j) = sum_k p(k | end (n, j)) [ L(k) + eta-S(n-k, j) ];     V- = sum_{end(j)} p_end(j) [ L(j) + eta-E(T, j) ]
+ *   eta+E(T, j) = 0;  eta+E(n, j) = sum_{m in succ(j)} p(m | end (n, j)) [ L(m) + eta+S(n, m) ]
+ *   eta+S(s, m) = sum_k p(k | start (s, m)) [ L(k) + eta+E(s+k, m) ];   V+ = sum_{start(m)} p(start m) [ L(m) + eta+S(0, m) ]
+ * V- = V+ = V.  Outputs: smm_align_graph_logz_bwd_f64's four layouts, times the upstream weight grad_out[i] (NULL: ones), summed
+ * over each group's videos in video order; all four are overwritten entirely.  A span's term goes to g_elp on each of its
+ * frames and to g_len[k][a_j], an edge's to g_trans[a_j][a_i], a start's to g_init[a_m]; there is no gradient for endpen.
+ * value_out (nullable): V- per video.  The gradient with respect to q's tables needs no call of its own:
+ * dH(p,q)/d theta_q = dKL/d theta_q = mu_q - mu_p from two smm_align_graph_logz_bwd_f64 calls.
+ *   scratch   dev, smm_align_graph_entropy_bwd_scratch_bytes: per video five [M][T+1] blocks (the four etas and the occupancy
+ *             differences), then the videos' parts of the tables, q's log Z as the call uses it, then V+ per video in its last
+ *             b doubles; its contents need
+ *             not be initialised.  The query is host arithmetic and returns 0 for whatever the calls refuse.
+ * Call order: one smm_align_graph_logz_f64 per side on the same stream first, each on its own workspace.  The call stages p's
+ * workspace as the backward call does (clearing its error word) and launches smm_align_graph_logz_bwd_f64's first kernel on it
+ * (smm_launch_align_graph_logz_bwd_columns) for p's q and bh columns.  The gradient also needs q's q and bh columns, so
+ * smm_align_graph_kl_bwd_f64 WRITES workspace_q: it launches that same kernel on it, with q's tables -- q's workspace receives
+ * exactly what q's own smm_align_graph_logz_bwd_f64 call would write first, a function of q's forward columns alone; nothing is
+ * staged there and its error word is not touched.  So q's later backward, sampler, entropy and KL results do not change by a
+ * bit, nor do p's.  BEFORE that kernel runs on workspace_q, a kernel of one workgroup per video compares the five ints each
+ * forward call recorded per column, as smm_align_graph_kl_f64 does: a video whose ranges differ (workspace_q was written for
+ * other graphs) is skipped by the q-side launch and by every kernel behind it -- nothing of workspace_q is read or written
+ * through ranges that were not compared --, gets the value NaN, contributes zeros, and sets the error word.  workspace_q must
+ * not be workspace_p (SMM_ERR_ARG): one posterior against itself is smm_align_graph_entropy_bwd_f64.  Then five kernels of
+ * its own: eta-, eta+, the assembly (one workgroup per video each), g_elp, and
+ * the sums over the videos.
+ * Numerics: every exponential is fp64 on both sides, in all three modes; every read of a column is gated by its recorded range;
+ * a decision or an occurrence without mass under p is not evaluated.  No atomics, every sum in a fixed order: two calls give the
+ * same bits.  Both sides run the same operations, so in KL mode bit-identical sides give exactly 0.0 in every output.
+ *   logz_g_p = -inf                          value NaN, exactly zero contributions; the error word stays clear
+ *   logz_g_p or logz_g_q NaN                 the same; the error word (of p's workspace) is set
+ *   grad_out[i] = 0                          exactly 0.0 contributions
+ *   a value of +inf (q excludes what p has)  NaN rows of g_elp for that video, NaN tables for its group
+ * Videos beside such a video keep their bits.
+ * Enqueued on `stream` only; never synchronises; a video is never split.
+ * Refusals: as smm_align_graph_kl_f64's (a NULL gradient or scratch pointer included; an unknown `mode`; workspace_q equal to
+ * workspace_p), and
+ * SMM_ERR_WORKSPACE for a scratch below smm_align_graph_entropy_bwd_scratch_bytes -- all before anything is staged.
+ */
+size_t smm_align_graph_entropy_bwd_scratch_bytes(const smm_shape *shape, const int64_t *lengths_host,
+                                                 const int64_t *node_offset_host);
+int smm_align_graph_entropy_bwd_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                    const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                    const double *elp, const double *trans, const double *init, const double *len_scores,
+                                    const double *endpen /* nullable */, const int32_t *node_class, const uint32_t *pred_mask,
+                                    const uint8_t *node_flags, const int64_t *node_offset_host, const double *logz_g /* dev [b] */,
+                                    const double *grad_out /* dev [b], nullable */, double *g_elp, double *g_trans, double *g_init,
+                                    double *g_len, double *value_out /* dev [b], nullable */, void *scratch, size_t scratch_bytes,
+                                    void *workspace, size_t workspace_bytes, void *stream);
+int smm_align_graph_kl_bwd_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                               const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                               const double *elp_p, const double *trans_p, const double *init_p, const double *len_scores_p,
+                               const double *endpen_p /* nullable */, const double *logz_g_p /* dev [b] */,
+                               void *workspace_p, size_t workspace_p_bytes,
+                               const double *trans_q, const double *len_scores_q, const double *endpen_q /* nullable */,
+                               const double *logz_g_q /* dev [b] */, void *workspace_q, size_t workspace_q_bytes,
+                               const int32_t *node_class, const uint32_t *pred_mask, const uint8_t *node_flags,
+                               const int64_t *node_offset_host, int32_t mode, const double *grad_out /* dev [b], nullable */,
+                               double *g_elp, double *g_trans, double *g_init, double *g_len,
+                               double *value_out /* dev [b], nullable */, void *scratch, size_t scratch_bytes, void *stream);
 
 /*
  * Factor tables of every parameter group from the model parameters (training steps), and their chain rule.
