@@ -72,7 +72,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_kernel(SmmA
     if (tid < 2) s_flag[tid] = 0;
     __syncthreads();
     // ---- the structure -> LDS (smm_align_graph.h)
-    graph_load(a, v, s_a, s_fl, s_mask, s_flag, tid);
+    graph_load<true>(a, v, s_a, s_fl, s_mask, s_flag, tid);
     if (tid < M) {
         s_gamT[tid] = SMM_NEG_INF;
         s_used[tid] = 0;

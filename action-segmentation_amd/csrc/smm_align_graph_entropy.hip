@@ -32,15 +32,24 @@
 #include "smm_align_lse.h"
 #include "smm_align_graph.h"
 
-#define SMM_AGE_RNG 5              // ints per column (smm_align_graph_logz.hip: SMM_AGL_RNG)
-
-// log Z and A / Z of one more weight list are two passes: this is the second one's step
+// Hloc of the weights cand(f) hands to f(w): log Z and A / Z are two passes over them
 __device__ __forceinline__ void age_add(double w, double ref, double &z, double &a)
 {
     const double x = w - ref;
     const double e = exp(x);
     z = z + e;
     a = a + (e > 0.0 ? e * x : 0.0);
+}
+
+template <class Cand>
+__device__ __forceinline__ double age_decide(Cand cand)
+{
+    double mx = SMM_NEG_INF;
+    cand([&](double w) { mx = align_max(mx, w); });
+    const double ref = align_nonfinite_bits(mx) ? 0.0 : mx;
+    double z = 0.0, dot = 0.0;
+    cand([&](double w) { age_add(w, ref, z, dot); });
+    return log(z) - dot / z;
 }
 
 __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_entropy_kernel(SmmAlignEntropyArgs a)
@@ -50,14 +59,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_entropy_ker
     __shared__ double s_tr[SMM_MAX_TRANSCRIPT];                // trans[a_m][a_j], j = s_pl[i]
     __shared__ double s_red[SMM_ALIGN_THREADS / 64];
     __shared__ uint32_t s_mask[SMM_MAX_TRANSCRIPT * SMM_GRAPH_WORDS];
-    __shared__ int s_a[SMM_MAX_TRANSCRIPT];
-    __shared__ int s_fl[SMM_MAX_TRANSCRIPT];
-    __shared__ int s_lo[SMM_MAX_TRANSCRIPT], s_hi[SMM_MAX_TRANSCRIPT];       // column m's cells
-    __shared__ int s_slo[SMM_MAX_TRANSCRIPT], s_shi[SMM_MAX_TRANSCRIPT];     // the positions > 0 that hold h[.][m] and bh[.][m]
-    __shared__ int s_z[SMM_MAX_TRANSCRIPT];                    // column m has an h[0]
-    __shared__ int s_pl[SMM_MAX_TRANSCRIPT];                   // the predecessors of the column
-    __shared__ int s_wcnt[4], s_wlo[4], s_whi[4];
-    __shared__ int s_flag[2];
+    GRAPH_SHARED_NODES;
 
     const int tid = threadIdx.x;
     const int vid = a.g.order[blockIdx.x];
@@ -69,7 +71,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_entropy_ker
     const int T = v.T, cm = v.cm, kw = v.kw, M = v.M;
     bool ok = !align_nonfinite_bits(lz);       // (-inf: no alignment, an ordinary "impossible"; a finite logZ_g had a valid structure)
     if (ok) {
-        graph_load(a.g, v, s_a, s_fl, s_mask, s_flag, tid);
+        graph_load<true>(a.g, v, s_a, s_fl, s_mask, s_flag, tid);
         __syncthreads();
         ok = s_flag[0] == 0;
     }
@@ -83,32 +85,18 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_entropy_ker
     }
     const double *trans = v.trans, *len = v.len, *cum = v.cum;
     const size_t T1 = v.T1;
-    const int *rng = reinterpret_cast<const int *>(a.g.cols + a.g.hoff[vid]);
-    const double *hcol = a.g.cols + a.g.hoff[vid] + 3 * (size_t)M;
-    const double *gcol = hcol + (size_t)M * T1;
-    const double *qcol = gcol + (size_t)M * T1;
-    const double *bhcol = qcol + (size_t)M * T1;
-    if (tid < M) {
-        const int *r = rng + SMM_AGE_RNG * tid;
-        s_lo[tid] = r[0]; s_hi[tid] = r[1]; s_slo[tid] = r[2]; s_shi[tid] = r[3]; s_z[tid] = r[4];
-    }
+    const double *block = a.g.cols + a.g.hoff[vid];
+    const GraphCols<const double> p = graph_cols(block, M, T1);
+    graph_load_ranges(graph_rng(block), nd, M, tid);
     __threadfence_block();
     __syncthreads();
 
-    // ---- the end node: the end nodes that have the cell (T, j), in index order
+    // ---- the end node
     double h_end = 0.0;
-    if (tid == 0) {
-        double mx = SMM_NEG_INF;
-        for (int j = 0; j < M; ++j)
-            if ((s_fl[j] & 2) && s_lo[j] <= T && T <= s_hi[j])
-                mx = align_max(mx, gcol[(size_t)j * T1 + T] + (v.endpen ? v.endpen[s_a[j]] : 0.0));
-        const double ref = align_nonfinite_bits(mx) ? 0.0 : mx;
-        double z = 0.0, dot = 0.0;
-        for (int j = 0; j < M; ++j)
-            if ((s_fl[j] & 2) && s_lo[j] <= T && T <= s_hi[j])
-                age_add(gcol[(size_t)j * T1 + T] + (v.endpen ? v.endpen[s_a[j]] : 0.0), ref, z, dot);
-        h_end = log(z) - dot / z;
-    }
+    if (tid == 0)
+        h_end = age_decide([&](auto f) {
+            graph_each_end(nd, M, T, [&](int j) { f(p.g[(size_t)j * T1 + T] + graph_closing(v.endpen, s_a[j])); });
+        });
 
     // ---- columns
     double x_span = 0.0, x_pred = 0.0;                         // this thread's cells, in the order it comes to them
@@ -119,35 +107,20 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_entropy_ker
         const int c = s_a[m];
         __syncthreads();                                       // the previous column's readers of s_len, s_h, s_pl, s_tr, s_w*
         if (lo > hi) continue;                                 // a node without a cell
-        const double *hm = hcol + (size_t)m * T1, *gm = gcol + (size_t)m * T1;
-        const double *qm = qcol + (size_t)m * T1, *bhm = bhcol + (size_t)m * T1;
+        const double *hm = p.h + (size_t)m * T1, *gm = p.g + (size_t)m * T1;
+        const double *qm = p.q + (size_t)m * T1, *bhm = p.bh + (size_t)m * T1;
         const double *cumc = cum + (size_t)c * T1;
         align_stage_len(len, cm, c, kw, d_all, s_len, tid);
         // ---- the node in front: pred(m) as the forward kernel lists it, one start s per thread
-        const bool is = tid < m && graph_edge(s_mask, m, tid) && s_lo[tid] <= s_hi[tid];
-        int slot, np, ulo, uhi;
-        graph_compact(is, is ? s_lo[tid] : 0, is ? s_hi[tid] : 0, s_wcnt, s_wlo, s_whi, tid, slot, np, ulo, uhi);
-        if (is) {
-            s_pl[slot] = tid;
-            s_tr[slot] = trans[(size_t)c * cm + s_a[tid]];
-        }
+        const int np = graph_list<false>(s_mask, m, M, nd, tid, [&](int slot, int j) { s_tr[slot] = trans[(size_t)c * cm + s_a[j]]; });
         __syncthreads();
         if (np > 1)                                            // (a single predecessor: exactly 0)
             for (int s = slo + tid; s <= shi; s += SMM_ALIGN_THREADS) {
                 const double ps = exp((hm[s] + bhm[s]) - lz);
                 if (!(ps > 0.0)) continue;                     // (nobody starts here: its candidates may all be -inf)
-                double mx = SMM_NEG_INF;
-                for (int i = 0; i < np; ++i) {
-                    const int j = s_pl[i];
-                    if (s >= s_lo[j] && s <= s_hi[j]) mx = align_max(mx, gcol[(size_t)j * T1 + s] + s_tr[i]);
-                }
-                const double ref = align_nonfinite_bits(mx) ? 0.0 : mx;
-                double z = 0.0, dot = 0.0;
-                for (int i = 0; i < np; ++i) {
-                    const int j = s_pl[i];
-                    if (s >= s_lo[j] && s <= s_hi[j]) age_add(gcol[(size_t)j * T1 + s] + s_tr[i], ref, z, dot);
-                }
-                x_pred = x_pred + ps * (log(z) - dot / z);
+                x_pred = x_pred + ps * age_decide([&](auto f) {
+                    graph_each_pred(nd, np, s, [&](int i, int j) { f(p.g[(size_t)j * T1 + s] + s_tr[i]); });
+                });
             }
         // ---- the start of the segment: the forward kernel's column again
         alogz_entropy_column(lo, hi, first ? 0 : slo, shi, d_all, s_h, s_len, tid,

@@ -36,7 +36,7 @@
 // The caller's scratch: per video five [M][T+1] blocks (eta-S, eta-E, eta+E, eta+S, D) in the order of the workspace's column
 // blocks, then per video its parts (g_len [k_rows][c_max], g_trans [c_max][c_max], g_init [c_max], V-, state), then the log Z of q the call
 // uses [b] (the check kernel's), then V+ [b].  The videos' five blocks lie in the order and at 5/4 of the cell offsets of the
-// workspace's column blocks (smm_api.hip: ALIGN_GRAPH_LOGZ holds 3 M + 4 M (T + 1) doubles per video; agb_video).
+// workspace's column blocks (smm_launch.h: smm_graph_cells_before).
 // No atomics, no private segment, every sum in a fixed order.  Static LDS: two s_len 16.2 KB, two s_tr 4 KB, eight int arrays 8 KB.
 #define SMM_ALIGN_THREADS 256
 #define SMM_ALIGN_R 3
@@ -44,7 +44,6 @@
 #include "smm_align_lse.h"
 #include "smm_align_graph.h"
 
-#define SMM_AGB_RNG 5              // ints per column (smm_align_graph_logz.hip: SMM_AGL_RNG)
 #define SMM_AGB_OCC_THREADS 256
 
 // a video's state in its parts: its terms are summed, it contributes nothing (no alignment under p, a NaN, other graphs), or
@@ -55,10 +54,12 @@
 
 __host__ __device__ inline size_t agb_part_doubles(int cm, int k_rows) { return (size_t)k_rows * cm + (size_t)cm * cm + cm + 2; }
 
-// the two sides' columns, tables and scratch blocks of one video
+// the two sides' columns, q's tables (p's are the AlignVideo's) and the scratch blocks of one video
 struct AgbVideo {
-    const double *hp, *gp, *qp, *bhp, *cump, *transp, *lenp, *endpenp;
-    const double *hq, *gq, *qq, *bhq, *cumq, *transq, *lenq, *endpenq;
+    const int *rng, *rngq;                                     // the columns' recorded ranges
+    GraphCols<const double> p, q;
+    SmmAlignSideQ tq;                                          // (trans, len, endpen: the video's)
+    const double *cumq;
     double *em_s, *em_e, *ep_e, *ep_s, *dd;                    // eta-S, eta-E, eta+E, eta+S, D: each [M][T+1]
     double *part, *vals;                                       // the video's parts; vals[0] = V-, vals[1] = state
     const uint32_t *masks;
@@ -70,40 +71,19 @@ __device__ __forceinline__ AgbVideo agb_video(const SmmAlignEntBwdArgs &a, const
     AgbVideo x;
     const size_t MT = (size_t)v.M * v.T1;
     const int64_t ho = a.g.hoff[vid];
-    x.hp = a.g.cols + ho + 3 * (size_t)v.M; x.gp = x.hp + MT; x.qp = x.gp + MT; x.bhp = x.qp + MT;
-    x.hq = a.cols_q + ho + 3 * (size_t)v.M; x.gq = x.hq + MT; x.qq = x.gq + MT; x.bhq = x.qq + MT;
-    x.cump = v.cum; x.transp = v.trans; x.lenp = v.len; x.endpenp = v.endpen;
-    x.cumq = a.hist_q + a.g.videos[vid].hist_off;
-    x.transq = a.trans_q + (size_t)v.g * v.cm * v.cm;
-    x.lenq = a.len_q + (size_t)v.g * a.g.k_rows * v.cm;
-    x.endpenq = a.endpen_q ? a.endpen_q + (size_t)vid * v.cm : nullptr;
-    // (a video's column block holds 3 M + 4 M (T + 1) doubles: the videos before it hold (hoff - 3 nodes) / 4 cells)
-    const int64_t cells = (ho - 3 * (v.t0 - a.g.toff[0])) / 4;
+    x.rng = graph_rng(a.g.cols + ho); x.rngq = graph_rng(a.q.cols + ho);
+    x.p = graph_cols<const double>(a.g.cols + ho, v.M, v.T1);
+    x.q = graph_cols<const double>(a.q.cols + ho, v.M, v.T1);
+    x.tq = graph_side_q(a.q, v, a.g.k_rows, vid);
+    x.cumq = a.q.hist + a.g.videos[vid].hist_off;
+    const int64_t cells = smm_graph_cells_before(ho, v.t0 - a.g.toff[0]);
     x.em_s = a.scratch + 5 * cells; x.em_e = x.em_s + MT; x.ep_e = x.em_e + MT; x.ep_s = x.ep_e + MT; x.dd = x.ep_s + MT;
     const size_t pf = agb_part_doubles(v.cm, a.g.k_rows);
     x.part = a.scratch + a.pv_base + (size_t)vid * pf;
     x.vals = x.part + pf - 2;
     x.masks = a.g.pred_mask + (size_t)v.t0 * SMM_GRAPH_WORDS;
-    x.lzp = a.g.logz[vid]; x.lzq = a.logz_q[vid];
+    x.lzp = a.g.logz[vid]; x.lzq = a.q.logz[vid];
     return x;
-}
-
-// classes, flags and p's ranges -> LDS; false where the structure is invalid or q's ranges are not p's (every thread calls it)
-__device__ __forceinline__ bool agb_load(const SmmAlignEntBwdArgs &a, const AlignVideo &v, int vid, int *s_a, int *s_fl, int *s_lo,
-                                         int *s_hi, int *s_slo, int *s_shi, int *s_z, int *s_flag, int tid)
-{
-    if (tid < 2) s_flag[tid] = 0;
-    __syncthreads();
-    graph_load_nodes(a.g, v, s_a, s_fl, s_flag, tid);
-    if (tid < v.M) {
-        const int *r = reinterpret_cast<const int *>(a.g.cols + a.g.hoff[vid]) + SMM_AGB_RNG * tid;
-        const int *rq = reinterpret_cast<const int *>(a.cols_q + a.g.hoff[vid]) + SMM_AGB_RNG * tid;
-        s_lo[tid] = r[0]; s_hi[tid] = r[1]; s_slo[tid] = r[2]; s_shi[tid] = r[3]; s_z[tid] = r[4];
-        if (rq[0] != r[0] || rq[1] != r[1] || rq[2] != r[2] || rq[3] != r[3] || rq[4] != r[4]) s_flag[1] = 1;
-    }
-    __threadfence_block();
-    __syncthreads();
-    return s_flag[0] == 0 && s_flag[1] == 0;
 }
 
 // ---- one decision: the sums of its second pass (smm_align_lse.h: akl_add) and the expected eta of the chosen candidate
@@ -159,15 +139,6 @@ __device__ __forceinline__ double agb_term(double xp, double xq, double eta, dou
     return po * ((eta + l) - val);
 }
 
-#define AGB_SHARED_NODES                                                                                                         \
-    __shared__ double s_lenp[SMM_ALIGN_LEN], s_lenq[SMM_ALIGN_LEN];                                                              \
-    __shared__ double s_trp[SMM_MAX_TRANSCRIPT], s_trq[SMM_MAX_TRANSCRIPT];                                                      \
-    __shared__ int s_a[SMM_MAX_TRANSCRIPT], s_fl[SMM_MAX_TRANSCRIPT];                                                            \
-    __shared__ int s_lo[SMM_MAX_TRANSCRIPT], s_hi[SMM_MAX_TRANSCRIPT], s_slo[SMM_MAX_TRANSCRIPT], s_shi[SMM_MAX_TRANSCRIPT];     \
-    __shared__ int s_z[SMM_MAX_TRANSCRIPT], s_pl[SMM_MAX_TRANSCRIPT];                                                            \
-    __shared__ int s_wcnt[4], s_wlo[4], s_whi[4];                                                                                \
-    __shared__ int s_flag[2]
-
 // ---- q's workspace, before anything in it is read or written through p's offsets: thread m compares the five ints the two
 // forward calls recorded for column m (a function of graph, T and span limit only).  out[vid] is the log Z of q that every later
 // kernel of the call sees, the q-side launch of smm_align_graph_logz_bwd_kernel included, which skips a video whose log Z is not
@@ -187,11 +158,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_entropy_bwd
     if (tid == 0) s_diff = 0;
     __syncthreads();
     const int M = (int)(a.g.toff[vid + 1] - a.g.toff[vid]);
-    if (tid < M) {
-        const int *r = reinterpret_cast<const int *>(a.g.cols + a.g.hoff[vid]) + SMM_AGB_RNG * tid;
-        const int *rq = reinterpret_cast<const int *>(a.cols_q + a.g.hoff[vid]) + SMM_AGB_RNG * tid;
-        if (rq[0] != r[0] || rq[1] != r[1] || rq[2] != r[2] || rq[3] != r[3] || rq[4] != r[4]) s_diff = 1;
-    }
+    if (tid < M && graph_range_differs(graph_rng(a.g.cols + a.g.hoff[vid]), graph_rng(a.q.cols + a.g.hoff[vid]), tid)) s_diff = 1;
     __syncthreads();
     if (tid == 0) out[vid] = s_diff ? __builtin_nan("") : lzq;
 }
@@ -199,87 +166,71 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_entropy_bwd
 // ---- eta-, V-, and each video's state
 __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_eta_minus_kernel(SmmAlignEntBwdArgs a)
 {
-    AGB_SHARED_NODES;
+    GRAPH_SHARED_SIDES;
     const int tid = threadIdx.x;
     const int vid = a.g.order[blockIdx.x];
     const AlignVideo v = align_video(a.g, vid);
     const AgbVideo x = agb_video(a, v, vid);
     const int T = v.T, cm = v.cm, kw = v.kw, M = v.M, kl = a.kl;
     const size_t T1 = v.T1;
-    const bool bad = align_bad_bits(x.lzp) || align_bad_bits(x.lzq);
-    const bool both = !bad && !align_nonfinite_bits(x.lzp) && !align_nonfinite_bits(x.lzq);
-    bool ok = both;
-    if (ok) ok = agb_load(a, v, vid, s_a, s_fl, s_lo, s_hi, s_slo, s_shi, s_z, s_flag, tid);
-    if (!ok) {
-        if (tid == 0) {
-            // p without an alignment: NaN, nothing to differentiate; p with one and q without: +inf; a NaN on either side, or a
-            // finite pair whose structure or ranges failed: NaN and the error word
-            const bool q_none = !bad && !align_nonfinite_bits(x.lzp) && align_nonfinite_bits(x.lzq);
-            const double out = q_none ? __builtin_huge_val() : __builtin_nan("");
-            if (bad || both) a.g.err[0] = 1;
-            if (a.value) a.value[vid] = out;
-            x.vals[0] = out;
-            x.vals[1] = q_none ? SMM_AGB_NAN : SMM_AGB_SKIP;
+    const GraphVerdict vd = graph_verdict(x.lzp, x.lzq);
+    if (!vd.both || !graph_load_sides(a.g, v, x.rng, x.rngq, nd, s_flag, tid)) {
+        if (tid == 0) {                                        // (p without an alignment: nothing to differentiate)
+            if (vd.error()) a.g.err[0] = 1;
+            if (a.value) a.value[vid] = vd.answer();
+            x.vals[0] = vd.answer();
+            x.vals[1] = vd.q_none ? SMM_AGB_NAN : SMM_AGB_SKIP;
         }
         return;
     }
 
     const int d_all = align_d_all(kw);
     for (int m = 0; m < M; ++m) {
-        const int lo = s_lo[m], hi = s_hi[m], slo = s_slo[m], shi = s_shi[m];
-        const bool first = s_z[m] != 0;
+        const GraphRange r = graph_range(nd, m);
         const int c = s_a[m];
         __syncthreads();                                       // the previous column's readers of s_len*, s_pl, s_tr*, s_w*
-        if (lo > hi) continue;                                 // a node without a cell
-        const double *hmp = x.hp + (size_t)m * T1, *hmq = x.hq + (size_t)m * T1;
+        if (r.lo > r.hi) continue;                             // a node without a cell
+        const double *hmp = x.p.h + (size_t)m * T1, *hmq = x.q.h + (size_t)m * T1;
         double *es = x.em_s + (size_t)m * T1, *ee = x.em_e + (size_t)m * T1;
-        align_stage_len(x.lenp, cm, c, kw, d_all, s_lenp, tid);
-        align_stage_len(x.lenq, cm, c, kw, d_all, s_lenq, tid);
+        align_stage_len(v.len, cm, c, kw, d_all, s_lenp, tid);
+        align_stage_len(x.tq.len, cm, c, kw, d_all, s_lenq, tid);
         // ---- the node in front: pred(m) as the forward kernel lists it, one start s per thread
-        const bool is = tid < m && graph_edge_row(x.masks + (size_t)m * SMM_GRAPH_WORDS, tid) && s_lo[tid] <= s_hi[tid];
-        int slot, np, ulo, uhi;
-        graph_compact(is, is ? s_lo[tid] : 0, is ? s_hi[tid] : 0, s_wcnt, s_wlo, s_whi, tid, slot, np, ulo, uhi);
-        if (is) {
-            s_pl[slot] = tid;
-            s_trp[slot] = x.transp[(size_t)c * cm + s_a[tid]];
-            s_trq[slot] = x.transq[(size_t)c * cm + s_a[tid]];
-        }
+        const int np = graph_list<false>(x.masks, m, M, nd, tid, [&](int slot, int j) {
+            s_trp[slot] = v.trans[(size_t)c * cm + s_a[j]];
+            s_trq[slot] = x.tq.trans[(size_t)c * cm + s_a[j]];
+        });
         __syncthreads();
-        for (int s = slo + tid; s <= shi; s += SMM_ALIGN_THREADS)
+        for (int s = r.slo + tid; s <= r.shi; s += SMM_ALIGN_THREADS)
             es[s] = agb_decide(kl, [&](auto f) {
-                for (int i = 0; i < np; ++i) {
-                    const int j = s_pl[i];
-                    if (s >= s_lo[j] && s <= s_hi[j]) {
-                        const size_t at = (size_t)j * T1 + s;
-                        f(x.gp[at] + s_trp[i], x.gq[at] + s_trq[i], x.em_e + at);
-                    }
-                }
+                graph_each_pred(nd, np, s, [&](int i, int j) {
+                    const size_t at = (size_t)j * T1 + s;
+                    f(x.p.g[at] + s_trp[i], x.q.g[at] + s_trq[i], x.em_e + at);
+                });
             });
-        if (first && tid == 0) es[0] = 0.0;
+        if (r.z && tid == 0) es[0] = 0.0;
         __threadfence_block();
         __syncthreads();
-        // ---- the start of the segment
-        for (int n = lo + tid; n <= hi; n += SMM_ALIGN_THREADS)
+        // ---- the start of the segment: the starts > 0 by rising k, then 0, which adds no eta (a loop of its own: through an
+        // enumerator shared with the assembly kernel this kernel measured 0.3 % slower, the assembly up to 2.6 %)
+        for (int n = r.lo + tid; n <= r.hi; n += SMM_ALIGN_THREADS)
             ee[n] = agb_decide(kl, [&](auto f) {
                 const int kmax = kw < n ? kw : n;
-                const int k0 = n - shi > 1 ? n - shi : 1, k1 = n - slo < kmax ? n - slo : kmax;
+                const int k0 = n - r.shi > 1 ? n - r.shi : 1, k1 = n - r.slo < kmax ? n - r.slo : kmax;
                 for (int k = k0; k <= k1; ++k)
                     f(hmp[n - k] + s_lenp[k + SMM_ALIGN_R], hmq[n - k] + s_lenq[k + SMM_ALIGN_R], es + (n - k));
-                if (first && n <= kw) f(hmp[0] + s_lenp[n + SMM_ALIGN_R], hmq[0] + s_lenq[n + SMM_ALIGN_R], nullptr);
+                if (r.z && n <= kw) f(hmp[0] + s_lenp[n + SMM_ALIGN_R], hmq[0] + s_lenq[n + SMM_ALIGN_R], nullptr);
             });
         __threadfence_block();
     }
     __syncthreads();
 
-    // ---- the end node: the end nodes that have the cell (T, j), in index order
+    // ---- the end node
     if (tid == 0) {
         const double val = agb_decide(kl, [&](auto f) {
-            for (int j = 0; j < M; ++j)
-                if ((s_fl[j] & 2) && s_lo[j] <= T && T <= s_hi[j]) {
-                    const size_t at = (size_t)j * T1 + T;
-                    f(x.gp[at] + (x.endpenp ? x.endpenp[s_a[j]] : 0.0), x.gq[at] + (x.endpenq ? x.endpenq[s_a[j]] : 0.0),
-                      x.em_e + at);
-                }
+            graph_each_end(nd, M, T, [&](int j) {
+                const size_t at = (size_t)j * T1 + T;
+                f(x.p.g[at] + graph_closing(v.endpen, s_a[j]), x.q.g[at] + graph_closing(x.tq.endpen, s_a[j]), x.em_e + at);
+            });
         });
         if (val != val) a.g.err[0] = 1;                        // (a posterior that does not add up: not reached from finite logZ_g)
         if (a.value) a.value[vid] = val;
@@ -291,7 +242,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_eta_minus_k
 // ---- eta+ and V+
 __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_eta_plus_kernel(SmmAlignEntBwdArgs a)
 {
-    AGB_SHARED_NODES;
+    GRAPH_SHARED_SIDES;
     const int tid = threadIdx.x;
     const int vid = a.g.order[blockIdx.x];
     const AlignVideo v = align_video(a.g, vid);
@@ -303,48 +254,49 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_eta_plus_ke
         if (tid == 0) vplus[0] = x.vals[0];
         return;
     }
-    agb_load(a, v, vid, s_a, s_fl, s_lo, s_hi, s_slo, s_shi, s_z, s_flag, tid);
+    graph_load_sides(a.g, v, x.rng, x.rngq, nd, s_flag, tid);
 
     const int d_all = align_d_all(kw);
     for (int m = M - 1; m >= 0; --m) {
-        const int lo = s_lo[m], hi = s_hi[m], slo = s_slo[m], shi = s_shi[m];
-        const bool first = s_z[m] != 0;
+        const GraphRange r = graph_range(nd, m);
         const int c = s_a[m];
         __syncthreads();
-        if (lo > hi) continue;
-        const double *qmp = x.qp + (size_t)m * T1, *qmq = x.qq + (size_t)m * T1;
+        if (r.lo > r.hi) continue;
+        const double *qmp = x.p.q + (size_t)m * T1, *qmq = x.q.q + (size_t)m * T1;
         double *es = x.ep_s + (size_t)m * T1, *ee = x.ep_e + (size_t)m * T1;
-        align_stage_len(x.lenp, cm, c, kw, d_all, s_lenp, tid);
-        align_stage_len(x.lenq, cm, c, kw, d_all, s_lenq, tid);
+        align_stage_len(v.len, cm, c, kw, d_all, s_lenp, tid);
+        align_stage_len(x.tq.len, cm, c, kw, d_all, s_lenq, tid);
         // ---- the node behind: succ(m) as the backward kernel lists it, one end n per thread
-        const bool is = tid > m && tid < M && graph_edge_row(x.masks + (size_t)tid * SMM_GRAPH_WORDS, m) && s_slo[tid] <= s_shi[tid];
+        // (graph_list<true>'s statements with the mask row's address formed first, as a copy: through the helper this kernel
+        // measured 0.4 % slower on cfg4)
+        const bool is = tid > m && tid < M && graph_edge(x.masks + (size_t)tid * SMM_GRAPH_WORDS, 0, m) && s_slo[tid] <= s_shi[tid];
         int slot, np, ulo, uhi;
         graph_compact(is, is ? s_slo[tid] : 0, is ? s_shi[tid] : 0, s_wcnt, s_wlo, s_whi, tid, slot, np, ulo, uhi);
         if (is) {
             s_pl[slot] = tid;
-            s_trp[slot] = x.transp[(size_t)s_a[tid] * cm + c];
-            s_trq[slot] = x.transq[(size_t)s_a[tid] * cm + c];
+            s_trp[slot] = v.trans[(size_t)s_a[tid] * cm + c];
+            s_trq[slot] = x.tq.trans[(size_t)s_a[tid] * cm + c];
         }
         __syncthreads();
-        for (int n = lo + tid; n <= hi; n += SMM_ALIGN_THREADS)
+        for (int n = r.lo + tid; n <= r.hi; n += SMM_ALIGN_THREADS)
             ee[n] = n == T ? 0.0 : agb_decide(kl, [&](auto f) {
                 for (int i = 0; i < np; ++i) {
                     const int t = s_pl[i];
                     if (n >= s_slo[t] && n <= s_shi[t]) {
                         const size_t at = (size_t)t * T1 + n, cu = (size_t)s_a[t] * T1 + n;
-                        f((s_trp[i] - x.cump[cu]) + x.bhp[at], (s_trq[i] - x.cumq[cu]) + x.bhq[at], x.ep_s + at);
+                        f((s_trp[i] - v.cum[cu]) + x.p.bh[at], (s_trq[i] - x.cumq[cu]) + x.q.bh[at], x.ep_s + at);
                     }
                 }
             });
         __threadfence_block();
         __syncthreads();
         // ---- the end of the segment
-        const int smin = first ? 0 : slo;
-        for (int s = smin + tid; s <= shi; s += SMM_ALIGN_THREADS) {
-            if (s != 0 && s < slo) continue;                   // (between an h[0] and the column's other starts)
+        const int smin = r.z ? 0 : r.slo;
+        for (int s = smin + tid; s <= r.shi; s += SMM_ALIGN_THREADS) {
+            if (s != 0 && s < r.slo) continue;                 // (between an h[0] and the column's other starts)
             es[s] = agb_decide(kl, [&](auto f) {
                 const int kmax = kw < T - s ? kw : T - s;
-                const int k0 = lo - s > 1 ? lo - s : 1, k1 = hi - s < kmax ? hi - s : kmax;
+                const int k0 = r.lo - s > 1 ? r.lo - s : 1, k1 = r.hi - s < kmax ? r.hi - s : kmax;
                 for (int k = k0; k <= k1; ++k)
                     f(s_lenp[k + SMM_ALIGN_R] + qmp[s + k], s_lenq[k + SMM_ALIGN_R] + qmq[s + k], ee + (s + k));
             });
@@ -359,7 +311,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_eta_plus_ke
             for (int m = 0; m < M; ++m)
                 if (s_z[m]) {
                     const size_t at = (size_t)m * T1;
-                    f(x.hp[at] + x.bhp[at], x.hq[at] + x.bhq[at], x.ep_s + at);
+                    f(x.p.h[at] + x.p.bh[at], x.q.h[at] + x.q.bh[at], x.ep_s + at);
                 }
         });
 }
@@ -367,7 +319,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_eta_plus_ke
 // ---- the video's parts of g_trans, g_init and g_len, and D
 __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_entropy_bwd_kernel(SmmAlignEntBwdArgs a)
 {
-    AGB_SHARED_NODES;
+    GRAPH_SHARED_SIDES;
     __shared__ double s_red[SMM_ALIGN_THREADS / 64];
     const int tid = threadIdx.x;
     const int vid = a.g.order[blockIdx.x];
@@ -379,7 +331,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_entropy_bwd
     const double val = x.vals[0], lzp = x.lzp, lzq = x.lzq;
     double *lpart = x.part, *tpart = x.part + (size_t)a.g.k_rows * cm, *ipart = tpart + (size_t)cm * cm;
     for (int e = tid; e < a.g.k_rows * cm + cm * cm + cm; e += SMM_ALIGN_THREADS) lpart[e] = 0.0;
-    agb_load(a, v, vid, s_a, s_fl, s_lo, s_hi, s_slo, s_shi, s_z, s_flag, tid);   // (its barriers: the zeros before the sums)
+    graph_load_sides(a.g, v, x.rng, x.rngq, nd, s_flag, tid);  // (its barriers: the zeros before the sums)
 
     const int d_all = align_d_all(kw);
     for (int m = 0; m < M; ++m) {
@@ -389,20 +341,21 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_entropy_bwd
         __syncthreads();
         if (lo > hi) continue;
         const size_t col = (size_t)m * T1;
-        const double *hmp = x.hp + col, *hmq = x.hq + col, *qmp = x.qp + col, *qmq = x.qq + col;
-        const double *bhmp = x.bhp + col, *bhmq = x.bhq + col;
-        const double *cump = x.cump + (size_t)c * T1, *cumq = x.cumq + (size_t)c * T1;
+        const double *hmp = x.p.h + col, *hmq = x.q.h + col, *qmp = x.p.q + col, *qmq = x.q.q + col;
+        const double *bhmp = x.p.bh + col, *bhmq = x.q.bh + col;
+        const double *cump = v.cum + (size_t)c * T1, *cumq = x.cumq + (size_t)c * T1;
         const double *es = x.em_s + col, *ee = x.ep_e + col, *ps = x.ep_s + col;
         double *dm = x.dd + col;
-        align_stage_len(x.lenp, cm, c, kw, d_all, s_lenp, tid);
-        align_stage_len(x.lenq, cm, c, kw, d_all, s_lenq, tid);
-        const bool is = tid < m && graph_edge_row(x.masks + (size_t)m * SMM_GRAPH_WORDS, tid) && s_lo[tid] <= s_hi[tid];
+        align_stage_len(v.len, cm, c, kw, d_all, s_lenp, tid);
+        align_stage_len(x.tq.len, cm, c, kw, d_all, s_lenq, tid);
+        // (graph_list's statements with the mask row's address formed first, as a copy: see the span loops below)
+        const bool is = tid < m && graph_edge(x.masks + (size_t)m * SMM_GRAPH_WORDS, 0, tid) && s_lo[tid] <= s_hi[tid];
         int slot, np, ulo, uhi;
         graph_compact(is, is ? s_lo[tid] : 0, is ? s_hi[tid] : 0, s_wcnt, s_wlo, s_whi, tid, slot, np, ulo, uhi);
         if (is) {
             s_pl[slot] = tid;
-            s_trp[slot] = x.transp[(size_t)c * cm + s_a[tid]];
-            s_trq[slot] = x.transq[(size_t)c * cm + s_a[tid]];
+            s_trp[slot] = v.trans[(size_t)c * cm + s_a[tid]];
+            s_trq[slot] = x.tq.trans[(size_t)c * cm + s_a[tid]];
         }
         __syncthreads();
         // ---- the edges into m: one block sum each, in the list's order
@@ -413,13 +366,15 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_entropy_bwd
             double acc = 0.0;
             for (int s = e0 + tid; s <= e1; s += SMM_ALIGN_THREADS) {
                 const size_t at = (size_t)j * T1 + s;
-                acc = acc + agb_term(x.gp[at] + ((trp - cump[s]) + bhmp[s]), x.gq[at] + ((trq - cumq[s]) + bhmq[s]),
+                acc = acc + agb_term(x.p.g[at] + ((trp - cump[s]) + bhmp[s]), x.q.g[at] + ((trq - cumq[s]) + bhmq[s]),
                                      x.em_e[at] + ps[s], lzp, lzq, val, kl);
             }
             const double tot = graph_block_sum(acc, s_red, tid);
             if (tid == 0) tpart[(size_t)c * cm + s_a[j]] += tot;
         }
         // ---- D[f][m]: the span terms that start at f minus those that end at f
+        // (eta+'s and eta-'s span loops again, as copies: through shared enumerators this kernel measured 1.5 % / 2.6 % slower
+        // on cfg2 / cfg4 at the same 120 VGPRs)
         const int dlo = first ? 0 : (slo <= shi && slo < lo ? slo : lo);
         for (int f = dlo + tid; f <= hi; f += SMM_ALIGN_THREADS) {
             double st = 0.0, en = 0.0;
@@ -465,7 +420,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_entropy_bwd
         for (int m = 0; m < M; ++m)
             if (s_z[m]) {
                 const size_t at = (size_t)m * T1;
-                ipart[s_a[m]] += agb_term(x.hp[at] + x.bhp[at], x.hq[at] + x.bhq[at], x.ep_s[at], lzp, lzq, val, kl);
+                ipart[s_a[m]] += agb_term(x.p.h[at] + x.p.bh[at], x.q.h[at] + x.q.bh[at], x.ep_s[at], lzp, lzq, val, kl);
             }
 }
 
@@ -493,7 +448,6 @@ __global__ void __launch_bounds__(SMM_AGB_OCC_THREADS) smm_align_graph_entropy_b
             if (e % cm < C) g_elp[e] = __builtin_nan("");
         return;
     }
-    const int *rng = reinterpret_cast<const int *>(a.g.cols + a.g.hoff[vid]);
     align_load_ids(a.g, v, s_a, tid, SMM_AGB_OCC_THREADS, [&](int m, bool) { s_carry[m] = 0.0; });
     __syncthreads();
     int set = 0;                                               // (two scans in a row never share their wave slots)
@@ -501,11 +455,9 @@ __global__ void __launch_bounds__(SMM_AGB_OCC_THREADS) smm_align_graph_entropy_b
         const int t = f0 + tid;
         double *row = g_elp + (size_t)t * cm;
         for (int m = 0; m < M; ++m) {
-            const int *r = rng + SMM_AGB_RNG * m;
-            const int lo = r[0], hi = r[1], slo = r[2], shi = r[3], z = r[4];
-            if (lo > hi) continue;
-            const int dlo = z ? 0 : (slo <= shi && slo < lo ? slo : lo);
-            const double e = (t < T && t >= dlo && t <= hi) ? x.dd[(size_t)m * T1 + t] : 0.0;
+            const GraphRange r = graph_range(x.rng, m);
+            if (r.lo > r.hi) continue;
+            const double e = (t < T && t >= r.dlo() && t <= r.hi) ? x.dd[(size_t)m * T1 + t] : 0.0;
             const double p = align_block_scan(e, s_carry[m], s_wave[set], tid);
             set ^= 1;
             if (tid == SMM_AGB_OCC_THREADS - 1) s_carry[m] = p;

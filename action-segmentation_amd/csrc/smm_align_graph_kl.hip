@@ -21,7 +21,7 @@
 //
 // One workgroup per video, the columns one after another, as smm_align_graph_entropy_kernel; the span part by
 // alogz_kl_column, whose tiles hold both sides' sources.  Two s_h and two s_len leave no room for the 8 KB of masks in LDS:
-// the structure is tested without storing them (graph_load_nodes) and a column reads its own mask row from global memory, one
+// the structure is tested without storing them (graph_load_sides) and a column reads its own mask row from global memory, one
 // word per thread.  A thread adds its cells in a fixed order; each total is one block sum.  No atomics, no private segment.
 // Static LDS: s_h 2 x 14.1 KB, s_len 2 x 8.1 KB, s_tr 2 x 2 KB, eight int arrays of a node each 8 KB: 56.4 KB of the 64 KB.
 #define SMM_ALIGN_THREADS 256
@@ -30,91 +30,60 @@
 #include "smm_align_lse.h"
 #include "smm_align_graph.h"
 
-#define SMM_AGK_RNG 5              // ints per column (smm_align_graph_logz.hip: SMM_AGL_RNG)
+// KLloc and Hloc of the weights cand(f) hands to f(wp, wq): two passes over them (smm_align_lse.h: akl_add, akl_loc)
+template <class Cand>
+__device__ __forceinline__ void akl_decide(Cand cand, double &kl, double &hl)
+{
+    double mp = SMM_NEG_INF, mq = SMM_NEG_INF;
+    cand([&](double wp, double wq) {
+        mp = align_max(mp, wp);
+        mq = align_max(mq, wq);
+    });
+    mp = align_nonfinite_bits(mp) ? 0.0 : mp;
+    mq = align_nonfinite_bits(mq) ? 0.0 : mq;
+    double sp = 0.0, sq = 0.0, y = 0.0, ap = 0.0;
+    bool cut = false;
+    cand([&](double wp, double wq) { akl_add(wp, wq, mp, mq, sp, sq, y, ap, cut); });
+    akl_loc(mp, mq, sp, sq, y, ap, cut, kl, hl);
+}
 
 __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_kl_kernel(SmmAlignKlArgs a)
 {
     __shared__ double s_hp[SMM_ALIGN_HS], s_hq[SMM_ALIGN_HS];
-    __shared__ double s_lenp[SMM_ALIGN_LEN], s_lenq[SMM_ALIGN_LEN];
-    __shared__ double s_trp[SMM_MAX_TRANSCRIPT], s_trq[SMM_MAX_TRANSCRIPT];   // trans[a_m][a_j], j = s_pl[i], of each side
     __shared__ double s_red[SMM_ALIGN_THREADS / 64];
-    __shared__ int s_a[SMM_MAX_TRANSCRIPT];
-    __shared__ int s_fl[SMM_MAX_TRANSCRIPT];
-    __shared__ int s_lo[SMM_MAX_TRANSCRIPT], s_hi[SMM_MAX_TRANSCRIPT];       // column m's cells
-    __shared__ int s_slo[SMM_MAX_TRANSCRIPT], s_shi[SMM_MAX_TRANSCRIPT];     // the positions > 0 that hold h[.][m] and bh[.][m]
-    __shared__ int s_z[SMM_MAX_TRANSCRIPT];                    // column m has an h[0]
-    __shared__ int s_pl[SMM_MAX_TRANSCRIPT];                   // the predecessors of the column
-    __shared__ int s_wcnt[4], s_wlo[4], s_whi[4];
-    __shared__ int s_flag[2];                                  // [0] an id or a mask bit out of range, [1] q's ranges are not p's
+    GRAPH_SHARED_SIDES;                                        // (s_flag[1]: q's ranges are not p's)
 
     const int tid = threadIdx.x;
     const int vid = a.g.order[blockIdx.x];
     double *parts = a.kl_parts ? a.kl_parts + 3 * (size_t)vid : nullptr;
-    const double lz = a.g.logz[vid], lzq = a.logz_q[vid];
-    if (tid < 2) s_flag[tid] = 0;
-    __syncthreads();
+    const double lz = a.g.logz[vid];
     const AlignVideo v = align_video(a.g, vid);
     const int T = v.T, cm = v.cm, kw = v.kw, M = v.M;
     const size_t T1 = v.T1;
-    const int *rng = reinterpret_cast<const int *>(a.g.cols + a.g.hoff[vid]);
-    const int *rngq = reinterpret_cast<const int *>(a.cols_q + a.g.hoff[vid]);
-    const bool bad = align_bad_bits(lz) || align_bad_bits(lzq);
-    const bool both = !bad && !align_nonfinite_bits(lz) && !align_nonfinite_bits(lzq);   // (-inf: an ordinary "impossible")
-    bool ok = both;
-    if (ok) {                                                  // (a finite logZ_g had a valid structure and wrote its ranges)
-        graph_load_nodes(a.g, v, s_a, s_fl, s_flag, tid);
-        if (tid < M) {
-            const int *r = rng + SMM_AGK_RNG * tid, *rq = rngq + SMM_AGK_RNG * tid;
-            s_lo[tid] = r[0]; s_hi[tid] = r[1]; s_slo[tid] = r[2]; s_shi[tid] = r[3]; s_z[tid] = r[4];
-            if (rq[0] != r[0] || rq[1] != r[1] || rq[2] != r[2] || rq[3] != r[3] || rq[4] != r[4]) s_flag[1] = 1;
-        }
-        __threadfence_block();
-        __syncthreads();
-        ok = s_flag[0] == 0 && s_flag[1] == 0;
-    }
-    if (!ok) {
+    const double *block = a.g.cols + a.g.hoff[vid], *blockq = a.q.cols + a.g.hoff[vid];
+    const GraphVerdict vd = graph_verdict(lz, a.q.logz[vid]);
+    if (!vd.both || !graph_load_sides(a.g, v, graph_rng(block), graph_rng(blockq), nd, s_flag, tid)) {
         if (tid == 0) {
-            // p without an alignment: NaN; p with one and q without: +inf; a NaN on either side, or a finite pair whose
-            // structure or ranges failed: NaN and the error word (staging cleared the word p's forward call had set)
-            const bool q_none = !bad && !align_nonfinite_bits(lz) && align_nonfinite_bits(lzq);
-            const double out = q_none ? __builtin_huge_val() : __builtin_nan("");
-            if (bad || both) a.g.err[0] = 1;
-            a.kl_out[vid] = out;
-            if (a.xent_out) a.xent_out[vid] = out;
-            if (parts) parts[0] = parts[1] = parts[2] = out;
+            if (vd.error()) a.g.err[0] = 1;
+            a.kl_out[vid] = vd.answer();
+            if (a.xent_out) a.xent_out[vid] = vd.answer();
+            if (parts) parts[0] = parts[1] = parts[2] = vd.answer();
         }
         return;
     }
-    const double *trans = v.trans, *len = v.len, *cum = v.cum;
-    const double *transq = a.trans_q + (size_t)v.g * cm * cm, *lenq = a.len_q + (size_t)v.g * a.g.k_rows * cm;
-    const double *endpenq = a.endpen_q ? a.endpen_q + (size_t)vid * cm : nullptr;
-    const double *hcol = a.g.cols + a.g.hoff[vid] + 3 * (size_t)M;
-    const double *gcol = hcol + (size_t)M * T1;
-    const double *qcol = gcol + (size_t)M * T1;
-    const double *bhcol = qcol + (size_t)M * T1;
-    const double *hcolq = a.cols_q + a.g.hoff[vid] + 3 * (size_t)M;
-    const double *gcolq = hcolq + (size_t)M * T1;
+    const double *len = v.len, *cum = v.cum;
+    const SmmAlignSideQ sq = graph_side_q(a.q, v, a.g.k_rows, vid);
+    const GraphCols<const double> p = graph_cols(block, M, T1), q = graph_cols(blockq, M, T1);
     const uint32_t *masks = a.g.pred_mask + (size_t)v.t0 * SMM_GRAPH_WORDS;
 
-    // ---- the end node: the end nodes that have the cell (T, j), in index order
+    // ---- the end node
     double kl_end = 0.0, h_end = 0.0;
-    if (tid == 0) {
-        double mp = SMM_NEG_INF, mq = SMM_NEG_INF;
-        for (int j = 0; j < M; ++j)
-            if ((s_fl[j] & 2) && s_lo[j] <= T && T <= s_hi[j]) {
-                mp = align_max(mp, gcol[(size_t)j * T1 + T] + (v.endpen ? v.endpen[s_a[j]] : 0.0));
-                mq = align_max(mq, gcolq[(size_t)j * T1 + T] + (endpenq ? endpenq[s_a[j]] : 0.0));
-            }
-        mp = align_nonfinite_bits(mp) ? 0.0 : mp;
-        mq = align_nonfinite_bits(mq) ? 0.0 : mq;
-        double sp = 0.0, sq = 0.0, y = 0.0, ap = 0.0;
-        bool cut = false;
-        for (int j = 0; j < M; ++j)
-            if ((s_fl[j] & 2) && s_lo[j] <= T && T <= s_hi[j])
-                akl_add(gcol[(size_t)j * T1 + T] + (v.endpen ? v.endpen[s_a[j]] : 0.0),
-                        gcolq[(size_t)j * T1 + T] + (endpenq ? endpenq[s_a[j]] : 0.0), mp, mq, sp, sq, y, ap, cut);
-        akl_loc(mp, mq, sp, sq, y, ap, cut, kl_end, h_end);
-    }
+    if (tid == 0)
+        akl_decide([&](auto f) {
+            graph_each_end(nd, M, T, [&](int j) {
+                f(p.g[(size_t)j * T1 + T] + graph_closing(v.endpen, s_a[j]), q.g[(size_t)j * T1 + T] + graph_closing(sq.endpen, s_a[j]));
+            });
+        }, kl_end, h_end);
 
     // ---- columns
     double k_span = 0.0, k_pred = 0.0, h_span = 0.0, h_pred = 0.0;   // this thread's cells, in the order it comes to them
@@ -125,45 +94,28 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_kl_kernel(S
         const int c = s_a[m];
         __syncthreads();                                       // the previous column's readers of s_len*, s_h*, s_pl, s_tr*, s_w*
         if (lo > hi) continue;                                 // a node without a cell
-        const double *hm = hcol + (size_t)m * T1, *gm = gcol + (size_t)m * T1;
-        const double *qm = qcol + (size_t)m * T1, *bhm = bhcol + (size_t)m * T1;
-        const double *hmq = hcolq + (size_t)m * T1;
+        const double *hm = p.h + (size_t)m * T1, *gm = p.g + (size_t)m * T1;
+        const double *qm = p.q + (size_t)m * T1, *bhm = p.bh + (size_t)m * T1;
+        const double *hmq = q.h + (size_t)m * T1;
         const double *cumc = cum + (size_t)c * T1;
         align_stage_len(len, cm, c, kw, d_all, s_lenp, tid);
-        align_stage_len(lenq, cm, c, kw, d_all, s_lenq, tid);
+        align_stage_len(sq.len, cm, c, kw, d_all, s_lenq, tid);
         // ---- the node in front: pred(m) as the forward kernel lists it, one start s per thread
-        const bool is = tid < m && graph_edge_row(masks + (size_t)m * SMM_GRAPH_WORDS, tid) && s_lo[tid] <= s_hi[tid];
-        int slot, np, ulo, uhi;
-        graph_compact(is, is ? s_lo[tid] : 0, is ? s_hi[tid] : 0, s_wcnt, s_wlo, s_whi, tid, slot, np, ulo, uhi);
-        if (is) {
-            s_pl[slot] = tid;
-            s_trp[slot] = trans[(size_t)c * cm + s_a[tid]];
-            s_trq[slot] = transq[(size_t)c * cm + s_a[tid]];
-        }
+        const int np = graph_list<false>(masks, m, M, nd, tid, [&](int slot, int j) {
+            s_trp[slot] = v.trans[(size_t)c * cm + s_a[j]];
+            s_trq[slot] = sq.trans[(size_t)c * cm + s_a[j]];
+        });
         __syncthreads();
         if (np > 0)                                            // (a single predecessor: exactly 0, or +inf where q cuts it)
             for (int s = slo + tid; s <= shi; s += SMM_ALIGN_THREADS) {
                 const double ps = exp((hm[s] + bhm[s]) - lz);
                 if (!(ps > 0.0)) continue;                     // (nobody starts here: its candidates may all be -inf)
-                double mp = SMM_NEG_INF, mq = SMM_NEG_INF;
-                for (int i = 0; i < np; ++i) {
-                    const int j = s_pl[i];
-                    if (s >= s_lo[j] && s <= s_hi[j]) {
-                        mp = align_max(mp, gcol[(size_t)j * T1 + s] + s_trp[i]);
-                        mq = align_max(mq, gcolq[(size_t)j * T1 + s] + s_trq[i]);
-                    }
-                }
-                mp = align_nonfinite_bits(mp) ? 0.0 : mp;
-                mq = align_nonfinite_bits(mq) ? 0.0 : mq;
-                double sp = 0.0, sq = 0.0, y = 0.0, ap = 0.0;
-                bool cut = false;
-                for (int i = 0; i < np; ++i) {
-                    const int j = s_pl[i];
-                    if (s >= s_lo[j] && s <= s_hi[j])
-                        akl_add(gcol[(size_t)j * T1 + s] + s_trp[i], gcolq[(size_t)j * T1 + s] + s_trq[i], mp, mq, sp, sq, y, ap, cut);
-                }
                 double kl, hl;
-                akl_loc(mp, mq, sp, sq, y, ap, cut, kl, hl);
+                akl_decide([&](auto f) {
+                    graph_each_pred(nd, np, s, [&](int i, int j) {
+                        f(p.g[(size_t)j * T1 + s] + s_trp[i], q.g[(size_t)j * T1 + s] + s_trq[i]);
+                    });
+                }, kl, hl);
                 k_pred = k_pred + ps * kl;
                 h_pred = h_pred + ps * (hl + kl);
             }

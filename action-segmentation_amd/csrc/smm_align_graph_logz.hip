@@ -42,7 +42,6 @@
 #include "smm_align_graph.h"
 
 #define SMM_GRAPH_U 4                                            // positions per thread and round when h is formed
-#define SMM_AGL_RNG 5                                            // ints per column (smm_align_opt_logz.hip: SMM_AOL_RNG)
 
 __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_logz_fwd_kernel(SmmAlignLogzArgs a)
 {
@@ -67,13 +66,13 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_logz_fwd_ke
     const int T = v.T, cm = v.cm, kw = v.kw, M = v.M;
     const double *trans = v.trans, *len = v.len, *endpen = v.endpen, *cum = v.cum;
     const size_t T1 = v.T1;
-    int *rng = reinterpret_cast<int *>(a.cols + a.hoff[vid]);  // [M][SMM_AGL_RNG], in 3 M doubles
-    double *hcol = a.cols + a.hoff[vid] + 3 * (size_t)M;       // [M][T+1]
-    double *gcol = hcol + (size_t)M * T1;                      // [M][T+1]
+    int *rng = reinterpret_cast<int *>(a.cols + a.hoff[vid]);  // [M][SMM_GRAPH_RNG]: this kernel is their only writer
+    const GraphCols<double> col = graph_cols(a.cols + a.hoff[vid], M, T1);
+    double *hcol = col.h, *gcol = col.g;
 
     if (tid < 2) s_flag[tid] = 0;
     __syncthreads();
-    graph_load(a, v, s_a, s_fl, s_mask, s_flag, tid);
+    graph_load<true>(a, v, s_a, s_fl, s_mask, s_flag, tid);
     if (tid < M) s_gamT[tid] = SMM_NEG_INF;
     __syncthreads();
     if (s_flag[0] != 0 || kw < 1) {
@@ -107,7 +106,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_logz_fwd_ke
             for (int k = 1 + tid; k <= kw; k += SMM_ALIGN_THREADS)
                 if (align_bad_bits(len[(size_t)k * cm + c])) s_flag[1] = 1;
             if (tid == 0) {
-                int *r = rng + SMM_AGL_RNG * m;
+                int *r = rng + SMM_GRAPH_RNG * m;
                 r[0] = 1; r[1] = 0; r[2] = 1; r[3] = 0; r[4] = 0;
             }
             continue;
@@ -125,7 +124,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_logz_fwd_ke
         int slo = ulo > lo - kw ? ulo : lo - kw, shi = uhi < hi - 1 ? uhi : hi - 1;
         if (np == 0 || slo > shi) { slo = 1; shi = 0; }
         if (tid == 0) {
-            int *r = rng + SMM_AGL_RNG * m;
+            int *r = rng + SMM_GRAPH_RNG * m;
             r[0] = lo; r[1] = hi; r[2] = slo; r[3] = shi; r[4] = first ? 1 : 0;
         }
         __syncthreads();
@@ -209,15 +208,8 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_logz_bwd_ke
     __shared__ double s_tr[SMM_MAX_TRANSCRIPT];                // trans[a_m][a_j], m = s_ps[i]
     __shared__ double s_red[SMM_ALIGN_THREADS / 64];
     __shared__ uint32_t s_mask[SMM_MAX_TRANSCRIPT * SMM_GRAPH_WORDS];
-    __shared__ int s_a[SMM_MAX_TRANSCRIPT];
-    __shared__ int s_fl[SMM_MAX_TRANSCRIPT];
-    __shared__ int s_lo[SMM_MAX_TRANSCRIPT], s_hi[SMM_MAX_TRANSCRIPT];       // column m's cells
-    __shared__ int s_slo[SMM_MAX_TRANSCRIPT], s_shi[SMM_MAX_TRANSCRIPT];     // the positions > 0 that hold h[.][m] and bh[.][m]
-    __shared__ int s_z[SMM_MAX_TRANSCRIPT];                    // column m has an h[0]
-    __shared__ int s_pl[SMM_MAX_TRANSCRIPT];                   // the successors of the column in index order
-    __shared__ int s_ps[SMM_MAX_TRANSCRIPT];                   // ... in (class, index) order
-    __shared__ int s_wcnt[4], s_wlo[4], s_whi[4];
-    __shared__ int s_flag[2];
+    __shared__ int s_ps[SMM_MAX_TRANSCRIPT];                   // the successors of the column in (class, index) order
+    GRAPH_SHARED_NODES;                                        // (s_pl: ... in index order)
 
     const int tid = threadIdx.x;
     const int vid = a.order[blockIdx.x];
@@ -237,11 +229,9 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_logz_bwd_ke
     const double *trans = v.trans, *len = v.len, *endpen = v.endpen;
     const size_t T1 = v.T1;
     const double *cum = v.cum;                                 // [C][T+1], the forward call's
-    const int *rng = reinterpret_cast<const int *>(a.cols + a.hoff[vid]);
-    const double *hcol = a.cols + a.hoff[vid] + 3 * (size_t)M;
-    const double *gcol = hcol + (size_t)M * T1;
-    double *qcol = a.cols + a.hoff[vid] + 3 * (size_t)M + 2 * (size_t)M * T1;   // [M][T+1]
-    double *bhcol = qcol + (size_t)M * T1;                     // [M][T+1]
+    const GraphCols<double> col = graph_cols(a.cols + a.hoff[vid], M, T1);
+    const double *hcol = col.h, *gcol = col.g;
+    double *qcol = col.q, *bhcol = col.bh;                     // (written here)
     const int rows = a.k_rows < T + 1 ? a.k_rows : T + 1;
     double *tpart = a.part + a.poff[vid] + (size_t)rows * cm;  // [c_max][c_max], then [c_max], then the backward pass's logZ_g
     double *ipart = tpart + (size_t)cm * cm;
@@ -251,11 +241,8 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_logz_bwd_ke
     if (tid < 2) s_flag[tid] = 0;
     for (int e = tid; e < cm * cm + cm; e += SMM_ALIGN_THREADS) tpart[e] = 0.0;
     __syncthreads();
-    graph_load(a, v, s_a, s_fl, s_mask, s_flag, tid);          // (a finite logZ_g had a valid structure)
-    if (tid < M) {
-        const int *r = rng + SMM_AGL_RNG * tid;
-        s_lo[tid] = r[0]; s_hi[tid] = r[1]; s_slo[tid] = r[2]; s_shi[tid] = r[3]; s_z[tid] = r[4];
-    }
+    graph_load<true>(a, v, s_a, s_fl, s_mask, s_flag, tid);          // (a finite logZ_g had a valid structure)
+    graph_load_ranges(graph_rng(a.cols + a.hoff[vid]), nd, M, tid);
     __threadfence_block();
     __syncthreads();
     if (s_flag[0] != 0) return;
@@ -277,10 +264,8 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_logz_bwd_ke
         const double *gm = gcol + (size_t)m * T1, *cumc = cum + (size_t)c * T1;
         double *qm = qcol + (size_t)m * T1, *bhm = bhcol + (size_t)m * T1;
         // ---- succ(m): the later nodes that name m in their own mask and hold bh values, first in index order ...
-        const bool is = tid > m && tid < M && graph_edge(s_mask, tid, m) && s_slo[tid] <= s_shi[tid];
-        int slot, np, ulo, uhi;
-        graph_compact(is, is ? s_slo[tid] : 0, is ? s_shi[tid] : 0, s_wcnt, s_wlo, s_whi, tid, slot, np, ulo, uhi);
-        if (is) s_pl[slot] = tid;
+        bool is = false;
+        const int np = graph_list<true>(s_mask, m, M, nd, tid, [&](int, int) { is = true; });
         __syncthreads();
         // ... then by class: a successor's place is the number of listed nodes of a smaller class, or of its class before it
         if (is) {

@@ -28,7 +28,6 @@
 #include "smm_align_graph.h"
 #include "smm_draw.h"
 
-#define SMM_AGS_RNG 5              // ints per column (smm_align_graph_logz.hip: SMM_AGL_RNG)
 #define SMM_AGS_NK 16              // span candidates per lane: 16 x 64 >= SMM_MAX_K_ROWS - 1
 #define SMM_AGS_NM 4               // node candidates per lane: 4 x 64 = SMM_MAX_TRANSCRIPT
 #define SMM_AGS_STREAM 1u          // the last counter word (smm_sample.hip: 0)
@@ -56,9 +55,9 @@ __device__ void ags_sample_one(const SmmAlignSampleArgs &a, int vid, int smp, in
     double lp = 0.0;                           // (wave-uniform)
     int segs = 0;
     if (ok) {
-        const int *rng = reinterpret_cast<const int *>(a.g.cols + a.g.hoff[vid]);
-        const double *hcol = a.g.cols + a.g.hoff[vid] + 3 * (size_t)M;
-        const double *gcol = hcol + (size_t)M * T1;
+        const int *rng = graph_rng(a.g.cols + a.g.hoff[vid]);
+        const GraphCols<const double> col = graph_cols<const double>(a.g.cols + a.g.hoff[vid], M, T1);
+        const double *hcol = col.h, *gcol = col.g;
         const int32_t *cls = a.g.transcript + v.t0;
         const uint8_t *fl = a.g.node_flags + v.t0;
         const uint32_t *mask = a.g.pred_mask + (size_t)v.t0 * SMM_GRAPH_WORDS;
@@ -72,18 +71,18 @@ __device__ void ags_sample_one(const SmmAlignSampleArgs &a, int vid, int smp, in
             const int m = i * 64 + lane;
             we[i] = SMM_NEG_INF;
             if (m < M && (fl[m] & 2)) {
-                const int *r = rng + SMM_AGS_RNG * m;
-                if (r[0] <= T && T <= r[1]) we[i] = gcol[(size_t)m * T1 + T] + (v.endpen ? v.endpen[cls[m]] : 0.0);
+                const GraphRange r = graph_range(rng, m);
+                if (r.lo <= T && T <= r.hi) we[i] = gcol[(size_t)m * T1 + T] + graph_closing(v.endpen, cls[m]);
             }
         }
         int j = smm_draw<SMM_AGS_NM>(we, smm_uniform53(a.seed, vid, smp, dec++, SMM_AGS_STREAM), lane);
         if (j < 0 || j >= M) ok = false;
-        else lp += v.endpen ? v.endpen[cls[j]] : 0.0;
+        else lp += graph_closing(v.endpen, cls[j]);
         while (ok) {
             // ---- the start of the segment of node j that ends at n
             const int c = cls[j];
-            const int *rj = rng + SMM_AGS_RNG * j;
-            const int slo = rj[2], shi = rj[3], z = rj[4];
+            const GraphRange rj = graph_range(rng, j);
+            const int slo = rj.slo, shi = rj.shi, z = rj.z;
             const double *hj = hcol + (size_t)j * T1;
             const int kmax = kw < n ? kw : n;
             double w[SMM_AGS_NK];
@@ -118,8 +117,8 @@ __device__ void ags_sample_one(const SmmAlignSampleArgs &a, int vid, int smp, in
                 const int m = i * 64 + lane;
                 wp[i] = SMM_NEG_INF;
                 if (m < j && ((mask[(size_t)j * SMM_GRAPH_WORDS + (m >> 5)] >> (m & 31)) & 1u)) {
-                    const int *r = rng + SMM_AGS_RNG * m;
-                    if (s >= r[0] && s <= r[1]) wp[i] = gcol[(size_t)m * T1 + s] + v.trans[(size_t)c * cm + cls[m]];
+                    const GraphRange r = graph_range(rng, m);
+                    if (s >= r.lo && s <= r.hi) wp[i] = gcol[(size_t)m * T1 + s] + v.trans[(size_t)c * cm + cls[m]];
                 }
             }
             const int jp = smm_draw<SMM_AGS_NM>(wp, smm_uniform53(a.seed, vid, smp, dec++, SMM_AGS_STREAM), lane);

@@ -2040,8 +2040,8 @@ static const AlignFamily ALIGN_OPT_LOGZ = {
     [](const smm_shape *s, int64_t t) { return glen_part(s, t) + (size_t)((int64_t)s->c_max * s->c_max + s->c_max + 1); }};
 
 // ... over the paths of a transcript graph: the same block without the running sums (a column reads its neighbours' columns)
-static const AlignFamily ALIGN_GRAPH_LOGZ = {
-    [](const smm_shape *, int64_t m, int64_t t) { return (size_t)(3 * m + 4 * m * (t + 1)); }, ALIGN_OPT_LOGZ.part};
+static const AlignFamily ALIGN_GRAPH_LOGZ = {[](const smm_shape *, int64_t m, int64_t t) { return smm_graph_block_doubles(m, t); },
+                                             ALIGN_OPT_LOGZ.part};
 
 struct AlignLayout {
     size_t o_toff, o_hoff, o_poff, o_order, meta_end, o_cols, o_part, total;
@@ -2380,6 +2380,25 @@ extern "C" size_t smm_align_graph_logz_workspace_bytes(const smm_shape *shape, c
     return align_workspace_bytes(ALIGN_GRAPH_LOGZ, shape, lengths_host, node_offset_host);
 }
 
+// What the forward call and every call behind it (backward, sampler, entropy, KL, their gradients) share up to their launch: the
+// graph pointers' null test, the likelihood family's refusals, staging and arguments (the same layout, so the same columns), the
+// graph into them
+static int align_graph_prepare(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                               const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host, const double *elp,
+                               const double *trans, const double *init, const double *len_scores, const double *endpen,
+                               const int32_t *node_class, const uint32_t *pred_mask, const uint8_t *node_flags,
+                               const int64_t *node_offset_host, const double *logz_g, void *workspace, size_t workspace_bytes,
+                               hipStream_t hs, SmmAlignLogzArgs *a)
+{
+    if (!pred_mask || !node_flags) return SMM_ERR_ARG;
+    const int rc = align_logz_prepare(ALIGN_GRAPH_LOGZ, shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host,
+                                      elp, trans, init, len_scores, endpen, node_class, node_offset_host, logz_g, workspace,
+                                      workspace_bytes, hs, a);
+    if (rc != SMM_OK) return rc;
+    a->pred_mask = pred_mask; a->node_flags = node_flags;
+    return SMM_OK;
+}
+
 extern "C" int smm_align_graph_logz_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
                                         const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
                                         const double *elp, const double *trans, const double *init, const double *len_scores,
@@ -2387,14 +2406,12 @@ extern "C" int smm_align_graph_logz_f64(const smm_shape *shape, const int64_t *l
                                         const uint8_t *node_flags, const int64_t *node_offset_host, double *logz_g,
                                         void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!pred_mask || !node_flags) return SMM_ERR_ARG;
     hipStream_t hs = static_cast<hipStream_t>(stream);
     SmmAlignLogzArgs a;
-    const int rc = align_logz_prepare(ALIGN_GRAPH_LOGZ, shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host,
-                                      elp, trans, init, len_scores, endpen, node_class, node_offset_host, logz_g, workspace,
-                                      workspace_bytes, hs, &a);
+    const int rc = align_graph_prepare(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp, trans, init,
+                                       len_scores, endpen, node_class, pred_mask, node_flags, node_offset_host, logz_g, workspace,
+                                       workspace_bytes, hs, &a);
     if (rc != SMM_OK) return rc;
-    a.pred_mask = pred_mask; a.node_flags = node_flags;
     smm_launch_align_graph_logz_fwd(a, hs);
     SMM_HIP(hipGetLastError());
     return SMM_OK;
@@ -2409,22 +2426,22 @@ extern "C" int smm_align_graph_logz_bwd_f64(const smm_shape *shape, const int64_
                                             double *g_len, double *p_used, double *p_end, void *workspace, size_t workspace_bytes,
                                             void *stream)
 {
-    if (!pred_mask || !node_flags || !g_elp || !g_trans || !g_init || !g_len) return SMM_ERR_ARG;
+    if (!g_elp || !g_trans || !g_init || !g_len) return SMM_ERR_ARG;
     hipStream_t hs = static_cast<hipStream_t>(stream);
     SmmAlignLogzArgs a;
-    int rc = align_logz_prepare(ALIGN_GRAPH_LOGZ, shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp,
-                                trans, init, len_scores, endpen, node_class, node_offset_host, logz_g, workspace,
-                                workspace_bytes, hs, &a);
+    int rc = align_graph_prepare(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp, trans, init,
+                                 len_scores, endpen, node_class, pred_mask, node_flags, node_offset_host, logz_g, workspace,
+                                 workspace_bytes, hs, &a);
     if (rc == SMM_OK) rc = align_logz_bwd_outputs(shape, grad_logz, g_elp, g_trans, g_init, g_len, hs, &a);
     if (rc != SMM_OK) return rc;
-    a.pred_mask = pred_mask; a.node_flags = node_flags; a.p_used = p_used; a.p_end = p_end;
+    a.p_used = p_used; a.p_end = p_end;
     smm_launch_align_graph_logz_bwd(a, hs);
     SMM_HIP(hipGetLastError());
     return SMM_OK;
 }
 
-// alignments drawn from the graph posterior (smm_align_graph_sample.hip): the forward call's staging and arguments again (the
-// same layout, so the same columns), then the sampler's own outputs
+// alignments drawn from the graph posterior (smm_align_graph_sample.hip): the forward call's staging and arguments again, then
+// the sampler's own outputs
 extern "C" int smm_align_graph_sample_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
                                           const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
                                           const double *elp, const double *trans, const double *init, const double *len_scores,
@@ -2434,15 +2451,14 @@ extern "C" int smm_align_graph_sample_f64(const smm_shape *shape, const int64_t 
                                           int64_t *labels_out, double *logp_out, int32_t *n_segs_out, int32_t *used_out,
                                           void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!pred_mask || !node_flags || n_samples <= 0) return SMM_ERR_ARG;
+    if (n_samples <= 0) return SMM_ERR_ARG;
     if (!spans_out && !labels_out && !logp_out && !n_segs_out && !used_out) return SMM_ERR_ARG;
     hipStream_t hs = static_cast<hipStream_t>(stream);
     SmmAlignSampleArgs a{};
-    const int rc = align_logz_prepare(ALIGN_GRAPH_LOGZ, shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host,
-                                      elp, trans, init, len_scores, endpen, node_class, node_offset_host, logz_g, workspace,
-                                      workspace_bytes, hs, &a.g);
+    const int rc = align_graph_prepare(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp, trans, init,
+                                       len_scores, endpen, node_class, pred_mask, node_flags, node_offset_host, logz_g, workspace,
+                                       workspace_bytes, hs, &a.g);
     if (rc != SMM_OK) return rc;
-    a.g.pred_mask = pred_mask; a.g.node_flags = node_flags;
     a.class_map = class_map;
     a.spans = spans_out; a.labels = labels_out; a.logp = logp_out; a.n_segs = n_segs_out; a.used = used_out;
     a.total_frames = shape->total_frames; a.n_nodes = node_offset_host[shape->b];
@@ -2461,14 +2477,13 @@ extern "C" int smm_align_graph_entropy_f64(const smm_shape *shape, const int64_t
                                            const uint8_t *node_flags, const int64_t *node_offset_host, const double *logz_g,
                                            double *h_out, double *h_parts, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!pred_mask || !node_flags || !h_out) return SMM_ERR_ARG;
+    if (!h_out) return SMM_ERR_ARG;
     hipStream_t hs = static_cast<hipStream_t>(stream);
     SmmAlignEntropyArgs a{};
-    const int rc = align_logz_prepare(ALIGN_GRAPH_LOGZ, shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host,
-                                      elp, trans, init, len_scores, endpen, node_class, node_offset_host, logz_g, workspace,
-                                      workspace_bytes, hs, &a.g);
+    const int rc = align_graph_prepare(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp, trans, init,
+                                       len_scores, endpen, node_class, pred_mask, node_flags, node_offset_host, logz_g, workspace,
+                                       workspace_bytes, hs, &a.g);
     if (rc != SMM_OK) return rc;
-    a.g.pred_mask = pred_mask; a.g.node_flags = node_flags;
     a.h_out = h_out; a.h_parts = h_parts;
     smm_launch_align_graph_logz_bwd_columns(a.g, hs);
     smm_launch_align_graph_entropy(a, hs);
@@ -2476,8 +2491,38 @@ extern "C" int smm_align_graph_entropy_f64(const smm_shape *shape, const int64_t
     return SMM_OK;
 }
 
+// What the two-sided calls (KL, the gradients) refuse before anything is staged: the null tests, the layout, with `distinct`
+// one workspace for both sides, both workspaces' sizes
+static int align_graph_two_sides(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                 const int32_t *n_states_host, const int64_t *node_offset_host, const double *elp_p,
+                                 const double *trans_p, const double *init_p, const double *len_p, const int32_t *node_class,
+                                 const double *logz_p, const void *ws_p, size_t ws_p_bytes, const double *trans_q,
+                                 const double *len_q, const double *logz_q, const void *ws_q, size_t ws_q_bytes, bool distinct,
+                                 AlignLayout *lo)
+{
+    if (!trans_q || !len_q || !logz_q || !ws_q) return SMM_ERR_ARG;
+    if (!shape_ok(shape) || !lengths_host || !frame_offset_host || !n_states_host || !node_offset_host) return SMM_ERR_ARG;
+    if (!elp_p || !trans_p || !init_p || !len_p || !node_class || !logz_p || !ws_p) return SMM_ERR_ARG;
+    const int rc = align_layout(ALIGN_GRAPH_LOGZ, shape, lengths_host, node_offset_host, lo);
+    if (rc != SMM_OK) return rc;
+    if (distinct && ws_q == ws_p) return SMM_ERR_ARG;          // (one posterior against itself is the entropy call's)
+    if (ws_p_bytes < lo->total || ws_q_bytes < lo->total) return SMM_ERR_WORKSPACE;
+    return SMM_OK;
+}
+
+// ... and q's side of such a call: its histories and columns lie where the same plan and layout put p's; nothing is staged in
+// q's workspace
+static SmmAlignSideQ align_graph_side_q(const smm_shape *shape, const int64_t *lengths_host, const AlignLayout &lo,
+                                        const double *trans_q, const double *len_q, const double *endpen_q, const double *logz_q,
+                                        void *ws_q)
+{
+    Staged sq;
+    plan_point(make_plan(shape, lengths_host), ws_q, &sq);
+    return {trans_q, len_q, endpen_q, logz_q, sq.hist, reinterpret_cast<double *>(static_cast<char *>(ws_q) + lo.o_cols)};
+}
+
 // KL and cross-entropy of two graph posteriors (smm_align_graph_kl.hip): the entropy call's staging, arguments and first kernel
-// on p's workspace; q's workspace is only read -- its columns lie where the same layout puts p's, nothing is staged there
+// on p's workspace; q's workspace is only read
 extern "C" int smm_align_graph_kl_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
                                       const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
                                       const double *elp_p, const double *trans_p, const double *init_p, const double *len_scores_p,
@@ -2488,22 +2533,20 @@ extern "C" int smm_align_graph_kl_f64(const smm_shape *shape, const int64_t *len
                                       const int64_t *node_offset_host, double *kl_out, double *xent_out, double *kl_parts,
                                       void *stream)
 {
-    if (!pred_mask || !node_flags || !kl_out || !trans_q || !len_scores_q || !logz_g_q || !workspace_q) return SMM_ERR_ARG;
-    if (!shape_ok(shape) || !lengths_host || !frame_offset_host || !n_states_host || !node_offset_host) return SMM_ERR_ARG;
-    if (!elp_p || !trans_p || !init_p || !len_scores_p || !node_class || !logz_g_p || !workspace_p) return SMM_ERR_ARG;
+    if (!pred_mask || !node_flags || !kl_out) return SMM_ERR_ARG;
     AlignLayout lo;
-    int rc = align_layout(ALIGN_GRAPH_LOGZ, shape, lengths_host, node_offset_host, &lo);
-    if (rc != SMM_OK) return rc;
-    if (workspace_p_bytes < lo.total || workspace_q_bytes < lo.total) return SMM_ERR_WORKSPACE;
-    hipStream_t hs = static_cast<hipStream_t>(stream);
     SmmAlignKlArgs a{};
-    rc = align_logz_prepare(ALIGN_GRAPH_LOGZ, shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp_p,
-                            trans_p, init_p, len_scores_p, endpen_p, node_class, node_offset_host, logz_g_p, workspace_p,
-                            workspace_p_bytes, hs, &a.g);
+    int rc = align_graph_two_sides(shape, lengths_host, frame_offset_host, n_states_host, node_offset_host, elp_p, trans_p, init_p,
+                                   len_scores_p, node_class, logz_g_p, workspace_p, workspace_p_bytes, trans_q, len_scores_q,
+                                   logz_g_q, workspace_q, workspace_q_bytes, false, &lo);
     if (rc != SMM_OK) return rc;
-    a.g.pred_mask = pred_mask; a.g.node_flags = node_flags;
-    a.trans_q = trans_q; a.len_q = len_scores_q; a.endpen_q = endpen_q; a.logz_q = logz_g_q;
-    a.cols_q = reinterpret_cast<const double *>(static_cast<const char *>(workspace_q) + lo.o_cols);
+    a.q = align_graph_side_q(shape, lengths_host, lo, trans_q, len_scores_q, endpen_q, logz_g_q,
+                             const_cast<void *>(workspace_q));   // (the KL kernel only reads it)
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    rc = align_graph_prepare(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp_p, trans_p, init_p,
+                             len_scores_p, endpen_p, node_class, pred_mask, node_flags, node_offset_host, logz_g_p, workspace_p,
+                             workspace_p_bytes, hs, &a.g);
+    if (rc != SMM_OK) return rc;
     a.kl_out = kl_out; a.xent_out = xent_out; a.kl_parts = kl_parts;
     smm_launch_align_graph_logz_bwd_columns(a.g, hs);
     smm_launch_align_graph_kl(a, hs);
@@ -2512,17 +2555,16 @@ extern "C" int smm_align_graph_kl_f64(const smm_shape *shape, const int64_t *len
 }
 
 // gradients of the entropy, cross-entropy and KL of graph posteriors (smm_align_graph_entropy_bwd.hip).  The caller's scratch:
-// per video five [M][T+1] blocks, one part per video, q's log Z as the call uses it and V+ per video.  The kernels find a
-// video's five blocks from the workspace's column offsets (ALIGN_GRAPH_LOGZ above: 3 M + 4 M (T + 1) doubles per video), so
-// a change of that family's cell formula is a change of smm_align_graph_entropy_bwd.hip's agb_video
+// per video five [M][T+1] blocks in the order of the workspace's column blocks (smm_launch.h: smm_graph_cells_before), one part
+// per video, q's log Z as the call uses it and V+ per video
 static bool agbwd_layout(const smm_shape *s, const int64_t *lengths, const int64_t *noff, size_t *pv_base, size_t *total_doubles)
 {
     AlignLayout lo;
     if (align_layout(ALIGN_GRAPH_LOGZ, s, lengths, noff, &lo) != SMM_OK) return false;
-    size_t cells = 0;
-    for (int i = 0; i < s->b; ++i) cells += (size_t)(noff[i + 1] - noff[i]) * (size_t)(lengths[i] + 1);
-    *pv_base = 5 * cells;
-    *total_doubles = 5 * cells + (size_t)s->b * (smm_align_graph_entropy_bwd_part_doubles(s->c_max, s->k_rows) + 2);
+    int64_t blocks = 0;
+    for (int i = 0; i < s->b; ++i) blocks += (int64_t)smm_graph_block_doubles(noff[i + 1] - noff[i], lengths[i]);
+    *pv_base = 5 * (size_t)smm_graph_cells_before(blocks, noff[s->b] - noff[0]);
+    *total_doubles = *pv_base + (size_t)s->b * (smm_align_graph_entropy_bwd_part_doubles(s->c_max, s->k_rows) + 2);
     return true;
 }
 
@@ -2534,57 +2576,49 @@ extern "C" size_t smm_align_graph_entropy_bwd_scratch_bytes(const smm_shape *sha
     return sizeof(double) * tot;
 }
 
-// both entry points (workspace_q null: the entropy, q is p): the refusals, p's staging, each side's q and bh columns, the launch
+// both entry points (`two` false: the entropy, q's arguments are p's): the refusals, p's staging, each side's q and bh columns,
+// the launch
 static int agbwd_run(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
                      const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host, const double *elp_p,
                      const double *trans_p, const double *init_p, const double *len_p, const double *endpen_p,
                      const double *logz_p, void *ws_p, size_t ws_p_bytes, const double *trans_q, const double *len_q,
-                     const double *endpen_q, const double *logz_q, void *ws_q, size_t ws_q_bytes, const int32_t *node_class,
-                     const uint32_t *pred_mask, const uint8_t *node_flags, const int64_t *node_offset_host, int kl,
-                     const double *grad_out, double *g_elp, double *g_trans, double *g_init, double *g_len, double *value_out,
-                     void *scratch, size_t scratch_bytes, hipStream_t hs)
+                     const double *endpen_q, const double *logz_q, void *ws_q, size_t ws_q_bytes, bool two,
+                     const int32_t *node_class, const uint32_t *pred_mask, const uint8_t *node_flags,
+                     const int64_t *node_offset_host, int kl, const double *grad_out, double *g_elp, double *g_trans,
+                     double *g_init, double *g_len, double *value_out, void *scratch, size_t scratch_bytes, hipStream_t hs)
 {
     if (!pred_mask || !node_flags || !g_elp || !g_trans || !g_init || !g_len || !scratch) return SMM_ERR_ARG;
-    if (!shape_ok(shape) || !lengths_host || !frame_offset_host || !n_states_host || !node_offset_host) return SMM_ERR_ARG;
-    if (!elp_p || !trans_p || !init_p || !len_p || !node_class || !logz_p || !ws_p) return SMM_ERR_ARG;
     AlignLayout lo;
-    int rc = align_layout(ALIGN_GRAPH_LOGZ, shape, lengths_host, node_offset_host, &lo);
+    SmmAlignEntBwdArgs a{};
+    int rc = align_graph_two_sides(shape, lengths_host, frame_offset_host, n_states_host, node_offset_host, elp_p, trans_p, init_p,
+                                   len_p, node_class, logz_p, ws_p, ws_p_bytes, trans_q, len_q, logz_q, ws_q, ws_q_bytes, two, &lo);
     if (rc != SMM_OK) return rc;
-    if (ws_q && ws_q == ws_p) return SMM_ERR_ARG;              // (one posterior against itself is the entropy call's)
-    if (ws_p_bytes < lo.total || (ws_q && ws_q_bytes < lo.total)) return SMM_ERR_WORKSPACE;
     size_t pv_base = 0, tot = 0;
     agbwd_layout(shape, lengths_host, node_offset_host, &pv_base, &tot);
     if (scratch_bytes < sizeof(double) * tot) return SMM_ERR_WORKSPACE;
-    SmmAlignEntBwdArgs a{};
-    rc = align_logz_prepare(ALIGN_GRAPH_LOGZ, shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp_p,
-                            trans_p, init_p, len_p, endpen_p, node_class, node_offset_host, logz_p, ws_p, ws_p_bytes, hs, &a.g);
+    rc = align_graph_prepare(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp_p, trans_p, init_p,
+                             len_p, endpen_p, node_class, pred_mask, node_flags, node_offset_host, logz_p, ws_p, ws_p_bytes, hs,
+                             &a.g);
     if (rc == SMM_OK) rc = align_logz_bwd_outputs(shape, grad_out, g_elp, g_trans, g_init, g_len, hs, &a.g);
     if (rc != SMM_OK) return rc;
-    a.g.pred_mask = pred_mask; a.g.node_flags = node_flags;
     smm_launch_align_graph_logz_bwd_columns(a.g, hs);
     a.scratch = static_cast<double *>(scratch);
-    if (ws_q) {
+    a.q = SmmAlignSideQ{trans_p, len_p, endpen_p, logz_p, a.g.hist, a.g.cols};
+    if (two) {
         // First the recorded ranges of the two sides, video by video: a video whose ranges differ gets a NaN in place of q's
         // log Z, which the q-side launch below skips (and answers with the error word) as every later kernel does -- nothing of
         // q's workspace is read or written through ranges that were not compared.  Then q's q and bh columns and parts,
         // exactly as q's own backward call would write them first: p's staged metadata (the two sides share it), q's tables,
         // histories, columns and parts
-        Staged sq;
-        plan_point(make_plan(shape, lengths_host), ws_q, &sq);
-        char *bq = static_cast<char *>(ws_q);
         double *lzq = a.scratch + pv_base + (size_t)shape->b * smm_align_graph_entropy_bwd_part_doubles(shape->c_max, shape->k_rows);
-        a.cols_q = reinterpret_cast<double *>(bq + lo.o_cols);
+        a.q = align_graph_side_q(shape, lengths_host, lo, trans_q, len_q, endpen_q, lzq, ws_q);
         smm_launch_align_graph_entropy_bwd_check(a, logz_q, lzq, hs);
         SmmAlignLogzArgs q = a.g;
         q.trans = trans_q; q.len = len_q; q.endpen = endpen_q; q.logz = lzq;
-        q.hist = sq.hist; q.cols = reinterpret_cast<double *>(bq + lo.o_cols); q.part = reinterpret_cast<double *>(bq + lo.o_part);
+        q.hist = a.q.hist; q.cols = a.q.cols;
+        q.part = reinterpret_cast<double *>(static_cast<char *>(ws_q) + lo.o_part);
         q.grad = nullptr; q.g_elp = q.g_trans = q.g_init = q.g_len = nullptr;
         smm_launch_align_graph_logz_bwd_columns(q, hs);
-        a.trans_q = trans_q; a.len_q = len_q; a.endpen_q = endpen_q; a.logz_q = lzq;
-        a.hist_q = sq.hist;
-    } else {
-        a.trans_q = trans_p; a.len_q = len_p; a.endpen_q = endpen_p; a.logz_q = logz_p;
-        a.hist_q = a.g.hist; a.cols_q = a.g.cols;
     }
     a.value = value_out;
     a.pv_base = (int64_t)pv_base;
@@ -2604,9 +2638,9 @@ extern "C" int smm_align_graph_entropy_bwd_f64(const smm_shape *shape, const int
                                                void *workspace, size_t workspace_bytes, void *stream)
 {
     return agbwd_run(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp, trans, init, len_scores,
-                     endpen, logz_g, workspace, workspace_bytes, nullptr, nullptr, nullptr, nullptr, nullptr, 0, node_class,
-                     pred_mask, node_flags, node_offset_host, 0, grad_out, g_elp, g_trans, g_init, g_len, value_out, scratch,
-                     scratch_bytes, static_cast<hipStream_t>(stream));
+                     endpen, logz_g, workspace, workspace_bytes, trans, len_scores, endpen, logz_g, workspace, workspace_bytes,
+                     false, node_class, pred_mask, node_flags, node_offset_host, 0, grad_out, g_elp, g_trans, g_init, g_len,
+                     value_out, scratch, scratch_bytes, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int smm_align_graph_kl_bwd_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
@@ -2621,10 +2655,9 @@ extern "C" int smm_align_graph_kl_bwd_f64(const smm_shape *shape, const int64_t 
                                           double *g_len, double *value_out, void *scratch, size_t scratch_bytes, void *stream)
 {
     if (mode != SMM_KL_BWD_CROSS_ENTROPY && mode != SMM_KL_BWD_KL) return SMM_ERR_ARG;
-    if (!trans_q || !len_scores_q || !logz_g_q || !workspace_q) return SMM_ERR_ARG;
     return agbwd_run(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp_p, trans_p, init_p,
                      len_scores_p, endpen_p, logz_g_p, workspace_p, workspace_p_bytes, trans_q, len_scores_q, endpen_q, logz_g_q,
-                     workspace_q, workspace_q_bytes, node_class, pred_mask, node_flags, node_offset_host,
+                     workspace_q, workspace_q_bytes, true, node_class, pred_mask, node_flags, node_offset_host,
                      mode == SMM_KL_BWD_KL ? 1 : 0, grad_out, g_elp, g_trans, g_init, g_len, value_out, scratch, scratch_bytes,
                      static_cast<hipStream_t>(stream));
 }

@@ -296,6 +296,27 @@ void smm_launch_align_graph_logz_bwd(const SmmAlignLogzArgs &a, hipStream_t stre
 // ... its first kernel alone: the q and bh columns, the videos' parts of g_trans and g_init and, where asked for, p_used / p_end
 void smm_launch_align_graph_logz_bwd_columns(const SmmAlignLogzArgs &a, hipStream_t stream);
 
+// The block of video i at cols + hoff[i]: the columns' ranges in 3 M doubles, then h | gam | q | bh, each [M][T+1].  Its size,
+// and from a video's offset and the nodes in front of it the [M][T+1] cells in front of it (smm_align_graph_entropy_bwd.hip keeps
+// its scratch blocks in the same order)
+#define SMM_GRAPH_HEAD 3           // doubles per node in front of the columns
+__host__ __device__ inline size_t smm_graph_block_doubles(int64_t m, int64_t t) { return (size_t)(SMM_GRAPH_HEAD * m + 4 * m * (t + 1)); }
+__host__ __device__ inline int64_t smm_graph_cells_before(int64_t hoff, int64_t nodes_before)
+{
+    return (hoff - SMM_GRAPH_HEAD * nodes_before) / 4;
+}
+
+// the second side of a call on two transcript-graph posteriors: q's tables and what its own forward call left
+struct SmmAlignSideQ {
+    const double *trans;       // [g][c_max][c_max]
+    const double *len;         // [g][k_rows][c_max]
+    const double *endpen;      // [b][c_max] or null
+    const double *logz;        // [b]
+    double *hist;              // q's history area: the same plan, so the videos' hist_off serve both
+    double *cols;              // q's workspace at the offset of `cols` in p's: the same layout, so hoff serves both (the KL call
+                               // only reads the two; the gradient calls' q-side launch of the q / bh kernel writes through them)
+};
+
 // the entropy of the transcript-graph posterior (smm_align_graph_entropy.hip): after smm_launch_align_graph_logz_fwd and
 // smm_launch_align_graph_logz_bwd_columns on the same workspace -- it reads cum, the h, gam, q and bh columns and the columns'
 // ranges, and writes the error word only
@@ -312,11 +333,7 @@ void smm_launch_align_graph_entropy(const SmmAlignEntropyArgs &a, hipStream_t st
 // writes p's error word only
 struct SmmAlignKlArgs {
     SmmAlignLogzArgs g;        // p's forward launch's arguments (logz: read; the backward call's fields: unused)
-    const double *trans_q;     // [g][c_max][c_max]
-    const double *len_q;       // [g][k_rows][c_max]
-    const double *endpen_q;    // [b][c_max] or null
-    const double *logz_q;      // [b]
-    const double *cols_q;      // q's workspace at the offset of `cols` in p's: the same layout, so hoff serves both
+    SmmAlignSideQ q;           // (hist: unused)
     double *kl_out;            // [b]
     double *xent_out;          // [b] or null
     double *kl_parts;          // [b][3]: end node, span, predecessor; or null
@@ -329,12 +346,7 @@ void smm_launch_align_graph_kl(const SmmAlignKlArgs &a, hipStream_t stream);
 // writes the caller's scratch, the gradients and p's error word
 struct SmmAlignEntBwdArgs {
     SmmAlignLogzArgs g;        // p's backward launch's arguments (grad: the upstream weights; g_elp zero at launch)
-    const double *trans_q;     // [g][c_max][c_max]
-    const double *len_q;       // [g][k_rows][c_max]
-    const double *endpen_q;    // [b][c_max] or null
-    const double *logz_q;      // [b]
-    const double *hist_q;      // q's history area: the same plan, so the videos' hist_off serve both
-    const double *cols_q;      // q's workspace at the offset of `cols` in p's
+    SmmAlignSideQ q;
     double *value;             // [b] or null: V-
     double *scratch;           // caller's: per video five [M][T+1] blocks, then the videos' parts at pv_base, then q's log Z as the
                                // call uses it [b], then V+ [b]

@@ -1147,6 +1147,25 @@ def align_graph_logz_bwd(batch, elp, trans, init, len_scores, graphs, logz_g, gr
                             endpen, ws, staged, node_prob=want_node_prob, end_prob=want_end_prob)
 
 
+def _after_graph_logz(what, batch, dev, graphs, staged, *workspaces):
+    """What a call that follows ``align_graph_logz`` checks on the host: every workspace is there, the supervision, every
+    workspace holds the layout.  -> the supervision."""
+    if any(ws is None for ws in workspaces):
+        raise ValueError("%s: pass the workspace the align_graph_logz call wrote" % what)
+    sup = _supervision('graph', 'likelihood', what, batch, dev, graphs, None, staged)
+    if any(ws.numel() < sup.need for ws in workspaces):
+        raise ValueError("%s: pass the workspace the align_graph_logz call wrote" % what)
+    return sup
+
+
+def _q_side(q):
+    """``q`` = (trans, len_scores, endpen or None, logz_g, ws) of a two-sided call, as the library takes it."""
+    trans_q, len_q, endpen_q, logz_q, ws_q = q
+    f64 = torch.float64
+    return (_dev(trans_q, f64, 'trans'), _dev(len_q, f64, 'len_scores'), _dev(endpen_q, f64, 'endpen'), _dev(logz_q, f64, 'logz_g'),
+            *_ws_args(ws_q))
+
+
 def align_graph_sample(batch, elp, trans, init, len_scores, graphs, logz_g, n_samples, seed=0, endpen=None, class_map=None,
                        ws=None, staged=None, want_spans=True, want_labels=True, want_used=True):
     """Alignments drawn from the transcript-graph posterior (smm_align_graph_sample_f64): per video ``n_samples`` independent
@@ -1164,14 +1183,10 @@ def align_graph_sample(batch, elp, trans, init, len_scores, graphs, logz_g, n_sa
     n_samples = int(n_samples)
     if n_samples <= 0:
         raise ValueError("align_graph_sample: n_samples must be positive, got %d" % n_samples)
-    if ws is None:
-        raise ValueError("align_graph_sample: pass the workspace the align_graph_logz call wrote")
     f64 = torch.float64
     dev = elp.device
-    sup = _supervision('graph', 'likelihood', 'align_graph_sample', batch, dev, graphs, None, staged)
+    sup = _after_graph_logz('align_graph_sample', batch, dev, graphs, staged, ws)
     tables = _tables(elp, trans, init, len_scores, endpen)
-    if ws.numel() < sup.need:
-        raise ValueError("align_graph_sample: pass the workspace the align_graph_logz call wrote")
     spans, labels, logp, n_segs = _device_outputs(batch, dev, want_spans, want_labels, (n_samples,))
     used = torch.empty((n_samples, sup.n), dtype=torch.int32, device=dev) if want_used else None
     _lib.check(lib.smm_align_graph_sample_f64(
@@ -1193,13 +1208,9 @@ def align_graph_entropy(batch, elp, trans, init, len_scores, graphs, logz_g, end
     posterior over the candidates --, of the segments' starts, and of the predecessors; they add up to ``entropy``) or None,
     _err, _staged, _keep).  A video without an alignment (log Z_g = -inf) gets NaN.  Gradient: ``align_graph_entropy_bwd``."""
     lib = _lib.load()
-    if ws is None:
-        raise ValueError("align_graph_entropy: pass the workspace the align_graph_logz call wrote")
     f64 = torch.float64
     dev = elp.device
-    sup = _supervision('graph', 'likelihood', 'align_graph_entropy', batch, dev, graphs, None, staged)
-    if ws.numel() < sup.need:
-        raise ValueError("align_graph_entropy: pass the workspace the align_graph_logz call wrote")
+    sup = _after_graph_logz('align_graph_entropy', batch, dev, graphs, staged, ws)
     tables = _tables(elp, trans, init, len_scores, endpen)
     entropy = torch.empty(batch.b, dtype=f64, device=dev)
     parts = torch.empty((batch.b, 3), dtype=f64, device=dev) if want_parts else None
@@ -1223,25 +1234,18 @@ def align_graph_kl(batch, p, q, graphs, staged=None, want_cross_entropy=False, w
     excludes.  Gradient: ``align_graph_kl_bwd``."""
     lib = _lib.load()
     elp, trans, init, len_scores, endpen, logz_p, ws_p = p
-    trans_q, len_q, endpen_q, logz_q, ws_q = q
-    if ws_p is None or ws_q is None:
-        raise ValueError("align_graph_kl: pass the workspace the align_graph_logz call wrote")
+    ws_q = tuple(q)[4:]                                           # (a malformed q fails in _q_side's unpacking)
     f64 = torch.float64
     dev = elp.device
-    sup = _supervision('graph', 'likelihood', 'align_graph_kl', batch, dev, graphs, None, staged)
-    if ws_p.numel() < sup.need or ws_q.numel() < sup.need:
-        raise ValueError("align_graph_kl: pass the workspace the align_graph_logz call wrote")
+    sup = _after_graph_logz('align_graph_kl', batch, dev, graphs, staged, ws_p, *ws_q)
     tables = _tables(elp, trans, init, len_scores, endpen)
-    node_class, pred_mask, node_flags, node_off = sup.args()
     kl = torch.empty(batch.b, dtype=f64, device=dev)
     xent = torch.empty(batch.b, dtype=f64, device=dev) if want_cross_entropy else None
     parts = torch.empty((batch.b, 3), dtype=f64, device=dev) if want_parts else None
     _lib.check(lib.smm_align_graph_kl_f64(
-        *batch.head(), *tables, _dev(logz_p, f64, 'logz_g'), *_ws_args(ws_p),
-        _dev(trans_q, f64, 'trans'), _dev(len_q, f64, 'len_scores'), _dev(endpen_q, f64, 'endpen'), _dev(logz_q, f64, 'logz_g'),
-        *_ws_args(ws_q), node_class, pred_mask, node_flags, node_off, _dev(kl, f64, 'kl'), _dev(xent, f64, 'cross_entropy'),
-        _dev(parts, f64, 'parts'), _stream()))
-    return dict(kl=kl, cross_entropy=xent, parts=parts, _err=_err_copy(batch, ws_p), _staged=sup.dev, _keep=(ws_p, ws_q))
+        *batch.head(), *tables, _dev(logz_p, f64, 'logz_g'), *_ws_args(ws_p), *_q_side(q), *sup.args(), _dev(kl, f64, 'kl'),
+        _dev(xent, f64, 'cross_entropy'), _dev(parts, f64, 'parts'), _stream()))
+    return dict(kl=kl, cross_entropy=xent, parts=parts, _err=_err_copy(batch, ws_p), _staged=sup.dev, _keep=(ws_p, *ws_q))
 
 
 def align_graph_entropy_bwd_scratch_bytes(batch, node_offset):
@@ -1261,18 +1265,14 @@ def _graph_value_bwd(what, batch, p, q, graphs, grad_out, staged, mode, scratch=
     ``align_graph_entropy_bwd_scratch_bytes`` (its contents do not matter); default: a private one."""
     lib = _lib.load()
     elp, trans, init, len_scores, endpen, logz_p, ws_p = p
-    if ws_p is None or (q is not None and q[4] is None):
-        raise ValueError("%s: pass the workspace the align_graph_logz call wrote" % what)
     f64 = torch.float64
     dev = elp.device
-    sup = _supervision('graph', 'likelihood', what, batch, dev, graphs, None, staged)
-    if ws_p.numel() < sup.need or (q is not None and q[4].numel() < sup.need):
-        raise ValueError("%s: pass the workspace the align_graph_logz call wrote" % what)
-    if q is not None and q[4].data_ptr() == ws_p.data_ptr():
+    ws_q = () if q is None else tuple(q)[4:]                      # (a malformed q fails in _q_side's unpacking)
+    sup = _after_graph_logz(what, batch, dev, graphs, staged, ws_p, *ws_q)
+    if ws_q and ws_q[0].data_ptr() == ws_p.data_ptr():
         raise ValueError("%s: the two sides need a workspace each (one posterior against itself: align_graph_entropy_bwd)" % what)
     need = align_graph_entropy_bwd_scratch_bytes(batch, sup.off)
     tables = _tables(elp, trans, init, len_scores, endpen)
-    node_class, pred_mask, node_flags, node_off = sup.args()
     g = _grad_outputs(elp, trans, init, len_scores)
     value = torch.empty(batch.b, dtype=f64, device=dev)
     if scratch is None:
@@ -1283,16 +1283,13 @@ def _graph_value_bwd(what, batch, p, q, graphs, grad_out, staged, mode, scratch=
             _dev(g['init'], f64, 'g_init'), _dev(g['len'], f64, 'g_len'), _dev(value, f64, 'value'), *_ws_args(scratch))
     if q is None:
         _lib.check(lib.smm_align_graph_entropy_bwd_f64(
-            *batch.head(), *tables, node_class, pred_mask, node_flags, node_off, _dev(logz_p, f64, 'logz_g'), *outs,
-            *_ws_args(ws_p), _stream()))
+            *batch.head(), *tables, *sup.args(), _dev(logz_p, f64, 'logz_g'), *outs, *_ws_args(ws_p), _stream()))
         keep = (ws_p, scratch)
     else:
-        trans_q, len_q, endpen_q, logz_q, ws_q = q
         _lib.check(lib.smm_align_graph_kl_bwd_f64(
-            *batch.head(), *tables, _dev(logz_p, f64, 'logz_g'), *_ws_args(ws_p),
-            _dev(trans_q, f64, 'trans'), _dev(len_q, f64, 'len_scores'), _dev(endpen_q, f64, 'endpen'), _dev(logz_q, f64, 'logz_g'),
-            *_ws_args(ws_q), node_class, pred_mask, node_flags, node_off, ctypes.c_int32(mode), *outs, _stream()))
-        keep = (ws_p, ws_q, scratch)
+            *batch.head(), *tables, _dev(logz_p, f64, 'logz_g'), *_ws_args(ws_p), *_q_side(q), *sup.args(), ctypes.c_int32(mode),
+            *outs, _stream()))
+        keep = (ws_p, *ws_q, scratch)
     g.update(value=value, value_plus=scratch[:need].view(f64)[-batch.b:], _err=_err_copy(batch, ws_p), _staged=sup.dev, _keep=keep)
     return g
 
