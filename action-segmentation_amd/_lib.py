@@ -10,7 +10,7 @@ SYMBOLS = [
     "smm_error_word_offset", "smm_dp_timing_enable", "smm_dp_timing_read", "smm_dp_timing_read_tagged", "smm_band_frame_ns", "smm_time_split_plan",
     "smm_env_reload", "smm_release_cached_plans", "smm_cached_plan_bytes", "smm_plan_feedback_info", "smm_plan_feedback_plan",
     "smm_emission_f64", "smm_emission_bwd_f64", "smm_viterbi_f64", "smm_viterbi_f32", "smm_decode_f32", "smm_logz_f64", "smm_logz_bwd_f64",
-    "smm_sample_f64", "smm_entropy_f64", "smm_kl_f64", "smm_kbest_workspace_bytes", "smm_kbest_f64",
+    "smm_sample_f64", "smm_entropy_f64", "smm_segment_posteriors_f64", "smm_kl_f64", "smm_kbest_workspace_bytes", "smm_kbest_f64",
     "smm_mbr_workspace_bytes", "smm_mbr_f64",
     "smm_align_workspace_bytes", "smm_align_f64", "smm_align_opt_workspace_bytes", "smm_align_opt_f64",
     "smm_align_graph_workspace_bytes", "smm_align_graph_f64",
@@ -18,6 +18,7 @@ SYMBOLS = [
     "smm_align_opt_logz_workspace_bytes", "smm_align_opt_logz_f64", "smm_align_opt_logz_bwd_f64",
     "smm_align_graph_logz_workspace_bytes", "smm_align_graph_logz_f64", "smm_align_graph_logz_bwd_f64",
     "smm_align_graph_sample_f64", "smm_align_graph_entropy_f64", "smm_align_graph_kl_f64",
+    "smm_align_graph_segment_posteriors_f64",
     "smm_entropy_bwd_scratch_bytes", "smm_entropy_bwd_f64", "smm_kl_bwd_f64",
     "smm_align_graph_entropy_bwd_scratch_bytes", "smm_align_graph_entropy_bwd_f64", "smm_align_graph_kl_bwd_f64",
     "smm_factor_tables_f64", "smm_factor_tables_bwd_f64",
@@ -142,6 +143,9 @@ def load():
     lib.smm_align_graph_entropy_f64.restype = ctypes.c_int
     lib.smm_align_graph_entropy_f64.argtypes = [ctypes.POINTER(SmmShape)] + [ctypes.c_void_p] * 17 + [ctypes.c_void_p, ctypes.c_size_t,
                                                                                                       ctypes.c_void_p]
+    lib.smm_align_graph_segment_posteriors_f64.restype = ctypes.c_int
+    lib.smm_align_graph_segment_posteriors_f64.argtypes = [ctypes.POINTER(SmmShape)] + [ctypes.c_void_p] * 18 + [ctypes.c_int32] \
+        + [ctypes.c_void_p] * 8 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     lib.smm_align_graph_kl_f64.restype = ctypes.c_int
     lib.smm_align_graph_kl_f64.argtypes = [ctypes.POINTER(SmmShape)] + [ctypes.c_void_p] * 11 + [ctypes.c_void_p, ctypes.c_size_t] \
         + [ctypes.c_void_p] * 4 + [ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 8
@@ -158,6 +162,9 @@ def load():
     lib.smm_entropy_f64.argtypes = [ctypes.POINTER(SmmShape)] + [ctypes.c_void_p] * 12 + [ctypes.c_void_p, ctypes.c_size_t,
                                                                                          ctypes.c_void_p]
     lib.smm_error_word_offset.argtypes = [ctypes.POINTER(SmmShape)]
+    lib.smm_segment_posteriors_f64.restype = ctypes.c_int
+    lib.smm_segment_posteriors_f64.argtypes = [ctypes.POINTER(SmmShape)] + [ctypes.c_void_p] * 13 + [ctypes.c_int32] \
+        + [ctypes.c_void_p] * 4 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     lib.smm_kl_f64.restype = ctypes.c_int
     lib.smm_kl_f64.argtypes = [ctypes.POINTER(SmmShape)] + [ctypes.c_void_p] * 11 + [ctypes.c_void_p, ctypes.c_size_t] \
         + [ctypes.c_void_p] * 6 + [ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 3

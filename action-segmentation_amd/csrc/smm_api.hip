@@ -1758,6 +1758,41 @@ extern "C" int smm_entropy_f64(const smm_shape *shape, const int64_t *lengths_ho
     return SMM_OK;
 }
 
+extern "C" int smm_segment_posteriors_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                          const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                          const double *elp, const double *trans, const double *init, const double *len_scores,
+                                          const double *endpen, const int64_t *class_map, const double *logz,
+                                          const int64_t *spans_in, int32_t n_sets, double *start_post, double *end_post,
+                                          double *bnd_post, double *seg_logp, void *workspace, size_t workspace_bytes,
+                                          void *stream)
+{
+    if (!elp || !trans || !init || !len_scores || !logz) return SMM_ERR_ARG;
+    if (!start_post && !end_post && !bnd_post && !seg_logp) return SMM_ERR_ARG;
+    if (seg_logp && !spans_in) return SMM_ERR_ARG;
+    if (spans_in && n_sets <= 0) return SMM_ERR_ARG;
+    Staged st;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes,
+                   hs, &st);
+    if (rc != SMM_OK) return rc;
+    if (seg_logp && (int64_t)shape->b * n_sets > 0x7fffffff) return SMM_ERR_UNSUPPORTED;
+    const Tables p{elp, trans, init, len_scores, endpen, logz};
+    rc = run_reversed(shape, st, st.hist, st.tabs, p, hs);
+    if (rc != SMM_OK) return rc;
+    {
+        const size_t fr = (size_t)shape->total_frames;
+        void *const zp[3] = {start_post, end_post, bnd_post};
+        const size_t zb[3] = {start_post ? sizeof(double) * fr * shape->c_max : 0, end_post ? sizeof(double) * fr * shape->c_max : 0,
+                              bnd_post ? sizeof(double) * fr : 0};
+        SMM_HIP((hipError_t)smm_zero_multi_async(zp, zb, 3, hs));
+    }
+    const SmmPostHead h = post_head(shape, st);
+    smm_launch_segpost(SmmSegPostArgs{h, post_side(h.no_eos, st.hist, p), class_map, spans_in, start_post, end_post, bnd_post,
+                                      seg_logp, shape->t_max, spans_in ? n_sets : 0}, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
 // The second workspace of the KL calls (q's forward histories) is only read: checked against the plan, before p's is staged,
 // and pointed into
 static int point_q(const smm_shape *shape, const int64_t *lengths_host, void *ws_q, size_t ws_q_bytes, Staged *sq)
@@ -2487,6 +2522,40 @@ extern "C" int smm_align_graph_entropy_f64(const smm_shape *shape, const int64_t
     a.h_out = h_out; a.h_parts = h_parts;
     smm_launch_align_graph_logz_bwd_columns(a.g, hs);
     smm_launch_align_graph_entropy(a, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
+// segment posteriors of given alignments and the nodes' boundary distributions (smm_align_graph_segpost.hip): the entropy call's
+// staging, arguments and first kernel, then the gathers
+extern "C" int smm_align_graph_segment_posteriors_f64(
+    const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host, const int32_t *group_host,
+    const int32_t *kp_host, const int32_t *n_states_host, const double *elp, const double *trans, const double *init,
+    const double *len_scores, const double *endpen, const int64_t *class_map, const int32_t *node_class, const uint32_t *pred_mask,
+    const uint8_t *node_flags, const int64_t *node_offset_host, const double *logz_g, const int64_t *spans_in,
+    const int32_t *used_in, int32_t n_sets, double *seg_logp, double *node_logp, double *end_mean, double *end_sd,
+    double *start_mean, double *start_sd, double *node_end_post, double *node_start_post, void *workspace, size_t workspace_bytes,
+    void *stream)
+{
+    if (!seg_logp && !node_logp && !end_mean && !end_sd && !start_mean && !start_sd && !node_end_post && !node_start_post)
+        return SMM_ERR_ARG;
+    if ((seg_logp || node_logp) && (!spans_in || !used_in)) return SMM_ERR_ARG;
+    if ((spans_in != nullptr) != (used_in != nullptr)) return SMM_ERR_ARG;
+    if (spans_in && n_sets <= 0) return SMM_ERR_ARG;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    SmmAlignSegPostArgs a{};
+    const int rc = align_graph_prepare(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp, trans, init,
+                                       len_scores, endpen, node_class, pred_mask, node_flags, node_offset_host, logz_g, workspace,
+                                       workspace_bytes, hs, &a.g);
+    if (rc != SMM_OK) return rc;
+    if (spans_in && (int64_t)shape->b * n_sets > 0x7fffffff) return SMM_ERR_UNSUPPORTED;
+    a.class_map = class_map; a.spans_in = spans_in; a.used_in = used_in;
+    a.seg_logp = seg_logp; a.node_logp = node_logp;
+    a.end_mean = end_mean; a.end_sd = end_sd; a.start_mean = start_mean; a.start_sd = start_sd;
+    a.node_end_post = node_end_post; a.node_start_post = node_start_post;
+    a.n_nodes = node_offset_host[shape->b]; a.t_max = shape->t_max; a.n_sets = spans_in ? n_sets : 0;
+    smm_launch_align_graph_logz_bwd_columns(a.g, hs);
+    smm_launch_align_graph_segpost(a, hs);
     SMM_HIP(hipGetLastError());
     return SMM_OK;
 }

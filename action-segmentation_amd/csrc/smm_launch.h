@@ -167,6 +167,21 @@ struct SmmEntropyArgs {
 };
 void smm_launch_entropy(const SmmEntropyArgs &a, int t_max, hipStream_t stream);
 
+// posteriors of segment boundaries and of given segments (smm_segpost.hip): after smm_launch_logz forward AND time-reversed on
+// the same workspace; the dense outputs are zero at launch
+struct SmmSegPostArgs {
+    SmmPostHead h;
+    SmmPostSide p;
+    const int64_t *class_map;  // [g][c_max+1] or null
+    const int64_t *spans_in;   // [n_sets][b][t_max+1] or null
+    double *start_post;        // [total_frames][c_max] or null
+    double *end_post;          // [total_frames][c_max] or null
+    double *bnd_post;          // [total_frames] or null
+    double *seg_logp;          // [n_sets][b][t_max+1] or null (needs spans_in)
+    int32_t t_max, n_sets;
+};
+void smm_launch_segpost(const SmmSegPostArgs &a, hipStream_t stream);
+
 // KL divergence and cross-entropy between two posteriors of one lattice (smm_kl.hip): after smm_launch_logz forward AND
 // time-reversed on p's workspace and forward on q's (the same shape and metadata, so the same history offsets)
 struct SmmKlArgs {
@@ -326,6 +341,24 @@ struct SmmAlignEntropyArgs {
     double *h_parts;           // [b][3]: end node, span, predecessor; or null
 };
 void smm_launch_align_graph_entropy(const SmmAlignEntropyArgs &a, hipStream_t stream);
+
+// segment posteriors of given alignments and the nodes' boundary distributions (smm_align_graph_segpost.hip): after
+// smm_launch_align_graph_logz_fwd and smm_launch_align_graph_logz_bwd_columns on the same workspace -- it reads cum, the four
+// column blocks and the columns' ranges, and writes the error word only
+struct SmmAlignSegPostArgs {
+    SmmAlignLogzArgs g;        // the forward launch's arguments (logz: read; the backward call's fields: unused)
+    const int64_t *class_map;  // [g][c_max+1] or null
+    const int64_t *spans_in;   // [n_sets][b][t_max+1] or null
+    const int32_t *used_in;    // [n_sets][n_nodes] or null (with spans_in)
+    double *seg_logp;          // [n_sets][b][t_max+1] or null
+    double *node_logp;         // [n_sets][n_nodes] or null
+    double *end_mean, *end_sd, *start_mean, *start_sd;   // [n_nodes] each, or null
+    double *node_end_post;     // [n_nodes][t_max+1] or null
+    double *node_start_post;   // [n_nodes][t_max+1] or null
+    int64_t n_nodes;
+    int32_t t_max, n_sets;
+};
+void smm_launch_align_graph_segpost(const SmmAlignSegPostArgs &a, hipStream_t stream);
 
 // KL(p || q) and the cross-entropy H(p, q) of two transcript-graph posteriors over the same videos and graphs
 // (smm_align_graph_kl.hip): after smm_launch_align_graph_logz_fwd per side and smm_launch_align_graph_logz_bwd_columns on p's

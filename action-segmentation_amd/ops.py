@@ -504,6 +504,49 @@ def entropy(batch, elp, trans, init, len_scores, logz_val, endpen=None, ws=None,
     return out
 
 
+def segment_posteriors(batch, elp, trans, init, len_scores, logz_val, spans=None, endpen=None, class_map=None, ws=None,
+                       with_backward=False):
+    """Exact posterior of every segment boundary, and of each segment of given segmentations (smm_segment_posteriors_f64).
+    Must follow ``logz`` for the same batch and tables with the same workspace (``with_backward``: as passed to ``logz``;
+    without it the call runs the time-reversed recursion itself); ``logz_val`` = its output.  ``spans``: int64 [n_sets, b,
+    t_max+1] or [b, t_max+1] on the device, segmentations in the span encoding ``viterbi`` / ``kbest`` / ``sample`` / ``mbr``
+    return (``class_map`` applied, if one is given).  Returns dict(start fp64 [total_frames, c_max]: P(a span of c starts at the
+    frame), end: P(a span of c has it as its last frame), boundary fp64 [total_frames]: P(a span starts at the frame), seg_logp
+    fp64 shaped like ``spans`` or None: the log posterior of each given span at its start, 0 at the EOS position, -inf at
+    continuations, past the video and for a span the lattice does not have).  Padded columns and frames no video covers are 0.
+    A video whose log Z is not finite, or whose histories a NaN reached, gets NaN and sets the error word
+    (``error_flag(batch, ws=ws)``).  Bit-identical run to run; values, not differentiable."""
+    n_sets = 0
+    if spans is not None:
+        if spans.dtype != torch.int64:
+            raise TypeError("spans: expected torch.int64, got %s" % spans.dtype)
+        if spans.dim() not in (2, 3) or tuple(spans.shape[-2:]) != (batch.b, batch.t_max + 1):
+            raise ValueError("spans: [n_sets, b, t_max+1] or [b, t_max+1] = [.., %d, %d] expected, got %s"
+                             % (batch.b, batch.t_max + 1, tuple(spans.shape)))
+        n_sets = int(spans.shape[0]) if spans.dim() == 3 else 1
+        if n_sets <= 0:
+            raise ValueError("spans: at least one set of segmentations is expected")
+    if tuple(elp.shape) != (batch.total_frames, batch.c_max):
+        raise ValueError("elp: [total_frames, c_max] = [%d, %d] expected, got %s"
+                         % (batch.total_frames, batch.c_max, tuple(elp.shape)))
+    lib = _lib.load()
+    head = batch.head(_lib.SHAPE_LOGZ_BOTH if with_backward else 0)
+    dev = elp.device
+    f64 = torch.float64
+    start = torch.empty((batch.total_frames, batch.c_max), dtype=f64, device=dev)
+    end = torch.empty_like(start)
+    bnd = torch.empty(batch.total_frames, dtype=f64, device=dev)
+    seg = None if spans is None else torch.empty(spans.shape, dtype=f64, device=dev)
+    if ws is None:
+        ws = workspace(batch.workspace_bytes(), dev)
+    _lib.check(lib.smm_segment_posteriors_f64(
+        *head, _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
+        _dev(endpen, f64, 'endpen'), _dev(class_map, torch.int64, 'class_map'), _dev(logz_val, f64, 'logz'),
+        _dev(spans, torch.int64, 'spans'), ctypes.c_int32(n_sets), _dev(start, f64, 'start'), _dev(end, f64, 'end'),
+        _dev(bnd, f64, 'boundary'), _dev(seg, f64, 'seg_logp'), *_ws_args(ws), _stream()))
+    return dict(start=start, end=end, boundary=bnd, seg_logp=seg, _err=_err_copy(batch, ws))
+
+
 def _kl_side(t, tag):
     """One side of ``kl`` / ``kl_bwd`` -- (elp, trans, init, len_scores, endpen, logz_val, ws) -- as the C ABI takes it."""
     f64 = torch.float64
@@ -1218,6 +1261,63 @@ def align_graph_entropy(batch, elp, trans, init, len_scores, graphs, logz_g, end
         *batch.head(), *tables, *sup.args(), _dev(logz_g, f64, 'logz_g'), _dev(entropy, f64, 'entropy'), _dev(parts, f64, 'parts'),
         *_ws_args(ws), _stream()))
     return dict(entropy=entropy, parts=parts, _err=_err_copy(batch, ws), _staged=sup.dev, _keep=(ws,))
+
+
+def align_graph_segment_posteriors(batch, elp, trans, init, len_scores, graphs, logz_g, spans=None, used=None, endpen=None,
+                                   class_map=None, ws=None, staged=None, want_moments=True, want_dense=False):
+    """The exact posterior of each segment of given alignments under the transcript-graph posterior, and where each node's
+    segment starts and ends (smm_align_graph_segment_posteriors_f64).  Must follow ``align_graph_logz`` for the same batch,
+    tables and graphs with the same workspace ``ws`` on the same stream (``ws`` and ``staged``: its ``ws`` and ``_staged``
+    entries); ``logz_g`` = its output.  ``align_graph_logz_bwd``, ``align_graph_sample`` and ``align_graph_entropy`` may run
+    before or after it: none's results change.  ``spans`` int64 [n_sets, b, t_max+1] or [b, t_max+1] and ``used`` int32
+    [n_sets, n_nodes] or [n_nodes] (or the list of per-video views ``align_graph`` / ``align_graph_sample`` return), both on the
+    device: alignments as those two write them, the k-th span of a video standing for its k-th used node; ``class_map`` as
+    given to them.  -> dict(seg_logp fp64 shaped like ``spans`` or None: at each span start the log posterior that this node
+    covers exactly these frames, 0 at the EOS position, -inf elsewhere; node_logp: a list of per-video fp64 views ([n_sets,] M_i),
+    the same value per used node, -inf for the others, or None; end_mean, end_sd, start_mean, start_sd (``want_moments``):
+    lists of per-video fp64 [M_i] views, mean and standard deviation in frames of the node's end and start position given that
+    the path crosses it, NaN for a node without mass; node_end_post, node_start_post (``want_dense``) fp64 [n_nodes, t_max+1]:
+    P(node m's segment ends / starts at position n), 8 (t_max+1) bytes per node each; _err, _staged, _keep).  An alignment the
+    graph does not admit -- its spans and used nodes differ in number, a span's class is not its node's, a span is longer than
+    the span limit -- gets -inf everywhere, without an error.  A video without an alignment (log Z_g = -inf) gets NaN.  Values,
+    not differentiable."""
+    f64 = torch.float64
+    dev = elp.device
+    if (spans is None) != (used is None):
+        raise ValueError("align_graph_segment_posteriors: pass spans and used together")
+    if spans is None and not want_moments and not want_dense:
+        raise ValueError("align_graph_segment_posteriors: nothing is asked for")
+    n_sets = 0
+    if spans is not None:
+        if isinstance(used, (list, tuple)):
+            used = torch.cat(list(used), dim=-1)
+        if spans.dtype != torch.int64 or used.dtype != torch.int32:
+            raise TypeError("align_graph_segment_posteriors: spans int64 and used int32 expected, got %s and %s" % (spans.dtype, used.dtype))
+        if spans.dim() not in (2, 3) or tuple(spans.shape[-2:]) != (batch.b, batch.t_max + 1):
+            raise ValueError("align_graph_segment_posteriors: spans [n_sets, b, t_max+1] or [b, t_max+1] = [.., %d, %d] expected, "
+                             "got %s" % (batch.b, batch.t_max + 1, tuple(spans.shape)))
+        n_sets = int(spans.shape[0]) if spans.dim() == 3 else 1
+        n_nodes = sum(len(g) for g in graphs)
+        if n_sets <= 0 or tuple(used.shape) != ((n_sets, n_nodes) if spans.dim() == 3 else (n_nodes,)):
+            raise ValueError("align_graph_segment_posteriors: used [n_sets, %d] to go with spans %s expected, got %s"
+                             % (n_nodes, tuple(spans.shape), tuple(used.shape)))
+        used = used.contiguous()
+    sup = _after_graph_logz('align_graph_segment_posteriors', batch, dev, graphs, staged, ws)
+    lib = _lib.load()
+    tables = _tables(elp, trans, init, len_scores, endpen)
+    seg = None if spans is None else torch.empty(spans.shape, dtype=f64, device=dev)
+    node = None if spans is None else torch.empty(used.shape, dtype=f64, device=dev)
+    mom = [torch.empty(sup.n, dtype=f64, device=dev) if want_moments else None for _ in range(4)]
+    dense = [torch.empty((sup.n, batch.t_max + 1), dtype=f64, device=dev) if want_dense else None for _ in range(2)]
+    _lib.check(lib.smm_align_graph_segment_posteriors_f64(
+        *batch.head(), *tables, _dev(class_map, torch.int64, 'class_map'), *sup.args(), _dev(logz_g, f64, 'logz_g'),
+        _dev(spans, torch.int64, 'spans'), _dev(used, torch.int32, 'used'), ctypes.c_int32(n_sets), _dev(seg, f64, 'seg_logp'),
+        _dev(node, f64, 'node_logp'), *[_dev(t, f64, 'moments') for t in mom], *[_dev(t, f64, 'dense') for t in dense],
+        *_ws_args(ws), _stream()))
+    per = lambda t, dim=0: None if t is None else sup.per_video(t, dim=dim)
+    return dict(seg_logp=seg, node_logp=per(node, node.dim() - 1 if node is not None else 0),
+                end_mean=per(mom[0]), end_sd=per(mom[1]), start_mean=per(mom[2]), start_sd=per(mom[3]),
+                node_end_post=dense[0], node_start_post=dense[1], _err=_err_copy(batch, ws), _staged=sup.dev, _keep=(ws,))
 
 
 def align_graph_kl(batch, p, q, graphs, staged=None, want_cross_entropy=False, want_parts=False):

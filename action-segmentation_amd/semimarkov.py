@@ -383,6 +383,45 @@ class SemiMarkovModel(object):
                 assert self.model.n_classes not in predictions[video], "predictions should not contain EOS"
         return predictions
 
+    def segment_confidence(self, data, labels_by_video=None, shard=None):
+        """``{video: [(start, end, class id, probability, probability of a boundary at start), ...]}``: how sure the model is of
+        each segment of a labelling, exactly.  ``labels_by_video[name]``: the video's frame labels (global class ids, one per
+        frame), as ``predict`` returns them; None: ``predict``'s own.  The labels become segments the way the training labels
+        do (``labels_to_spans``: a run of one label is one segment, cut every span limit - 1 frames, the limit being the
+        video's own); a segment covers the frames [start, end).  ``probability`` is the posterior probability that exactly this
+        segment -- class, start and end -- is part of the segmentation (0 for a segment the lattice does not have, such as a
+        class outside the video's task); the last entry is the posterior probability that a segment of any class starts at
+        ``start``.  One emission launch, one log Z launch and one smm_segment_posteriors_f64 launch on the packed corpus
+        (``SemiMarkovModule.segment_posteriors_packed``).  Values, not differentiable."""
+        self.model.eval()
+        pc = self.prepare(data, shard=shard)
+        if pc.n_videos == 0:
+            return {}
+        if labels_by_video is None:
+            labels_by_video = self.predict_packed(pc)
+        labels = self._per_video(pc, labels_by_video, "segment_confidence: no labels for video %r")
+        batch = pc.batch
+        spans = np.full((pc.n_videos, batch.t_max + 1), -1, dtype=np.int64)
+        for i, (name, lab, t) in enumerate(zip(pc.video_names, labels, batch.lengths.tolist())):
+            lab = np.asarray(lab, dtype=np.int64).reshape(-1)
+            if lab.shape[0] != t:
+                raise ValueError("segment_confidence: video %r has %d frames, %d labels were given" % (name, t, lab.shape[0]))
+            if lab.size and int(lab.min()) < 0:
+                raise ValueError("segment_confidence: video %r has a negative label" % (name,))
+            kp = int(batch.kp[i]) if batch.kp is not None else min(batch.k_rows, batch.t_max)
+            spans[i, :t] = semimarkov_utils.labels_to_spans(lab[None], max_k=kp)[0]
+            spans[i, t] = self.model.n_classes                 # the EOS position closes the last segment
+        out = self.model.segment_posteriors_packed(pc, torch.from_numpy(spans))
+        prob = torch.exp(out['seg_logp']).cpu().numpy()
+        bnd = out['boundary'].cpu().numpy()
+        result = {}
+        for i, (name, off, t) in enumerate(zip(pc.video_names, pc.frame_offset, batch.lengths.tolist())):
+            starts = np.flatnonzero(spans[i, :t] != -1)
+            ends = np.append(starts[1:], t)
+            result[name] = [(int(s), int(e), int(spans[i, s]), float(prob[i, s]), float(bnd[int(off) + s]))
+                            for s, e in zip(starts, ends)]
+        return result
+
     def align(self, data, transcripts_by_video, shard=None, *, optional_by_video=None, optional_classes=None):
         """Forced alignment of every video of ``data`` to its transcript: ``transcripts_by_video[name]`` is the video's class
         sequence in global class ids, one entry per segment.  Returns what ``predict`` returns, ``{video: int64[T]}``: the frame
@@ -603,6 +642,60 @@ class SemiMarkovModel(object):
         else:
             graphs = [ops.TranscriptGraph.from_optional(t, f) for t, f in zip(transcripts, optional)]
         return dict(zip(pc.video_names, self.model.alignment_entropy_packed(pc, graphs).tolist()))
+
+    def _alignment_confidence(self, pc, graphs):
+        """The best alignment of every video of ``pc`` to its graph with the exact posterior of each of its segments:
+        ``{video: [(node index, class id, start, end, probability, end_mean, end_sd), ...]}``."""
+        out = self.model.alignment_segment_posteriors_packed(pc, graphs)
+        spans = out['spans'].cpu().numpy()
+        prob = torch.exp(out['seg_logp']).cpu().numpy()
+        result = {}
+        for i, (name, t) in enumerate(zip(pc.video_names, pc.batch.lengths.tolist())):
+            nodes = np.flatnonzero(out['used'][i].cpu().numpy())
+            starts = np.flatnonzero(spans[i, :t] != -1)
+            mean, sd = out['end_mean'][i].cpu().numpy(), out['end_sd'][i].cpu().numpy()
+            result[name] = [(int(m), int(spans[i, s]), int(s), int(e), float(prob[i, s]), float(mean[m]), float(sd[m]))
+                            for m, s, e in zip(nodes, starts, np.append(starts[1:], t))]
+        return result
+
+    def alignment_confidence(self, data, transcripts_by_video, shard=None, *, optional_by_video=None, optional_classes=None):
+        """``{video: [(entry index, class id, start, end, probability, end_mean, end_sd), ...]}``: the best alignment of every
+        video to its transcript (``align``'s conventions for ``transcripts_by_video``, ``optional_by_video`` and
+        ``optional_classes``), one row per entry that got a segment, on the frames [start, end).  ``probability`` is the exact
+        posterior probability, under the distribution ``sample_alignments`` draws from, that this entry covers exactly these
+        frames; ``end_mean`` and ``end_sd`` are the mean and the standard deviation, in frames, of where the entry's segment
+        ends, given that the entry is kept.  An empty list where the transcript cannot be laid over the video.  One emission
+        launch, one alignment launch, the forward launch and one smm_align_graph_segment_posteriors_f64 launch on the packed
+        corpus (``SemiMarkovModule.alignment_segment_posteriors_packed``).  Values, not differentiable."""
+        from . import ops
+        self._one_kind_of_flags(optional_by_video, optional_classes, 'alignment_confidence')
+        self.model.eval()
+        pc = self.prepare(data, shard=shard)
+        if pc.n_videos == 0:
+            return {}
+        transcripts = self._per_video(pc, transcripts_by_video, "alignment_confidence: no transcript for video %r")
+        optional = self._optional_flags(pc, transcripts, optional_by_video, optional_classes, 'alignment_confidence')
+        if optional is None:
+            graphs = [ops.TranscriptGraph.chain(t) for t in transcripts]
+        else:
+            graphs = [ops.TranscriptGraph.from_optional(t, f) for t, f in zip(transcripts, optional)]
+        return self._alignment_confidence(pc, graphs)
+
+    def candidate_confidence(self, data, candidates_by_video, shard=None):
+        """``alignment_confidence`` given "the video follows one of these transcripts" (``candidates_by_video`` as in
+        ``align_candidates``): the rows of the best alignment over every candidate, the first entry of a row being the node of
+        the candidates' prefix trie (``ops.TranscriptGraph.from_candidates``); the probabilities are under the joint posterior
+        over candidate and boundaries.  ValueError for an empty set or one whose trie needs more than ``ops.MAX_TRANSCRIPT``
+        nodes, as in ``candidate_entropy``."""
+        from . import ops
+        self._one_trie_each(candidates_by_video, 'candidate_confidence')
+        self.model.eval()
+        pc = self.prepare(data, shard=shard)
+        if pc.n_videos == 0:
+            return {}
+        graphs = [ops.TranscriptGraph.from_candidates(cands)
+                  for cands in self._per_video(pc, candidates_by_video, "candidate_confidence: no candidates for video %r")]
+        return self._alignment_confidence(pc, graphs)
 
     def candidate_entropy(self, data, candidates_by_video, shard=None):
         """``{video: dict(total=, candidates=, boundaries=)}`` in nats, given the frames and "the video follows one of these

@@ -127,6 +127,28 @@ def _entropy(r, with_backward):
     return h, r, None
 
 
+def _segment_posteriors(r, spans, with_backward, want_spans=True):
+    """Boundary posteriors of a launched posterior and the posterior of each segment of ``spans`` ([n_sets, b, t_max+1] or
+    [b, t_max+1], any device; a row of t_max entries -- ``viterbi``'s add_eos=False format -- gets its last column back; None:
+    the Viterbi decode on the same emissions).  -> dict(start, end, boundary, seg_logp, spans), all on the device."""
+    batch = r['batch']
+    if want_spans and spans is None:
+        out = ops.viterbi(batch, r['elp'], r['trans'], r['init'], r['len'], endpen=r['endpen'], class_map=r['class_map'],
+                          want_spans=True, want_labels=False)
+        ops.check_decoded(batch, out)
+        spans = out['spans']
+    if spans is not None:
+        spans = torch.as_tensor(spans).to(device=r['elp'].device, dtype=torch.int64)
+        if spans.size(-1) == batch.t_max:
+            spans = torch.nn.functional.pad(spans, (0, 1), value=-1)
+        spans = spans.contiguous()
+    out = ops.segment_posteriors(batch, spans=spans, class_map=r['class_map'], with_backward=with_backward, **_after_logz(r))
+    _check_workspace(r)
+    out['spans'] = spans
+    del out['_err']
+    return out
+
+
 def _kl(r, q, what, with_backward, want_cross_entropy):
     """-> (KL(p || q) or H(p, q), p's launch, q's launch).  ``with_backward``: as given to p's log Z launch."""
     SemiMarkovModule._check_same_batch(r['batch'], q['batch'], what)
@@ -186,6 +208,31 @@ def _alignment_entropy(r, sup, want_parts):
                                   ws=z['ws'], staged=z['_staged'], want_parts=want_parts)
     ops.check_decoded(b, out)
     return out['entropy'], out['parts'], (z,)
+
+
+def _alignment_segment_posteriors(r, sup, spans=None, used=None, want_alignment=True, want_dense=False):
+    """The forward launch over the graphs of ``sup`` on a private workspace, then the segment-posterior launch on it, for the
+    alignments ``spans`` / ``used`` (None with ``want_alignment``: the best alignment, one launch more, in front).  -> the dict of
+    ``ops.align_graph_segment_posteriors`` with the alignments under ``spans`` and ``used``.  A video without an alignment is no
+    error: NaN."""
+    b = r['batch']
+    graphs = sup[1][0]
+    if want_alignment and spans is None:
+        best = ops.align_graph(b, r['elp'], r['trans'], r['init'], r['len'], graphs, endpen=r['endpen'], class_map=r['class_map'],
+                               want_spans=True, want_labels=False, want_used=True)
+        ops.check_decoded(b, best)
+        spans, used = best['spans'], best['used']
+    if spans is not None:
+        spans = torch.as_tensor(spans).to(device=r['elp'].device, dtype=torch.int64).contiguous()
+    z = _supervised(_LOGZ, r, sup)
+    out = ops.align_graph_segment_posteriors(b, r['elp'], r['trans'], r['init'], r['len'], graphs, z['logz'], spans=spans, used=used,
+                                             endpen=r['endpen'], class_map=r['class_map'], ws=z['ws'], staged=z['_staged'],
+                                             want_dense=want_dense)
+    ops.check_decoded(b, out)
+    out['spans'], out['used'], out['logz'] = spans, used, z['logz']
+    for key in ('_err', '_staged'):
+        del out[key]
+    return out
 
 
 def _alignment_kl(r, q, sup, what, want_cross_entropy, want_parts):
@@ -1112,6 +1159,53 @@ class SemiMarkovModule(nn.Module):
         st = self.stacked_tables(pc, differentiable=True)[0]
         return _PosteriorValue.apply('entropy', launch, *(st[k] for k in TABLE_NAMES))
 
+    # ------------------------------------------------------------------ segment and boundary posteriors (smm_segment_posteriors_f64)
+    @torch.no_grad()
+    def segment_posteriors(self, features, lengths, valid_classes_per_instance, spans=None, add_eos=True,
+                           additional_allowed_ends_per_instance=None, constraints=None):
+        """How sure the posterior is of each segment of ``spans`` and of each boundary, exactly (argument conventions of
+        ``viterbi``).  ``spans``: b x (Tmax+1) or n_sets x b x (Tmax+1) in ``viterbi``'s pred_spans format (Tmax columns with
+        add_eos=False), on any device; None: the Viterbi decode.  One emission launch, one log Z launch (forward and
+        time-reversed), one smm_segment_posteriors_f64 launch.
+
+        Returns a dict of device tensors: ``seg_logp`` fp64 shaped like the spans (Tmax+1 columns): at each span start the log
+        posterior that exactly this segment -- class, start, end -- is part of the segmentation, 0 at the EOS position, -inf
+        elsewhere and for a segment the lattice does not have; ``start`` / ``end`` fp64 b x Tmax x C: P(a span of class c starts
+        at / has as its last frame the frame), columns in the order of the batch's valid classes; ``boundary`` fp64 b x Tmax:
+        P(a span starts at the frame); ``spans`` int64: the segmentations ``seg_logp`` speaks of.  Padded frames are 0.  Raises
+        SmmError when a NaN reached the DP.  Values, not differentiable."""
+        r = self._posterior_launch(features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
+                                   constraints, 'segment_posteriors', with_backward=True)
+        out = _segment_posteriors(r, spans, with_backward=True)
+        b, tmax = features.shape[:2]
+        out['start'], out['end'] = out['start'].view(b, tmax, -1), out['end'].view(b, tmax, -1)
+        out['boundary'] = out['boundary'].view(b, tmax)
+        return out
+
+    @torch.no_grad()
+    def segment_posteriors_packed(self, pc, spans=None):
+        """``segment_posteriors`` for a whole PackedCorpus.  ``spans``: int64 n_videos x (t_max+1) or n_sets x n_videos x
+        (t_max+1) in the span encoding ``decode_packed(want_spans=True)`` returns, videos in the order of ``pc.video_names``;
+        None: the Viterbi decode of ``pc``.  ``start`` / ``end`` are fp64 total_frames x c_max and ``boundary`` fp64
+        total_frames on the packed frame axis; column c of a frame is local state c of its video's group
+        (``pc.tables['class_map']`` maps it to a global id).  Values, not differentiable."""
+        return _segment_posteriors(self._packed_posterior_launch(pc, 'segment_posteriors_packed'), spans, with_backward=False)
+
+    @torch.no_grad()
+    def boundary_posteriors(self, features, lengths, valid_classes_per_instance, add_eos=True,
+                            additional_allowed_ends_per_instance=None, constraints=None):
+        """P(a segment starts at the frame | x), exactly: fp64 b x Tmax on the device (1 at frame 0, 0 on padded frames).
+        Argument conventions of ``viterbi``; the launches of ``segment_posteriors``.  Values, not differentiable."""
+        r = self._posterior_launch(features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
+                                   constraints, 'boundary_posteriors', with_backward=True)
+        return _segment_posteriors(r, None, with_backward=True, want_spans=False)['boundary'].view(features.shape[:2])
+
+    @torch.no_grad()
+    def boundary_posteriors_packed(self, pc):
+        """``boundary_posteriors`` for a whole PackedCorpus: fp64 total_frames on the packed frame axis."""
+        return _segment_posteriors(self._packed_posterior_launch(pc, 'boundary_posteriors_packed'), None, with_backward=False,
+                                   want_spans=False)['boundary']
+
     # ------------------------------------------------------------------ KL divergence and cross-entropy (smm_kl_f64)
     def _check_same_lattice(self, other, what):
         if not isinstance(other, SemiMarkovModule):
@@ -1393,6 +1487,42 @@ class SemiMarkovModule(nn.Module):
         used): device int64 total_frames (-1 on frames no video covers and on videos without an alignment), fp64 n_videos and
         the per-video flags of the nodes on the path."""
         return _align(*self._supervised_packed(pc, 'align_graph_packed', graphs, graphs=True), want_spans=False)
+
+    # ------------------------------------------------------------------ segment posteriors under a transcript graph
+    @torch.no_grad()
+    def alignment_segment_posteriors(self, features, lengths, valid_classes_per_instance, graphs, spans=None, used=None,
+                                     add_eos=True, additional_allowed_ends_per_instance=None, constraints=None, want_dense=False):
+        """How sure the transcript-graph posterior is of each segment of an alignment, and where each node's segment starts and
+        ends, exactly (argument conventions of ``align_graph``).  ``spans`` (b x (Tmax+1) or n_sets x b x (Tmax+1)) and ``used``
+        (the per-video int32 flags, [M_i] or [n_sets, M_i]): alignments as ``align_graph`` / ``sample_alignments`` return them;
+        None: ``align_graph``'s own result.  One emission launch, the forward launch and one
+        smm_align_graph_segment_posteriors_f64 launch (one alignment launch more for the default).
+
+        Returns the dict of ``ops.align_graph_segment_posteriors`` (``seg_logp``, ``node_logp``, ``end_mean``, ``end_sd``,
+        ``start_mean``, ``start_sd``; with ``want_dense`` ``node_end_post`` / ``node_start_post``) with ``spans``, ``used`` and
+        ``logz``.  A video without an alignment gets NaN; an alignment its graph does not admit gets -inf.  Values, not
+        differentiable."""
+        if len(graphs) != len(lengths):
+            raise ValueError("alignment_segment_posteriors: %d graphs for %d videos" % (len(graphs), len(lengths)))
+        r, sup = self._supervised_padded('alignment_segment_posteriors', features, lengths, valid_classes_per_instance, add_eos,
+                                         additional_allowed_ends_per_instance, constraints, graphs, graphs=True)
+        return _alignment_segment_posteriors(r, sup, spans, used, want_dense=want_dense)
+
+    @torch.no_grad()
+    def alignment_segment_posteriors_packed(self, pc, graphs, spans=None, used=None, want_dense=False):
+        """``alignment_segment_posteriors`` for a whole PackedCorpus; ``graphs``, ``spans`` and ``used`` in the order of
+        ``pc.video_names``; None means ``align_graph_packed``'s alignment.  Values, not differentiable."""
+        r, sup = self._supervised_packed(pc, 'alignment_segment_posteriors_packed', graphs, graphs=True)
+        return _alignment_segment_posteriors(r, sup, spans, used, want_dense=want_dense)
+
+    @torch.no_grad()
+    def alignment_boundaries_packed(self, pc, graphs):
+        """Where each node's segment starts and ends under the transcript-graph posterior of a whole PackedCorpus: dict(end_mean,
+        end_sd, start_mean, start_sd), lists of per-video fp64 [M_i] device tensors in frames, given that the path crosses the
+        node (NaN for a node without mass or a video without an alignment).  Values, not differentiable."""
+        r, sup = self._supervised_packed(pc, 'alignment_boundaries_packed', graphs, graphs=True)
+        out = _alignment_segment_posteriors(r, sup, want_alignment=False)
+        return {key: out[key] for key in ('end_mean', 'end_sd', 'start_mean', 'start_sd')}
 
     # ------------------------------------------------------------------ transcript likelihood (smm_align_logz_f64)
     def transcript_log_partition(self, features, lengths, valid_classes_per_instance, transcripts, add_eos=True,

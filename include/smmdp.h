@@ -16,6 +16,8 @@
  *   smm_sample_f64          <- pytorch-struct's SemiMarkovCRF(...).sample (posterior samples; the reference never calls it)
  *   smm_entropy_f64         <- pytorch-struct's SemiMarkovCRF(...).entropy (exact H(y | x) per video; the reference never
  *                              calls it)
+ *   smm_segment_posteriors_f64 <- the exact posterior of each segment boundary and of each segment of given segmentations (what
+ *                              pytorch-struct's marginals hold per dense edge; the reference never calls them)
  *   smm_kl_f64              <- pytorch-struct's SemiMarkovCRF(...).kl / cross_entropy (exact KL(p || q) and H(p, q) per
  *                              video between two posteriors of one lattice; the reference never calls them)
  *   smm_entropy_bwd_f64 /   <- autograd through pytorch-struct's entropy / kl / cross_entropy (the gradients of the three
@@ -41,6 +43,8 @@
  *                              for stochastic EM from transcripts, boundary uncertainty; the reference has none)
  *   smm_align_graph_entropy_f64 <- ... and the exact entropy of that posterior: how sure the model is of the alignment, of the
  *                              candidate and of the boundaries (the reference has none)
+ *   smm_align_graph_segment_posteriors_f64 <- ... and the exact posterior of each segment of given alignments, with the mean and
+ *                              deviation of every node's boundaries (the reference has none)
  *   smm_align_graph_kl_f64    <- ... and the exact KL divergence and cross-entropy between two such posteriors over the same
  *                              videos and graphs: teacher against student, one EM epoch against the next (the reference has none)
  *   smm_align_graph_entropy_bwd_f64 / <- ... and the gradients of those three values with respect to p's tables: entropy
@@ -135,9 +139,10 @@ int smm_device_count(void);
 
 /* Bytes of device workspace any entry point below needs for this shape (lengths: host array [b]).
  * Returns 0 on invalid arguments.  The workspace is scratch: its contents are undefined after a call,
- * except between smm_logz_f64 and smm_logz_bwd_f64 / smm_sample_f64 / smm_entropy_f64 / smm_kl_f64, and between a transcript
- * likelihood call and the calls its comment names (smm_align_graph_logz_f64: smm_align_graph_logz_bwd_f64,
- * smm_align_graph_sample_f64, smm_align_graph_entropy_f64 and smm_align_graph_kl_f64, in any order). */
+ * except between smm_logz_f64 and smm_logz_bwd_f64 / smm_sample_f64 / smm_entropy_f64 / smm_segment_posteriors_f64 / smm_kl_f64,
+ * and between a transcript likelihood call and the calls its comment names (smm_align_graph_logz_f64:
+ * smm_align_graph_logz_bwd_f64, smm_align_graph_sample_f64, smm_align_graph_entropy_f64,
+ * smm_align_graph_segment_posteriors_f64 and smm_align_graph_kl_f64, in any order). */
 size_t smm_workspace_bytes(const smm_shape *shape, const int64_t *lengths_host);
 
 /* Byte offset, inside the workspace, of the int32 error word the kernels set.  1: a NaN / inf-inf reached the DP of
@@ -369,6 +374,41 @@ int smm_entropy_f64(const smm_shape *shape, const int64_t *lengths_host, const i
                     const double *elp, const double *trans, const double *init, const double *len_scores,
                     const double *endpen, const double *logz, double *entropy_out,
                     void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Exact posterior of each segment boundary and of each segment of given segmentations under p(y | x) (csrc/smm_segpost.hip:
+ * gathers over the two histories, no recursion).  Call order as smm_entropy_f64: it must follow smm_logz_f64 on the same shape,
+ * tables and workspace; without SMM_SHAPE_LOGZ_BOTH the call runs the time-reversed recursion itself; the histories are left as
+ * they were (smm_sample_f64 / smm_entropy_f64 / smm_logz_bwd_f64 may follow, and give the bits they give without this call).
+ * It has no size query of its own: the workspace is smm_workspace_bytes'.  T below is the number of DP positions of a video,
+ * lengths[i] with EOS and lengths[i] - 1 under SMM_SHAPE_NO_EOS; frame f of video i is row frame_offset[i] + f.
+ *   class_map   dev int64 [n_groups][c_max + 1], as in smm_sample_f64: the global ids spans_in is written in     (nullable: local ids)
+ *   spans_in    dev int64 [n_sets][b][t_max + 1]  segmentations in the Viterbi entry points' span encoding, class map applied,
+ *               as smm_viterbi_f64 / smm_kbest_f64 / smm_sample_f64 / smm_mbr_f64 write them                      (nullable)
+ *   n_sets      segmentations per video in spans_in (ignored without spans_in)
+ *   start_post  dev fp64 [total_frames][c_max]  P(a span of class c starts at frame f)                            (nullable)
+ *   end_post    dev fp64 [total_frames][c_max]  P(a span of class c has frame f as its last frame)                (nullable)
+ *   bnd_post    dev fp64 [total_frames]         sum over c of start_post, in index order: P(a span starts at f); 1 at frame 0
+ *               up to rounding                                                                                    (nullable)
+ *   seg_logp    dev fp64 [n_sets][b][t_max + 1] laid out like spans_in (and it needs spans_in): at every span start s < T the
+ *               log posterior that exactly this span -- class, start, end = the next span start -- is part of y; 0.0 at the EOS
+ *               position; -inf at continuations and past the video                                                (nullable)
+ * Columns c >= n_states and frames no video covers are 0.0 in the three dense outputs.  Under SMM_SHAPE_NO_EOS the closing label
+ * of frame T counts as a one-frame span of its class: its entry in the dense outputs and in seg_logp is P(closing label = c).
+ * A span gets -inf, without an error, when it is longer than kp - 1 frames, when its class is not in the video's class set, or
+ * when its posterior is 0.  A video whose log Z is -inf or NaN gets NaN in every probability (seg_logp: at its span starts) and
+ * sets the error word; a NaN that reached the histories does the same in the entries it reaches.  No atomics but the error word
+ * and no sum across workgroups: the outputs are bit-identical run to run.
+ * SMM_ERR_ARG, before anything is staged, when a required input (elp, trans, init, len_scores, logz) is NULL, when every output
+ * is NULL, when seg_logp is given without spans_in, or when spans_in is given with n_sets <= 0.
+ */
+int smm_segment_posteriors_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                               const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                               const double *elp, const double *trans, const double *init, const double *len_scores,
+                               const double *endpen, const int64_t *class_map, const double *logz,
+                               const int64_t *spans_in, int32_t n_sets,
+                               double *start_post, double *end_post, double *bnd_post, double *seg_logp,
+                               void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Exact KL divergence KL(p || q) = sum_y p(y | x) log(p(y | x) / q(y | x)) and cross-entropy H(p, q) = H(p) + KL(p || q) between
@@ -917,6 +957,46 @@ int smm_align_graph_entropy_f64(const smm_shape *shape, const int64_t *lengths_h
                                 const uint8_t *node_flags, const int64_t *node_offset_host, const double *logz_g /* dev [b] */,
                                 double *h_out /* dev [b] */, double *h_parts /* dev [b][3]: end, span, pred; nullable */,
                                 void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * The exact posterior of each segment of given alignments under the transcript-graph posterior, and where each node's segment
+ * starts and ends (csrc/smm_align_graph_segpost.hip: gathers over the columns, no recursion).  With the E and S of
+ * smm_align_graph_entropy_f64 -- E[n][m], S[s][m]: the posteriors that a segment of node m ends at position n / starts at s --
+ * the posterior that node m covers exactly the frames [s, e) is exp(h[s][m] + len[e-s][a_m] + q[e][m] - logZ_g).
+ * Call order as smm_align_graph_entropy_f64: it follows smm_align_graph_logz_f64 on the same workspace and stream, launches the
+ * backward call's first kernel itself for the q and bh columns, computes nothing of a gradient, and may run before, after or
+ * between backward, sampler and entropy calls without changing a bit of theirs.  SMM_SHAPE_NO_EOS is refused as by its siblings.
+ * It has no size query of its own: the workspace is smm_align_graph_logz_workspace_bytes'.
+ *   class_map  dev int64 [n_groups][c_max + 1], the ids spans_in is written in                            (nullable: local ids)
+ *   spans_in   dev int64 [n_sets][b][t_max + 1] and
+ *   used_in    dev int32 [n_sets][node_offset_host[b]]: alignments as smm_align_graph_f64 and smm_align_graph_sample_f64 write
+ *              them; the k-th span of a video belongs to its k-th used node in index order            (nullable, both or neither)
+ *   seg_logp   dev fp64 [n_sets][b][t_max + 1]: at each span start log P(its node covers exactly [s, e)), e the next span
+ *              start; 0.0 at the EOS position; -inf elsewhere                                          (nullable; needs spans_in)
+ *   node_logp  dev fp64 [n_sets][node_offset_host[b]]: the same value per used node, -inf for the others (nullable; needs spans_in)
+ *   end_mean, end_sd, start_mean, start_sd  dev fp64 [node_offset_host[b]], laid out like node_class: mean and standard
+ *              deviation, in frames, of node m's end and start position under E[.][m] and S[.][m] given that the path crosses m;
+ *              summed over the column's recorded range in a fixed order in fp64, the variance about the mean in a second pass;
+ *              NaN where the node's mass is 0                                                          (each nullable)
+ *   node_end_post, node_start_post  dev fp64 [node_offset_host[b]][t_max + 1]: the dense E and S, 0.0 outside a column's range.
+ *              They cost 8 (t_max + 1) bytes per node each: 256 nodes at T = 10 000 are 20 MB per video  (each nullable)
+ * An alignment the graph does not admit has probability 0: when a (set, video)'s number of spans differs from its number of
+ * used nodes, when a span's class, after the class map, is not its node's, or when a span is longer than kw = kp - 1, that
+ * set's video is -inf everywhere in seg_logp and node_logp, and no error is set.  A video whose logZ_g is -inf gets NaN (seg_logp:
+ * at its positions 0 .. T) with the error word clear; a NaN logZ_g gives NaN with the error word set.
+ * SMM_ERR_ARG when every output is NULL, when seg_logp or node_logp is given without spans_in and used_in, when only one of the
+ * two is given, when n_sets <= 0 with them, and under smm_align_graph_entropy_f64's refusals.
+ */
+int smm_align_graph_segment_posteriors_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                           const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                           const double *elp, const double *trans, const double *init, const double *len_scores,
+                                           const double *endpen /* nullable */, const int64_t *class_map /* nullable */,
+                                           const int32_t *node_class, const uint32_t *pred_mask, const uint8_t *node_flags,
+                                           const int64_t *node_offset_host, const double *logz_g /* dev [b] */,
+                                           const int64_t *spans_in, const int32_t *used_in, int32_t n_sets,
+                                           double *seg_logp, double *node_logp, double *end_mean, double *end_sd,
+                                           double *start_mean, double *start_sd, double *node_end_post, double *node_start_post,
+                                           void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * The exact KL divergence and cross-entropy between two transcript-graph posteriors (csrc/smm_align_graph_kl.hip): per video
