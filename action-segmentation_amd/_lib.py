@@ -20,6 +20,7 @@ SYMBOLS = [
     "smm_align_graph_sample_f64", "smm_align_graph_entropy_f64", "smm_align_graph_kl_f64",
     "smm_align_graph_segment_posteriors_f64",
     "smm_entropy_bwd_scratch_bytes", "smm_entropy_bwd_f64", "smm_kl_bwd_f64",
+    "smm_expected_reward_bwd_scratch_bytes", "smm_expected_reward_f64", "smm_expected_reward_bwd_f64",
     "smm_align_graph_entropy_bwd_scratch_bytes", "smm_align_graph_entropy_bwd_f64", "smm_align_graph_kl_bwd_f64",
     "smm_factor_tables_f64", "smm_factor_tables_bwd_f64",
     "smm_dense_workspace_bytes", "smm_dense_dp_f32", "smm_dense_marginals_f32",
@@ -176,6 +177,14 @@ def load():
     lib.smm_kl_bwd_f64.restype = ctypes.c_int
     lib.smm_kl_bwd_f64.argtypes = [ctypes.POINTER(SmmShape)] + [ctypes.c_void_p] * 11 + [ctypes.c_void_p, ctypes.c_size_t] \
         + [ctypes.c_void_p] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32] + [ctypes.c_void_p] * 6 \
+        + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.smm_expected_reward_bwd_scratch_bytes.restype = ctypes.c_size_t
+    lib.smm_expected_reward_bwd_scratch_bytes.argtypes = [ctypes.POINTER(SmmShape), ctypes.c_void_p]
+    lib.smm_expected_reward_f64.restype = ctypes.c_int
+    lib.smm_expected_reward_f64.argtypes = [ctypes.POINTER(SmmShape)] + [ctypes.c_void_p] * 15 + [ctypes.c_void_p, ctypes.c_size_t,
+                                                                                                  ctypes.c_void_p]
+    lib.smm_expected_reward_bwd_f64.restype = ctypes.c_int
+    lib.smm_expected_reward_bwd_f64.argtypes = [ctypes.POINTER(SmmShape)] + [ctypes.c_void_p] * 19 + [ctypes.c_void_p, ctypes.c_size_t] \
         + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     lib.smm_align_graph_entropy_bwd_scratch_bytes.restype = ctypes.c_size_t
     lib.smm_align_graph_entropy_bwd_scratch_bytes.argtypes = [ctypes.POINTER(SmmShape), ctypes.c_void_p, ctypes.c_void_p]

@@ -1927,6 +1927,83 @@ extern "C" int smm_kl_bwd_f64(const smm_shape *shape, const int64_t *lengths_hos
                     g_len, value_out, scratch, hs);
 }
 
+// ------------------------------------------------------------------------------------------------ expected reward
+// (smm_expected_reward.hip).  The gradient's scratch has smm_entropy_bwd_f64's layout: its last two kernels run as they are.
+extern "C" size_t smm_expected_reward_bwd_scratch_bytes(const smm_shape *shape, const int64_t *lengths_host)
+{
+    return smm_entropy_bwd_scratch_bytes(shape, lengths_host);
+}
+
+extern "C" int smm_expected_reward_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                       const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                       const double *elp, const double *trans, const double *init, const double *len_scores,
+                                       const double *endpen, const double *logz, const double *reward, const double *seg_reward,
+                                       double *value_out, double *parts_out, void *workspace, size_t workspace_bytes,
+                                       void *stream)
+{
+    if (!value_out || !elp || !trans || !init || !len_scores || !logz || (!reward && !seg_reward)) return SMM_ERR_ARG;
+    Staged st;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes,
+                   hs, &st);
+    if (rc != SMM_OK) return rc;
+    const Tables p{elp, trans, init, len_scores, endpen, logz};
+    rc = run_reversed(shape, st, st.hist, st.tabs, p, hs);
+    if (rc != SMM_OK) return rc;
+    SmmExpRewardArgs a{};
+    a.e.h = post_head(shape, st);
+    a.e.p = a.e.r = post_side(a.e.h.no_eos, st.hist, p);
+    a.reward = reward; a.seg_reward = seg_reward; a.value = value_out; a.parts = parts_out;
+    smm_launch_expected_reward(a, shape->t_max, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
+extern "C" int smm_expected_reward_bwd_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                           const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                           const double *elp, const double *trans, const double *init, const double *len_scores,
+                                           const double *endpen, const double *logz, const double *reward,
+                                           const double *seg_reward, const double *grad_out, double *g_elp, double *g_trans,
+                                           double *g_init, double *g_len, double *value_out, void *scratch, size_t scratch_bytes,
+                                           void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!elp || !trans || !init || !len_scores || !logz || (!reward && !seg_reward) || !g_elp || !g_trans || !g_init || !g_len ||
+        !scratch)
+        return SMM_ERR_ARG;
+    const size_t need = smm_expected_reward_bwd_scratch_bytes(shape, lengths_host);
+    if (need == 0) return SMM_ERR_ARG;
+    if (scratch_bytes < need) return SMM_ERR_WORKSPACE;
+    Staged st;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes,
+                   hs, &st);
+    if (rc != SMM_OK) return rc;
+    const Tables p{elp, trans, init, len_scores, endpen, logz};
+    rc = run_reversed(shape, st, st.hist, st.tabs, p, hs);
+    if (rc != SMM_OK) return rc;
+    size_t pv_base = 0, tot = 0;
+    ebwd_layout(shape, lengths_host, &pv_base, &tot);
+    double *sc = static_cast<double *>(scratch);
+    {
+        void *const zp[2] = {g_elp, sc + pv_base};
+        const size_t zb[2] = {sizeof(double) * (size_t)shape->total_frames * shape->c_max, sizeof(double) * (tot - pv_base)};
+        SMM_HIP((hipError_t)smm_zero_multi_async(zp, zb, 2, hs));
+    }
+    SmmExpRewardArgs a{};
+    a.e.h = post_head(shape, st);
+    a.e.p = a.e.r = post_side(a.e.h.no_eos, st.hist, p);
+    a.e.grad_out = grad_out;
+    a.e.g_elp = g_elp; a.e.g_trans = g_trans; a.e.g_init = g_init; a.e.g_len = g_len;
+    a.e.value = value_out;
+    a.e.scratch = sc;
+    a.e.pv_base = (int64_t)pv_base;
+    a.e.n_groups = shape->n_groups;
+    a.reward = reward; a.seg_reward = seg_reward;
+    smm_launch_expected_reward_bwd(a, shape->t_max, st.kp_max, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ k best
 // Behind the plan's workspace (its `total`): the length table state-major, the H lists of the last `ring` positions (and their
 // heads apart, class-major), the back-pointers of G and H at every position, the closing lists, the back-trace's scratch.

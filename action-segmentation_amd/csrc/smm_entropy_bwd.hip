@@ -96,33 +96,6 @@ __device__ double smm_eb_decide(int kl, int i0, int n, int step, Wf w, Xf x)
     return smm_eb_node(kl, mp, sp, mr, sr, a1, a2, a3, rinf, nan);
 }
 
-// per-video layout of the caller's scratch: 4 eta blocks and D, each [T+1][c_max], at 6/8 of the video's history offset; the
-// fixed part (smm_eb_pv) behind all of them
-struct SmmEbPv {
-    int64_t len, trans, init, close, val, stride;
-};
-__device__ __host__ __forceinline__ SmmEbPv smm_eb_pv(int cm, int k_rows)
-{
-    SmmEbPv p;
-    p.len = 0;
-    p.trans = (int64_t)k_rows * cm;
-    p.init = p.trans + (int64_t)cm * cm;
-    p.close = p.init + cm;
-    p.val = p.close + cm;
-    p.stride = (p.val + 4 + 3) / 4 * 4;
-    return p;
-}
-
-__device__ __forceinline__ double *smm_eb_video(const SmmEntBwdArgs &a, const SmmVideo &mv)
-{
-    return a.scratch + mv.hist_off / 8 * 6;
-}
-
-__device__ __forceinline__ double *smm_eb_fixed(const SmmEntBwdArgs &a, int vid)
-{
-    return a.scratch + a.pv_base + (int64_t)vid * smm_eb_pv(a.h.c_max, a.h.k_rows).stride;
-}
-
 __global__ void __launch_bounds__(SMM_EB_THREADS) smm_ebwd_eta_kernel(SmmEntBwdArgs a)
 {
     __shared__ double s_end[SMM_MAX_STATES_DEV];
@@ -236,14 +209,6 @@ __device__ __forceinline__ double smm_eb_term(int kl, double lp, double lr, doub
     if (lp == SMM_NEG_INF) return 0.0;
     const double l = kl ? lp - lr : -lr;
     return exp(lp) * ((l + eta) - V);
-}
-
-// the value V- every assembly kernel subtracts; false when the video gets NaN rows
-__device__ __forceinline__ bool smm_eb_value(const SmmEntBwdArgs &a, int vid, double *V)
-{
-    const double *f = smm_eb_fixed(a, vid) + smm_eb_pv(a.h.c_max, a.h.k_rows).val;
-    *V = f[0];
-    return f[0] > SMM_NEG_INF && f[0] < -SMM_NEG_INF && f[1] > SMM_NEG_INF && f[1] < -SMM_NEG_INF;
 }
 
 // log p(span (s, k, c)) on one side: F_h[s][c] + len[k][c] + B_h[T-s-k][c] + cumE[T][c] - logZ
@@ -455,6 +420,13 @@ size_t smm_entropy_bwd_fixed_doubles(int c_max, int k_rows)
     return (size_t)smm_eb_pv(c_max, k_rows).stride;
 }
 
+void smm_launch_entropy_bwd_tail(const SmmEntBwdArgs &a, hipStream_t stream)
+{
+    hipLaunchKernelGGL(smm_ebwd_elp_kernel, dim3(a.h.b), dim3(1024), 0, stream, a);
+    const int64_t n = (int64_t)smm_eb_pv(a.h.c_max, a.h.k_rows).val * a.n_groups;
+    hipLaunchKernelGGL(smm_ebwd_group_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+}
+
 void smm_launch_entropy_bwd(const SmmEntBwdArgs &a, int t_max, int kp_max, hipStream_t stream)
 {
     hipLaunchKernelGGL(smm_ebwd_eta_kernel, dim3(a.h.b, 2), dim3(SMM_EB_THREADS), 0, stream, a);
@@ -462,7 +434,5 @@ void smm_launch_entropy_bwd(const SmmEntBwdArgs &a, int t_max, int kp_max, hipSt
     hipLaunchKernelGGL(smm_ebwd_pairs_kernel, dim3(a.h.b), dim3(1024), 0, stream, a);
     if (kp_max >= 2)
         hipLaunchKernelGGL(smm_ebwd_len_kernel, dim3(a.h.b * a.h.c_max, (kp_max - 1 + 255) / 256), dim3(256), 0, stream, a);
-    hipLaunchKernelGGL(smm_ebwd_elp_kernel, dim3(a.h.b), dim3(1024), 0, stream, a);
-    const int64_t n = (int64_t)smm_eb_pv(a.h.c_max, a.h.k_rows).val * a.n_groups;
-    hipLaunchKernelGGL(smm_ebwd_group_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+    smm_launch_entropy_bwd_tail(a, stream);
 }

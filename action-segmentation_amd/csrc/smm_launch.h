@@ -206,6 +206,22 @@ struct SmmEntBwdArgs {
 };
 size_t smm_entropy_bwd_fixed_doubles(int c_max, int k_rows);   // the fixed part of one video
 void smm_launch_entropy_bwd(const SmmEntBwdArgs &a, int t_max, int kp_max, hipStream_t stream);
+// ... its last two kernels alone (g_elp as the running sum of D, the groups' tables): what follows kernels that left D and the
+// per-video sums in that unit's scratch layout (smm_expected_reward.hip does)
+void smm_launch_entropy_bwd_tail(const SmmEntBwdArgs &a, hipStream_t stream);
+
+// expected frame- and segment-additive reward and its gradient with respect to p's tables (smm_expected_reward.hip): after
+// smm_launch_logz forward AND time-reversed on the same workspace.  The value launch reads e.h and e.p only; the gradient launch
+// uses e as smm_launch_entropy_bwd does (e.r and e.kl unused; e.value: V-, V+)
+struct SmmExpRewardArgs {
+    SmmEntBwdArgs e;
+    const double *reward;      // [total_frames][c_max] or null
+    const double *seg_reward;  // [g][c_max] or null
+    double *value;             // [b]               (value launch)
+    double *parts;             // [b][2] or null: frame part, segment part   (value launch)
+};
+void smm_launch_expected_reward(const SmmExpRewardArgs &a, int t_max, hipStream_t stream);
+void smm_launch_expected_reward_bwd(const SmmExpRewardArgs &a, int t_max, int kp_max, hipStream_t stream);
 
 // minimum-Bayes-risk decode under frame loss (smm_mbr.hip): the Viterbi DP on the substituted inputs of smmdp.h (smm_mbr_f64);
 // per video, behind hist_off: cum, h, bt (the transition max before - cum), the suffix maxima of h, each [T+1][c_max], then

@@ -192,3 +192,39 @@ __device__ __forceinline__ void smm_post_video_sum(const double *part, int ns, i
 #pragma unroll
     for (int i = 0; i < NA; ++i) out[i] = smm_group_sum<64>(t[i]);
 }
+
+// ---- the caller's scratch of the gradient units (smm_entropy_bwd.hip, smm_expected_reward.hip), one layout for both
+// per-video layout of the caller's scratch: 4 eta blocks and D, each [T+1][c_max], at 6/8 of the video's history offset; the
+// fixed part (smm_eb_pv) behind all of them
+struct SmmEbPv {
+    int64_t len, trans, init, close, val, stride;
+};
+__device__ __host__ __forceinline__ SmmEbPv smm_eb_pv(int cm, int k_rows)
+{
+    SmmEbPv p;
+    p.len = 0;
+    p.trans = (int64_t)k_rows * cm;
+    p.init = p.trans + (int64_t)cm * cm;
+    p.close = p.init + cm;
+    p.val = p.close + cm;
+    p.stride = (p.val + 4 + 3) / 4 * 4;
+    return p;
+}
+
+__device__ __forceinline__ double *smm_eb_video(const SmmEntBwdArgs &a, const SmmVideo &mv)
+{
+    return a.scratch + mv.hist_off / 8 * 6;
+}
+
+__device__ __forceinline__ double *smm_eb_fixed(const SmmEntBwdArgs &a, int vid)
+{
+    return a.scratch + a.pv_base + (int64_t)vid * smm_eb_pv(a.h.c_max, a.h.k_rows).stride;
+}
+
+// the value V- every assembly kernel subtracts; false when the video gets NaN rows
+__device__ __forceinline__ bool smm_eb_value(const SmmEntBwdArgs &a, int vid, double *V)
+{
+    const double *f = smm_eb_fixed(a, vid) + smm_eb_pv(a.h.c_max, a.h.k_rows).val;
+    *V = f[0];
+    return f[0] > SMM_NEG_INF && f[0] < -SMM_NEG_INF && f[1] > SMM_NEG_INF && f[1] < -SMM_NEG_INF;
+}

@@ -631,6 +631,76 @@ def kl_bwd(batch, p, q, grad_out=None, with_backward=False, cross_entropy=False,
     return g
 
 
+def _check_rewards(batch, reward, seg_reward):
+    if reward is None and seg_reward is None:
+        raise ValueError("expected_reward: at least one of reward and seg_reward is needed")
+    if reward is not None and tuple(reward.shape) != (batch.total_frames, batch.c_max):
+        raise ValueError("reward: [total_frames, c_max] = [%d, %d] expected, got %s"
+                         % (batch.total_frames, batch.c_max, tuple(reward.shape)))
+    if seg_reward is not None and tuple(seg_reward.shape) != (batch.n_groups, batch.c_max):
+        raise ValueError("seg_reward: [n_groups, c_max] = [%d, %d] expected, got %s"
+                         % (batch.n_groups, batch.c_max, tuple(seg_reward.shape)))
+
+
+def expected_reward(batch, elp, trans, init, len_scores, logz_val, reward=None, seg_reward=None, endpen=None, ws=None,
+                    with_backward=False, want_parts=False):
+    """Posterior expectation V = E_p[R(y)] of a reward that is additive over frames and segments (smm_expected_reward_f64):
+    R(y) = sum over the spans (s, k, c) of y of seg_reward[c] + sum of reward[t][c] over the span's frames.  fp64 [b]; with
+    ``want_parts`` the pair (V, parts fp64 [b, 2]: the frame part and the segment part).  ``reward``: fp64 [total_frames, c_max]
+    on local states, ``seg_reward``: fp64 [n_groups, c_max]; either may be None.  Must follow ``logz`` for the same batch and
+    tables with the same workspace (``with_backward``: as passed to ``logz``; without it the call runs the time-reversed
+    recursion itself); ``logz_val`` = its output.  Padded columns and frames no video covers are ignored.  A video whose log Z
+    is not finite, or with a non-finite reward in a covered entry, gets NaN and sets the error word
+    (``error_flag(batch, ws=ws)``).  Bit-identical run to run.  Its gradient: ``expected_reward_bwd``."""
+    _check_rewards(batch, reward, seg_reward)
+    lib = _lib.load()
+    head = batch.head(_lib.SHAPE_LOGZ_BOTH if with_backward else 0)
+    dev = elp.device
+    f64 = torch.float64
+    out = torch.empty(batch.b, dtype=f64, device=dev)
+    parts = torch.empty((batch.b, 2), dtype=f64, device=dev) if want_parts else None
+    if ws is None:
+        ws = workspace(batch.workspace_bytes(), dev)
+    _lib.check(lib.smm_expected_reward_f64(
+        *head, _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
+        _dev(endpen, f64, 'endpen'), _dev(logz_val, f64, 'logz'), _dev(reward, f64, 'reward'), _dev(seg_reward, f64, 'seg_reward'),
+        _dev(out, f64, 'value'), _dev(parts, f64, 'parts'), *_ws_args(ws), _stream()))
+    return (out, parts) if want_parts else out
+
+
+def expected_reward_bwd_scratch_bytes(batch):
+    """Bytes of the caller's scratch ``expected_reward_bwd`` needs (smm_expected_reward_bwd_scratch_bytes; host only)."""
+    n = _lib.load().smm_expected_reward_bwd_scratch_bytes(ctypes.byref(batch.shape), batch.lengths.ctypes.data)
+    if n == 0:
+        raise _lib.SmmError("libsmmdp: invalid batch shape for the expected-reward gradient")
+    return n
+
+
+def expected_reward_bwd(batch, elp, trans, init, len_scores, logz_val, reward=None, seg_reward=None, grad_out=None, endpen=None,
+                        ws=None, with_backward=False, want_value=False):
+    """Gradient of sum_i grad_out[i] * V_i, V = ``expected_reward``, with respect to the tables (smm_expected_reward_bwd_f64): a
+    Hessian-vector product of log Z.  Call order as ``expected_reward``.  -> dict(elp [total_frames, c_max], trans, init, len)
+    fp64 in ``logz_bwd``'s layouts, and ``value`` fp64 [b, 2] (V by the two decompositions) with ``want_value``.  The rewards
+    get no gradient.  A video whose V is not finite gets NaN rows.  Bit-identical run to run."""
+    _check_rewards(batch, reward, seg_reward)
+    lib = _lib.load()
+    head = batch.head(_lib.SHAPE_LOGZ_BOTH if with_backward else 0)
+    f64 = torch.float64
+    dev = elp.device
+    g = _grad_outputs(elp, trans, init, len_scores)
+    g['value'] = torch.empty((batch.b, 2), dtype=f64, device=dev) if want_value else None
+    scratch = torch.empty(expected_reward_bwd_scratch_bytes(batch), dtype=torch.uint8, device=dev)
+    if ws is None:
+        ws = workspace(batch.workspace_bytes(), dev)
+    _lib.check(lib.smm_expected_reward_bwd_f64(
+        *head, _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
+        _dev(endpen, f64, 'endpen'), _dev(logz_val, f64, 'logz'), _dev(reward, f64, 'reward'), _dev(seg_reward, f64, 'seg_reward'),
+        _dev(grad_out, f64, 'grad_out'), _dev(g['elp'], f64, 'g_elp'), _dev(g['trans'], f64, 'g_trans'),
+        _dev(g['init'], f64, 'g_init'), _dev(g['len'], f64, 'g_len'), _dev(g['value'], f64, 'value'), *_ws_args(scratch),
+        *_ws_args(ws), _stream()))
+    return g
+
+
 MAX_KBEST = 16
 
 

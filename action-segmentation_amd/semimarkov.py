@@ -422,6 +422,43 @@ class SemiMarkovModel(object):
                             for s, e in zip(starts, ends)]
         return result
 
+    def expected_accuracy(self, data, labels_by_video=None, shard=None):
+        """``{video: expected number of frames on which a segmentation drawn from the posterior agrees with the labels}``,
+        exactly.  ``labels_by_video[name]``: the video's frame labels (global class ids, one per frame), as ``predict`` returns
+        them; None: the ground truth of ``data`` (``gt_single``).  A label outside the video's task is never correct.  Against
+        ``predict(decoder='mbr')``'s labels it is the calibrated estimate of that decode's frame accuracy.  One emission launch,
+        one log Z launch and one smm_expected_reward_f64 launch on the packed corpus
+        (``SemiMarkovModule.expected_accuracy_packed``).  Values, not differentiable."""
+        self.model.eval()
+        pc = self.prepare(data, shard=shard)
+        if pc.n_videos == 0:
+            return {}
+        if labels_by_video is None:
+            loader = make_data_loader(self.args, data, batch_by_task=False, shuffle=False, batch_size=1)
+            labels_by_video = {batch['video_name'][0]: batch['gt_single'].squeeze(0).cpu().numpy() for batch in loader}
+        labels = self._per_video(pc, labels_by_video, "expected_accuracy: no labels for video %r")
+        batch = pc.batch
+        packed = np.full(batch.total_frames, -1, dtype=np.int64)
+        for name, lab, off, t in zip(pc.video_names, labels, pc.frame_offset, batch.lengths.tolist()):
+            lab = np.asarray(lab, dtype=np.int64).reshape(-1)
+            if lab.shape[0] != t:
+                raise ValueError("expected_accuracy: video %r has %d frames, %d labels were given" % (name, t, lab.shape[0]))
+            packed[int(off):int(off) + t] = lab
+        with torch.no_grad():
+            v = self.model.expected_accuracy_packed(pc, torch.from_numpy(packed)).cpu().numpy()
+        return {name: float(x) for name, x in zip(pc.video_names, v)}
+
+    def expected_segment_counts(self, data, shard=None):
+        """``{video: expected number of segments under the posterior}``, exactly
+        (``SemiMarkovModule.expected_segment_count_packed``).  Values, not differentiable."""
+        self.model.eval()
+        pc = self.prepare(data, shard=shard)
+        if pc.n_videos == 0:
+            return {}
+        with torch.no_grad():
+            v = self.model.expected_segment_count_packed(pc).cpu().numpy()
+        return {name: float(x) for name, x in zip(pc.video_names, v)}
+
     def align(self, data, transcripts_by_video, shard=None, *, optional_by_video=None, optional_classes=None):
         """Forced alignment of every video of ``data`` to its transcript: ``transcripts_by_video[name]`` is the video's class
         sequence in global class ids, one entry per segment.  Returns what ``predict`` returns, ``{video: int64[T]}``: the frame

@@ -127,6 +127,27 @@ def _entropy(r, with_backward):
     return h, r, None
 
 
+def _expected_reward(r, reward, seg_reward, with_backward):
+    """-> (V, p's launch, None): what _PosteriorValue's ``launch`` returns; the launch keeps the rewards for the backward."""
+    r['reward'], r['seg_reward'] = reward, seg_reward
+    v = ops.expected_reward(r['batch'], reward=reward, seg_reward=seg_reward, with_backward=with_backward, **_after_logz(r))
+    _check_workspace(r)
+    return v, r, None
+
+
+def _reward_tensor(t, shape, dev, what):
+    """A reward as the launch takes it: fp64, contiguous, on the device, of the given shape; one that requires grad is refused."""
+    if t is None:
+        return None
+    t = torch.as_tensor(t)
+    if t.requires_grad:
+        raise ValueError("%s requires grad: the expected reward is differentiable with respect to the model's parameters "
+                         "only (d V / d reward is the frame posterior, ``frame_posteriors``)" % what)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("%s: shape %s expected, got %s" % (what, tuple(shape), tuple(t.shape)))
+    return t.detach().to(device=dev, dtype=torch.float64).contiguous()
+
+
 def _segment_posteriors(r, spans, with_backward, want_spans=True):
     """Boundary posteriors of a launched posterior and the posterior of each segment of ``spans`` ([n_sets, b, t_max+1] or
     [b, t_max+1], any device; a row of t_max entries -- ``viterbi``'s add_eos=False format -- gets its last column back; None:
@@ -397,11 +418,11 @@ def _table_grads(batch, x, g, ws):
 
 
 class _PosteriorValue(torch.autograd.Function):
-    """The entropy H(p), cross-entropy H(p, q) or KL(p || q) of every video as a differentiable function of the fp64 factor
-    tables (w, cst, trans, init, len) of p, and of q for the two-sided values.  ``launch()`` computes the value exactly as the
+    """The entropy H(p), the expected reward E_p[R], the cross-entropy H(p, q) or KL(p || q) of every video as a differentiable
+    function of the fp64 factor tables (w, cst, trans, init, len) of p, and of q for the two-sided values.  ``launch()`` computes the value exactly as the
     non-differentiable method does and returns (value, p's launch, q's launch or None); each launch keeps its private workspace
-    (forward and time-reversed histories) until the backward runs.  Backward: smm_entropy_bwd_f64 / smm_kl_bwd_f64 for p's
-    tables, mu_q - mu_p (two smm_logz_bwd_f64) for q's, then the emission chain rule of each side."""
+    (forward and time-reversed histories) until the backward runs.  Backward: smm_entropy_bwd_f64 / smm_expected_reward_bwd_f64 /
+    smm_kl_bwd_f64 for p's tables, mu_q - mu_p (two smm_logz_bwd_f64) for q's, then the emission chain rule of each side."""
 
     @staticmethod
     def forward(ctx, kind, launch, *tables):
@@ -416,6 +437,10 @@ class _PosteriorValue(torch.autograd.Function):
         b = r['batch']
         if ctx.kind == 'entropy':
             g = ops.entropy_bwd(b, grad_out=up, with_backward=True, **_after_logz(r))
+            return (None, None) + _table_grads(b, r['x'], g, r['ws'])
+        if ctx.kind == 'expected_reward':
+            g = ops.expected_reward_bwd(b, reward=r['reward'], seg_reward=r['seg_reward'], grad_out=up, with_backward=True,
+                                        **_after_logz(r))
             return (None, None) + _table_grads(b, r['x'], g, r['ws'])
         # (kl_bwd runs both sides' time-reversed recursions: q's launch ran only the forward one)
         g = ops.kl_bwd(b, _side(r), _side(q), grad_out=up, cross_entropy=ctx.kind == 'cross_entropy')
@@ -1158,6 +1183,119 @@ class SemiMarkovModule(nn.Module):
         self._require_device(pc.x, 'entropy_packed')
         st = self.stacked_tables(pc, differentiable=True)[0]
         return _PosteriorValue.apply('entropy', launch, *(st[k] for k in TABLE_NAMES))
+
+    # ------------------------------------------------------------------ expected reward (smm_expected_reward_f64)
+    def expected_reward(self, features, lengths, valid_classes_per_instance, reward=None, seg_reward=None, add_eos=True,
+                        additional_allowed_ends_per_instance=None, constraints=None, *, differentiable=False):
+        """Posterior expectation E_{p(y | x)}[R(y)] of a reward that is additive over frames and segments, exactly: fp64 b on the
+        device (argument conventions of ``viterbi``).  R(y) = sum over the segments (class c) of y of seg_reward[c] + the sum
+        of reward[t, c] over the segment's frames.  ``reward``: b x Tmax x C, columns in the order of the batch's valid classes
+        (the layout ``frame_posteriors`` returns; padded frames are ignored); ``seg_reward``: length C; either may be None.
+        reward = one-hot labels: the expected number of correct frames (``expected_accuracy``); seg_reward = 1: the expected
+        number of segments (``expected_segment_count``); reward[:, :, c] = 1: the expected time in class c.  One emission
+        launch, one log Z launch (forward and time-reversed), one smm_expected_reward_f64 launch.  Raises SmmError when a NaN
+        reached the DP or a reward is not finite.
+        ``differentiable``: the same value (bit for bit), differentiable with respect to the module's parameters (not the
+        rewards: one that requires grad is refused): the backward runs smm_expected_reward_bwd_f64, a Hessian-vector product
+        of log Z, and the chain rule through the emission scorer and the factor tables (``log_partition``'s)."""
+        self._require_device(features, 'expected_reward')
+        b, tmax = features.shape[:2]
+        dev = features.device
+        vc = self._check_valid_classes(valid_classes_per_instance)
+        c = self.n_classes if vc is None else int(vc.numel())
+        rw = _reward_tensor(reward, (b, tmax, c), dev, 'reward')
+        sg = _reward_tensor(seg_reward, (c,), dev, 'seg_reward')
+        if rw is None and sg is None:
+            raise ValueError("expected_reward: at least one of reward and seg_reward is needed")
+        rw = None if rw is None else rw.view(b * tmax, c)
+        sg = None if sg is None else sg.view(1, c)
+        launch = lambda: _expected_reward(self._posterior_launch(
+            features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance, constraints,
+            'expected_reward', with_backward=True), rw, sg, with_backward=True)
+        if not differentiable:
+            with torch.no_grad():
+                return launch()[0]
+        return _PosteriorValue.apply('expected_reward', launch, *self._differentiable_tables(vc, dev))
+
+    def expected_reward_packed(self, pc, reward=None, seg_reward=None, *, differentiable=False):
+        """``expected_reward`` for a whole PackedCorpus: fp64 n_videos on the device, in the order of ``pc.video_names``.
+        ``reward``: total_frames x c_max on local states (the layout of ``frame_posteriors_packed``), ``seg_reward``:
+        n_groups x c_max.  ``differentiable``: as ``expected_reward``'s; the tables are ``stacked_tables(pc,
+        differentiable=True)``."""
+        self._require_device(pc.x, 'expected_reward_packed')
+        self.prepare_packed(pc)
+        batch = pc.batch
+        rw = _reward_tensor(reward, (batch.total_frames, batch.c_max), pc.x.device, 'reward')
+        sg = _reward_tensor(seg_reward, (batch.n_groups, batch.c_max), pc.x.device, 'seg_reward')
+        if rw is None and sg is None:
+            raise ValueError("expected_reward_packed: at least one of reward and seg_reward is needed")
+        launch = lambda: _expected_reward(self._packed_posterior_launch(pc, 'expected_reward_packed'), rw, sg, with_backward=False)
+        if not differentiable:
+            with torch.no_grad():
+                return launch()[0]
+        st = self.stacked_tables(pc, differentiable=True)[0]
+        return _PosteriorValue.apply('expected_reward', launch, *(st[k] for k in TABLE_NAMES))
+
+    def expected_accuracy(self, features, lengths, valid_classes_per_instance, labels, add_eos=True,
+                          additional_allowed_ends_per_instance=None, constraints=None, normalize=False, *, differentiable=False):
+        """Expected number of frames of each video on which a segmentation drawn from p(y | x) agrees with ``labels`` (b x Tmax,
+        GLOBAL class ids; padded frames are ignored; an id outside the batch's class set, or a negative one, is never
+        correct): fp64 b on the device; with ``normalize`` the fraction of the video's frames.  ``expected_reward`` with
+        reward = one-hot(labels): the quantity ``mbr_decode`` maximises over segmentations, here as a training signal for
+        the given labels (``differentiable``) or as a quality estimate of a decode."""
+        self._require_device(features, 'expected_accuracy')
+        dev = features.device
+        vc = self._check_valid_classes(valid_classes_per_instance)
+        ids = self._decode_tables(vc, dev)['class_map']
+        c = self.n_classes if vc is None else int(vc.numel())
+        lab = torch.as_tensor(labels).to(device=dev, dtype=torch.int64)
+        if tuple(lab.shape) != tuple(features.shape[:2]):
+            raise ValueError("labels: shape %s expected, got %s" % (tuple(features.shape[:2]), tuple(lab.shape)))
+        onehot = ((lab.unsqueeze(-1) == ids[:c].view(1, 1, c)) & (lab.unsqueeze(-1) >= 0)).to(torch.float64)
+        v = self.expected_reward(features, lengths, valid_classes_per_instance, reward=onehot, add_eos=add_eos,
+                                 additional_allowed_ends_per_instance=additional_allowed_ends_per_instance,
+                                 constraints=constraints, differentiable=differentiable)
+        return v / lengths.to(device=dev, dtype=torch.float64) if normalize else v
+
+    def expected_accuracy_packed(self, pc, labels, normalize=False, *, differentiable=False):
+        """``expected_accuracy`` for a whole PackedCorpus.  ``labels``: int64 total_frames, global class ids on the packed frame
+        axis (what ``decode_packed`` returns); fp64 n_videos in the order of ``pc.video_names``."""
+        self._require_device(pc.x, 'expected_accuracy_packed')
+        self.prepare_packed(pc)
+        batch, dev = pc.batch, pc.x.device
+        lab = torch.as_tensor(labels).to(device=dev, dtype=torch.int64)
+        if tuple(lab.shape) != (batch.total_frames,):
+            raise ValueError("labels: shape %s expected, got %s" % ((batch.total_frames,), tuple(lab.shape)))
+        group = np.zeros(batch.b, dtype=np.int64) if batch.group is None else batch.group.astype(np.int64)
+        cmap = pc.tables['class_map'][:, :batch.c_max]                         # n_groups x c_max global ids
+        live = torch.arange(batch.c_max, device=dev).view(1, -1) < torch.as_tensor(batch.n_states, device=dev).view(-1, 1)
+        frame_group = torch.zeros(batch.total_frames, dtype=torch.int64, device=dev)
+        covered = torch.zeros(batch.total_frames, dtype=torch.bool, device=dev)
+        for off, t, g in zip(batch.frame_offset.tolist(), batch.lengths.tolist(), group.tolist()):
+            frame_group[off:off + t] = g
+            covered[off:off + t] = True
+        onehot = (lab.view(-1, 1) == cmap[frame_group]) & live[frame_group] & (lab.view(-1, 1) >= 0) & covered.view(-1, 1)
+        v = self.expected_reward_packed(pc, reward=onehot.to(torch.float64), differentiable=differentiable)
+        return v / torch.as_tensor(batch.lengths, device=dev).to(torch.float64) if normalize else v
+
+    def expected_segment_count(self, features, lengths, valid_classes_per_instance, add_eos=True,
+                               additional_allowed_ends_per_instance=None, constraints=None, *, differentiable=False):
+        """Expected number of segments of each video under p(y | x): fp64 b on the device.  ``expected_reward`` with
+        seg_reward = 1 -- differentiable, it is an over-segmentation penalty.  With add_eos=False the closing label of the last
+        frame counts as a segment (``segment_posteriors``' convention)."""
+        vc = self._check_valid_classes(valid_classes_per_instance)
+        c = self.n_classes if vc is None else int(vc.numel())
+        return self.expected_reward(features, lengths, valid_classes_per_instance,
+                                    seg_reward=torch.ones(c, dtype=torch.float64, device=features.device), add_eos=add_eos,
+                                    additional_allowed_ends_per_instance=additional_allowed_ends_per_instance,
+                                    constraints=constraints, differentiable=differentiable)
+
+    def expected_segment_count_packed(self, pc, *, differentiable=False):
+        """``expected_segment_count`` for a whole PackedCorpus: fp64 n_videos in the order of ``pc.video_names``."""
+        self._require_device(pc.x, 'expected_segment_count_packed')
+        self.prepare_packed(pc)
+        ones = torch.ones((pc.batch.n_groups, pc.batch.c_max), dtype=torch.float64, device=pc.x.device)
+        return self.expected_reward_packed(pc, seg_reward=ones, differentiable=differentiable)
 
     # ------------------------------------------------------------------ segment and boundary posteriors (smm_segment_posteriors_f64)
     @torch.no_grad()

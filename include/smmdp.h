@@ -22,6 +22,9 @@
  *                              video between two posteriors of one lattice; the reference never calls them)
  *   smm_entropy_bwd_f64 /   <- autograd through pytorch-struct's entropy / kl / cross_entropy (the gradients of the three
  *   smm_kl_bwd_f64             values with respect to p's tables)
+ *   smm_expected_reward_f64 / <- the posterior expectation of a frame- and segment-additive reward (expected correct frames,
+ *   smm_expected_reward_bwd_f64  expected segment count, expected time in a class) and its gradient with respect to p's tables,
+ *                              a Hessian-vector product of log Z (minimum-risk training; the reference has none)
  *   smm_kbest_f64           <- pytorch-struct's SemiMarkovCRF(...).kmax / topk (the k best segmentations; the reference never
  *                              calls it)
  *   smm_mbr_f64             <- minimum-Bayes-risk decode under frame loss: the feasible segmentation with the most expected
@@ -473,6 +476,58 @@ int smm_kl_bwd_f64(const smm_shape *shape, const int64_t *lengths_host, const in
                    const double *endpen_q, const double *logz_q, void *ws_q, size_t ws_q_bytes, int32_t mode,
                    const double *grad_out, double *g_elp, double *g_trans, double *g_init, double *g_len, double *value_out,
                    void *scratch, size_t scratch_bytes, void *stream);
+
+/*
+ * Posterior expectation of a reward that is additive over frames and segments, and its gradient with respect to p's tables
+ * (csrc/smm_expected_reward.hip):
+ *   R(y) = sum over the spans (s, k, c) of y of ( seg_reward[c] + sum_{t = s .. s+k-1} reward[t][c] ),   V = E_{p(y | x)}[ R(y) ]
+ * reward = onehot(labels) makes V the expected number of correct frames (smm_mbr_f64 decodes for it, this trains for it),
+ * seg_reward = 1 the expected number of segments, reward[:, c] = 1 the expected time spent in class c.  The value gathers over
+ * the two histories (<reward, frame posteriors> + <seg_reward, span-start posteriors>, no recursion).  The gradient
+ * dV / d theta_o = Cov_p(R, phi_o) is a Hessian-vector product of log Z: each occurrence's probability times
+ * r(o) + eta-(S_o) + eta+(E_o) - V, from the prefix and suffix expectations eta- and eta+ over the sampler's decisions (two serial
+ * passes per video, one per direction; smm_entropy_bwd_f64's scheme with one side and no logarithms).  Sums run in a fixed
+ * order: value and gradient are bit-identical run to run.  Under SMM_SHAPE_NO_EOS the closing label `to` of frame T counts as a
+ * one-frame span, as in smm_segment_posteriors_f64: it carries reward[T][to] + seg_reward[to].
+ * Call order and workspace as smm_entropy_f64 / smm_entropy_bwd_f64: the call must follow smm_logz_f64 on the same shape, tables
+ * and workspace; without SMM_SHAPE_LOGZ_BOTH it runs the time-reversed recursion itself; the histories are left as they were
+ * (the scratch rows behind them are written: smm_logz_bwd_f64's and smm_entropy_f64's, which rewrite them, may follow).
+ *   reward      dev fp64 [total_frames][c_max], local states as columns                                        (nullable)
+ *   seg_reward  dev fp64 [n_groups][c_max]                                                                    (nullable)
+ *   value_out   smm_expected_reward_f64: dev fp64 [b], V
+ *               smm_expected_reward_bwd_f64: dev fp64 [b][2] or NULL: V by the two decompositions, V- at the sampler's final
+ *               decision and V+ at the initial class; both are smm_expected_reward_f64's value up to rounding
+ *   parts_out   dev fp64 [b][2] or NULL: the frame part <reward, frame posteriors> and the segment part of V
+ *   grad_out    dev fp64 [b] upstream gradient (NULL = ones)
+ *   g_elp, g_trans, g_init, g_len   smm_logz_bwd_f64's outputs and layouts (overwritten; padded rows and columns 0)
+ *   scratch     dev, smm_expected_reward_bwd_scratch_bytes; its contents are undefined after the call.  smm_workspace_bytes does
+ *               not change.
+ * Columns c >= n_states and frames no video covers are ignored in both rewards.  A masked potential has p(o) = 0 and
+ * contributes 0 to the value and gets gradient 0.  The rewards get no gradient here (dV / d reward is the frame posterior,
+ * smm_logz_bwd_f64's g_elp; dV / d seg_reward the span-start posterior, smm_segment_posteriors_f64's start_post).
+ * A video whose log Z is not finite, or with a non-finite reward in a covered entry (or in its group's seg_reward), gets NaN:
+ * its value, its g_elp rows and its group's tables; the error word is set.
+ * Accuracy: a span's frame reward is a difference of prefix sums of `reward`, so it carries the rounding of sum_t |reward[t][c]|
+ * in fp64: rewards are meant to be O(1) per frame.
+ * SMM_ERR_ARG, before anything is staged, when a required input (elp, trans, init, len_scores, logz) or output (value_out of the
+ * value call; g_elp, g_trans, g_init, g_len) is NULL, when both reward and seg_reward are NULL, or when scratch is NULL;
+ * SMM_ERR_WORKSPACE for a short workspace or scratch.
+ */
+/* host only; 0 on invalid arguments (those of smm_entropy_bwd_scratch_bytes) */
+size_t smm_expected_reward_bwd_scratch_bytes(const smm_shape *shape, const int64_t *lengths_host);
+int smm_expected_reward_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                            const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                            const double *elp, const double *trans, const double *init, const double *len_scores,
+                            const double *endpen, const double *logz, const double *reward, const double *seg_reward,
+                            double *value_out, double *parts_out,
+                            void *workspace, size_t workspace_bytes, void *stream);
+int smm_expected_reward_bwd_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                const double *elp, const double *trans, const double *init, const double *len_scores,
+                                const double *endpen, const double *logz, const double *reward, const double *seg_reward,
+                                const double *grad_out,
+                                double *g_elp, double *g_trans, double *g_init, double *g_len, double *value_out,
+                                void *scratch, size_t scratch_bytes, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * The k highest-scoring segmentations (k-best Viterbi: the DP in the k-max semiring; csrc/smm_kbest.hip).  The candidate set
