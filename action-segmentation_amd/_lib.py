@@ -22,6 +22,8 @@ SYMBOLS = [
     "smm_entropy_bwd_scratch_bytes", "smm_entropy_bwd_f64", "smm_kl_bwd_f64",
     "smm_expected_reward_bwd_scratch_bytes", "smm_expected_reward_f64", "smm_expected_reward_bwd_f64",
     "smm_align_graph_entropy_bwd_scratch_bytes", "smm_align_graph_entropy_bwd_f64", "smm_align_graph_kl_bwd_f64",
+    "smm_align_graph_expected_reward_scratch_bytes", "smm_align_graph_expected_reward_bwd_scratch_bytes",
+    "smm_align_graph_expected_reward_f64", "smm_align_graph_expected_reward_bwd_f64",
     "smm_factor_tables_f64", "smm_factor_tables_bwd_f64",
     "smm_dense_workspace_bytes", "smm_dense_dp_f32", "smm_dense_marginals_f32",
     "smm_eval_workspace_bytes", "smm_eval_confusion_i64", "smm_eval_videos_i64",
@@ -195,6 +197,15 @@ def load():
     lib.smm_align_graph_kl_bwd_f64.argtypes = [ctypes.POINTER(SmmShape)] + [ctypes.c_void_p] * 11 + [ctypes.c_void_p, ctypes.c_size_t] \
         + [ctypes.c_void_p] * 4 + [ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 4 + [ctypes.c_int32] \
         + [ctypes.c_void_p] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    for query in (lib.smm_align_graph_expected_reward_scratch_bytes, lib.smm_align_graph_expected_reward_bwd_scratch_bytes):
+        query.restype = ctypes.c_size_t
+        query.argtypes = [ctypes.POINTER(SmmShape), ctypes.c_void_p, ctypes.c_void_p]
+    lib.smm_align_graph_expected_reward_f64.restype = ctypes.c_int
+    lib.smm_align_graph_expected_reward_f64.argtypes = [ctypes.POINTER(SmmShape)] + [ctypes.c_void_p] * 19 \
+        + [ctypes.c_void_p, ctypes.c_size_t] * 2 + [ctypes.c_void_p]
+    lib.smm_align_graph_expected_reward_bwd_f64.restype = ctypes.c_int
+    lib.smm_align_graph_expected_reward_bwd_f64.argtypes = [ctypes.POINTER(SmmShape)] + [ctypes.c_void_p] * 23 \
+        + [ctypes.c_void_p, ctypes.c_size_t] * 2 + [ctypes.c_void_p]
     lib.smm_dp_timing_enable.restype = None
     lib.smm_dp_timing_enable.argtypes = [ctypes.c_int]
     lib.smm_dp_timing_read.restype = ctypes.c_int

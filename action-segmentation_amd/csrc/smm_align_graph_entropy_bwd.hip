@@ -46,13 +46,8 @@
 
 #define SMM_AGB_OCC_THREADS 256
 
-// a video's state in its parts: its terms are summed, it contributes nothing (no alignment under p, a NaN, other graphs), or
-// its value is not finite (NaN rows, NaN tables for its group)
-#define SMM_AGB_RUN 0.0
-#define SMM_AGB_SKIP 1.0
-#define SMM_AGB_NAN 2.0
-
-__host__ __device__ inline size_t agb_part_doubles(int cm, int k_rows) { return (size_t)k_rows * cm + (size_t)cm * cm + cm + 2; }
+// (a video's state in its parts, SMM_AGB_RUN / _SKIP / _NAN, and the size of the parts: smm_launch.h)
+__host__ __device__ inline size_t agb_part_doubles(int cm, int k_rows) { return smm_agb_part_doubles(cm, k_rows); }
 
 // the two sides' columns, q's tables (p's are the AlignVideo's) and the scratch blocks of one video
 struct AgbVideo {
@@ -503,7 +498,12 @@ void smm_launch_align_graph_entropy_bwd(const SmmAlignEntBwdArgs &a, hipStream_t
     hipLaunchKernelGGL(smm_align_graph_eta_minus_kernel, grid, block, 0, stream, a);
     hipLaunchKernelGGL(smm_align_graph_eta_plus_kernel, grid, block, 0, stream, a);
     hipLaunchKernelGGL(smm_align_graph_entropy_bwd_kernel, grid, block, 0, stream, a);
-    hipLaunchKernelGGL(smm_align_graph_entropy_bwd_occ_kernel, grid, dim3(SMM_AGB_OCC_THREADS), 0, stream, a);
+    smm_launch_align_graph_entropy_bwd_tail(a, stream);
+}
+
+void smm_launch_align_graph_entropy_bwd_tail(const SmmAlignEntBwdArgs &a, hipStream_t stream)
+{
+    hipLaunchKernelGGL(smm_align_graph_entropy_bwd_occ_kernel, dim3((unsigned)a.g.b), dim3(SMM_AGB_OCC_THREADS), 0, stream, a);
     const unsigned cells = (unsigned)(a.g.k_rows * a.g.c_max + a.g.c_max * a.g.c_max + a.g.c_max);
     hipLaunchKernelGGL(smm_align_graph_entropy_bwd_reduce_kernel, dim3((cells + 255) / 256, (unsigned)a.g.n_groups),
                        dim3(256), 0, stream, a);

@@ -2808,6 +2808,129 @@ extern "C" int smm_align_graph_kl_bwd_f64(const smm_shape *shape, const int64_t 
                      static_cast<hipStream_t>(stream));
 }
 
+// expected reward under the graph posterior and its gradient (smm_align_graph_expected_reward.hip).  The caller's scratch, in
+// doubles: the value call's is the videos' cumW offsets [b], cumW ((T + 1) c_max per video), two partials per node; the gradient
+// call's is the entropy-gradient call's layout, then the offsets and cumW
+struct AgerLayout {
+    size_t pv_base, o_off, o_cumw, o_partial, total;
+};
+
+static bool ager_layout(const smm_shape *s, const int64_t *lengths, const int64_t *noff, bool bwd, AgerLayout *lo)
+{
+    size_t front = 0;
+    lo->pv_base = 0;
+    if (bwd) {
+        if (!agbwd_layout(s, lengths, noff, &lo->pv_base, &front)) return false;
+    } else {
+        AlignLayout al;
+        if (align_layout(ALIGN_GRAPH_LOGZ, s, lengths, noff, &al) != SMM_OK) return false;
+    }
+    size_t rows = 0;
+    for (int i = 0; i < s->b; ++i) rows += (size_t)lengths[i] + 1;
+    lo->o_off = front;
+    lo->o_cumw = lo->o_off + (size_t)s->b;
+    lo->o_partial = lo->o_cumw + rows * (size_t)s->c_max;
+    lo->total = lo->o_partial + (bwd ? 0 : 2 * (size_t)(noff[s->b] - noff[0]));
+    return true;
+}
+
+extern "C" size_t smm_align_graph_expected_reward_scratch_bytes(const smm_shape *shape, const int64_t *lengths_host,
+                                                                const int64_t *node_offset_host)
+{
+    AgerLayout lo;
+    return ager_layout(shape, lengths_host, node_offset_host, false, &lo) ? sizeof(double) * lo.total : 0;
+}
+
+extern "C" size_t smm_align_graph_expected_reward_bwd_scratch_bytes(const smm_shape *shape, const int64_t *lengths_host,
+                                                                    const int64_t *node_offset_host)
+{
+    AgerLayout lo;
+    return ager_layout(shape, lengths_host, node_offset_host, true, &lo) ? sizeof(double) * lo.total : 0;
+}
+
+// both entry points up to their launch: the entropy-gradient call's refusals, their own, the staging, the q and bh columns
+static int ager_prepare(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                        const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host, const double *elp,
+                        const double *trans, const double *init, const double *len_scores, const double *endpen,
+                        const int32_t *node_class, const uint32_t *pred_mask, const uint8_t *node_flags,
+                        const int64_t *node_offset_host, const double *logz_g, const double *reward, const double *node_reward,
+                        bool outputs_ok, bool bwd, void *scratch, size_t scratch_bytes, void *workspace, size_t workspace_bytes,
+                        hipStream_t hs, SmmAlignExpRewardArgs *a)
+{
+    if (!pred_mask || !node_flags || !outputs_ok || !scratch || (!reward && !node_reward)) return SMM_ERR_ARG;
+    AlignLayout al;
+    int rc = align_graph_two_sides(shape, lengths_host, frame_offset_host, n_states_host, node_offset_host, elp, trans, init,
+                                   len_scores, node_class, logz_g, workspace, workspace_bytes, trans, len_scores, logz_g, workspace,
+                                   workspace_bytes, false, &al);
+    if (rc != SMM_OK) return rc;
+    AgerLayout lo;
+    ager_layout(shape, lengths_host, node_offset_host, bwd, &lo);
+    if (scratch_bytes < sizeof(double) * lo.total) return SMM_ERR_WORKSPACE;
+    *a = SmmAlignExpRewardArgs{};
+    rc = align_graph_prepare(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp, trans, init,
+                             len_scores, endpen, node_class, pred_mask, node_flags, node_offset_host, logz_g, workspace,
+                             workspace_bytes, hs, &a->e.g);
+    if (rc != SMM_OK) return rc;
+    double *sc = static_cast<double *>(scratch);
+    a->e.scratch = sc;
+    a->e.pv_base = (int64_t)lo.pv_base;
+    a->e.q = SmmAlignSideQ{trans, len_scores, endpen, logz_g, a->e.g.hist, a->e.g.cols};
+    a->reward = reward; a->node_reward = node_reward;
+    a->cw_off = reinterpret_cast<int64_t *>(sc + lo.o_off);
+    a->cumw = sc + lo.o_cumw;
+    a->partial = sc + lo.o_partial;
+    a->n_nodes = node_offset_host[shape->b] - node_offset_host[0];
+    return SMM_OK;
+}
+
+extern "C" int smm_align_graph_expected_reward_f64(const smm_shape *shape, const int64_t *lengths_host,
+                                                   const int64_t *frame_offset_host, const int32_t *group_host,
+                                                   const int32_t *kp_host, const int32_t *n_states_host, const double *elp,
+                                                   const double *trans, const double *init, const double *len_scores,
+                                                   const double *endpen, const int32_t *node_class, const uint32_t *pred_mask,
+                                                   const uint8_t *node_flags, const int64_t *node_offset_host, const double *logz_g,
+                                                   const double *reward, const double *node_reward, double *value_out,
+                                                   double *parts_out, void *scratch, size_t scratch_bytes, void *workspace,
+                                                   size_t workspace_bytes, void *stream)
+{
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    SmmAlignExpRewardArgs a;
+    const int rc = ager_prepare(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp, trans, init,
+                                len_scores, endpen, node_class, pred_mask, node_flags, node_offset_host, logz_g, reward,
+                                node_reward, value_out != nullptr, false, scratch, scratch_bytes, workspace, workspace_bytes, hs, &a);
+    if (rc != SMM_OK) return rc;
+    a.value = value_out; a.parts = parts_out;
+    smm_launch_align_graph_logz_bwd_columns(a.e.g, hs);
+    smm_launch_align_graph_expected_reward(a, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
+extern "C" int smm_align_graph_expected_reward_bwd_f64(const smm_shape *shape, const int64_t *lengths_host,
+                                                       const int64_t *frame_offset_host, const int32_t *group_host,
+                                                       const int32_t *kp_host, const int32_t *n_states_host, const double *elp,
+                                                       const double *trans, const double *init, const double *len_scores,
+                                                       const double *endpen, const int32_t *node_class, const uint32_t *pred_mask,
+                                                       const uint8_t *node_flags, const int64_t *node_offset_host,
+                                                       const double *logz_g, const double *reward, const double *node_reward,
+                                                       const double *grad_out, double *g_elp, double *g_trans, double *g_init,
+                                                       double *g_len, double *value_out, void *scratch, size_t scratch_bytes,
+                                                       void *workspace, size_t workspace_bytes, void *stream)
+{
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    SmmAlignExpRewardArgs a;
+    int rc = ager_prepare(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, elp, trans, init, len_scores,
+                          endpen, node_class, pred_mask, node_flags, node_offset_host, logz_g, reward, node_reward,
+                          g_elp && g_trans && g_init && g_len, true, scratch, scratch_bytes, workspace, workspace_bytes, hs, &a);
+    if (rc == SMM_OK) rc = align_logz_bwd_outputs(shape, grad_out, g_elp, g_trans, g_init, g_len, hs, &a.e.g);
+    if (rc != SMM_OK) return rc;
+    a.vpm = value_out;
+    smm_launch_align_graph_logz_bwd_columns(a.e.g, hs);
+    smm_launch_align_graph_expected_reward_bwd(a, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ dense boundary
 struct DenseLayout {
     size_t o_len, o_alpha, o_beta, o_bp_from, o_bp_k, o_rmsg, total;

@@ -403,10 +403,39 @@ struct SmmAlignEntBwdArgs {
     int32_t kl;                // 0: cross-entropy (entropy), 1: KL
 };
 size_t smm_align_graph_entropy_bwd_part_doubles(int c_max, int k_rows);   // the parts of one video
+// ... on the device: g_len [k_rows][c_max], g_trans [c_max][c_max], g_init [c_max], V-, state
+__host__ __device__ inline size_t smm_agb_part_doubles(int cm, int k_rows) { return (size_t)k_rows * cm + (size_t)cm * cm + cm + 2; }
+// a video's state in its parts: its terms are summed, it contributes nothing (no alignment under p, a NaN, other graphs), or
+// its value is not finite (NaN rows, NaN tables for its group)
+#define SMM_AGB_RUN 0.0
+#define SMM_AGB_SKIP 1.0
+#define SMM_AGB_NAN 2.0
 void smm_launch_align_graph_entropy_bwd(const SmmAlignEntBwdArgs &a, hipStream_t stream);
+// ... its last two kernels alone (g_elp as the running sum of D, the groups' tables): what follows kernels that left D, the
+// videos' parts and their states in that unit's scratch layout (smm_align_graph_expected_reward.hip does)
+void smm_launch_align_graph_entropy_bwd_tail(const SmmAlignEntBwdArgs &a, hipStream_t stream);
 // ... before q's workspace is touched: out[i] = logz_q[i] where the two sides' recorded ranges agree, NaN where they differ
 // (g.cols, g.hoff, g.toff, g.logz and cols_q are read)
 void smm_launch_align_graph_entropy_bwd_check(const SmmAlignEntBwdArgs &a, const double *logz_q, double *out, hipStream_t stream);
+
+// expected frame- and node-additive reward under the transcript-graph posterior and its gradient with respect to the tables
+// (smm_align_graph_expected_reward.hip): after smm_launch_align_graph_logz_fwd and smm_launch_align_graph_logz_bwd_columns on
+// the same workspace.  The value launch reads e.g only; the gradient launch uses e as smm_launch_align_graph_entropy_bwd does
+// (e.q: p's own pointers; e.kl and e.value unused)
+struct SmmAlignExpRewardArgs {
+    SmmAlignEntBwdArgs e;
+    const double *reward;      // [total_frames][c_max] or null
+    const double *node_reward; // [toff[b]] or null
+    int64_t *cw_off;           // [b] caller's scratch: the doubles in front of each video's cumW (the prefix kernel writes them)
+    double *cumw;              // caller's scratch: per video cumW [C][T+1], (T+1) c_max doubles each
+    double *partial;           // caller's scratch: [n_nodes][2] frame part, node part     (value launch)
+    double *value;             // [b]                                                      (value launch)
+    double *parts;             // [b][2] or null: frame part, node part                    (value launch)
+    double *vpm;               // [b][2] or null: V-, V+                                   (gradient launch)
+    int64_t n_nodes;
+};
+void smm_launch_align_graph_expected_reward(const SmmAlignExpRewardArgs &a, hipStream_t stream);
+void smm_launch_align_graph_expected_reward_bwd(const SmmAlignExpRewardArgs &a, hipStream_t stream);
 
 // alignments drawn from the transcript-graph posterior (smm_align_graph_sample.hip): after smm_launch_align_graph_logz_fwd on
 // the same workspace -- it reads cum, the h and gam columns and the columns' ranges, and writes the error word only

@@ -1490,6 +1490,106 @@ def align_graph_kl_bwd(batch, p, q, graphs, grad_out=None, staged=None, cross_en
                             _lib.KL_BWD_CROSS_ENTROPY if cross_entropy else _lib.KL_BWD_KL, scratch)
 
 
+def _graph_reward_scratch_bytes(symbol, batch, node_offset):
+    off = np.ascontiguousarray(node_offset, dtype=np.int64)
+    n = getattr(_lib.load(), symbol)(ctypes.byref(batch.shape), ctypes.c_void_p(batch.lengths.ctypes.data),
+                                     ctypes.c_void_p(off.ctypes.data))
+    if n == 0:
+        raise ValueError("align_graph_expected_reward: the library refuses this batch and these node offsets")
+    return int(n)
+
+
+def align_graph_expected_reward_scratch_bytes(batch, node_offset):
+    """Bytes of scratch smm_align_graph_expected_reward_f64 needs for this batch and these node offsets (int64 [b + 1]; host
+    only); raises ValueError for what the call refuses."""
+    return _graph_reward_scratch_bytes('smm_align_graph_expected_reward_scratch_bytes', batch, node_offset)
+
+
+def align_graph_expected_reward_bwd_scratch_bytes(batch, node_offset):
+    """... smm_align_graph_expected_reward_bwd_f64 needs."""
+    return _graph_reward_scratch_bytes('smm_align_graph_expected_reward_bwd_scratch_bytes', batch, node_offset)
+
+
+def _graph_reward_call(what, batch, elp, graphs, reward, node_reward, ws, staged, scratch, need_of):
+    """What both expected-reward calls check before a device is touched: the workspace and the supervision as every call behind
+    ``align_graph_logz``, the rewards' shapes, the scratch.  ``node_reward``: one fp64 tensor over all nodes or a list of
+    per-video ones.  -> (supervision, reward, node_reward, scratch, bytes needed)."""
+    dev = elp.device
+    if reward is None and node_reward is None:
+        raise ValueError("%s: pass reward, node_reward or both" % what)
+    sup = _after_graph_logz(what, batch, dev, graphs, staged, ws)
+    if reward is not None and (reward.dtype != torch.float64 or tuple(reward.shape) != tuple(elp.shape)):
+        raise ValueError("%s: reward must be fp64 %s like elp, got %s %s" % (what, tuple(elp.shape), reward.dtype, tuple(reward.shape)))
+    if isinstance(node_reward, (list, tuple)):
+        node_reward = torch.cat([r.reshape(-1) for r in node_reward])
+    if node_reward is not None and (node_reward.dtype != torch.float64 or tuple(node_reward.shape) != (sup.n,)):
+        raise ValueError("%s: node_reward must be fp64 [%d], one entry per node, got %s %s"
+                         % (what, sup.n, node_reward.dtype, tuple(node_reward.shape)))
+    need = need_of(batch, sup.off)
+    if scratch is not None and (scratch.dtype != torch.uint8 or scratch.numel() < need):
+        raise ValueError("%s: scratch must be a uint8 tensor of at least %d bytes" % (what, need))
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    return sup, reward, node_reward, scratch, need
+
+
+def align_graph_expected_reward(batch, elp, trans, init, len_scores, graphs, logz_g, reward=None, node_reward=None, endpen=None,
+                                ws=None, staged=None, scratch=None, want_parts=False):
+    """The expectation of a frame- and node-additive reward under the transcript-graph posterior
+    (smm_align_graph_expected_reward_f64): per video V = E[ sum over the segments (node j, frames s .. n-1) of the alignment of
+    node_reward[j] + sum_t reward[t, a_j] ].  ``reward`` fp64 [total_frames, c_max] (local states as columns) and/or
+    ``node_reward`` fp64 [n_nodes] (or a list of per-video tensors), laid out like the graphs' nodes.  Must follow
+    ``align_graph_logz`` for the same batch, tables and graphs with the same workspace ``ws`` on the same stream (``ws`` and
+    ``staged``: its ``ws`` and ``_staged`` entries); ``logz_g`` = its output.  The backward, sampler, entropy, segment-posterior
+    and KL results on that workspace do not change.  -> dict(value fp64 [b], parts fp64 [b, 2] (with ``want_parts``: the frame
+    part and the node part) or None, _err, _staged, _keep).  A video without an alignment (log Z_g = -inf) gets NaN; a reward
+    that is not finite gives its video NaN and sets the error word.  ``scratch``: the caller's, of
+    ``align_graph_expected_reward_scratch_bytes`` (uint8; it need not be initialised); default: a private one.
+    Gradient: ``align_graph_expected_reward_bwd``."""
+    what = 'align_graph_expected_reward'
+    sup, reward, node_reward, scratch, _ = _graph_reward_call(what, batch, elp, graphs, reward, node_reward, ws, staged, scratch,
+                                                              align_graph_expected_reward_scratch_bytes)
+    lib = _lib.load()
+    f64 = torch.float64
+    dev = elp.device
+    tables = _tables(elp, trans, init, len_scores, endpen)
+    value = torch.empty(batch.b, dtype=f64, device=dev)
+    parts = torch.empty((batch.b, 2), dtype=f64, device=dev) if want_parts else None
+    _lib.check(lib.smm_align_graph_expected_reward_f64(
+        *batch.head(), *tables, *sup.args(), _dev(logz_g, f64, 'logz_g'), _dev(reward, f64, 'reward'),
+        _dev(node_reward, f64, 'node_reward'), _dev(value, f64, 'value'), _dev(parts, f64, 'parts'), *_ws_args(scratch),
+        *_ws_args(ws), _stream()))
+    return dict(value=value, parts=parts, _err=_err_copy(batch, ws), _staged=sup.dev, _keep=(ws, scratch, reward, node_reward))
+
+
+def align_graph_expected_reward_bwd(batch, elp, trans, init, len_scores, graphs, logz_g, reward=None, node_reward=None,
+                                    grad_out=None, endpen=None, ws=None, staged=None, scratch=None, want_value=False):
+    """Gradient of sum_i grad_out[i] * V_i, the value ``align_graph_expected_reward`` returns, with respect to the tables
+    (smm_align_graph_expected_reward_bwd_f64): a Hessian-vector product of log Z_g.  Arguments and call order as
+    ``align_graph_expected_reward``.  -> dict(elp [total_frames, c_max], trans, init, len fp64, value fp64 [b] (with
+    ``want_value``, else None): V by the message pass over the sampler's decisions, value_plus: by the time-forward walk's,
+    _err, _staged, _keep).  There is no gradient for the rewards: V is linear in them (``align_graph_logz_bwd``'s elp and
+    node_prob).  A video without an alignment contributes zeros; ``grad_out[i] = 0`` gives exact zeros.  ``scratch``: the
+    caller's, of ``align_graph_expected_reward_bwd_scratch_bytes``."""
+    what = 'align_graph_expected_reward_bwd'
+    sup, reward, node_reward, scratch, _ = _graph_reward_call(what, batch, elp, graphs, reward, node_reward, ws, staged, scratch,
+                                                              align_graph_expected_reward_bwd_scratch_bytes)
+    lib = _lib.load()
+    f64 = torch.float64
+    dev = elp.device
+    tables = _tables(elp, trans, init, len_scores, endpen)
+    g = _grad_outputs(elp, trans, init, len_scores)
+    both = torch.empty((batch.b, 2), dtype=f64, device=dev) if want_value else None
+    _lib.check(lib.smm_align_graph_expected_reward_bwd_f64(
+        *batch.head(), *tables, *sup.args(), _dev(logz_g, f64, 'logz_g'), _dev(reward, f64, 'reward'),
+        _dev(node_reward, f64, 'node_reward'), _dev(grad_out, f64, 'grad_out'), _dev(g['elp'], f64, 'g_elp'),
+        _dev(g['trans'], f64, 'g_trans'), _dev(g['init'], f64, 'g_init'), _dev(g['len'], f64, 'g_len'), _dev(both, f64, 'value'),
+        *_ws_args(scratch), *_ws_args(ws), _stream()))
+    g.update(value=None if both is None else both[:, 0], value_plus=None if both is None else both[:, 1],
+             _err=_err_copy(batch, ws), _staged=sup.dev, _keep=(ws, scratch, reward, node_reward))
+    return g
+
+
 def transcript_is_ambiguous(ids, optional):
     """Host only: True when two different subsets of the optional entries of this transcript give the same non-empty class
     sequence -- ``align_opt_logz`` then counts the segmentations with that class sequence once per subset.  Exact: over the

@@ -433,19 +433,68 @@ class SemiMarkovModel(object):
         pc = self.prepare(data, shard=shard)
         if pc.n_videos == 0:
             return {}
+        packed = self._packed_labels(pc, data, labels_by_video, 'expected_accuracy')
+        with torch.no_grad():
+            v = self.model.expected_accuracy_packed(pc, packed).cpu().numpy()
+        return {name: float(x) for name, x in zip(pc.video_names, v)}
+
+    def _packed_labels(self, pc, data, labels_by_video, what):
+        """``labels_by_video`` (None: the ground truth of ``data``, ``gt_single``) on the packed frame axis of ``pc``: int64
+        total_frames, -1 on frames no video covers."""
         if labels_by_video is None:
             loader = make_data_loader(self.args, data, batch_by_task=False, shuffle=False, batch_size=1)
             labels_by_video = {batch['video_name'][0]: batch['gt_single'].squeeze(0).cpu().numpy() for batch in loader}
-        labels = self._per_video(pc, labels_by_video, "expected_accuracy: no labels for video %r")
+        labels = self._per_video(pc, labels_by_video, what + ": no labels for video %r")
         batch = pc.batch
         packed = np.full(batch.total_frames, -1, dtype=np.int64)
         for name, lab, off, t in zip(pc.video_names, labels, pc.frame_offset, batch.lengths.tolist()):
             lab = np.asarray(lab, dtype=np.int64).reshape(-1)
             if lab.shape[0] != t:
-                raise ValueError("expected_accuracy: video %r has %d frames, %d labels were given" % (name, t, lab.shape[0]))
+                raise ValueError("%s: video %r has %d frames, %d labels were given" % (what, name, t, lab.shape[0]))
             packed[int(off):int(off) + t] = lab
+        return torch.from_numpy(packed)
+
+    def alignment_expected_accuracy(self, data, transcripts_by_video, labels_by_video=None, shard=None, *, optional_by_video=None,
+                                    optional_classes=None):
+        """``{video: expected number of frames on which an alignment drawn from the posterior given the video's transcript agrees
+        with the labels}``, exactly (``align``'s conventions for ``transcripts_by_video``, ``optional_by_video`` and
+        ``optional_classes``; ``expected_accuracy``'s for ``labels_by_video``, None: the ground truth of ``data``).  The frame
+        accuracy weak supervision can reach without committing to the best alignment; NaN where the transcript cannot be laid
+        over the video.  One emission launch, the forward launch and one smm_align_graph_expected_reward_f64 launch on the
+        packed corpus (``SemiMarkovModule.alignment_expected_accuracy_packed``).  Values, not differentiable."""
+        from . import ops
+        self._one_kind_of_flags(optional_by_video, optional_classes, 'alignment_expected_accuracy')
+        self.model.eval()
+        pc = self.prepare(data, shard=shard)
+        if pc.n_videos == 0:
+            return {}
+        transcripts = self._per_video(pc, transcripts_by_video, "alignment_expected_accuracy: no transcript for video %r")
+        optional = self._optional_flags(pc, transcripts, optional_by_video, optional_classes, 'alignment_expected_accuracy')
+        if optional is None:
+            graphs = [ops.TranscriptGraph.chain(t) for t in transcripts]
+        else:
+            graphs = [ops.TranscriptGraph.from_optional(t, f) for t, f in zip(transcripts, optional)]
+        packed = self._packed_labels(pc, data, labels_by_video, 'alignment_expected_accuracy')
         with torch.no_grad():
-            v = self.model.expected_accuracy_packed(pc, torch.from_numpy(packed)).cpu().numpy()
+            v = self.model.alignment_expected_accuracy_packed(pc, graphs, packed).cpu().numpy()
+        return {name: float(x) for name, x in zip(pc.video_names, v)}
+
+    def candidate_expected_accuracy(self, data, candidates_by_video, labels_by_video=None, shard=None):
+        """``alignment_expected_accuracy`` given "the video follows one of these transcripts" (``candidates_by_video`` as in
+        ``align_candidates``): the expectation under the joint posterior over candidate and boundaries, which is the sum over
+        the candidates of ``candidate_posteriors`` times the candidate's own expected accuracy.  One prefix trie per video:
+        ValueError as ``candidate_entropy``."""
+        from . import ops
+        self._one_trie_each(candidates_by_video, 'candidate_expected_accuracy')
+        self.model.eval()
+        pc = self.prepare(data, shard=shard)
+        if pc.n_videos == 0:
+            return {}
+        graphs = [ops.TranscriptGraph.from_candidates(cands)
+                  for cands in self._per_video(pc, candidates_by_video, "candidate_expected_accuracy: no candidates for video %r")]
+        packed = self._packed_labels(pc, data, labels_by_video, 'candidate_expected_accuracy')
+        with torch.no_grad():
+            v = self.model.alignment_expected_accuracy_packed(pc, graphs, packed).cpu().numpy()
         return {name: float(x) for name, x in zip(pc.video_names, v)}
 
     def expected_segment_counts(self, data, shard=None):

@@ -231,6 +231,40 @@ def _alignment_entropy(r, sup, want_parts):
     return out['entropy'], out['parts'], (z,)
 
 
+def _node_rewards(sup, node_reward, seg_reward, group, dev, what):
+    """The rewards of the nodes as the launch takes them: fp64 [n_nodes] on the device, or None.  ``node_reward``: one tensor
+    over all nodes or one sequence per video, laid out like the graphs' nodes; ``seg_reward``: n_groups x c_max on LOCAL states,
+    broadcast over each node's class and added (a node whose class is no valid class of its video -- it leaves the video without
+    an alignment -- gets none)."""
+    graphs = sup[1][0]
+    n = sum(len(g) for g in graphs)
+    if isinstance(node_reward, (list, tuple)):
+        if len(node_reward) != len(graphs):
+            raise ValueError("%s: %d sequences of node rewards for %d videos" % (what, len(node_reward), len(graphs)))
+        node_reward = torch.cat([torch.as_tensor(v, dtype=torch.float64).reshape(-1) for v in node_reward])
+    nr = _reward_tensor(node_reward, (n,), dev, 'node_reward')
+    if seg_reward is None:
+        return nr
+    ids = np.concatenate([np.asarray(g.ids, np.int64) for g in graphs])
+    grp = np.concatenate([np.full(len(g), int(j), np.int64) for g, j in zip(graphs, group)])
+    valid = torch.as_tensor(ids >= 0, device=dev)
+    per_node = seg_reward[torch.as_tensor(grp, device=dev), torch.as_tensor(np.maximum(ids, 0), device=dev)]
+    per_node = torch.where(valid, per_node, torch.zeros_like(per_node))
+    return per_node.contiguous() if nr is None else nr + per_node
+
+
+def _alignment_expected_reward(r, sup, want_parts):
+    """The forward launch over the graphs of ``sup`` on a private workspace, then the expected-reward launch on it with the
+    rewards the record holds: (V, parts or None, (the forward launch,)).  A video without an alignment is no error: NaN."""
+    b = r['batch']
+    z = _supervised(_LOGZ, r, sup)
+    out = ops.align_graph_expected_reward(b, r['elp'], r['trans'], r['init'], r['len'], sup[1][0], z['logz'], reward=r['reward'],
+                                          node_reward=r['node_reward'], endpen=r['endpen'], ws=z['ws'], staged=z['_staged'],
+                                          want_parts=want_parts)
+    ops.check_decoded(b, out)
+    return out['value'], out['parts'], (z,)
+
+
 def _alignment_segment_posteriors(r, sup, spans=None, used=None, want_alignment=True, want_dense=False):
     """The forward launch over the graphs of ``sup`` on a private workspace, then the segment-posterior launch on it, for the
     alignments ``spans`` / ``used`` (None with ``want_alignment``: the best alignment, one launch more, in front).  -> the dict of
@@ -451,12 +485,12 @@ class _PosteriorValue(torch.autograd.Function):
 
 
 class _AlignmentValue(torch.autograd.Function):
-    """``_PosteriorValue`` for the transcript-graph posteriors: the entropy, cross-entropy or KL of every video's posterior over
-    its ALIGNMENTS as a differentiable function of the fp64 factor tables of p, and of q for the two-sided values.  ``launch()``
+    """``_PosteriorValue`` for the transcript-graph posteriors: the entropy, expected reward, cross-entropy or KL of every video's
+    posterior over its ALIGNMENTS as a differentiable function of the fp64 factor tables of p, and of q for the two-sided values.  ``launch()``
     computes the value exactly as the non-differentiable method does and returns (value, [p's record, q's], the supervision,
     (p's forward launch, q's)); the forward launches keep their workspaces until the backward runs.  Backward:
-    smm_align_graph_entropy_bwd_f64 / smm_align_graph_kl_bwd_f64 for p's tables, mu_q - mu_p (two smm_align_graph_logz_bwd_f64)
-    for q's, then the emission chain rule of each side."""
+    smm_align_graph_entropy_bwd_f64 / smm_align_graph_expected_reward_bwd_f64 / smm_align_graph_kl_bwd_f64 for p's tables,
+    mu_q - mu_p (two smm_align_graph_logz_bwd_f64) for q's, then the emission chain rule of each side."""
 
     @staticmethod
     def forward(ctx, kind, launch, *tables):
@@ -473,6 +507,10 @@ class _AlignmentValue(torch.autograd.Function):
         if ctx.kind == 'entropy':
             g = ops.align_graph_entropy_bwd(b, *side[:4], graphs, zp['logz'], grad_out=up, endpen=r['endpen'], ws=zp['ws'],
                                             staged=zp['_staged'])
+            return (None, None) + _table_grads(b, r['x'], g, zp['ws'])
+        if ctx.kind == 'expected_reward':
+            g = ops.align_graph_expected_reward_bwd(b, *side[:4], graphs, zp['logz'], reward=r['reward'], node_reward=r['node_reward'],
+                                                    grad_out=up, endpen=r['endpen'], ws=zp['ws'], staged=zp['_staged'])
             return (None, None) + _table_grads(b, r['x'], g, zp['ws'])
         q, zq = ctx.recs[1], ctx.fwd[1]
         g = ops.align_graph_kl_bwd(b, side, (q['trans'], q['len'], q['endpen'], zq['logz'], zq['ws']), graphs, grad_out=up,
@@ -496,6 +534,8 @@ def _alignment_value(kind, what, names, sides, tables, want_parts):
         recs = [r for r, _ in sides]
         if kind == 'entropy':
             value, pt, fwd = _alignment_entropy(recs[0], sup, want_parts)
+        elif kind == 'expected_reward':
+            value, pt, fwd = _alignment_expected_reward(recs[0], sup, want_parts)
         else:
             value, pt, fwd = _alignment_kl(recs[0], recs[1], sup, what, kind == 'cross_entropy', want_parts)
         for z in fwd:
@@ -1245,13 +1285,7 @@ class SemiMarkovModule(nn.Module):
         the given labels (``differentiable``) or as a quality estimate of a decode."""
         self._require_device(features, 'expected_accuracy')
         dev = features.device
-        vc = self._check_valid_classes(valid_classes_per_instance)
-        ids = self._decode_tables(vc, dev)['class_map']
-        c = self.n_classes if vc is None else int(vc.numel())
-        lab = torch.as_tensor(labels).to(device=dev, dtype=torch.int64)
-        if tuple(lab.shape) != tuple(features.shape[:2]):
-            raise ValueError("labels: shape %s expected, got %s" % (tuple(features.shape[:2]), tuple(lab.shape)))
-        onehot = ((lab.unsqueeze(-1) == ids[:c].view(1, 1, c)) & (lab.unsqueeze(-1) >= 0)).to(torch.float64)
+        onehot = self._onehot_labels(features, valid_classes_per_instance, labels)
         v = self.expected_reward(features, lengths, valid_classes_per_instance, reward=onehot, add_eos=add_eos,
                                  additional_allowed_ends_per_instance=additional_allowed_ends_per_instance,
                                  constraints=constraints, differentiable=differentiable)
@@ -1262,6 +1296,26 @@ class SemiMarkovModule(nn.Module):
         axis (what ``decode_packed`` returns); fp64 n_videos in the order of ``pc.video_names``."""
         self._require_device(pc.x, 'expected_accuracy_packed')
         self.prepare_packed(pc)
+        batch, dev = pc.batch, pc.x.device
+        v = self.expected_reward_packed(pc, reward=self._onehot_labels_packed(pc, labels), differentiable=differentiable)
+        return v / torch.as_tensor(batch.lengths, device=dev).to(torch.float64) if normalize else v
+
+    def _onehot_labels(self, features, valid_classes_per_instance, labels):
+        """``labels`` (b x Tmax, GLOBAL class ids) as a reward: fp64 b x Tmax x C, 1 where the frame's label is the column's
+        class; an id outside the batch's class set, or a negative one, matches no column."""
+        dev = features.device
+        vc = self._check_valid_classes(valid_classes_per_instance)
+        ids = self._decode_tables(vc, dev)['class_map']
+        c = self.n_classes if vc is None else int(vc.numel())
+        lab = torch.as_tensor(labels).to(device=dev, dtype=torch.int64)
+        if tuple(lab.shape) != tuple(features.shape[:2]):
+            raise ValueError("labels: shape %s expected, got %s" % (tuple(features.shape[:2]), tuple(lab.shape)))
+        return ((lab.unsqueeze(-1) == ids[:c].view(1, 1, c)) & (lab.unsqueeze(-1) >= 0)).to(torch.float64)
+
+    @staticmethod
+    def _onehot_labels_packed(pc, labels):
+        """``labels`` (int64 total_frames, GLOBAL class ids on the packed frame axis of a prepared corpus) as a reward: fp64
+        total_frames x c_max on local states; frames no video covers match no column."""
         batch, dev = pc.batch, pc.x.device
         lab = torch.as_tensor(labels).to(device=dev, dtype=torch.int64)
         if tuple(lab.shape) != (batch.total_frames,):
@@ -1275,8 +1329,7 @@ class SemiMarkovModule(nn.Module):
             frame_group[off:off + t] = g
             covered[off:off + t] = True
         onehot = (lab.view(-1, 1) == cmap[frame_group]) & live[frame_group] & (lab.view(-1, 1) >= 0) & covered.view(-1, 1)
-        v = self.expected_reward_packed(pc, reward=onehot.to(torch.float64), differentiable=differentiable)
-        return v / torch.as_tensor(batch.lengths, device=dev).to(torch.float64) if normalize else v
+        return onehot.to(torch.float64)
 
     def expected_segment_count(self, features, lengths, valid_classes_per_instance, add_eos=True,
                                additional_allowed_ends_per_instance=None, constraints=None, *, differentiable=False):
@@ -1833,6 +1886,99 @@ class SemiMarkovModule(nn.Module):
         st = self.stacked_tables(pc, differentiable=True)[0]
         return _alignment_value('entropy', 'alignment_entropy_packed', list(pc.video_names), [side], tuple(st[k] for k in TABLE_NAMES),
                                 want_parts)
+
+    # ------------------------------------------------------------------ expected reward under the graph posterior (smm_align_graph_expected_reward_f64)
+    def _alignment_reward_value(self, what, names, side, rw, node_reward, sg, tables, want_parts, differentiable):
+        """Both ``alignment_expected_reward`` methods behind their staging: the rewards into the record, the node rewards (with
+        the per-class ``sg`` broadcast into them), then the value, or the autograd Function on it.  ``tables``: a callable
+        that returns the differentiable tables."""
+        r, sup = side
+        batch = r['batch']
+        group = batch.group if batch.group is not None else np.zeros(batch.b, np.int64)
+        with torch.no_grad():
+            r['reward'], r['node_reward'] = rw, _node_rewards(sup, node_reward, sg, group, r['elp'].device, what)
+            if r['reward'] is None and r['node_reward'] is None:
+                raise ValueError("%s: at least one of reward, node_reward and seg_reward is needed" % what)
+            if not differentiable:
+                v, parts, _ = _alignment_expected_reward(r, sup, want_parts)
+                return (v, parts) if want_parts else v
+        return _alignment_value('expected_reward', what, names, [side], tables(), want_parts)
+
+    def alignment_expected_reward(self, features, lengths, valid_classes_per_instance, graphs, reward=None, node_reward=None,
+                                  seg_reward=None, add_eos=True, additional_allowed_ends_per_instance=None, constraints=None,
+                                  want_parts=False, *, differentiable=False):
+        """The expectation, under the posterior ``sample_alignments`` draws from, of a reward that is additive over the frames
+        and the nodes of an alignment, exactly: fp64 b on the device (argument conventions of ``alignment_entropy``; graphs in
+        GLOBAL class ids).  R(y) = sum over the segments (node j of class c) of y of node_reward[j] + seg_reward[c] + the sum of
+        reward[t, c] over the segment's frames.  ``reward``: b x Tmax x C, columns in the order of the batch's valid classes
+        (``expected_reward``'s convention; padded frames are ignored); ``node_reward``: one sequence per video, one entry per
+        node of its graph (or one tensor over all nodes); ``seg_reward``: length C, a convenience that is broadcast into the node
+        rewards over each node's class; at least one of the three.  reward = one-hot labels: the expected number of correct
+        frames of an alignment (``alignment_expected_accuracy``); node_reward = 1: the expected number of segments, which says
+        how many optional entries are used; node_reward = one-hot of an end node of a trie: that candidate's posterior.  One
+        emission launch, the forward launch (smm_align_graph_logz_f64) and the smm_align_graph_expected_reward_f64 launch.  With
+        ``want_parts`` the pair (value, parts fp64 b x 2: the frame part and the node part).  A video none of whose paths can be
+        laid over it gives NaN.  Raises SmmError when a NaN reached the DP or a reward is not finite.
+        ``differentiable``: the same value (bit for bit, from the same launches), differentiable with respect to the module's
+        parameters (not the rewards: one that requires grad is refused): the backward runs
+        smm_align_graph_expected_reward_bwd_f64, a Hessian-vector product of log Z_g, and the chain rule through the emission
+        scorer and the factor tables; the parts carry no gradient.  A video without an alignment is then a ValueError that
+        names it (``transcript_graph_log_partition``'s)."""
+        what = 'alignment_expected_reward'
+        with torch.no_grad():
+            side = self._supervised_padded(what, features, lengths, valid_classes_per_instance, graphs=True, ambiguous='allow',
+                                           add_eos=add_eos, additional_allowed_ends_per_instance=additional_allowed_ends_per_instance,
+                                           constraints=constraints, given=graphs)
+        b, tmax = features.shape[:2]
+        dev = features.device
+        vc = self._check_valid_classes(valid_classes_per_instance)
+        c = self.n_classes if vc is None else int(vc.numel())
+        rw = _reward_tensor(reward, (b, tmax, c), dev, 'reward')
+        sg = _reward_tensor(seg_reward, (c,), dev, 'seg_reward')
+        return self._alignment_reward_value(what, None, side, None if rw is None else rw.view(b * tmax, c), node_reward,
+                                            None if sg is None else sg.view(1, c), lambda: self._differentiable_tables(vc, dev),
+                                            want_parts, differentiable)
+
+    def alignment_expected_reward_packed(self, pc, graphs, reward=None, node_reward=None, seg_reward=None, want_parts=False, *,
+                                         differentiable=False):
+        """``alignment_expected_reward`` for a whole PackedCorpus: fp64 n_videos on the device, in the order of
+        ``pc.video_names``.  ``graphs``: one ``ops.TranscriptGraph`` in GLOBAL class ids per video; ``reward``: total_frames x
+        c_max on local states (the layout of ``frame_posteriors_packed``); ``node_reward``: as the padded method's;
+        ``seg_reward``: n_groups x c_max.  ``differentiable``: as ``alignment_expected_reward``'s; the tables are
+        ``stacked_tables(pc, differentiable=True)``."""
+        what = 'alignment_expected_reward_packed'
+        with torch.no_grad():
+            side = self._supervised_packed(pc, what, graphs, graphs=True, ambiguous='allow')
+        batch, dev = pc.batch, pc.x.device
+        rw = _reward_tensor(reward, (batch.total_frames, batch.c_max), dev, 'reward')
+        sg = _reward_tensor(seg_reward, (batch.n_groups, batch.c_max), dev, 'seg_reward')
+        tables = lambda: tuple(self.stacked_tables(pc, differentiable=True)[0][k] for k in TABLE_NAMES)
+        return self._alignment_reward_value(what, list(pc.video_names), side, rw, node_reward, sg, tables, want_parts, differentiable)
+
+    def alignment_expected_accuracy(self, features, lengths, valid_classes_per_instance, graphs, labels, normalize=False,
+                                    add_eos=True, additional_allowed_ends_per_instance=None, constraints=None, *,
+                                    differentiable=False):
+        """Expected number of frames of each video on which an alignment drawn from the transcript-graph posterior agrees with
+        ``labels`` (b x Tmax, GLOBAL class ids; ``expected_accuracy``'s conventions): fp64 b on the device; with ``normalize``
+        the fraction of the video's frames.  ``alignment_expected_reward`` with reward = one-hot(labels): against held-out
+        labels a quality estimate of the weak supervision, against pseudo-labels or a teacher (``differentiable``) risk
+        training from transcripts; with a few annotated frames (every other label negative) the expected number of
+        timestamps hit."""
+        self._require_device(features, 'alignment_expected_accuracy')
+        onehot = self._onehot_labels(features, valid_classes_per_instance, labels)
+        v = self.alignment_expected_reward(features, lengths, valid_classes_per_instance, graphs, reward=onehot, add_eos=add_eos,
+                                           additional_allowed_ends_per_instance=additional_allowed_ends_per_instance,
+                                           constraints=constraints, differentiable=differentiable)
+        return v / lengths.to(device=features.device, dtype=torch.float64) if normalize else v
+
+    def alignment_expected_accuracy_packed(self, pc, graphs, labels, normalize=False, *, differentiable=False):
+        """``alignment_expected_accuracy`` for a whole PackedCorpus.  ``labels``: int64 total_frames, global class ids on the
+        packed frame axis; fp64 n_videos in the order of ``pc.video_names``."""
+        self._require_device(pc.x, 'alignment_expected_accuracy_packed')
+        self.prepare_packed(pc)
+        v = self.alignment_expected_reward_packed(pc, graphs, reward=self._onehot_labels_packed(pc, labels),
+                                                  differentiable=differentiable)
+        return v / torch.as_tensor(pc.batch.lengths, device=pc.x.device).to(torch.float64) if normalize else v
 
     # ------------------------------------------------------------------ KL of two graph posteriors (smm_align_graph_kl_f64)
     def _alignment_kl_padded(self, other, what, features, lengths, valid_classes_per_instance, graphs, add_eos,

@@ -52,6 +52,9 @@
  *                              videos and graphs: teacher against student, one EM epoch against the next (the reference has none)
  *   smm_align_graph_entropy_bwd_f64 / <- ... and the gradients of those three values with respect to p's tables: entropy
  *   smm_align_graph_kl_bwd_f64   regularisation, distillation of an alignment posterior (the reference has none)
+ *   smm_align_graph_expected_reward_f64 / <- ... and the expectation under that posterior of a frame- and node-additive reward
+ *   smm_align_graph_expected_reward_bwd_f64  (expected correct frames of an alignment, expected segments, a candidate's posterior)
+ *                              and its gradient with respect to the tables (the reference has none)
  *
  * The reference has no FFI: its boundary is the Python call SemiMarkovCRF(scores, lengths) on a dense
  * b x N x K x C x C tensor.  These entry points take the FACTORS of that tensor instead,
@@ -1185,6 +1188,87 @@ int smm_align_graph_kl_bwd_f64(const smm_shape *shape, const int64_t *lengths_ho
                                const int64_t *node_offset_host, int32_t mode, const double *grad_out /* dev [b], nullable */,
                                double *g_elp, double *g_trans, double *g_init, double *g_len,
                                double *value_out /* dev [b], nullable */, void *scratch, size_t scratch_bytes, void *stream);
+
+/*
+ * The expectation of a frame- and node-additive reward under the transcript-graph posterior, and its gradient with respect to
+ * the tables (csrc/smm_align_graph_expected_reward.hip).  What smm_expected_reward_f64 / _bwd_f64 are to the unconstrained
+ * posterior: the expected number of correct frames of an alignment against held-out labels or a teacher, the expected time in
+ * a class, the expected number of segments (of optional entries used), a candidate's posterior on the end nodes of a trie --
+ * each without committing to the best alignment, and each trainable.
+ * For an alignment y (a start -> end path and the boundaries of its nodes' segments), in smm_align_graph_logz_f64's notation:
+ *   R(y) = sum over the segments (node j, start s, end n) of y of ( node_reward[j] + sum_{t = s .. n-1} reward[t][a_j] )
+ *   V    = E_{p(y | x, graph)}[ R(y) ]
+ *   reward       dev fp64 [total_frames][c_max], local states as columns (the columns past a video's state count and the frames
+ *                no video covers are not read); nullable
+ *   node_reward  dev fp64, laid out like node_class; nullable -- but not both.  The EOS step carries no reward.
+ * With cumW[n][c] = sum_{t < n} reward[t][c] per video, r(j, s, n) = node_reward[j] + cumW[n][a_j] - cumW[s][a_j], and the
+ * value gathers smm_align_graph_segment_posteriors_f64's E (a segment of node j ends at n) and S (starts at s), no recursion:
+ *   V = sum_j ( sum_n E[n][j] cumW[n][a_j] - sum_s S[s][j] cumW[s][a_j] )  +  sum_j node_reward[j] sum_n E[n][j]
+ * value_out: dev [b]; parts_out (nullable): dev [b][2], the frame part and the node part.
+ * The gradient is a Hessian-vector product of log Z_g, over smm_align_graph_entropy_bwd_f64's occurrences (span, edge, start):
+ *   dV / d theta = sum over the occurrences o that read the entry of  p(o) ( r(o) + eta-(S_o) + eta+(E_o) - V )
+ * r(o) = 0 for edges and starts; eta- / eta+ the expected reward in front of / behind a decision node, message passes over the
+ * sampler's decisions and those of the time-forward walk:
+ *   eta-S(0, j) = 0;  eta-S(s, j) = sum_{i in pred(j)} p(i | start (s, j)) eta-E(s, i)
+ *   eta-E(n, j) = sum_k p(k | end (n, j)) [ r(j, n-k, n) + eta-S(n-k, j) ];     V- = sum_{end(j)} p_end(j) eta-E(T, j)
+ *   eta+E(T, j) = 0;  eta+E(n, j) = sum_{m in succ(j)} p(m | end (n, j)) eta+S(n, m)
+ *   eta+S(s, m) = sum_k p(k | start (s, m)) [ r(m, s, s+k) + eta+E(s+k, m) ];   V+ = sum_{start(m)} p(start m) eta+S(0, m)
+ * V- = V+ = V up to rounding.  Outputs of the gradient call: smm_align_graph_logz_bwd_f64's four layouts, times the upstream
+ * weight grad_out[i] (NULL: ones), summed over each group's videos in video order; all four are overwritten entirely.  There is
+ * no gradient for endpen, and none for the rewards: V is linear in them, dV / d reward is smm_align_graph_logz_bwd_f64's g_elp
+ * and dV / d node_reward its p_used.  value_out of the gradient call (nullable): dev [b][2], V- and V+.
+ *   scratch   dev; its contents need not be initialised and are undefined after the call.
+ *             smm_align_graph_expected_reward_scratch_bytes: the videos' cumW offsets [b], cumW ((T + 1) c_max doubles per
+ *             video, class-major like cum), two partials per node.
+ *             smm_align_graph_expected_reward_bwd_scratch_bytes: smm_align_graph_entropy_bwd_f64's layout (five [M][T+1] blocks
+ *             per video, the videos' parts, V+), then the offsets and cumW.
+ *             The queries are host arithmetic and return 0 for whatever the calls refuse.  smm_align_graph_logz_workspace_bytes
+ *             does not change.
+ * Call order: smm_align_graph_logz_f64 on the same workspace and stream first.  Both calls stage the workspace as the backward
+ * call does (clearing its error word) and launch smm_align_graph_logz_bwd_f64's first kernel on it
+ * (smm_launch_align_graph_logz_bwd_columns), which rewrites the q and bh columns with the same bits; they never launch its g_elp /
+ * g_len / reduce kernels.  So they may run before, after or between the backward, sampler, entropy, segment-posterior, KL and
+ * gradient calls without changing a bit of theirs.  Then the value call launches three kernels (prefix sums, one wave per node,
+ * one wave per video), the gradient call the prefix sums, eta-, eta+, the assembly (one workgroup per video each) and
+ * smm_align_graph_entropy_bwd_f64's last two kernels (g_elp, the sums over the videos).
+ * Numerics: every exponential is fp64; each decision takes a maximum pass and a pass of exponentials, nothing is rescaled; every
+ * read of a column is gated by its recorded range; a decision or an occurrence without mass is not evaluated.  No atomics,
+ * every sum in a fixed order: two calls give the same bits.  The rounding of V scales with the sum of |reward| over the covered
+ * entries plus the sum of |node_reward|.
+ *   logz_g = -inf                            value NaN, exactly zero contributions; the error word stays clear
+ *   logz_g NaN                               the same; the error word is set
+ *   grad_out[i] = 0                          exactly 0.0 contributions
+ *   a reward that is not finite, in a covered entry or on one of the video's nodes
+ *                                            value NaN, NaN rows of g_elp for that video, NaN tables for its group; the error
+ *                                            word is set
+ * Videos beside such a video keep their bits.
+ * Enqueued on `stream` only; never synchronises; a video is never split.
+ * Refusals: smm_align_graph_entropy_bwd_f64's (SMM_SHAPE_NO_EOS: SMM_ERR_UNSUPPORTED), SMM_ERR_ARG when both rewards are NULL,
+ * when value_out of the value call or a gradient pointer of the gradient call is NULL, or when the scratch is NULL, and
+ * SMM_ERR_WORKSPACE for a scratch below its query -- all before anything is staged.
+ */
+size_t smm_align_graph_expected_reward_scratch_bytes(const smm_shape *shape, const int64_t *lengths_host,
+                                                     const int64_t *node_offset_host);
+size_t smm_align_graph_expected_reward_bwd_scratch_bytes(const smm_shape *shape, const int64_t *lengths_host,
+                                                         const int64_t *node_offset_host);
+int smm_align_graph_expected_reward_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                        const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                        const double *elp, const double *trans, const double *init, const double *len_scores,
+                                        const double *endpen /* nullable */, const int32_t *node_class, const uint32_t *pred_mask,
+                                        const uint8_t *node_flags, const int64_t *node_offset_host, const double *logz_g /* dev [b] */,
+                                        const double *reward /* nullable */, const double *node_reward /* nullable */,
+                                        double *value_out /* dev [b] */, double *parts_out /* dev [b][2], nullable */,
+                                        void *scratch, size_t scratch_bytes, void *workspace, size_t workspace_bytes, void *stream);
+int smm_align_graph_expected_reward_bwd_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                            const int32_t *group_host, const int32_t *kp_host, const int32_t *n_states_host,
+                                            const double *elp, const double *trans, const double *init, const double *len_scores,
+                                            const double *endpen /* nullable */, const int32_t *node_class,
+                                            const uint32_t *pred_mask, const uint8_t *node_flags, const int64_t *node_offset_host,
+                                            const double *logz_g /* dev [b] */, const double *reward /* nullable */,
+                                            const double *node_reward /* nullable */, const double *grad_out /* dev [b], nullable */,
+                                            double *g_elp, double *g_trans, double *g_init, double *g_len,
+                                            double *value_out /* dev [b][2]: V-, V+; nullable */, void *scratch,
+                                            size_t scratch_bytes, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Factor tables of every parameter group from the model parameters (training steps), and their chain rule.
