@@ -28,6 +28,7 @@ SYMBOLS = [
     "smm_dense_workspace_bytes", "smm_dense_dp_f32", "smm_dense_marginals_f32",
     "smm_eval_workspace_bytes", "smm_eval_confusion_i64", "smm_eval_videos_i64",
     "smm_fit_workspace_bytes", "smm_fit_error_word_offset", "smm_fit_stats_f64",
+    "smm_emission_bwd_x_f64", "smm_flow_scratch_bytes", "smm_flow_bwd_scratch_bytes", "smm_flow_f32", "smm_flow_bwd_f32",
 ]
 
 
@@ -46,6 +47,11 @@ class SmmPlanFeedbackInfo(ctypes.Structure):
 class SmmTablesShape(ctypes.Structure):
     _fields_ = [("n_classes", ctypes.c_int32), ("d", ctypes.c_int32), ("n_groups", ctypes.c_int32),
                 ("c_max", ctypes.c_int32), ("k_rows", ctypes.c_int32), ("allow_self_transitions", ctypes.c_int32)]
+
+
+class SmmFlowShape(ctypes.Structure):
+    _fields_ = [("n_rows", ctypes.c_int64), ("d", ctypes.c_int32), ("hidden_units", ctypes.c_int32),
+                ("hidden_layers", ctypes.c_int32), ("couple_layers", ctypes.c_int32)]
 
 
 SHAPE_NO_EOS = 1
@@ -206,6 +212,17 @@ def load():
     lib.smm_align_graph_expected_reward_bwd_f64.restype = ctypes.c_int
     lib.smm_align_graph_expected_reward_bwd_f64.argtypes = [ctypes.POINTER(SmmShape)] + [ctypes.c_void_p] * 23 \
         + [ctypes.c_void_p, ctypes.c_size_t] * 2 + [ctypes.c_void_p]
+    lib.smm_emission_bwd_x_f64.restype = ctypes.c_int
+    lib.smm_emission_bwd_x_f64.argtypes = [ctypes.POINTER(SmmShape)] + [ctypes.c_void_p] * 9 + [ctypes.c_void_p, ctypes.c_size_t,
+                                                                                               ctypes.c_void_p]
+    for query in (lib.smm_flow_scratch_bytes, lib.smm_flow_bwd_scratch_bytes):
+        query.restype = ctypes.c_size_t
+        query.argtypes = [ctypes.POINTER(SmmFlowShape)]
+    lib.smm_flow_f32.restype = ctypes.c_int
+    lib.smm_flow_f32.argtypes = [ctypes.POINTER(SmmFlowShape)] + [ctypes.c_void_p] * 3 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.smm_flow_bwd_f32.restype = ctypes.c_int
+    lib.smm_flow_bwd_f32.argtypes = [ctypes.POINTER(SmmFlowShape)] + [ctypes.c_void_p] * 5 + [ctypes.c_void_p, ctypes.c_size_t,
+                                                                                             ctypes.c_void_p]
     lib.smm_dp_timing_enable.restype = None
     lib.smm_dp_timing_enable.argtypes = [ctypes.c_int]
     lib.smm_dp_timing_read.restype = ctypes.c_int

@@ -3009,3 +3009,90 @@ extern "C" int smm_dense_marginals_f32(const float *scores, const int64_t *lengt
     SMM_HIP(hipGetLastError());
     return SMM_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ feature projection (smm_flow.hip)
+extern "C" int smm_emission_bwd_x_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                                      const int32_t *group_host, const int32_t *n_states_host, const float *x,
+                                      const double *g_elp, const double *w, const double *inv_var, float *g_x,
+                                      void *workspace, size_t workspace_bytes, void *stream)
+{
+    Staged st;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    if (!x || !g_elp || !w || !inv_var || !g_x || !shape || shape->d < 1) return SMM_ERR_ARG;
+    int rc = stage(shape, lengths_host, frame_offset_host, group_host, nullptr, n_states_host, workspace, workspace_bytes,
+                   hs, &st, false, smm_emission_bwd_chunk());
+    if (rc != SMM_OK) return rc;
+    int64_t covered = 0;
+    for (int i = 0; i < shape->b; ++i) covered += lengths_host[i];
+    if (covered != shape->total_frames)                         // (a padded layout: the rows between the videos)
+        SMM_HIP((hipError_t)smm_zero_async(g_x, sizeof(float) * (size_t)shape->total_frames * shape->d, hs));
+    SmmEmBwdXArgs a{st.videos, st.order, st.n_states, st.em_cum, x, g_elp, w, inv_var, g_x,
+                    shape->d, shape->c_max, shape->b, st.em_blocks, smm_emission_bwd_chunk()};
+    smm_launch_emission_bwd_x(a, st.c_need, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
+// SMM_OK and the launch plan, or the refusal: host logic only
+static int flow_check(const smm_flow_shape *s, bool bwd, SmmFlowPlan *plan)
+{
+    if (!s || s->n_rows < 1 || (s->d & 1)) return SMM_ERR_ARG;
+    if (s->d < 2 || s->d > 512 || s->hidden_units < 1 || s->hidden_units > 256 || s->hidden_layers < 0 || s->hidden_layers > 4 ||
+        s->couple_layers < 1 || s->couple_layers > 16)
+        return SMM_ERR_UNSUPPORTED;
+    return smm_flow_plan(s->n_rows, s->d, s->hidden_units, s->hidden_layers, s->couple_layers, bwd, plan) ? SMM_OK : SMM_ERR_UNSUPPORTED;
+}
+
+static SmmFlowArgs flow_args(const smm_flow_shape *s, const SmmFlowPlan &p, const float *x, const float *g_y, const float *params,
+                             float *out, double *partials)
+{
+    float *keep_global = p.keep == 2 ? reinterpret_cast<float *>(partials + p.n_params * (size_t)p.grid) : nullptr;
+    return SmmFlowArgs{x, g_y, params, out, partials, keep_global, s->n_rows, (int64_t)p.n_params, s->d, s->hidden_units, s->hidden_layers,
+                       s->couple_layers, p.strips, p.slab_rows, p.n_tiles, p.keep};
+}
+
+// the fp64 partials of every workgroup, then (keep = 2) every workgroup's kept halves
+static size_t flow_bwd_bytes(const SmmFlowPlan &p)
+{
+    return sizeof(double) * p.n_params * (size_t)p.grid + sizeof(float) * p.keep_floats * (size_t)p.grid;
+}
+
+extern "C" size_t smm_flow_scratch_bytes(const smm_flow_shape *) { return 0; }
+
+extern "C" size_t smm_flow_bwd_scratch_bytes(const smm_flow_shape *shape)
+{
+    SmmFlowPlan p{};
+    if (flow_check(shape, true, &p) != SMM_OK) return 0;
+    return flow_bwd_bytes(p);
+}
+
+extern "C" int smm_flow_f32(const smm_flow_shape *shape, const float *x, const float *params, float *y, void *scratch,
+                            size_t scratch_bytes, void *stream)
+{
+    (void)scratch; (void)scratch_bytes;
+    SmmFlowPlan p{};
+    const int rc = flow_check(shape, false, &p);
+    if (rc != SMM_OK) return rc;
+    if (!x || !params || !y) return SMM_ERR_ARG;
+    smm_launch_flow_fwd(flow_args(shape, p, x, nullptr, params, y, nullptr), p, static_cast<hipStream_t>(stream));
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}
+
+extern "C" int smm_flow_bwd_f32(const smm_flow_shape *shape, const float *x, const float *g_y, const float *params,
+                                double *g_params, float *g_x, void *scratch, size_t scratch_bytes, void *stream)
+{
+    SmmFlowPlan p{};
+    const int rc = flow_check(shape, true, &p);
+    if (rc != SMM_OK) return rc;
+    if (!x || !g_y || !params || !g_params || !scratch) return SMM_ERR_ARG;
+    const size_t need = flow_bwd_bytes(p);
+    if (scratch_bytes < need) return SMM_ERR_WORKSPACE;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    double *partials = static_cast<double *>(scratch);
+    SMM_HIP((hipError_t)smm_zero_async(partials, sizeof(double) * p.n_params * (size_t)p.grid, hs));
+    smm_launch_flow_bwd(flow_args(shape, p, x, g_y, params, g_x, partials), p, hs);
+    smm_launch_flow_reduce(partials, p.grid, p.n_params, g_params, hs);
+    SMM_HIP(hipGetLastError());
+    return SMM_OK;
+}

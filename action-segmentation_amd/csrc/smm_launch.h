@@ -452,3 +452,47 @@ struct SmmAlignSampleArgs {
     int32_t t_max, n_samples;
 };
 void smm_launch_align_graph_sample(const SmmAlignSampleArgs &a, hipStream_t stream);
+
+// NICE coupling flow in front of the emission scorer (smm_flow.hip).  A workgroup of four waves owns `strips` x 16 rows and
+// carries them through every coupling layer in LDS; `slab_rows` k-rows of a weight matrix are staged through LDS at a time.
+struct SmmFlowPlan {
+    int32_t strips;            // 16-row MFMA strips per tile: 4, 2 or 1 (the largest whose tile fits the LDS)
+    int32_t slab_rows;         // 16, or 8 where nothing else fits
+    int32_t keep;              // backward: every coupling layer's active half as it came in is kept in LDS (1) or in the scratch (2)
+    size_t keep_floats;        // keep = 2: floats of scratch per workgroup, behind the partials
+    int32_t grid;              // workgroups (backward: each owns an fp64 partial of every parameter gradient)
+    int32_t n_tiles;
+    size_t lds_bytes;
+    size_t n_params;           // floats of the packed parameter buffer
+};
+// false: no tile of this shape fits the LDS (never for the sizes smmdp.h admits); host only
+bool smm_flow_plan(int64_t n_rows, int d, int h, int hidden_layers, int couple_layers, bool bwd, SmmFlowPlan *out);
+struct SmmFlowArgs {
+    const float *x;            // [n_rows][d]
+    const float *g_y;          // [n_rows][d]                 (backward)
+    const float *params;       // packed (smmdp.h: smm_flow_shape)
+    float *out;                // forward: y [n_rows][d]; backward: g_x or null
+    double *partials;          // backward: [grid][n_params], zero at launch
+    float *keep_global;        // backward, keep = 2: [grid][couple_layers][rows of a tile][d / 2]
+    int64_t n_rows, n_params;
+    int32_t d, h, hidden_layers, couple_layers, strips, slab_rows, n_tiles, keep;
+};
+void smm_launch_flow_fwd(const SmmFlowArgs &a, const SmmFlowPlan &p, hipStream_t stream);
+void smm_launch_flow_bwd(const SmmFlowArgs &a, const SmmFlowPlan &p, hipStream_t stream);
+// g_params[i] = partials[0][i] + partials[1][i] + ... in that order
+void smm_launch_flow_reduce(const double *partials, int grid, size_t n_params, double *g_params, hipStream_t stream);
+
+// gradient of the emission scores with respect to the features (smm_flow.hip); rows no video covers are not written
+struct SmmEmBwdXArgs {
+    const SmmVideo *videos;
+    const int32_t *order;    // [b]
+    const int32_t *n_states;
+    const int32_t *cum;      // [b + 1] chunks of smm_emission_bwd_chunk() frames before each video of `order`
+    const float *x;          // [total_frames][d]
+    const double *g_elp;     // [total_frames][c_max]
+    const double *w;         // [g][d][c_max]
+    const double *inv_var;   // [d]
+    float *g_x;              // [total_frames][d]
+    int32_t d, c_max, b, n_chunks, chunk;   // chunk: smm_emission_bwd_chunk()
+};
+void smm_launch_emission_bwd_x(const SmmEmBwdXArgs &a, int c_need, hipStream_t stream);

@@ -112,8 +112,9 @@ def broadcast_parameters(module, src=0):
 
 
 def all_reduce_gradients(parameters, average=False):
-    """Sum (or mean) of the gradients over the ranks, as ONE collective on a flat fp32/fp64 buffer (five small tensors:
-    SURVEY.md 8e, "a gradient all-reduce of the 5 small parameter tensors per step").  Parameters without a gradient
+    """Sum (or mean) of the gradients over the ranks, as ONE collective on a flat fp64 buffer of however many tensors there
+    are (five small ones -- SURVEY.md 8e, "a gradient all-reduce of the 5 small parameter tensors per step" -- and the flow's
+    under --sm_feature_projection).  Parameters without a gradient
     on this rank (it had no batch of that step) count as zeros.  No-op for a single process."""
     if not active():
         return

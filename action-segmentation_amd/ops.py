@@ -271,6 +271,93 @@ def emission_bwd(batch, x, g_elp, ws=None):
     return g_w.transpose(1, 2), g_cst, g_iv
 
 
+def emission_bwd_x(batch, x, g_elp, w, inv_var, ws=None):
+    """The gradient of the emission scores with respect to the features (smm_emission_bwd_x_f64): g_elp fp64
+    [total_frames, c_max], w fp64 [n_groups, d, c_max] and inv_var fp64 [d] (``emission``'s) -> g_x fp32 [total_frames, d];
+    rows no video covers are 0."""
+    lib = _lib.load()
+    dev = x.device
+    f64 = torch.float64
+    g, cm, d = batch.n_groups, batch.c_max, int(x.size(1))
+    if d != batch.d or x.size(0) < batch.total_frames or tuple(g_elp.shape) != (batch.total_frames, cm) or \
+            tuple(w.shape) != (g, d, cm) or tuple(inv_var.shape) != (d,):
+        raise ValueError("emission_bwd_x: x [>= total_frames, batch.d], g_elp [total_frames, c_max], w [n_groups, d, c_max] and "
+                         "inv_var [d] expected")
+    g_x = torch.empty((batch.total_frames, d), dtype=torch.float32, device=dev)
+    if ws is None:
+        ws = workspace(batch.workspace_bytes(), dev)
+    _lib.check(lib.smm_emission_bwd_x_f64(
+        *batch.head(with_kp=False), _dev(x, torch.float32, 'x'), _dev(g_elp, f64, 'g_elp'), _dev(w, f64, 'w'),
+        _dev(inv_var, f64, 'inv_var'), _dev(g_x, torch.float32, 'g_x'), *_ws_args(ws), _stream()))
+    return g_x
+
+
+class FlowShape:
+    """Sizes of a NICE coupling flow (include/smmdp.h: smm_flow_shape, without the row count): feature dimension ``d``,
+    ``hidden_units``, ``hidden_layers`` and ``couple_layers``."""
+
+    def __init__(self, d, hidden_units=100, hidden_layers=1, couple_layers=4):
+        self.d, self.hidden_units = int(d), int(hidden_units)
+        self.hidden_layers, self.couple_layers = int(hidden_layers), int(couple_layers)
+
+    @property
+    def layer_sizes(self):
+        """(in_features, out_features) of the linear layers of one coupling layer, in packing order."""
+        dh, h = self.d // 2, self.hidden_units
+        return [(dh, h)] + [(h, h)] * self.hidden_layers + [(h, dh)]
+
+    @property
+    def n_params(self):
+        return self.couple_layers * sum(i * o + o for i, o in self.layer_sizes)
+
+    def c_shape(self, n_rows):
+        return _lib.SmmFlowShape(int(n_rows), self.d, self.hidden_units, self.hidden_layers, self.couple_layers)
+
+
+def _flow_operands(x, packed, shape, what):
+    if x.dim() != 2 or int(x.size(1)) != shape.d:
+        raise ValueError("%s: x [n_rows, %d] expected, got %s" % (what, shape.d, tuple(x.shape)))
+    if packed.dim() != 1 or packed.numel() != shape.n_params:
+        raise ValueError("%s: %d packed parameters expected, got %s" % (what, shape.n_params, tuple(packed.shape)))
+
+
+def flow(x, packed, shape):
+    """y = flow(x) row by row (smm_flow_f32): x fp32 [n_rows, d], ``packed`` the flow's parameters in the ABI's layout
+    (flow.FeatureProjector.packed), ``shape`` a FlowShape -> y fp32 [n_rows, d]."""
+    lib = _lib.load()
+    _flow_operands(x, packed, shape, 'flow')
+    px, pp = _dev(x, torch.float32, 'x'), _dev(packed, torch.float32, 'packed')
+    y = torch.empty_like(x)
+    if x.size(0) == 0:
+        return y
+    _lib.check(lib.smm_flow_f32(ctypes.byref(shape.c_shape(x.size(0))), px, pp, _dev(y, torch.float32, 'y'),
+                                None, ctypes.c_size_t(0), _stream()))
+    return y
+
+
+def flow_bwd(x, g_y, packed, shape, want_g_x=False):
+    """Chain rule through ``flow`` (smm_flow_bwd_f32; the activations are computed again): g_y fp32 [n_rows, d] ->
+    (g_packed fp64 [n_params] in the packed layout, g_x fp32 [n_rows, d] or None)."""
+    lib = _lib.load()
+    _flow_operands(x, packed, shape, 'flow_bwd')
+    if tuple(g_y.shape) != tuple(x.shape):
+        raise ValueError("flow_bwd: g_y of x's shape expected")
+    px, pg, pp = _dev(x, torch.float32, 'x'), _dev(g_y, torch.float32, 'g_y'), _dev(packed, torch.float32, 'packed')
+    dev = x.device
+    g_packed = torch.empty(shape.n_params, dtype=torch.float64, device=dev)
+    g_x = torch.empty_like(x) if want_g_x else None
+    if x.size(0) == 0:
+        return g_packed.zero_(), g_x
+    cs = shape.c_shape(x.size(0))
+    need = lib.smm_flow_bwd_scratch_bytes(ctypes.byref(cs))
+    if need == 0:
+        raise _lib.SmmError("libsmmdp: flow shape not supported (include/smmdp.h: smm_flow_shape)")
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    _lib.check(lib.smm_flow_bwd_f32(ctypes.byref(cs), px, pg, pp, _dev(g_packed, torch.float64, 'g_params'),
+                                    _dev(g_x, torch.float32, 'g_x'), *_ws_args(scratch), _stream()))
+    return g_packed, g_x
+
+
 class TablesMeta:
     """Which class sets a launch's parameter groups are (device index tensors, built once per PackedCorpus):
     classes / merged int64 [g, c_max], n_states int32 [g]; plus the scalars of smm_tables_shape."""

@@ -124,7 +124,8 @@ class SemiMarkovModel(object):
         # Data-parallel training under torch.distributed: every rank walks the same shuffled batch order
         # (the sampler's RNG is seeded identically), the batches of one optimiser step are dealt round-robin to the
         # ranks, each rank back-propagates the sum of its batches' losses / --batch_accumulation, and ONE all-reduce
-        # sums the gradients of the five parameter tensors: the step is the single-process step.  (One batch per step,
+        # sums the gradients of every trained parameter (the five table tensors, and the flow's under --sm_feature_projection):
+        # the step is the single-process step.  (One batch per step,
         # --batch_accumulation 1, cannot be split: the ranks then repeat the batch and average, which keeps their
         # parameters bit-identical although the kernels' atomics round differently from run to run.)
         from . import distributed

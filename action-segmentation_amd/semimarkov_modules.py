@@ -24,6 +24,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import ops
+from .flow import FeatureProjector
 from .semimarkov_utils import semimarkov_sufficient_stats, semimarkov_sufficient_stats_device
 
 BIG_NEG = -1e9  # reference semimarkov_modules.py:20
@@ -323,6 +324,23 @@ def _transcript_posteriors(r, sup, what, **want):
     return grads
 
 
+def _feature_grad_inputs(ctx, slot, w, inv_var):
+    """What the backward of a likelihood Function keeps beside its own tensors when the features (input ``slot``) want a
+    gradient -- they are a feature projection's output then: the emission factors smm_emission_bwd_x_f64 reads."""
+    return (w, inv_var) if ctx.needs_input_grad[slot] else ()
+
+
+def _feature_grad(ctx, slot, x, g_elp, kept):
+    """d L / d x from d L / d elp (smm_emission_bwd_x_f64), or None when the features carry no gradient."""
+    if not ctx.needs_input_grad[slot]:
+        return None
+    w, inv_var = kept
+    g_x = ops.emission_bwd_x(ctx.batch, x, g_elp, w.detach().contiguous(), inv_var.detach().contiguous(), ws=ctx.ws)
+    if g_x.size(0) != x.size(0):                                  # (features longer than the launch's frame axis: no gradient there)
+        g_x = torch.cat([g_x, g_x.new_zeros((x.size(0) - g_x.size(0), g_x.size(1)))])
+    return g_x
+
+
 class _LogPartition(torch.autograd.Function):
     """log Z of every video of one launch as a differentiable function of the fp64 factor tables (emission factors w,
     cst; transition, initial and length tables; stacked per parameter group).  Forward: smm_emission_f64 +
@@ -336,7 +354,7 @@ class _LogPartition(torch.autograd.Function):
         both = any(ctx.needs_input_grad)
         r = _emit_logz(batch, x, cons, endpen, (w, cst, trans, init, len_scores, None), inv_var, with_backward=both)
         ctx.batch, ctx.endpen, ctx.ws, ctx.both = batch, endpen, r['ws'], both
-        ctx.save_for_backward(x, r['elp'], trans, init, len_scores, r['logz'])
+        ctx.save_for_backward(x, r['elp'], trans, init, len_scores, r['logz'], *_feature_grad_inputs(ctx, 1, w, inv_var))
         return r['logz']
 
     @staticmethod
@@ -345,7 +363,8 @@ class _LogPartition(torch.autograd.Function):
         g = ops.logz_bwd(ctx.batch, grad_logz=gz.to(torch.float64).contiguous(), with_backward=ctx.both, **_after_logz(r))
         # chain rule through elp = cst + x.w - 0.5 x^2.inv_var: one pass over x (smm_emission_bwd_f64)
         g_w, g_cst, g_iv = ops.emission_bwd(ctx.batch, r['x'], g['elp'], ws=ctx.ws)
-        return None, None, None, None, g_w, g_cst, g_iv, g['trans'], g['init'], g['len']
+        g_x = _feature_grad(ctx, 1, r['x'], g['elp'], ctx.saved_tensors[6:])
+        return None, g_x, None, None, g_w, g_cst, g_iv, g['trans'], g['init'], g['len']
 
 
 class _AlignmentLogPartition(torch.autograd.Function):
@@ -365,16 +384,17 @@ class _AlignmentLogPartition(torch.autograd.Function):
         else:                       # ... and the other kinds as they came, beside what the forward launch staged of them
             ctx.sup, ctx.staged = sup, dict(staged=out['_staged'])
         ctx.batch, ctx.endpen, ctx.ws = batch, endpen, out['ws']
-        ctx.save_for_backward(x, r['elp'], trans, init, len_scores, out['logz'])
+        ctx.save_for_backward(x, r['elp'], trans, init, len_scores, out['logz'], *_feature_grad_inputs(ctx, 1, w, inv_var))
         return out['logz']
 
     @staticmethod
     def backward(ctx, gz):
-        x, elp, trans, init, len_scores, logz = ctx.saved_tensors
+        x, elp, trans, init, len_scores, logz = ctx.saved_tensors[:6]
         r = dict(batch=ctx.batch, elp=elp, trans=trans, init=init, len=len_scores, endpen=ctx.endpen)
         g = _supervised(_LOGZ_BWD, r, ctx.sup, logz, grad_logz=gz.to(torch.float64).contiguous(), ws=ctx.ws, **ctx.staged)
         g_w, g_cst, g_iv = ops.emission_bwd(ctx.batch, x, g['elp'], ws=ctx.ws)
-        return None, None, None, None, None, g_w, g_cst, g_iv, g['trans'], g['init'], g['len']
+        g_x = _feature_grad(ctx, 1, x, g['elp'], ctx.saved_tensors[6:])
+        return None, g_x, None, None, None, g_w, g_cst, g_iv, g['trans'], g['init'], g['len']
 
 
 def _alignment_log_partition(staged, sup):
@@ -580,15 +600,20 @@ class _FactorTables(torch.autograd.Function):
 class SemiMarkovModule(nn.Module):
     @classmethod
     def add_args(cls, parser):
-        # reference :54-65 (the NICE-flow flags of --sm_feature_projection are accepted but the flow is not built)
+        # reference :54-65, and the flags of the flow behind --sm_feature_projection (reference src/models/flow.py)
         parser.add_argument('--sm_max_span_length', type=int, default=20)
         parser.add_argument('--sm_supervised_state_smoothing', type=float, default=1e-2)
         parser.add_argument('--sm_supervised_length_smoothing', type=float, default=1e-1)
         parser.add_argument('--sm_supervised_method',
                             choices=['closed-form', 'gradient-based', 'closed-then-gradient'],
                             default='closed-form')
-        parser.add_argument('--sm_feature_projection', action='store_true', help='use a flow (not built here)')
+        parser.add_argument('--sm_feature_projection', action='store_true', help='use a flow')
         parser.add_argument('--sm_init_non_projection_parameters_from')
+        parser.add_argument('--flow_hidden_layers', type=int, default=1)
+        parser.add_argument('--flow_hidden_units', type=int, default=100)
+        parser.add_argument('--flow_couple_layers', type=int, default=4)
+        parser.add_argument('--flow_scale', action='store_true')
+        parser.add_argument('--flow_scale_no_zero', action='store_true')
 
     def __init__(self, args, n_classes, n_dims, allow_self_transitions=False, allowed_starts: Set[int] = None,
                  allowed_transitions: Dict[int, Set[int]] = None, allowed_ends: Set[int] = None,
@@ -608,9 +633,7 @@ class SemiMarkovModule(nn.Module):
         if getattr(args, 'sm_init_non_projection_parameters_from', None) is not None:
             with open(args.sm_init_non_projection_parameters_from, 'rb') as f:
                 self.init_nonproject_parameters(pickle.load(f).model)
-        if getattr(args, 'sm_feature_projection', False):
-            raise NotImplementedError("--sm_feature_projection (NICE flow) is outside the decode path built here")
-        self.feature_projector = None
+        self.init_projector()
         self.max_k = args.sm_max_span_length
         self._merge_classes = merge_classes
         self.kl = None
@@ -623,6 +646,53 @@ class SemiMarkovModule(nn.Module):
     def init_nonproject_parameters(self, model):
         inc = self.load_state_dict(model.state_dict(), strict=False)
         assert not inc.unexpected_keys, inc.unexpected_keys
+        assert all(k.startswith('feature_projector') for k in inc.missing_keys), inc.missing_keys
+
+    def init_projector(self):
+        """reference :131-140.  The additive flow (log det = 0) is built; --flow_scale, whose log-determinant the reference sums
+        over padded frames as well, is not."""
+        self.feature_projector = None
+        if getattr(self.args, 'sm_feature_projection', False):
+            if getattr(self.args, 'flow_scale', False):
+                raise NotImplementedError("--flow_scale (the multiplicative coupling flow, with a non-zero log-determinant) is not "
+                                          "built: --sm_feature_projection runs the additive flow only")
+            self.feature_projector = FeatureProjector.from_args(self.args, self.feature_dim)
+
+    def _project(self, x, projected=False):
+        """Features fp32 [rows, D] on the device as the emission scorer sees them: through the feature projection when the
+        module has one (smm_flow_f32; with gradients enabled the result carries the flow's autograd node), else as they are.
+        ``projected``: x already IS the projection (``log_likelihood`` projects once for everything it calls)."""
+        fp = getattr(self, 'feature_projector', None)
+        return x if fp is None or projected else fp(x)
+
+    def _project_packed(self, pc, x, differentiable=False):
+        """``_project`` for the features of a PackedCorpus.  The projection of the resident ``pc.x`` is made once per parameter
+        state and kept on the corpus -- one more copy of the features -- while ``pc.x`` (identity, version) and the flow's
+        parameters (versions) stay what they were; ``differentiable`` with gradients enabled: a fresh autograd node instead.  A
+        slab passed beside the corpus (``predict_host``) is projected and not kept."""
+        fp = getattr(self, 'feature_projector', None)
+        if fp is None:
+            return x
+        if differentiable and torch.is_grad_enabled():
+            return fp(x)
+        with torch.no_grad():
+            # a slab beside the corpus is not kept; under stream capture the kept copy is neither read nor written: the captured
+            # graph must hold the flow launch (a replay projects what pc.x holds then), and a buffer from the graph's pool is
+            # not filled until the first replay
+            if x is not pc.x or (x.is_cuda and torch.cuda.is_current_stream_capturing()):
+                return fp(x)
+            key = (x.data_ptr(), x._version, tuple(x.shape), fp.version_key())
+            kept = pc.__dict__.get('_projected')
+            if kept is None or kept[0] != key:
+                kept = pc.__dict__['_projected'] = (key, fp(x))
+            return kept[1]
+
+    def _no_projected_gradient(self, *others):
+        """The differentiable posterior values (entropy, KL, cross-entropy, expected reward, and their alignment forms) stop at
+        the factor tables: with a feature projection they would silently leave the flow untrained."""
+        if any(getattr(m, 'feature_projector', None) is not None for m in (self,) + others):
+            raise NotImplementedError("differentiable=True does not reach through --sm_feature_projection: the gradients of the "
+                                      "posterior values with respect to the flow's parameters are not built (log_likelihood's are)")
 
     def init_params(self):
         self.poisson_log_rates = nn.Parameter(torch.zeros(self.n_classes), requires_grad=True)
@@ -656,6 +726,8 @@ class SemiMarkovModule(nn.Module):
 
     # ------------------------------------------------------------------ closed-form supervised fit (:195-256)
     def fit_supervised(self, feature_list, label_list):
+        if getattr(self, 'feature_projector', None) is not None:
+            raise NotImplementedError("fit_supervised closed form with feature projector")
         if self.transition_constraints is not None or self.init_constraints is not None:
             raise NotImplementedError("fit_supervised closed form with constrained state transitions")
         a = self.args
@@ -692,6 +764,9 @@ class SemiMarkovModule(nn.Module):
 
     def initialize_gaussian_from_feature_list(self, features):
         feats = torch.cat(features, dim=0)
+        if getattr(self, 'feature_projector', None) is not None:
+            with torch.no_grad():
+                feats = self._project(feats.to(device=self.gaussian_means.device, dtype=torch.float32))
         assert feats.dim() == 2 and feats.size(1) == self.feature_dim
         with torch.no_grad():
             self.gaussian_means.copy_(feats.mean(dim=0, keepdim=True).expand(self.n_classes, self.feature_dim))
@@ -856,6 +931,9 @@ class SemiMarkovModule(nn.Module):
         """Dense potentials like the reference (:553-595).  Compatibility API -- O(b*N*K*C*C) memory."""
         self.set_z(features, lengths, use_mean=use_mean_z)
         log_det = torch.zeros(features.size(0), device=features.device)
+        if getattr(self, 'feature_projector', None) is not None:      # reference :560-563 (device only, like the projector)
+            self._require_device(features, 'score_features')
+            features = self._project(features.to(torch.float32).contiguous()).to(features.dtype)
         ends = self._allowed_ends_per_instance(valid_classes, additional_allowed_ends_per_instance, features.size(0))
         elp = self.emission_log_probs(features, valid_classes, constraints)
         scores = self.log_hsmm(self.transition_log_probs(valid_classes), elp, self.initial_log_probs(valid_classes),
@@ -1068,6 +1146,8 @@ class SemiMarkovModule(nn.Module):
             batch = ops.Batch(lengths_host, [c], tab['len'].size(0), c_max=c, t_max=tmax, total_frames=total, d=d,
                               frame_offset=off, kp=[min(tab['len'].size(0), tmax)] * b, no_time_split=self._hard_masks())
             x = torch.cat([f.detach().to(torch.float32) for f in feature_list]) if b > 1 else x0.detach().to(torch.float32).contiguous()
+            with torch.no_grad():
+                x = self._project(x)                          # (the third place features meet the scorer: this decode stages itself)
             endpen = self._endpen(valid_classes, additional_allowed_ends_per_instance, b, c, dev)
             g1 = _one_group(tab)
             labels = ops.pinned_labels(('ragged', slot), dev, total)
@@ -1094,7 +1174,7 @@ class SemiMarkovModule(nn.Module):
                              "in the reference's lattice)")
 
     def _stage_padded(self, features, lengths, valid_classes, additional_allowed_ends_per_instance, constraints, no_eos=False,
-                      no_time_split=False, check_no_eos=True, tables=None):
+                      no_time_split=False, check_no_eos=True, tables=None, projected=False):
         """A zero-padded single-task batch as the launchers take it -> (batch, x, cons, endpen, tab, g1): the ``ops.Batch``, the
         features fp32 [b * Tmax, D], the constraints fp32 [b * Tmax, C] or None, the end penalties (None with ``no_eos``), the
         factor tables and their stack of one group.
@@ -1114,7 +1194,15 @@ class SemiMarkovModule(nn.Module):
         c = tab['init'].numel()
         batch = ops.Batch(lengths_host, [c], tab['len'].size(-2), c_max=c, t_max=tmax, total_frames=b * tmax, d=d, no_eos=no_eos,
                           no_time_split=no_time_split)
-        x = features.detach().to(torch.float32).contiguous().view(b * tmax, d)
+        # The likelihoods (``tables``: theirs, with autograd history) give their features a gradient (smm_emission_bwd_x_f64): the
+        # projection then carries the flow's autograd node, and features that ask for a gradient themselves -- another module's
+        # output -- keep theirs.  Every other entry point computes values: no node, nothing kept alive.
+        if tables is not None and torch.is_grad_enabled():
+            x = self._project((features if features.requires_grad else features.detach()).to(torch.float32).contiguous()
+                              .view(b * tmax, d), projected)
+        else:
+            with torch.no_grad():
+                x = self._project(features.detach().to(torch.float32).contiguous().view(b * tmax, d), projected)
         cons = None
         if constraints is not None:
             cons = constraints.detach().to(device=dev, dtype=torch.float32).contiguous().view(b * tmax, c)
@@ -1186,6 +1274,7 @@ class SemiMarkovModule(nn.Module):
             with torch.no_grad():
                 return launch()[0]
         self._require_device(features, 'entropy')
+        self._no_projected_gradient()
         tabs = self._differentiable_tables(self._check_valid_classes(valid_classes_per_instance), features.device)
         return _PosteriorValue.apply('entropy', launch, *tabs)
 
@@ -1195,7 +1284,7 @@ class SemiMarkovModule(nn.Module):
         self._require_device(pc.x, what)
         self.prepare_packed(pc, differentiable)
         t = pc.tables
-        return pc.batch, pc.x, pc.cons, pc.endpen, tuple(t[k] for k in TABLE_NAMES) + (t['class_map'],), t['inv_var']
+        return pc.batch, self._project_packed(pc, pc.x, differentiable), pc.cons, pc.endpen, tuple(t[k] for k in TABLE_NAMES) + (t['class_map'],), t['inv_var']
 
     def _packed_posterior_launch(self, pc, what, with_backward=False):
         return _emit_logz(*self._packed_stage(pc, what), with_backward)
@@ -1221,6 +1310,7 @@ class SemiMarkovModule(nn.Module):
             with torch.no_grad():
                 return launch()[0]
         self._require_device(pc.x, 'entropy_packed')
+        self._no_projected_gradient()
         st = self.stacked_tables(pc, differentiable=True)[0]
         return _PosteriorValue.apply('entropy', launch, *(st[k] for k in TABLE_NAMES))
 
@@ -1255,6 +1345,7 @@ class SemiMarkovModule(nn.Module):
         if not differentiable:
             with torch.no_grad():
                 return launch()[0]
+        self._no_projected_gradient()
         return _PosteriorValue.apply('expected_reward', launch, *self._differentiable_tables(vc, dev))
 
     def expected_reward_packed(self, pc, reward=None, seg_reward=None, *, differentiable=False):
@@ -1273,6 +1364,7 @@ class SemiMarkovModule(nn.Module):
         if not differentiable:
             with torch.no_grad():
                 return launch()[0]
+        self._no_projected_gradient()
         st = self.stacked_tables(pc, differentiable=True)[0]
         return _PosteriorValue.apply('expected_reward', launch, *(st[k] for k in TABLE_NAMES))
 
@@ -1434,6 +1526,7 @@ class SemiMarkovModule(nn.Module):
         features = args[0]
         self._require_device(features, what)
         valid = self._check_valid_classes(args[2])
+        self._no_projected_gradient(other)
         tabs = self._differentiable_tables(valid, features.device) + other._differentiable_tables(valid, features.device)
         return _PosteriorValue.apply(what, lambda: self._kl(other, *args, what, want_cross_entropy), *tabs)
 
@@ -1587,7 +1680,7 @@ class SemiMarkovModule(nn.Module):
         return ('chain', (local,)) if optional is None else ('optional', (local, optional))
 
     def _supervised_padded(self, what, features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
-                           constraints, given, optional=None, graphs=False, ambiguous=None, differentiable=False):
+                           constraints, given, optional=None, graphs=False, ambiguous=None, differentiable=False, projected=False):
         """Stage a transcript-family launch on a zero-padded single-task batch -> (the record of ``_emit``, supervision); with
         ``differentiable`` the first is (batch, x, cons, endpen, tables with autograd history, inv_var) for
         ``_alignment_log_partition``, which emits itself.  Every check on the host comes before a device is touched.  (Staged
@@ -1603,7 +1696,7 @@ class SemiMarkovModule(nn.Module):
         self._require_device(features, what)
         st = self._one_group_tables(valid_classes, features.device) if differentiable else None
         batch, x, cons, endpen, tab, g1 = self._stage_padded(features, lengths, valid_classes, additional_allowed_ends_per_instance,
-                                                             constraints, check_no_eos=False, tables=st)
+                                                             constraints, check_no_eos=False, tables=st, projected=projected)
         if differentiable:
             return (batch, x, cons, endpen, tuple(st[k] for k in TABLE_NAMES) + (None,), st['inv_var']), sup
         return _emit(batch, x, cons, endpen, g1, tab['inv_var']), sup
@@ -1717,7 +1810,8 @@ class SemiMarkovModule(nn.Module):
 
     # ------------------------------------------------------------------ transcript likelihood (smm_align_logz_f64)
     def transcript_log_partition(self, features, lengths, valid_classes_per_instance, transcripts, add_eos=True,
-                                 additional_allowed_ends_per_instance=None, constraints=None, optional=None, ambiguous='raise'):
+                                 additional_allowed_ends_per_instance=None, constraints=None, optional=None, ambiguous='raise',
+                                 projected=False):
         """log Z_a per video of a zero-padded single-task batch (argument conventions of ``align``): the log of the sum over
         every segmentation whose class sequence is ``transcripts[i]`` (GLOBAL class ids, one entry per segment, consecutive
         repeats are two segments) -- the joint log-likelihood of frames and transcript; minus ``log_partition`` it is the
@@ -1735,7 +1829,7 @@ class SemiMarkovModule(nn.Module):
             raise ValueError("transcript_log_partition: %d transcripts for %d videos" % (len(transcripts), features.size(0)))
         z = _alignment_log_partition(*self._supervised_padded(
             'transcript_log_partition', features, lengths, valid_classes_per_instance, add_eos, additional_allowed_ends_per_instance,
-            constraints, transcripts, optional, ambiguous=ambiguous, differentiable=True))
+            constraints, transcripts, optional, ambiguous=ambiguous, differentiable=True, projected=projected))
         _check_transcript_logz(z, None, 'transcript_log_partition')
         return z
 
@@ -1771,7 +1865,8 @@ class SemiMarkovModule(nn.Module):
 
     # ------------------------------------------------------------------ transcript-graph likelihood (smm_align_graph_logz_f64)
     def transcript_graph_log_partition(self, features, lengths, valid_classes_per_instance, graphs, add_eos=True,
-                                       additional_allowed_ends_per_instance=None, constraints=None, ambiguous='raise'):
+                                       additional_allowed_ends_per_instance=None, constraints=None, ambiguous='raise',
+                                       projected=False):
         """log Z_g per video of a zero-padded single-task batch (argument conventions of ``align_graph``): the log of the sum
         over every segmentation whose class sequence is a start -> end path of ``graphs[i]`` (an ``ops.TranscriptGraph`` in
         GLOBAL class ids) -- for a candidate set (``TranscriptGraph.from_candidates``) the joint log-likelihood of the frames and
@@ -1783,7 +1878,8 @@ class SemiMarkovModule(nn.Module):
         class that is not valid for the video does that); SmmError when a NaN reached the DP."""
         z = _alignment_log_partition(*self._supervised_padded(
             'transcript_graph_log_partition', features, lengths, valid_classes_per_instance, add_eos,
-            additional_allowed_ends_per_instance, constraints, graphs, graphs=True, ambiguous=ambiguous, differentiable=True))
+            additional_allowed_ends_per_instance, constraints, graphs, graphs=True, ambiguous=ambiguous, differentiable=True,
+            projected=projected))
         _check_transcript_logz(z, None, 'transcript_graph_log_partition')
         return z
 
@@ -1870,6 +1966,7 @@ class SemiMarkovModule(nn.Module):
             if not differentiable:
                 h, parts, _ = _alignment_entropy(*side, want_parts)
                 return (h, parts) if want_parts else h
+        self._no_projected_gradient()
         tabs = self._differentiable_tables(self._check_valid_classes(valid_classes_per_instance), features.device)
         return _alignment_value('entropy', 'alignment_entropy', None, [side], tabs, want_parts)
 
@@ -1883,6 +1980,7 @@ class SemiMarkovModule(nn.Module):
             if not differentiable:
                 h, parts, _ = _alignment_entropy(*side, want_parts)
                 return (h, parts) if want_parts else h
+        self._no_projected_gradient()
         st = self.stacked_tables(pc, differentiable=True)[0]
         return _alignment_value('entropy', 'alignment_entropy_packed', list(pc.video_names), [side], tuple(st[k] for k in TABLE_NAMES),
                                 want_parts)
@@ -1902,6 +2000,7 @@ class SemiMarkovModule(nn.Module):
             if not differentiable:
                 v, parts, _ = _alignment_expected_reward(r, sup, want_parts)
                 return (v, parts) if want_parts else v
+        self._no_projected_gradient()
         return _alignment_value('expected_reward', what, names, [side], tables(), want_parts)
 
     def alignment_expected_reward(self, features, lengths, valid_classes_per_instance, graphs, reward=None, node_reward=None,
@@ -1994,6 +2093,7 @@ class SemiMarkovModule(nn.Module):
                 value, parts, _ = _alignment_kl(p[0], q[0], p[1], what, want_cross_entropy, want_parts)
                 return (value, parts) if want_parts else value
         valid = self._check_valid_classes(valid_classes_per_instance)
+        self._no_projected_gradient(other)
         tabs = self._differentiable_tables(valid, features.device) + other._differentiable_tables(valid, features.device)
         return _alignment_value('cross_entropy' if want_cross_entropy else 'kl', what, None, [p, q], tabs, want_parts)
 
@@ -2010,6 +2110,7 @@ class SemiMarkovModule(nn.Module):
             if not differentiable:
                 value, parts, _ = _alignment_kl(p[0], q[0], p[1], what, want_cross_entropy, want_parts)
                 return (value, parts) if want_parts else value
+        self._no_projected_gradient(other)
         tabs = tuple(m.stacked_tables(pc, differentiable=True)[0][k] for m in (self, other) for k in TABLE_NAMES)
         return _alignment_value('cross_entropy' if want_cross_entropy else 'kl', what, list(pc.video_names), [p, q], tabs, want_parts)
 
@@ -2208,6 +2309,7 @@ class SemiMarkovModule(nn.Module):
         slab); ``labels_out``: where the frame labels go (a device tensor, or pinned host memory)."""
         x = pc.x if x is None else x
         self._require_device(x, 'decode_packed')
+        x = self._project_packed(pc, x)
         if pc.tables is None:
             self.prepare_packed(pc)
         t = pc.tables
@@ -2229,13 +2331,16 @@ class SemiMarkovModule(nn.Module):
 
     # ------------------------------------------------------------------ likelihoods (reference :597-658)
     def gold_score(self, features, lengths, valid_classes, spans, additional_allowed_ends_per_instance=None,
-                   constraints=None, no_eos=False):
+                   constraints=None, no_eos=False, projected=False):
         """Joint score of given span encodings = sum(potentials * to_parts(spans)) of the reference (:641-655),
         evaluated on the factors (differentiable torch ops, O(T*C); no dense tensor).  spans: b x Tmax global ids.
         ``no_eos`` (add_eos=False): ``to_parts`` has an edge per span START after the first, so the last span is not
         scored, except that its label's emission of the last frame counts when it starts there (modules:519-521)."""
         tab = self.factor_tables(valid_classes, features.device)
         f64 = torch.float64
+        if getattr(self, 'feature_projector', None) is not None:     # (the reference scores the projected features: :560-563;
+            self._require_device(features, 'gold_score')             # from ``log_likelihood`` they already are)
+            features = self._project(features.to(torch.float32).contiguous(), projected)
         x = features.to(f64)
         elp = tab['cst'] + x @ tab['w'] - 0.5 * (x * x) @ tab['inv_var'].unsqueeze(1)
         if constraints is not None:
@@ -2310,13 +2415,14 @@ class SemiMarkovModule(nn.Module):
         return tuple(st[k] for k in TABLE_NAMES)
 
     def log_partition(self, features, lengths, valid_classes, additional_allowed_ends_per_instance=None,
-                      constraints=None, no_eos=False):
+                      constraints=None, no_eos=False, projected=False):
         """log Z per instance on the device, differentiable w.r.t. the module's parameters
         (smm_emission_f64 + smm_logz_f64 forward, smm_logz_bwd_f64 backward)."""
         self._require_device(features, 'log_partition')
         st = self._one_group_tables(valid_classes, features.device)
         batch, x, cons, endpen, _, _ = self._stage_padded(features, lengths, valid_classes, additional_allowed_ends_per_instance,
-                                                          constraints, no_eos=no_eos, no_time_split=self._hard_masks(), tables=st)
+                                                          constraints, no_eos=no_eos, no_time_split=self._hard_masks(), tables=st,
+                                                          projected=projected)
         return _LogPartition.apply(batch, x, cons, endpen, st['w'], st['cst'], st['inv_var'], st['trans'], st['init'], st['len'])
 
     def log_partition_packed(self, pc):
@@ -2327,7 +2433,7 @@ class SemiMarkovModule(nn.Module):
         self._require_device(pc.x, 'log_partition_packed')
         self.prepare_packed(pc, differentiable=True)
         t = pc.tables
-        return _LogPartition.apply(pc.batch, pc.x, pc.cons, pc.endpen, t['w'], t['cst'], t['inv_var'], t['trans'], t['init'],
+        return _LogPartition.apply(pc.batch, self._project_packed(pc, pc.x, differentiable=True), pc.cons, pc.endpen, t['w'], t['cst'], t['inv_var'], t['trans'], t['init'],
                                    t['len'])
 
     def log_likelihood_packed(self, pc):
@@ -2381,28 +2487,45 @@ class SemiMarkovModule(nn.Module):
         valid_classes = self._check_valid_classes(valid_classes_per_instance)
         self.set_z(features, lengths, use_mean=use_mean_z)
         log_det = torch.zeros(features.size(0), device=features.device)
+        if getattr(self, 'feature_projector', None) is not None:
+            # project ONCE: the gold score and the likelihood launches of one step read the same y, and the flow runs forward and
+            # backward once per step
+            self._require_device(features, 'log_likelihood')
+            features = self._project((features if features.requires_grad else features.detach()).to(torch.float32).contiguous())
+            return self._log_likelihood_value(features, lengths, valid_classes, valid_classes_per_instance, spans, add_eos,
+                                              additional_allowed_ends_per_instance, constraints, transcripts,
+                                              transcript_optional, transcript_graphs, True), log_det.mean()
+        return self._log_likelihood_value(features, lengths, valid_classes, valid_classes_per_instance, spans, add_eos,
+                                          additional_allowed_ends_per_instance, constraints, transcripts, transcript_optional,
+                                          transcript_graphs, False), log_det.mean()
+
+    def _log_likelihood_value(self, features, lengths, valid_classes, valid_classes_per_instance, spans, add_eos,
+                              additional_allowed_ends_per_instance, constraints, transcripts, transcript_optional,
+                              transcript_graphs, projected):
+        """The mean of ``log_likelihood``; ``projected``: the features are the projection already, and every call below is told."""
+        no_eos = not add_eos
         if transcripts is not None:
             ll = self.transcript_log_partition(features, lengths, valid_classes_per_instance, transcripts, add_eos=add_eos,
                                                additional_allowed_ends_per_instance=additional_allowed_ends_per_instance,
-                                               constraints=constraints, optional=transcript_optional)
+                                               constraints=constraints, optional=transcript_optional, projected=projected)
             if getattr(self.args, 'sm_train_discriminatively', False):
                 ll = ll - self.log_partition(features, lengths, valid_classes, additional_allowed_ends_per_instance,
-                                             constraints)
+                                             constraints, projected=projected)
         elif transcript_graphs is not None:
             ll = self.transcript_graph_log_partition(features, lengths, valid_classes_per_instance, transcript_graphs,
                                                      add_eos=add_eos,
                                                      additional_allowed_ends_per_instance=additional_allowed_ends_per_instance,
-                                                     constraints=constraints)
+                                                     constraints=constraints, projected=projected)
             if getattr(self.args, 'sm_train_discriminatively', False):
                 ll = ll - self.log_partition(features, lengths, valid_classes, additional_allowed_ends_per_instance,
-                                             constraints)
+                                             constraints, projected=projected)
         elif spans is not None:
             ll = self.gold_score(features, lengths, valid_classes, spans, additional_allowed_ends_per_instance, constraints,
-                                 no_eos=no_eos)
+                                 no_eos=no_eos, projected=projected)
             if getattr(self.args, 'sm_train_discriminatively', False):
                 ll = ll - self.log_partition(features, lengths, valid_classes, additional_allowed_ends_per_instance,
-                                             constraints, no_eos=no_eos)
+                                             constraints, no_eos=no_eos, projected=projected)
         else:
             ll = self.log_partition(features, lengths, valid_classes, additional_allowed_ends_per_instance, constraints,
-                                    no_eos=no_eos)
-        return ll.mean(), log_det.mean()
+                                    no_eos=no_eos, projected=projected)
+        return ll.mean()

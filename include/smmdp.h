@@ -292,6 +292,63 @@ int smm_emission_bwd_f64(const smm_shape *shape, const int64_t *lengths_host, co
                          void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * The rest of that chain rule, the gradient with respect to the features (what a feature projection in front of the scorer
+ * trains on; smm_flow_bwd_f32 reads it as g_y):
+ *   g_x[t][d] = sum_c g_elp[t][c] w[g][d][c] - x[t][d] inv_var[d] sum_c g_elp[t][c]        (g the group of the frame's video)
+ * computed in fp64 and rounded once.  w and inv_var are smm_emission_f64's (feature-major w).  Rows of g_x that no video covers
+ * are 0.  One pass over x and g_elp, no atomics: two runs give the same bits.
+ *   g_x        dev fp32 [total_frames][d]   (overwritten)
+ */
+int smm_emission_bwd_x_f64(const smm_shape *shape, const int64_t *lengths_host, const int64_t *frame_offset_host,
+                           const int32_t *group_host, const int32_t *n_states_host,
+                           const float *x, const double *g_elp, const double *w, const double *inv_var, float *g_x,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Feature projection: the NICE additive coupling flow of the reference's --sm_feature_projection (src/models/flow.py,
+ * NICETrans without --flow_scale), applied to every row of x on its own: y = flow(x), log det = 0.
+ *
+ * Coupling layer i (0-based) splits a row into halves (h1, h2) of d/2.  For even i the passive half is h1 and the active half h2,
+ * for odd i the other way round.  The passive half is copied; the active half becomes active + t_i(passive), where t_i is a
+ * ReLU MLP: in_layer (d/2 -> hidden_units), hidden_layers layers hidden_units -> hidden_units, out_layer (hidden_units -> d/2),
+ * with ReLU behind every layer but the last.  Everything is fp32; every dot product is a fused-multiply-add chain in ascending
+ * input index that starts from the bias, so a row's result does not depend on n_rows or on the row's place.
+ *
+ * params: ONE packed fp32 device buffer.  For coupling layer 0, 1, ... in turn: for its linear layers in_layer, cell0, cell1, ...,
+ * out_layer in turn: the weight, then the bias.  A weight is stored INPUT-major, [in_features][out_features] (the transpose of
+ * torch.nn.Linear.weight), unpadded; a bias is [out_features].  With dh = d/2, H = hidden_units, L = hidden_layers the buffer holds
+ * couple_layers * (dh*H + H + L*(H*H + H) + H*dh + dh) floats.  smm_flow_bwd_f32 returns the gradients in the same layout, fp64.
+ *
+ * Supported: d even, 2 <= d <= 512; 1 <= hidden_units <= 256; 0 <= hidden_layers <= 4; 1 <= couple_layers <= 16; n_rows >= 1.
+ * Anything else is SMM_ERR_UNSUPPORTED (an odd d, n_rows < 1 or a NULL shape: SMM_ERR_ARG), a NULL x / params / y / g_y /
+ * g_params / scratch SMM_ERR_ARG, a short scratch SMM_ERR_WORKSPACE -- all before a device is touched.
+ *
+ * smm_flow_f32:      x dev fp32 [n_rows][d] -> y dev fp32 [n_rows][d] (y may be x).  The tile lives on chip, so the call needs no
+ *                    scratch today: smm_flow_scratch_bytes is 0 and scratch may be NULL; a caller that passes what the query
+ *                    returns stays correct if that changes.
+ * smm_flow_bwd_f32:  x and g_y = dL/dy (dev fp32 [n_rows][d]) -> g_params dev fp64 (packed layout, overwritten) and, when g_x is
+ *                    not NULL, g_x = dL/dx dev fp32 [n_rows][d].  Activations are recomputed, nothing is kept from the forward
+ *                    call.  Products are fp32 within a tile of rows; sums across tiles are fp64, per workgroup, added in a fixed
+ *                    order: two runs give the same bits.  scratch: smm_flow_bwd_scratch_bytes (0 for an invalid shape): the
+ *                    partials and, at the sizes whose tile leaves no room for them in LDS, each coupling layer's input half of
+ *                    the tiles in flight; its contents are undefined after the call.
+ * Neither call synchronises or allocates; both run on `stream` and can be captured into a hipGraph.
+ */
+typedef struct smm_flow_shape {
+    int64_t n_rows;
+    int32_t d;
+    int32_t hidden_units;
+    int32_t hidden_layers;
+    int32_t couple_layers;
+} smm_flow_shape;
+size_t smm_flow_scratch_bytes(const smm_flow_shape *shape);
+size_t smm_flow_bwd_scratch_bytes(const smm_flow_shape *shape);
+int smm_flow_f32(const smm_flow_shape *shape, const float *x, const float *params, float *y,
+                 void *scratch, size_t scratch_bytes, void *stream);
+int smm_flow_bwd_f32(const smm_flow_shape *shape, const float *x, const float *g_y, const float *params,
+                     double *g_params, float *g_x, void *scratch, size_t scratch_bytes, void *stream);
+
+/*
  * Viterbi decode on emission scores (fp64 path).
  *   elp       dev fp64 [total_frames][c_max]
  *   spans     dev int64 [b][t_max + 1]  span encoding of modules:679-691: global class id at each span start,
