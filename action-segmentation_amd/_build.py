@@ -17,7 +17,7 @@ SOURCES = ["smm_api.hip", "smm_emission.hip", "smm_viterbi.hip", "smm_chunk.hip"
            "smm_align_graph_sample.hip", "smm_align_graph_entropy.hip", "smm_align_graph_kl.hip",
            "smm_align_graph_entropy_bwd.hip", "smm_segpost.hip", "smm_align_graph_segpost.hip", "smm_expected_reward.hip",
            "smm_align_graph_expected_reward.hip", "smm_flow.hip"]
-HEADERS = ["smm_device.h", "smm_launch.h", "smm_align_tile.h", "smm_align_lse.h", "smm_align_graph.h", "smm_posterior.h", "smm_draw.h", "smm_plan_feedback.h", os.path.join("..", "..", "include", "smmdp.h")]
+HEADERS = ["smm_device.h", "smm_launch.h", "smm_align_tile.h", "smm_align_lse.h", "smm_align_graph.h", "smm_posterior.h", "smm_posterior_grad.h", "smm_draw.h", "smm_plan_feedback.h", os.path.join("..", "..", "include", "smmdp.h")]
 # -ffp-contract=off: every a+b in the DP must be ONE IEEE add (bit-exact twin of oracle/smm_oracle.c)
 # unroll thresholds: the frame loops must unroll completely, or the register-resident rings become scratch arrays
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17",

@@ -9,7 +9,8 @@
 // alignment, the test of the tables the structure reads, the compaction of a ballot into a list.  Then what the readers of the
 // forward kernel's workspace block share (from "the posterior" on): the recorded range of a column, the column blocks of a
 // video, the neighbour lists of a column, the candidates of the end and predecessor decisions, what a video of a two-sided
-// kernel answers that cannot be evaluated, q's side of such a call, and the block sum.
+// kernel answers that cannot be evaluated, q's side of such a call, the block sum, and the scratch view and the video states of
+// the two gradient units (smm_align_graph_entropy_bwd.hip, smm_align_graph_expected_reward.hip).
 // Include after smm_align_tile.h.
 #pragma once
 
@@ -338,6 +339,33 @@ __device__ __forceinline__ SmmAlignSideQ graph_side_q(SmmAlignSideQ q, const Ali
     q.len += (size_t)v.g * k_rows * v.cm;
     q.endpen = q.endpen ? q.endpen + (size_t)vid * v.cm : nullptr;
     return q;
+}
+
+// ---- the caller's scratch of the gradient units, one layout for both (smm_launch.h: SmmAlignEntBwdArgs): per video five
+// [M][T+1] blocks behind 5 x the cells in front of it; behind pv_base the videos' parts, [b] doubles of the entropy unit, V+ [b]
+struct GraphGradScratch {
+    double *em_s, *em_e, *ep_e, *ep_s, *dd;                    // eta-S, eta-E, eta+E, eta+S, D: each [M][T+1]
+    double *part, *vals;                                       // the video's parts; vals[0] = V-, vals[1] = state
+    double *vplus;
+};
+
+__device__ __forceinline__ GraphGradScratch graph_grad_scratch(const SmmAlignEntBwdArgs &a, const AlignVideo &v, int vid)
+{
+    GraphGradScratch x;
+    const size_t MT = (size_t)v.M * v.T1;
+    const int64_t cells = smm_graph_cells_before(a.g.hoff[vid], v.t0 - a.g.toff[0]);
+    x.em_s = a.scratch + 5 * cells; x.em_e = x.em_s + MT; x.ep_e = x.em_e + MT; x.ep_s = x.ep_e + MT; x.dd = x.ep_s + MT;
+    const size_t pf = smm_agb_part_doubles(v.cm, a.g.k_rows);
+    x.part = a.scratch + a.pv_base + (size_t)vid * pf;
+    x.vals = x.part + pf - 2;
+    x.vplus = a.scratch + a.pv_base + (size_t)a.g.b * (pf + 1) + vid;
+    return x;
+}
+
+// a video's state (smm_launch.h) from its V-: NaN: nothing to sum; +inf or -inf: NaN rows; finite: its terms are summed
+__device__ __forceinline__ double graph_grad_state(double val)
+{
+    return align_nonfinite_bits(val) ? (val != val ? SMM_AGB_SKIP : SMM_AGB_NAN) : SMM_AGB_RUN;
 }
 
 // the sum of x over the workgroup, in every thread: a butterfly per wave, the waves in order

@@ -49,14 +49,12 @@
 // (a video's state in its parts, SMM_AGB_RUN / _SKIP / _NAN, and the size of the parts: smm_launch.h)
 __host__ __device__ inline size_t agb_part_doubles(int cm, int k_rows) { return smm_agb_part_doubles(cm, k_rows); }
 
-// the two sides' columns, q's tables (p's are the AlignVideo's) and the scratch blocks of one video
-struct AgbVideo {
+// the two sides' columns, q's tables (p's are the AlignVideo's) and the scratch blocks (smm_align_graph.h) of one video
+struct AgbVideo : GraphGradScratch {
     const int *rng, *rngq;                                     // the columns' recorded ranges
     GraphCols<const double> p, q;
     SmmAlignSideQ tq;                                          // (trans, len, endpen: the video's)
     const double *cumq;
-    double *em_s, *em_e, *ep_e, *ep_s, *dd;                    // eta-S, eta-E, eta+E, eta+S, D: each [M][T+1]
-    double *part, *vals;                                       // the video's parts; vals[0] = V-, vals[1] = state
     const uint32_t *masks;
     double lzp, lzq;
 };
@@ -64,18 +62,13 @@ struct AgbVideo {
 __device__ __forceinline__ AgbVideo agb_video(const SmmAlignEntBwdArgs &a, const AlignVideo &v, int vid)
 {
     AgbVideo x;
-    const size_t MT = (size_t)v.M * v.T1;
+    static_cast<GraphGradScratch &>(x) = graph_grad_scratch(a, v, vid);
     const int64_t ho = a.g.hoff[vid];
     x.rng = graph_rng(a.g.cols + ho); x.rngq = graph_rng(a.q.cols + ho);
     x.p = graph_cols<const double>(a.g.cols + ho, v.M, v.T1);
     x.q = graph_cols<const double>(a.q.cols + ho, v.M, v.T1);
     x.tq = graph_side_q(a.q, v, a.g.k_rows, vid);
     x.cumq = a.q.hist + a.g.videos[vid].hist_off;
-    const int64_t cells = smm_graph_cells_before(ho, v.t0 - a.g.toff[0]);
-    x.em_s = a.scratch + 5 * cells; x.em_e = x.em_s + MT; x.ep_e = x.em_e + MT; x.ep_s = x.ep_e + MT; x.dd = x.ep_s + MT;
-    const size_t pf = agb_part_doubles(v.cm, a.g.k_rows);
-    x.part = a.scratch + a.pv_base + (size_t)vid * pf;
-    x.vals = x.part + pf - 2;
     x.masks = a.g.pred_mask + (size_t)v.t0 * SMM_GRAPH_WORDS;
     x.lzp = a.g.logz[vid]; x.lzq = a.q.logz[vid];
     return x;
@@ -230,7 +223,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_eta_minus_k
         if (val != val) a.g.err[0] = 1;                        // (a posterior that does not add up: not reached from finite logZ_g)
         if (a.value) a.value[vid] = val;
         x.vals[0] = val;
-        x.vals[1] = align_nonfinite_bits(val) ? (val != val ? SMM_AGB_SKIP : SMM_AGB_NAN) : SMM_AGB_RUN;
+        x.vals[1] = graph_grad_state(val);
     }
 }
 
@@ -244,9 +237,8 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_eta_plus_ke
     const AgbVideo x = agb_video(a, v, vid);
     const int T = v.T, cm = v.cm, kw = v.kw, M = v.M, kl = a.kl;
     const size_t T1 = v.T1;
-    double *vplus = a.scratch + a.pv_base + (size_t)a.g.b * (agb_part_doubles(cm, a.g.k_rows) + 1) + vid;
     if (x.vals[1] != SMM_AGB_RUN) {                            // (nothing to walk: V+ is what the eta- kernel answered)
-        if (tid == 0) vplus[0] = x.vals[0];
+        if (tid == 0) x.vplus[0] = x.vals[0];
         return;
     }
     graph_load_sides(a.g, v, x.rng, x.rngq, nd, s_flag, tid);
@@ -302,7 +294,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_eta_plus_ke
 
     // ---- the start node: the start nodes that have cells, in index order
     if (tid == 0)
-        vplus[0] = agb_decide(kl, [&](auto f) {
+        x.vplus[0] = agb_decide(kl, [&](auto f) {
             for (int m = 0; m < M; ++m)
                 if (s_z[m]) {
                     const size_t at = (size_t)m * T1;

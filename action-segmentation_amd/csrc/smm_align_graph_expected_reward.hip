@@ -53,13 +53,11 @@
 
 #define SMM_AGER_CHUNKS (SMM_ALIGN_THREADS / SMM_MAX_STATES_DEV)  // the prefix kernel's chunks of frames per state
 
-// the columns, the scratch blocks, the prefix sums and the node rewards of one video
-struct AgerVideo {
+// the columns, the scratch blocks (smm_align_graph.h; here em_s holds eta-S - cumW and ep_e eta+E + cumW), the prefix sums and
+// the node rewards of one video
+struct AgerVideo : GraphGradScratch {
     const int *rng;                                            // the columns' recorded ranges
     GraphCols<const double> p;
-    double *em_s, *em_e, *ep_e, *ep_s, *dd;                    // eta-S - cumW, eta-E, eta+E + cumW, eta+S, D: each [M][T+1]
-    double *part, *vals;                                       // the video's parts; vals[0] = V-, vals[1] = state
-    double *vplus;
     const double *cw;                                          // cumW [C][T+1]
     const double *nr;                                          // the rewards of the video's nodes, or null
     const uint32_t *masks;
@@ -69,16 +67,10 @@ struct AgerVideo {
 __device__ __forceinline__ AgerVideo ager_video(const SmmAlignExpRewardArgs &a, const AlignVideo &v, int vid)
 {
     AgerVideo x;
-    const size_t MT = (size_t)v.M * v.T1;
+    static_cast<GraphGradScratch &>(x) = graph_grad_scratch(a.e, v, vid);
     const int64_t ho = a.e.g.hoff[vid];
     x.rng = graph_rng(a.e.g.cols + ho);
     x.p = graph_cols<const double>(a.e.g.cols + ho, v.M, v.T1);
-    const int64_t cells = smm_graph_cells_before(ho, v.t0 - a.e.g.toff[0]);
-    x.em_s = a.e.scratch + 5 * cells; x.em_e = x.em_s + MT; x.ep_e = x.em_e + MT; x.ep_s = x.ep_e + MT; x.dd = x.ep_s + MT;
-    const size_t pf = smm_agb_part_doubles(v.cm, a.e.g.k_rows);
-    x.part = a.e.scratch + a.e.pv_base + (size_t)vid * pf;
-    x.vals = x.part + pf - 2;
-    x.vplus = a.e.scratch + a.e.pv_base + (size_t)a.e.g.b * (pf + 1) + vid;
     x.cw = a.cumw + a.cw_off[vid];
     x.nr = a.node_reward ? a.node_reward + v.t0 : nullptr;
     x.masks = a.e.g.pred_mask + (size_t)v.t0 * SMM_GRAPH_WORDS;
@@ -320,7 +312,7 @@ __global__ void __launch_bounds__(SMM_ALIGN_THREADS) smm_align_graph_er_eta_minu
         if (val != val) a.e.g.err[0] = 1;                      // (a posterior that does not add up: not reached from finite logZ_g)
         if (a.vpm) a.vpm[2 * vid] = val;
         x.vals[0] = val;
-        x.vals[1] = align_nonfinite_bits(val) ? (val != val ? SMM_AGB_SKIP : SMM_AGB_NAN) : SMM_AGB_RUN;
+        x.vals[1] = graph_grad_state(val);
     }
 }
 

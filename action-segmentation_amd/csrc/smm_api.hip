@@ -1270,6 +1270,21 @@ static int run_reversed(const smm_shape *shape, const Staged &st, double *hist, 
     return smm_launch_logz(a, rt.logz_b, ring_regs(st.kp_max), st.c_need, hs);
 }
 
+// What the calls that read both directions of p's lattice open with: the launch staged into the workspace, then p's
+// time-reversed histories.  `held`: a refusal that ranks behind staging's own.
+static int stage_both(const smm_shape *shape, const int64_t *lengths, const int64_t *frame_off, const int32_t *group,
+                      const int32_t *kp, const int32_t *n_states, void *ws, size_t ws_bytes, const Tables &p, hipStream_t hs,
+                      Staged *st, int held = SMM_OK)
+{
+    const int rc = stage(shape, lengths, frame_off, group, kp, n_states, ws, ws_bytes, hs, st);
+    if (rc != SMM_OK) return rc;
+    if (held != SMM_OK) return held;
+    return run_reversed(shape, *st, st->hist, st->tabs, p, hs);
+}
+
+// a caller's buffer against the size its query returns: 0 is the query's refusal of the shape
+static int room_ok(size_t need, size_t have) { return need == 0 ? SMM_ERR_ARG : have < need ? SMM_ERR_WORKSPACE : SMM_OK; }
+
 static int run_emission(const smm_shape *s, const Staged &st, const float *x, const double *w, const double *cst,
                         const double *inv_var, const float *cons, double *elp64, float *elp32, hipStream_t stream,
                         int first = 0, int count = -1)
@@ -1746,11 +1761,9 @@ extern "C" int smm_entropy_f64(const smm_shape *shape, const int64_t *lengths_ho
     if (!entropy_out || !elp || !trans || !init || !len_scores || !logz) return SMM_ERR_ARG;
     Staged st;
     hipStream_t hs = static_cast<hipStream_t>(stream);
-    int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes,
-                   hs, &st);
-    if (rc != SMM_OK) return rc;
     const Tables p{elp, trans, init, len_scores, endpen, logz};
-    rc = run_reversed(shape, st, st.hist, st.tabs, p, hs);
+    const int rc = stage_both(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace,
+                              workspace_bytes, p, hs, &st);
     if (rc != SMM_OK) return rc;
     const SmmPostHead h = post_head(shape, st);
     smm_launch_entropy(SmmEntropyArgs{h, post_side(h.no_eos, st.hist, p), entropy_out}, shape->t_max, hs);
@@ -1772,12 +1785,10 @@ extern "C" int smm_segment_posteriors_f64(const smm_shape *shape, const int64_t 
     if (spans_in && n_sets <= 0) return SMM_ERR_ARG;
     Staged st;
     hipStream_t hs = static_cast<hipStream_t>(stream);
-    int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes,
-                   hs, &st);
-    if (rc != SMM_OK) return rc;
-    if (seg_logp && (int64_t)shape->b * n_sets > 0x7fffffff) return SMM_ERR_UNSUPPORTED;
     const Tables p{elp, trans, init, len_scores, endpen, logz};
-    rc = run_reversed(shape, st, st.hist, st.tabs, p, hs);
+    const int rc = stage_both(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace,
+                              workspace_bytes, p, hs, &st,
+                              (seg_logp && shape && (int64_t)shape->b * n_sets > 0x7fffffff) ? SMM_ERR_UNSUPPORTED : SMM_OK);
     if (rc != SMM_OK) return rc;
     {
         const size_t fr = (size_t)shape->total_frames;
@@ -1797,9 +1808,8 @@ extern "C" int smm_segment_posteriors_f64(const smm_shape *shape, const int64_t 
 // and pointed into
 static int point_q(const smm_shape *shape, const int64_t *lengths_host, void *ws_q, size_t ws_q_bytes, Staged *sq)
 {
-    const size_t need = smm_workspace_bytes(shape, lengths_host);
-    if (need == 0) return SMM_ERR_ARG;
-    if (ws_q_bytes < need) return SMM_ERR_WORKSPACE;
+    const int rc = room_ok(smm_workspace_bytes(shape, lengths_host), ws_q_bytes);
+    if (rc != SMM_OK) return rc;
     plan_point(make_plan(shape, lengths_host), ws_q, sq);
     return SMM_OK;
 }
@@ -1820,10 +1830,9 @@ extern "C" int smm_kl_f64(const smm_shape *shape, const int64_t *lengths_host, c
     if (rq != SMM_OK) return rq;
     Staged st;
     hipStream_t hs = static_cast<hipStream_t>(stream);
-    int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, ws_p, ws_p_bytes, hs, &st);
-    if (rc != SMM_OK) return rc;
     const Tables p{elp_p, trans_p, init_p, len_p, endpen_p, logz_p}, q{elp_q, trans_q, init_q, len_q, endpen_q, logz_q};
-    rc = run_reversed(shape, st, st.hist, st.tabs, p, hs);          // (p's side only)
+    const int rc = stage_both(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, ws_p, ws_p_bytes, p,
+                              hs, &st);                              // (p's side only)
     if (rc != SMM_OK) return rc;
     const SmmPostHead h = post_head(shape, st);
     smm_launch_kl(SmmKlArgs{h, post_side(h.no_eos, st.hist, p), post_side(h.no_eos, sq.hist, q), kl_out, xent_out}, shape->t_max,
@@ -1852,10 +1861,11 @@ extern "C" size_t smm_entropy_bwd_scratch_bytes(const smm_shape *shape, const in
     return sizeof(double) * tot;
 }
 
-// both entry points: p's histories in st, r's in hist_r (r = p for the entropy)
-static int ebwd_run(const smm_shape *shape, const int64_t *lengths_host, const Staged &st, const double *hist_r,
-                    const Tables &p, const Tables &r, int kl, const double *grad_out, double *g_elp, double *g_trans,
-                    double *g_init, double *g_len, double *value_out, void *scratch, hipStream_t hs)
+// what the gradient units launch on (the expected reward's too): g_elp and the scratch's fixed parts zeroed, and the argument
+// block.  p's histories in st, r's in hist_r (r = p for the entropy and the reward)
+static int ebwd_args(const smm_shape *shape, const int64_t *lengths_host, const Staged &st, const double *hist_r,
+                     const Tables &p, const Tables &r, int kl, const double *grad_out, double *g_elp, double *g_trans,
+                     double *g_init, double *g_len, double *value_out, void *scratch, hipStream_t hs, SmmEntBwdArgs *e)
 {
     size_t pv_base = 0, tot = 0;
     ebwd_layout(shape, lengths_host, &pv_base, &tot);
@@ -1866,8 +1876,20 @@ static int ebwd_run(const smm_shape *shape, const int64_t *lengths_host, const S
         SMM_HIP((hipError_t)smm_zero_multi_async(zp, zb, 2, hs));
     }
     const SmmPostHead h = post_head(shape, st);
-    const SmmEntBwdArgs e{h, post_side(h.no_eos, st.hist, p), post_side(h.no_eos, hist_r, r), grad_out, g_elp, g_trans, g_init,
-                          g_len, value_out, sc, (int64_t)pv_base, shape->n_groups, kl};
+    *e = SmmEntBwdArgs{h, post_side(h.no_eos, st.hist, p), post_side(h.no_eos, hist_r, r), grad_out, g_elp, g_trans, g_init,
+                       g_len, value_out, sc, (int64_t)pv_base, shape->n_groups, kl};
+    return SMM_OK;
+}
+
+// both entropy / KL entry points
+static int ebwd_run(const smm_shape *shape, const int64_t *lengths_host, const Staged &st, const double *hist_r,
+                    const Tables &p, const Tables &r, int kl, const double *grad_out, double *g_elp, double *g_trans,
+                    double *g_init, double *g_len, double *value_out, void *scratch, hipStream_t hs)
+{
+    SmmEntBwdArgs e;
+    const int rc = ebwd_args(shape, lengths_host, st, hist_r, p, r, kl, grad_out, g_elp, g_trans, g_init, g_len, value_out,
+                             scratch, hs, &e);
+    if (rc != SMM_OK) return rc;
     smm_launch_entropy_bwd(e, shape->t_max, st.kp_max, hs);
     SMM_HIP(hipGetLastError());
     return SMM_OK;
@@ -1882,16 +1904,13 @@ extern "C" int smm_entropy_bwd_f64(const smm_shape *shape, const int64_t *length
 {
     if (!elp || !trans || !init || !len_scores || !logz || !g_elp || !g_trans || !g_init || !g_len || !scratch)
         return SMM_ERR_ARG;
-    const size_t need = smm_entropy_bwd_scratch_bytes(shape, lengths_host);
-    if (need == 0) return SMM_ERR_ARG;
-    if (scratch_bytes < need) return SMM_ERR_WORKSPACE;
     Staged st;
     hipStream_t hs = static_cast<hipStream_t>(stream);
-    int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes,
-                   hs, &st);
+    int rc = room_ok(smm_entropy_bwd_scratch_bytes(shape, lengths_host), scratch_bytes);
     if (rc != SMM_OK) return rc;
     const Tables p{elp, trans, init, len_scores, endpen, logz};
-    rc = run_reversed(shape, st, st.hist, st.tabs, p, hs);
+    rc = stage_both(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes, p, hs,
+                    &st);
     if (rc != SMM_OK) return rc;
     return ebwd_run(shape, lengths_host, st, st.hist, p, p, 0, grad_out, g_elp, g_trans, g_init, g_len, value_out, scratch, hs);
 }
@@ -1912,15 +1931,13 @@ extern "C" int smm_kl_bwd_f64(const smm_shape *shape, const int64_t *lengths_hos
     Staged sq;
     const int rq = point_q(shape, lengths_host, ws_q, ws_q_bytes, &sq);
     if (rq != SMM_OK) return rq;
-    const size_t sneed = smm_entropy_bwd_scratch_bytes(shape, lengths_host);
-    if (sneed == 0) return SMM_ERR_ARG;
-    if (scratch_bytes < sneed) return SMM_ERR_WORKSPACE;
     Staged st;
     hipStream_t hs = static_cast<hipStream_t>(stream);
-    int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, ws_p, ws_p_bytes, hs, &st);
+    int rc = room_ok(smm_entropy_bwd_scratch_bytes(shape, lengths_host), scratch_bytes);
     if (rc != SMM_OK) return rc;
     const Tables p{elp_p, trans_p, init_p, len_p, endpen_p, logz_p}, q{elp_q, trans_q, init_q, len_q, endpen_q, logz_q};
-    rc = run_reversed(shape, st, st.hist, st.tabs, p, hs);          // both sides' backward histories
+    rc = stage_both(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, ws_p, ws_p_bytes, p, hs,
+                    &st);                                           // both sides' backward histories
     if (rc == SMM_OK && sq.hist != st.hist) rc = run_reversed(shape, st, sq.hist, sq.tabs, q, hs);
     if (rc != SMM_OK) return rc;
     return ebwd_run(shape, lengths_host, st, sq.hist, p, q, mode == SMM_KL_BWD_KL ? 1 : 0, grad_out, g_elp, g_trans, g_init,
@@ -1944,11 +1961,9 @@ extern "C" int smm_expected_reward_f64(const smm_shape *shape, const int64_t *le
     if (!value_out || !elp || !trans || !init || !len_scores || !logz || (!reward && !seg_reward)) return SMM_ERR_ARG;
     Staged st;
     hipStream_t hs = static_cast<hipStream_t>(stream);
-    int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes,
-                   hs, &st);
-    if (rc != SMM_OK) return rc;
     const Tables p{elp, trans, init, len_scores, endpen, logz};
-    rc = run_reversed(shape, st, st.hist, st.tabs, p, hs);
+    const int rc = stage_both(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace,
+                              workspace_bytes, p, hs, &st);
     if (rc != SMM_OK) return rc;
     SmmExpRewardArgs a{};
     a.e.h = post_head(shape, st);
@@ -1970,34 +1985,18 @@ extern "C" int smm_expected_reward_bwd_f64(const smm_shape *shape, const int64_t
     if (!elp || !trans || !init || !len_scores || !logz || (!reward && !seg_reward) || !g_elp || !g_trans || !g_init || !g_len ||
         !scratch)
         return SMM_ERR_ARG;
-    const size_t need = smm_expected_reward_bwd_scratch_bytes(shape, lengths_host);
-    if (need == 0) return SMM_ERR_ARG;
-    if (scratch_bytes < need) return SMM_ERR_WORKSPACE;
     Staged st;
     hipStream_t hs = static_cast<hipStream_t>(stream);
-    int rc = stage(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes,
-                   hs, &st);
+    int rc = room_ok(smm_expected_reward_bwd_scratch_bytes(shape, lengths_host), scratch_bytes);
     if (rc != SMM_OK) return rc;
     const Tables p{elp, trans, init, len_scores, endpen, logz};
-    rc = run_reversed(shape, st, st.hist, st.tabs, p, hs);
+    rc = stage_both(shape, lengths_host, frame_offset_host, group_host, kp_host, n_states_host, workspace, workspace_bytes, p, hs,
+                    &st);
     if (rc != SMM_OK) return rc;
-    size_t pv_base = 0, tot = 0;
-    ebwd_layout(shape, lengths_host, &pv_base, &tot);
-    double *sc = static_cast<double *>(scratch);
-    {
-        void *const zp[2] = {g_elp, sc + pv_base};
-        const size_t zb[2] = {sizeof(double) * (size_t)shape->total_frames * shape->c_max, sizeof(double) * (tot - pv_base)};
-        SMM_HIP((hipError_t)smm_zero_multi_async(zp, zb, 2, hs));
-    }
     SmmExpRewardArgs a{};
-    a.e.h = post_head(shape, st);
-    a.e.p = a.e.r = post_side(a.e.h.no_eos, st.hist, p);
-    a.e.grad_out = grad_out;
-    a.e.g_elp = g_elp; a.e.g_trans = g_trans; a.e.g_init = g_init; a.e.g_len = g_len;
-    a.e.value = value_out;
-    a.e.scratch = sc;
-    a.e.pv_base = (int64_t)pv_base;
-    a.e.n_groups = shape->n_groups;
+    rc = ebwd_args(shape, lengths_host, st, st.hist, p, p, 0, grad_out, g_elp, g_trans, g_init, g_len, value_out, scratch, hs,
+                   &a.e);
+    if (rc != SMM_OK) return rc;
     a.reward = reward; a.seg_reward = seg_reward;
     smm_launch_expected_reward_bwd(a, shape->t_max, st.kp_max, hs);
     SMM_HIP(hipGetLastError());

@@ -32,24 +32,18 @@
 //                          (smm_segpost_dense_kernel's split): six history loads, one cumW load, two fp64 exp per node; one
 //                          (frame part, segment part) pair of fp64 partials per workgroup, summed per video in a fixed order
 //                          by smm_er_sum_kernel.  Bounded by the history loads.
-//   smm_er_eta_kernel      one workgroup per (video, direction) walks the positions in order (smm_ebwd_eta_kernel's layout): 32
-//                          lanes per class share each node's candidates and reduce them with butterflies.  Each node has two
-//                          passes -- maxima, then fp64 exponentials and sums -- so that nothing is rescaled.  The start-node
-//                          values it stores carry the prefix sum of their position (eta- - cumW, eta+ + cumW): a span's frame
-//                          reward then costs no load per candidate, and none in the assembly.  Bounded by the serial chain: T
-//                          steps of two dependent decisions each.
-//   smm_er_nodes_kernel    grid (video, slab), thread = node (n, c): D[n][c] = the p(o) dev(o) of the spans starting at n minus
-//                          those ending at n.  O(T K C) exponentials: the most arithmetic of the call.
-//   smm_er_pairs_kernel    per video the transitions, the initial class and the closing transition.
-//   smm_er_len_kernel      per (video, state) the length sums, thread = k, blocks of 256 lengths.
+//   smm_er_eta_kernel, smm_er_nodes_kernel, smm_er_pairs_kernel, smm_er_len_kernel   smm_posterior_grad.h's skeletons (the
+//                          work split is described there) under this file's policy: one side, an expectation per decision
+//                          (smm_er_decide: maxima, then fp64 exponentials and sums, nothing rescaled).  The start-node values
+//                          the walk stores carry the prefix sum of their position (eta- - cumW, eta+ + cumW): a span's frame
+//                          reward then costs no load per candidate, and none in the assembly.
 //   then smm_ebwd_elp_kernel (g_elp = running sum of D over t, x the upstream gradient) and smm_ebwd_group_kernel (the
 //   per-video tables summed over each group's videos in video order) as they are: the scratch layout is SmmEntBwdArgs'.
 // No atomics but the error word: the results are bit-identical run to run.  A video whose log Z is not finite, or with a
 // non-finite reward in a covered entry, gets NaN for its value, its g_elp rows and its group's tables.
-#include "smm_posterior.h"
+#include "smm_posterior_grad.h"
 #include "../../include/smmdp.h"
 
-#define SMM_ER_THREADS 1024        // serial pass: 32 classes x 32 lanes
 #define SMM_ER_VAL_THREADS 256
 
 __device__ __forceinline__ bool smm_er_finite(double x) { return x > SMM_NEG_INF && x < -SMM_NEG_INF; }
@@ -211,102 +205,6 @@ __device__ double smm_er_decide(int i0, int n, int step, Wf w, Xf x)
     return acc / s;
 }
 
-__global__ void __launch_bounds__(SMM_ER_THREADS) smm_er_eta_kernel(SmmExpRewardArgs a)
-{
-    __shared__ double s_end[SMM_MAX_STATES_DEV];
-    const int vid = blockIdx.x, dir = blockIdx.y;
-    const SmmVideo mv = a.e.h.videos[vid];
-    const int T = mv.T - a.e.h.no_eos, g = mv.group, cm = a.e.h.c_max;
-    const int C = a.e.h.n_states[g];
-    const int tid = threadIdx.x, c = tid >> 5, l = tid & 31;
-    const bool act = c < C;
-    const size_t blk = (size_t)cm * (T + 1);
-    const SmmHistDir P = smm_hist_dir(a.e.p.hist, mv, cm, T, dir);
-    const double *trp = a.e.p.trans + (size_t)g * cm * cm;
-    const double *lenp = a.e.p.len + (size_t)g * a.e.h.k_rows * cm;
-    double *sv = smm_eb_video(a.e, mv);
-    // E: eta at the end nodes.  S: eta at the start nodes with the prefix sum of the node's position folded in -- forward
-    // eta-(start (s, c)) - cumW[s][c], time-reversed (index j = T - s) eta+(end (s, c)) + cumW[s][c] -- so that a span's frame
-    // reward, a difference of two prefix sums, costs no load per candidate here and none at all in the assembly
-    double *E = sv + (dir ? 2 * blk : 0), *S = E + blk;
-    // transitions of this direction: from node class c to candidate c' (time-reversed: transposed)
-    const int ts = dir ? 1 : cm, tt = dir ? cm : 1;
-    bool ok = T > 0 && C > 0 && C <= SMM_MAX_STATES_DEV;
-    const double *cw = ok ? smm_er_cum(a, mv, cm, T) : nullptr;
-    if (ok && cw[0] != cw[0]) ok = false;               // (a non-finite reward: smm_er_prefix_kernel)
-    if (ok) {
-        const double sg = act ? smm_er_seg(a, g, cm, c) : 0.0;
-        // boundary: eta at start (0, c)
-        if (act && l == 0) {
-            double b0 = 0.0;
-            if (dir == 1 && a.e.h.no_eos) {
-                const size_t fr = (size_t)(mv.frame_off + T) * cm;
-                b0 = smm_er_decide<1>(
-                    0, C, 1, [&](int to) { return trp[(size_t)to * cm + c] + a.e.p.elp[fr + to]; },
-                    [&](int to) { return smm_er_close_frame(a, mv, cm, T, to) + smm_er_seg(a, g, cm, to); });
-            }
-            S[c] = b0 + (dir ? cw[(size_t)T * cm + c] : -cw[c]);
-        }
-        __syncthreads();
-        for (int n = 1; n <= T; ++n) {
-            // end nodes (n, c): the span's length.  Forward the span covers [n - k, n) and earns cumW[n] - cumW[n - k],
-            // time-reversed [T - n, T - n + k) and cumW[T - n + k] - cumW[T - n]: the far end's cumW is inside S
-            const int kmax = (mv.kp - 1 < n) ? mv.kp - 1 : n;
-            const double *hp = P.h + (size_t)n * cm + c, *sx = S + (size_t)n * cm + c;
-            const double cw_n = act ? (dir ? -cw[(size_t)(T - n) * cm + c] : cw[(size_t)n * cm + c]) : 0.0;
-            double ve = smm_er_decide<32>(
-                1 + l, act ? kmax + 1 : 0, 32, [&](int k) { return hp[-(ptrdiff_t)k * cm] + lenp[(size_t)k * cm + c]; },
-                [&](int k) { return sx[-(ptrdiff_t)k * cm]; });
-            ve += sg + cw_n;
-            if (act && l == 0) {
-                E[(size_t)n * cm + c] = ve;
-                s_end[c] = ve;
-            }
-            __syncthreads();
-            // start nodes (n, c), 0 < n < T: the class of the span on the other side
-            if (n < T) {
-                const double vs = smm_er_decide<32>(
-                    l, (act && l < C) ? l + 1 : 0, 32,
-                    [&](int cc) { return P.g[(size_t)n * cm + cc] + trp[(size_t)c * ts + (size_t)cc * tt]; },
-                    [&](int cc) { return s_end[cc]; });
-                if (act && l == 0) S[(size_t)n * cm + c] = vs - cw_n;
-            }
-            __syncthreads();
-        }
-    }
-    // the last decision (wave 0): dir 0 the sampler's final decision, dir 1 the initial class
-    if (tid >= 64) return;
-    double v = __builtin_nan("");
-    const double lzp = a.e.p.logz[vid];
-    if (ok && smm_er_finite(lzp)) {
-        const int lane = tid;
-        if (dir == 1) {
-            v = smm_er_decide<64>(
-                lane, lane < C ? lane + 1 : 0, 64,
-                [&](int j) { return P.g[(size_t)T * cm + j] + a.e.p.init[(size_t)g * cm + j]; },
-                [&](int j) { return E[(size_t)T * cm + j]; });
-        } else {
-            // the sampler's final decision: EOS the class j; no EOS the closing label `to`, then the span label j in front of it
-            const double *FpT = P.g + (size_t)T * cm;
-            v = smm_er_decide<64>(
-                lane, lane < C ? lane + 1 : 0, 64,
-                [&](int j) { return smm_post_final_weight(a.e.h, a.e.p, mv, vid, T, C, FpT, j); },
-                [&](int to) {
-                    if (!a.e.h.no_eos) return E[(size_t)T * cm + to];
-                    return smm_er_close_frame(a, mv, cm, T, to) + smm_er_seg(a, g, cm, to)
-                           + smm_er_decide<1>(
-                               0, C, 1, [&](int j) { return FpT[j] + trp[(size_t)to * cm + j]; },
-                               [&](int j) { return E[(size_t)T * cm + j]; });
-                });
-        }
-    }
-    if (tid == 0) {
-        if (v != v) atomicExch(a.e.h.err, 1);
-        smm_eb_fixed(a.e, vid)[smm_eb_pv(cm, a.e.h.k_rows).val + dir] = v;
-        if (a.e.value) a.e.value[2 * vid + dir] = v;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ assembly
 // p(o) dev(o) of one occurrence: lp its log-probability, cond = E[R | o] = r(o) + eta-(S_o) + eta+(E_o), V the value
 __device__ __forceinline__ double smm_er_term(double lp, double cond, double V)
@@ -315,141 +213,63 @@ __device__ __forceinline__ double smm_er_term(double lp, double cond, double V)
     return exp(lp) * (cond - V);
 }
 
-// log p(span (s, k, c)): F_h[s][c] + len[k][c] + B_h[T-s-k][c] + cumE[T][c] - logZ
-__device__ __forceinline__ double smm_er_span(const SmmHist &H, const double *len, int T, int cm, int s, int k, int c, double lz)
-{
-    return H.F.h[(size_t)s * cm + c] + len[(size_t)k * cm + c] + H.B.h[(size_t)(T - s - k) * cm + c] + H.F.cum[(size_t)T * cm + c] - lz;
-}
+// The policy of smm_posterior_grad.h's skeletons: one side.  The walk's S blocks hold eta at the start nodes with the prefix sum
+// of the node's position folded in -- forward eta-(start (s, c)) - cumW[s][c], time-reversed (index j = T - s) eta+(end (s, c))
+// + cumW[s][c] -- so a span's frame reward, a difference of two prefix sums, is the near end's cumW (position()) on the end
+// node's value and nothing in the assembly; its segment reward rides on one end's eta (near())
+struct SmmErPolicy {
+    const SmmExpRewardArgs &a;
+    const SmmVideo &mv;
+    const int T, dir, cm;
+    SmmPgSide p;
+    const double *cw;              // (the walk's)
+    double sg;
+    static __device__ __forceinline__ const SmmEntBwdArgs &base(const SmmExpRewardArgs &a) { return a.e; }
+    __device__ __forceinline__ SmmErPolicy(const SmmExpRewardArgs &a_, const SmmVideo &mv_, int vid, int T_, int dir_)
+        : a(a_), mv(mv_), T(T_), dir(dir_), cm(a_.e.h.c_max), p(smm_pg_side(a_.e.h, a_.e.p, mv_, vid, T_, dir_)), cw(nullptr), sg(0.0)
+    {
+    }
+    template <int W, class Wf, class Xf>
+    __device__ __forceinline__ double decide(int i0, int n, int step, Wf w, Xf x) const
+    {
+        return smm_er_decide<W>(i0, n, step, [&](int i) { return w(p, i); }, x);
+    }
+    __device__ __forceinline__ bool walk_begin(bool ok, int c, bool act)
+    {
+        cw = ok ? smm_er_cum(a, mv, cm, T) : nullptr;
+        if (ok && cw[0] != cw[0]) ok = false;               // (a non-finite reward: smm_er_prefix_kernel)
+        sg = (ok && act) ? smm_er_seg(a, mv.group, cm, c) : 0.0;
+        return ok;
+    }
+    // end node (n, c): forward the span covers [n - k, n) and earns cumW[n] - cumW[n - k], time-reversed [T - n, T - n + k) and
+    // cumW[T - n + k] - cumW[T - n]: the far end's cumW is inside S
+    __device__ __forceinline__ double position(int n, int c, bool act) const
+    {
+        return act ? (dir ? -cw[(size_t)(T - n) * cm + c] : cw[(size_t)n * cm + c]) : 0.0;
+    }
+    __device__ __forceinline__ double end_value(double v, double cw_n) const { return v + (sg + cw_n); }
+    __device__ __forceinline__ double start_value(double v, double cw_n) const { return v - cw_n; }
+    __device__ __forceinline__ double boundary(double b0, int c) const { return b0 + (dir ? cw[(size_t)T * cm + c] : -cw[c]); }
+    __device__ __forceinline__ double closing(int to) const { return smm_er_close_frame(a, mv, cm, T, to) + smm_er_seg(a, mv.group, cm, to); }
+    __device__ __forceinline__ double closed(int to, double x) const { return closing(to) + x; }
+    __device__ __forceinline__ double near(double eta, int c) const { return eta + smm_er_seg(a, mv.group, cm, c); }
+    template <class Lf>
+    __device__ __forceinline__ double each(Lf lp) const
+    {
+        return lp(p);
+    }
+    template <class Lf>
+    __device__ __forceinline__ double each(double v, Lf lp) const
+    {
+        return lp(p, v);
+    }
+    __device__ __forceinline__ double term(double lp, double eta, double V) const { return smm_er_term(lp, eta, V); }
+};
 
-__global__ void __launch_bounds__(256) smm_er_nodes_kernel(SmmExpRewardArgs a)
-{
-    const int vid = blockIdx.x, y = blockIdx.y;
-    const SmmVideo mv = a.e.h.videos[vid];
-    const int T = mv.T - a.e.h.no_eos, g = mv.group, cm = a.e.h.c_max;
-    const int C = a.e.h.n_states[g];
-    if (T <= 0 || C <= 0) return;
-    const int n0 = y * SMM_POST_SLAB;
-    if (n0 > T) return;
-    const size_t blk = (size_t)cm * (T + 1);
-    const SmmHist H = smm_hist(a.e.p.hist, mv, cm, T);
-    const double *len = a.e.p.len + (size_t)g * a.e.h.k_rows * cm;
-    double *sv = smm_eb_video(a.e, mv);
-    const double *S0 = sv + blk, *S1 = sv + 3 * blk;        // (the prefix sums are inside: smm_er_eta_kernel)
-    double *D = sv + 4 * blk;
-    double V;
-    const bool fin = smm_eb_value(a.e, vid, &V);
-    const double lz = a.e.p.logz[vid];
-    const int n1 = smm_post_slab_end(n0, T);
-    for (int i = threadIdx.x; i < (n1 - n0) * cm; i += blockDim.x) {
-        const int dn = i / cm, c = i - dn * cm, n = n0 + dn;
-        double d = 0.0;
-        if (c < C && fin) {
-            const double sg = smm_er_seg(a, g, cm, c);
-            // spans of c that start at n
-            const int ks = (mv.kp - 1 < T - n) ? mv.kp - 1 : T - n;
-            const double s0 = S0[(size_t)n * cm + c] + sg;
-            for (int k = 1; k <= ks; ++k)
-                d += smm_er_term(smm_er_span(H, len, T, cm, n, k, c, lz), s0 + S1[(size_t)(T - n - k) * cm + c], V);
-            // ... minus those that end at n
-            const int ke = (mv.kp - 1 < n) ? mv.kp - 1 : n;
-            const double s1 = S1[(size_t)(T - n) * cm + c] + sg;
-            double e = 0.0;
-            for (int k = 1; k <= ke; ++k)
-                e += smm_er_term(smm_er_span(H, len, T, cm, n - k, k, c, lz), s1 + S0[(size_t)(n - k) * cm + c], V);
-            d -= e;
-        }
-        D[(size_t)n * cm + c] = d;
-    }
-}
-
-// per video: the transitions (pair = (to, from), slices of the boundaries merged in a fixed order), the initial class, the closing
-// transition without EOS
-__global__ void __launch_bounds__(1024) smm_er_pairs_kernel(SmmExpRewardArgs a)
-{
-    __shared__ double s_acc[1024];
-    const int vid = blockIdx.x;
-    const SmmVideo mv = a.e.h.videos[vid];
-    const int T = mv.T - a.e.h.no_eos, g = mv.group, cm = a.e.h.c_max;
-    const int C = a.e.h.n_states[g];
-    if (T <= 0 || C <= 0) return;
-    const size_t blk = (size_t)cm * (T + 1);
-    const SmmHist H = smm_hist(a.e.p.hist, mv, cm, T);
-    const double *tr = a.e.p.trans + (size_t)g * cm * cm;
-    const double *sv = smm_eb_video(a.e, mv);
-    const double *E0 = sv, *E1 = sv + 2 * blk;
-    const SmmEbPv lo = smm_eb_pv(cm, a.e.h.k_rows);
-    double *pv = smm_eb_fixed(a.e, vid);
-    double V;
-    const bool fin = smm_eb_value(a.e, vid, &V);
-    const double lz = a.e.p.logz[vid];
-    const int tid = threadIdx.x, P = C * C, ng = blockDim.x / P;
-    const int pair = tid % P, sl = tid / P;
-    const int to = pair / C, from = pair - to * C;
-    double acc = 0.0;
-    if (sl < ng && fin) {
-        const double tw = tr[(size_t)to * cm + from] - lz;
-        for (int n = 1 + sl; n < T; n += ng)
-            acc += smm_er_term(H.F.g[(size_t)n * cm + from] + tw + H.B.g[(size_t)(T - n) * cm + to],
-                               E0[(size_t)n * cm + from] + E1[(size_t)(T - n) * cm + to], V);
-    }
-    s_acc[tid] = acc;
-    __syncthreads();
-    double cl = 0.0;                                    // without EOS: the closing transition from -> to
-    if (tid < P && a.e.h.no_eos && fin) {
-        const double lp = H.F.g[(size_t)T * cm + from] + tr[(size_t)to * cm + from] + a.e.p.elp[(size_t)(mv.frame_off + T) * cm + to] - lz;
-        cl = smm_er_term(lp, smm_er_close_frame(a, mv, cm, T, to) + smm_er_seg(a, g, cm, to) + E0[(size_t)T * cm + from], V);
-    }
-    if (tid < P) {
-        double t = s_acc[tid];
-        for (int q = 1; q < ng; ++q) t += s_acc[q * P + tid];
-        pv[lo.trans + (size_t)to * cm + from] = fin ? t + cl : __builtin_nan("");
-    }
-    __syncthreads();
-    s_acc[tid] = cl;
-    __syncthreads();
-    if (tid < C) {
-        const int c = tid;
-        double ini = __builtin_nan(""), cls = __builtin_nan("");
-        if (fin) {
-            ini = smm_er_term(H.F.h[c] + H.F.cum[c] + H.B.g[(size_t)T * cm + c] - lz, E1[(size_t)T * cm + c], V);
-            cls = 0.0;
-            for (int f = 0; f < C; ++f) cls += s_acc[c * C + f];     // (pair = to * C + from: to = c)
-        }
-        pv[lo.init + c] = ini;
-        pv[lo.close + c] = cls;
-    }
-}
-
-// per (video, state): the length sums, thread = k, loop over the span's start
-__global__ void __launch_bounds__(256) smm_er_len_kernel(SmmExpRewardArgs a)
-{
-    const int cm = a.e.h.c_max;
-    const int vid = blockIdx.x / cm, c = blockIdx.x - vid * cm;
-    const SmmVideo mv = a.e.h.videos[vid];
-    const int T = mv.T - a.e.h.no_eos, g = mv.group;
-    const int C = a.e.h.n_states[g];
-    if (T <= 0 || c >= C) return;
-    const int k = 1 + blockIdx.y * blockDim.x + threadIdx.x;
-    const int kmax = (mv.kp - 1 < T) ? mv.kp - 1 : T;
-    if (k > kmax) return;
-    const size_t blk = (size_t)cm * (T + 1);
-    const SmmHist H = smm_hist(a.e.p.hist, mv, cm, T);
-    const double *len = a.e.p.len + (size_t)g * a.e.h.k_rows * cm;
-    const double *sv = smm_eb_video(a.e, mv);
-    const double *S0 = sv + blk, *S1 = sv + 3 * blk;        // (the prefix sums are inside: smm_er_eta_kernel)
-    double V;
-    const bool fin = smm_eb_value(a.e, vid, &V);
-    const double lz = a.e.p.logz[vid];
-    double acc = __builtin_nan("");
-    if (fin) {
-        const double sg = smm_er_seg(a, g, cm, c);
-        acc = 0.0;
-        for (int s = 0; s + k <= T; ++s)
-            acc += smm_er_term(smm_er_span(H, len, T, cm, s, k, c, lz),
-                               (sg + S0[(size_t)s * cm + c]) + S1[(size_t)(T - s - k) * cm + c], V);
-    }
-    smm_eb_fixed(a.e, vid)[smm_eb_pv(cm, a.e.h.k_rows).len + (size_t)k * cm + c] = acc;
-}
+__global__ void __launch_bounds__(SMM_PG_WALK_THREADS) smm_er_eta_kernel(SmmExpRewardArgs a) { smm_pg_walk<SmmErPolicy>(a); }
+__global__ void __launch_bounds__(256) smm_er_nodes_kernel(SmmExpRewardArgs a) { smm_pg_nodes<SmmErPolicy>(a); }
+__global__ void __launch_bounds__(1024) smm_er_pairs_kernel(SmmExpRewardArgs a) { smm_pg_pairs<SmmErPolicy>(a); }
+__global__ void __launch_bounds__(256) smm_er_len_kernel(SmmExpRewardArgs a) { smm_pg_len<SmmErPolicy>(a); }
 
 void smm_launch_expected_reward(const SmmExpRewardArgs &a, int t_max, hipStream_t stream)
 {
@@ -461,7 +281,7 @@ void smm_launch_expected_reward(const SmmExpRewardArgs &a, int t_max, hipStream_
 void smm_launch_expected_reward_bwd(const SmmExpRewardArgs &a, int t_max, int kp_max, hipStream_t stream)
 {
     hipLaunchKernelGGL(smm_er_prefix_kernel, dim3(a.e.h.b), dim3(1024), 0, stream, a);
-    hipLaunchKernelGGL(smm_er_eta_kernel, dim3(a.e.h.b, 2), dim3(SMM_ER_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(smm_er_eta_kernel, dim3(a.e.h.b, 2), dim3(SMM_PG_WALK_THREADS), 0, stream, a);
     hipLaunchKernelGGL(smm_er_nodes_kernel, dim3(a.e.h.b, t_max / SMM_POST_SLAB + 1), dim3(256), 0, stream, a);
     hipLaunchKernelGGL(smm_er_pairs_kernel, dim3(a.e.h.b), dim3(1024), 0, stream, a);
     if (kp_max >= 2)

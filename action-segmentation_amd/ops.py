@@ -523,8 +523,7 @@ def logz(batch, elp, trans, init, len_scores, endpen=None, ws=None, with_backwar
     if ws is None:
         ws = workspace(batch.workspace_bytes(), dev)
     _lib.check(lib.smm_logz_f64(
-        *head, _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
-        _dev(endpen, f64, 'endpen'), _dev(out, f64, 'logz'), *_ws_args(ws), _stream()))
+        *head, *_tables(elp, trans, init, len_scores, endpen), _dev(out, f64, 'logz'), *_ws_args(ws), _stream()))
     return out
 
 
@@ -540,9 +539,9 @@ def logz_bwd(batch, elp, trans, init, len_scores, logz_val, grad_logz=None, endp
     if ws is None:
         ws = workspace(batch.workspace_bytes(), dev)
     _lib.check(lib.smm_logz_bwd_f64(
-        *head, _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
-        _dev(endpen, f64, 'endpen'), _dev(logz_val, f64, 'logz'), _dev(grad_logz, f64, 'grad_logz'), _dev(g['elp'], f64, 'g_elp'),
-        _dev(g['trans'], f64, 'g_trans'), _dev(g['init'], f64, 'g_init'), _dev(g['len'], f64, 'g_len'), *_ws_args(ws), _stream()))
+        *head, *_tables(elp, trans, init, len_scores, endpen), _dev(logz_val, f64, 'logz'), _dev(grad_logz, f64, 'grad_logz'),
+        _dev(g['elp'], f64, 'g_elp'), _dev(g['trans'], f64, 'g_trans'), _dev(g['init'], f64, 'g_init'), _dev(g['len'], f64, 'g_len'),
+        *_ws_args(ws), _stream()))
     return g
 
 
@@ -564,8 +563,7 @@ def sample(batch, elp, trans, init, len_scores, logz_val, n_samples, seed=0, end
     if ws is None:
         ws = workspace(batch.workspace_bytes(), dev)
     _lib.check(lib.smm_sample_f64(
-        *head, _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
-        _dev(endpen, f64, 'endpen'), _dev(class_map, torch.int64, 'class_map'), _dev(logz_val, f64, 'logz'),
+        *head, *_tables(elp, trans, init, len_scores, endpen), _dev(class_map, torch.int64, 'class_map'), _dev(logz_val, f64, 'logz'),
         ctypes.c_int32(n_samples), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _dev(spans, torch.int64, 'spans'),
         _dev(labels, torch.int64, 'labels'), _dev(logp, f64, 'logp'), *_ws_args(ws), _stream()))
     return dict(spans=spans, labels=labels, logp=logp, _err=_err_copy(batch, ws))
@@ -586,8 +584,8 @@ def entropy(batch, elp, trans, init, len_scores, logz_val, endpen=None, ws=None,
     if ws is None:
         ws = workspace(batch.workspace_bytes(), dev)
     _lib.check(lib.smm_entropy_f64(
-        *head, _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
-        _dev(endpen, f64, 'endpen'), _dev(logz_val, f64, 'logz'), _dev(out, f64, 'entropy'), *_ws_args(ws), _stream()))
+        *head, *_tables(elp, trans, init, len_scores, endpen), _dev(logz_val, f64, 'logz'), _dev(out, f64, 'entropy'),
+        *_ws_args(ws), _stream()))
     return out
 
 
@@ -627,8 +625,7 @@ def segment_posteriors(batch, elp, trans, init, len_scores, logz_val, spans=None
     if ws is None:
         ws = workspace(batch.workspace_bytes(), dev)
     _lib.check(lib.smm_segment_posteriors_f64(
-        *head, _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
-        _dev(endpen, f64, 'endpen'), _dev(class_map, torch.int64, 'class_map'), _dev(logz_val, f64, 'logz'),
+        *head, *_tables(elp, trans, init, len_scores, endpen), _dev(class_map, torch.int64, 'class_map'), _dev(logz_val, f64, 'logz'),
         _dev(spans, torch.int64, 'spans'), ctypes.c_int32(n_sets), _dev(start, f64, 'start'), _dev(end, f64, 'end'),
         _dev(bnd, f64, 'boundary'), _dev(seg, f64, 'seg_logp'), *_ws_args(ws), _stream()))
     return dict(start=start, end=end, boundary=bnd, seg_logp=seg, _err=_err_copy(batch, ws))
@@ -671,12 +668,13 @@ def entropy_bwd_scratch_bytes(batch):
     return n
 
 
-def _ebwd_outputs(batch, elp, trans, init, len_scores, want_value):
+def _ebwd_outputs(batch, elp, trans, init, len_scores, want_value, scratch_bytes=entropy_bwd_scratch_bytes):
+    """The gradients, ``value`` and the caller's scratch of a gradient unit; ``scratch_bytes``: the unit's scratch query."""
     f64 = torch.float64
     dev = elp.device
     g = _grad_outputs(elp, trans, init, len_scores)
     g['value'] = torch.empty((batch.b, 2), dtype=f64, device=dev) if want_value else None
-    scratch = torch.empty(entropy_bwd_scratch_bytes(batch), dtype=torch.uint8, device=dev)
+    scratch = torch.empty(scratch_bytes(batch), dtype=torch.uint8, device=dev)
     return g, scratch
 
 
@@ -694,9 +692,8 @@ def entropy_bwd(batch, elp, trans, init, len_scores, logz_val, grad_out=None, en
     if ws is None:
         ws = workspace(batch.workspace_bytes(), elp.device)
     _lib.check(lib.smm_entropy_bwd_f64(
-        *head, _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
-        _dev(endpen, f64, 'endpen'), _dev(logz_val, f64, 'logz'), _dev(grad_out, f64, 'grad_out'), _dev(g['elp'], f64, 'g_elp'),
-        _dev(g['trans'], f64, 'g_trans'), _dev(g['init'], f64, 'g_init'), _dev(g['len'], f64, 'g_len'),
+        *head, *_tables(elp, trans, init, len_scores, endpen), _dev(logz_val, f64, 'logz'), _dev(grad_out, f64, 'grad_out'),
+        _dev(g['elp'], f64, 'g_elp'), _dev(g['trans'], f64, 'g_trans'), _dev(g['init'], f64, 'g_init'), _dev(g['len'], f64, 'g_len'),
         _dev(g['value'], f64, 'value'), *_ws_args(scratch), *_ws_args(ws), _stream()))
     return g
 
@@ -749,9 +746,8 @@ def expected_reward(batch, elp, trans, init, len_scores, logz_val, reward=None, 
     if ws is None:
         ws = workspace(batch.workspace_bytes(), dev)
     _lib.check(lib.smm_expected_reward_f64(
-        *head, _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
-        _dev(endpen, f64, 'endpen'), _dev(logz_val, f64, 'logz'), _dev(reward, f64, 'reward'), _dev(seg_reward, f64, 'seg_reward'),
-        _dev(out, f64, 'value'), _dev(parts, f64, 'parts'), *_ws_args(ws), _stream()))
+        *head, *_tables(elp, trans, init, len_scores, endpen), _dev(logz_val, f64, 'logz'), _dev(reward, f64, 'reward'),
+        _dev(seg_reward, f64, 'seg_reward'), _dev(out, f64, 'value'), _dev(parts, f64, 'parts'), *_ws_args(ws), _stream()))
     return (out, parts) if want_parts else out
 
 
@@ -773,18 +769,14 @@ def expected_reward_bwd(batch, elp, trans, init, len_scores, logz_val, reward=No
     lib = _lib.load()
     head = batch.head(_lib.SHAPE_LOGZ_BOTH if with_backward else 0)
     f64 = torch.float64
-    dev = elp.device
-    g = _grad_outputs(elp, trans, init, len_scores)
-    g['value'] = torch.empty((batch.b, 2), dtype=f64, device=dev) if want_value else None
-    scratch = torch.empty(expected_reward_bwd_scratch_bytes(batch), dtype=torch.uint8, device=dev)
+    g, scratch = _ebwd_outputs(batch, elp, trans, init, len_scores, want_value, expected_reward_bwd_scratch_bytes)
     if ws is None:
-        ws = workspace(batch.workspace_bytes(), dev)
+        ws = workspace(batch.workspace_bytes(), elp.device)
     _lib.check(lib.smm_expected_reward_bwd_f64(
-        *head, _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'), _dev(len_scores, f64, 'len_scores'),
-        _dev(endpen, f64, 'endpen'), _dev(logz_val, f64, 'logz'), _dev(reward, f64, 'reward'), _dev(seg_reward, f64, 'seg_reward'),
-        _dev(grad_out, f64, 'grad_out'), _dev(g['elp'], f64, 'g_elp'), _dev(g['trans'], f64, 'g_trans'),
-        _dev(g['init'], f64, 'g_init'), _dev(g['len'], f64, 'g_len'), _dev(g['value'], f64, 'value'), *_ws_args(scratch),
-        *_ws_args(ws), _stream()))
+        *head, *_tables(elp, trans, init, len_scores, endpen), _dev(logz_val, f64, 'logz'), _dev(reward, f64, 'reward'),
+        _dev(seg_reward, f64, 'seg_reward'), _dev(grad_out, f64, 'grad_out'), _dev(g['elp'], f64, 'g_elp'),
+        _dev(g['trans'], f64, 'g_trans'), _dev(g['init'], f64, 'g_init'), _dev(g['len'], f64, 'g_len'),
+        _dev(g['value'], f64, 'value'), *_ws_args(scratch), *_ws_args(ws), _stream()))
     return g
 
 
@@ -815,8 +807,7 @@ def kbest(batch, elp, trans, init, len_scores, k, endpen=None, class_map=None, w
     if ws is None:
         ws = torch.empty(kbest_workspace_bytes(batch, k), dtype=torch.uint8, device=dev)
     _lib.check(lib.smm_kbest_f64(
-        *batch.head(), _dev(elp, f64, 'elp'), _dev(trans, f64, 'trans'), _dev(init, f64, 'init'),
-        _dev(len_scores, f64, 'len_scores'), _dev(endpen, f64, 'endpen'), _dev(class_map, torch.int64, 'class_map'),
+        *batch.head(), *_tables(elp, trans, init, len_scores, endpen), _dev(class_map, torch.int64, 'class_map'),
         ctypes.c_int32(k), _dev(spans, torch.int64, 'spans'), _dev(labels, torch.int64, 'labels'), _dev(score, f64, 'score'),
         _dev(n_segs, torch.int32, 'n_segs'), *_ws_args(ws), _stream()))
     return dict(spans=spans, labels=labels, score=score, n_segs=n_segs, _err=_err_copy(batch, ws))

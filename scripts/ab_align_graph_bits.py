@@ -1,10 +1,10 @@
 """Same bits from two builds of libsmmdp.so on the transcript-graph posterior calls: the cases of
-tests/test_gpu_transcript_{graph,sample,entropy,kl,entropy_grad}.py and a few of its own run through
+tests/test_gpu_transcript_{graph,sample,entropy,kl,entropy_grad,expected_reward}.py and a few of its own run through
 action-segmentation_amd/libsmmdp_prev.so and action-segmentation_amd/libsmmdp.so, one fresh child process per library
 (SMM_LIB_PATH), each under its own time limit; the second child starts only if the first exited 0.  Every output array is
 compared byte for byte: log Z and the backward gradients with p_used / p_end; samples (spans, labels, logp, n_segs, used);
-entropy and parts; KL, cross-entropy and parts; the four gradients, value and value_plus in the three gradient modes; the
-error word of every call that returns one (the backward call of log Z does not).  Workspaces and scratch are pre-filled with 0xFF bytes.  Prints the counts; exit status 1 on a difference.
+entropy and parts; KL, cross-entropy and parts; the four gradients, value and value_plus in the three gradient modes; value
+and parts of the expected reward, and the four gradients, value and value_plus of its gradient call; the error word of every call that returns one (the backward call of log Z does not).  Workspaces and scratch are pre-filled with 0xFF bytes.  Prints the counts; exit status 1 on a difference.
 usage: python scripts/ab_align_graph_bits.py              (the driver)
        python scripts/ab_align_graph_bits.py --child OUT.npz   (one library's run)"""
 import os
@@ -46,6 +46,7 @@ def child(path):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, 'tests'))
     import test_gpu_transcript_entropy_grad as GG
+    import test_gpu_transcript_expected_reward as GR
     import test_gpu_transcript_graph as GT
     import test_gpu_transcript_kl as GK
     import test_gpu_transcript_sample as GS
@@ -82,6 +83,12 @@ def child(path):
             scratch = torch.full((need,), 0xFF, dtype=torch.uint8, device='cuda:0')
             g = GG._launch(pc, qc, mode, batch, dp, fp, dq, fq, scratch=scratch)
             keep('%s grad %s' % (name, mode), err=err(g), **{key: g[key] for key in GG.KEYS + ('value', 'value_plus')})
+        rewards = GR.device_rewards(pc, GR.draw_rewards(pc, 31))
+        fill = lambda n: torch.full((n,), 0xFF, dtype=torch.uint8, device='cuda:0')
+        v = GR._value(pc, rewards, batch, dp, fp, scratch=fill(ops.align_graph_expected_reward_scratch_bytes(batch, GS._node_offsets(pc))))
+        keep(name + ' expected reward', value=v['value'], parts=v['parts'], err=err(v))
+        g = GR._grad(pc, rewards, batch, dp, fp, scratch=fill(ops.align_graph_expected_reward_bwd_scratch_bytes(batch, GS._node_offsets(pc))))
+        keep(name + ' expected reward grad', err=err(g), **{key: g[key] for key in GR.KEYS + ('value', 'value_plus')})
         torch.cuda.synchronize()
 
     # ---- the test files' cases
